@@ -38,7 +38,8 @@ enum {
   RSBA_ERR_HIP = 4,       /* a HIP runtime call failed                                       */
   RSBA_ERR_NO_DEVICE = 5, /* no gfx950 device visible: the product has no CPU path           */
   RSBA_ERR_COMM = 6,      /* RCCL failure                                                    */
-  RSBA_ERR_UNSUPPORTED = 7
+  RSBA_ERR_UNSUPPORTED = 7,
+  RSBA_ERR_RANK_DEFICIENT = 8 /* rsba_solver_covariance_compute: J'J is singular (Covariance::Compute returns false) */
 };
 
 /* ---- models */
@@ -261,6 +262,33 @@ int rsba_solver_kernel_stats(const rsba_solver* s, rsba_kernel_stat* out, int32_
 int rsba_solver_full_report(const rsba_solver* s, char* buf, int32_t capacity);
 int rsba_solver_final_costs(const rsba_solver* s, double* cost, double* sum_sq_residuals);
 void rsba_solver_destroy(rsba_solver* s);
+
+/* ------------------------------------------------------------------ covariance of the solution (ceres::Covariance)
+ * Not used by the reference; how well the solve determined each block.  The result is (J'J)^-1 of the unscaled parameters,
+ * J evaluated at the solver's current device parameters (after rsba_solver_run: the solution; before it: the uploaded start),
+ * with no sigma^2 factor and no LM damping, as Covariance::Compute gives it.  Blocks are named by their parameter offsets
+ * (the convention of rsba_problem_set_parameter_block_constant).  A constant block has a zero covariance; a block no residual
+ * references is RSBA_ERR_ARG.  The solver's trust radius, scales, iteration log, parameters and schedule are left untouched.
+ *
+ * Point model: every camera x camera block (6 x 6) and the 3 x 3 marginal of every point; camera x point and cross-point blocks
+ * are RSBA_ERR_UNSUPPORTED.  Marker-chain models (dense and time-eliminating paths alike): every camera / marker x camera / marker
+ * block (6 x 6); time blocks are RSBA_ERR_UNSUPPORTED; no loss (the marker-chain solve applies none).  world_size > 1 returns
+ * RSBA_ERR_UNSUPPORTED on every rank without issuing a collective. */
+typedef struct rsba_covariance_options { /* ceres::Covariance::Options, Ceres 1.14 defaults */
+  double min_reciprocal_condition_number; /* 1e-14: a Cholesky pivot of the Jacobi-scaled reduced system (or of a point block)
+                                             at or below this -> RSBA_ERR_RANK_DEFICIENT */
+  int32_t apply_loss_function;            /* 1: J through the solve's loss corrector (sqrt(rho') scaling) */
+  int32_t reserved;
+} rsba_covariance_options;
+
+void rsba_covariance_options_default(rsba_covariance_options* o);
+/* Linearise at the current parameters, invert the reduced camera system and form the point marginals on the GPU (o: NULL =
+ * defaults).  RSBA_ERR_RANK_DEFICIENT leaves no result: the block queries then return RSBA_ERR_ARG. */
+int rsba_solver_covariance_compute(rsba_solver* s, const rsba_covariance_options* o);
+/* Covariance block of the blocks at parameter offsets a and b: na x nb, row-major.  block(b, a) is block(a, b)' exactly. */
+int rsba_solver_covariance_block(const rsba_solver* s, int64_t offset_a, int64_t offset_b, double* out);
+/* Point model: P x 3 x 3 marginals in the problem's point order (zeros for constant and unreferenced points); RSBA_ERR_UNSUPPORTED otherwise. */
+int rsba_solver_point_covariances(const rsba_solver* s, double* out);
 
 /* Stage-level entry (tests): one linearisation of the point model at the current parameters with a
  * given trust-region radius.  Any output may be NULL.

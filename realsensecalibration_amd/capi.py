@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # library is never overwritten)
 LIB_PATH = os.environ.get("RSBA_LIB") or os.path.join(HERE, "librsba.so")
 
-OK, ERR_IO, ERR_FORMAT, ERR_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_COMM, ERR_UNSUPPORTED = range(8)
+OK, ERR_IO, ERR_FORMAT, ERR_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_COMM, ERR_UNSUPPORTED, ERR_RANK_DEFICIENT = range(9)
 MODEL_POINTS, MODEL_MARKER_CHAIN, MODEL_MARKER_CHAIN_TEST2 = 0, 1, 2
 CONVERGENCE, NO_CONVERGENCE, FAILURE = 0, 1, 2
 
@@ -29,6 +29,7 @@ EXPORTS = [
     "rsba_base_pose_from_marker_detection", "rsba_marker_pose_in_camera", "rsba_marker_corners_in_camera", "rsba_solve_pnp_epnp",
     "rsba_problem_initial_camera_poses", "rsba_problem_set_camera_constant", "rsba_problem_set_point_constant", "rsba_problem_set_parameter_block_constant", "rsba_solver_full_report", "rsba_solver_configure_run",
     "rsba_solver_comm_nranks", "rsba_solver_schedule_info", "rsba_comm_shm_id", "rsba_comm_finalize",
+    "rsba_covariance_options_default", "rsba_solver_covariance_compute", "rsba_solver_covariance_block", "rsba_solver_point_covariances",
 ]
 
 
@@ -66,6 +67,10 @@ class KernelStat(C.Structure):
 class ScheduleInfo(C.Structure):
     _fields_ = [("schedule", C.c_int32), ("stalls", C.c_int32), ("fallbacks", C.c_int32), ("comm_nranks", C.c_int32),
                 ("chol_workgroups", C.c_int32), ("schur_impl", C.c_int32), ("comm_kind", C.c_char * 16)]
+
+
+class CovarianceOptions(C.Structure):
+    _fields_ = [("min_reciprocal_condition_number", C.c_double), ("apply_loss_function", C.c_int32), ("reserved", C.c_int32)]
 
 
 class RsbaError(RuntimeError):
@@ -140,6 +145,10 @@ def load():
     lib.rsba_problem_set_camera_constant.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     lib.rsba_problem_set_point_constant.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     lib.rsba_problem_set_parameter_block_constant.argtypes = [C.c_void_p, C.c_int64, C.c_int32]
+    lib.rsba_covariance_options_default.argtypes = [C.c_void_p]
+    lib.rsba_solver_covariance_compute.argtypes = [C.c_void_p, C.c_void_p]
+    lib.rsba_solver_covariance_block.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+    lib.rsba_solver_point_covariances.argtypes = [C.c_void_p, C.c_void_p]
     _LIB = lib
     return lib
 
@@ -326,6 +335,46 @@ class Solver:
         buf = C.create_string_buffer(n + 1)
         load().rsba_solver_full_report(self.h, buf, n + 1)
         return buf.value.decode()
+
+    # ---- covariance of the solution (ceres::Covariance; point model)
+    def covariance_compute(self, **opts):
+        """(J'J)^-1 at the solver's current parameters.  opts: min_reciprocal_condition_number, apply_loss_function.
+        Raises RsbaError with code ERR_RANK_DEFICIENT when J'J is singular."""
+        o = CovarianceOptions()
+        load().rsba_covariance_options_default(C.byref(o))
+        for k, v in opts.items():
+            setattr(o, k, v)
+        _chk(load().rsba_solver_covariance_compute(self.h, C.byref(o)), "rsba_solver_covariance_compute")
+
+    def covariance_block(self, offset_a, offset_b):
+        """Covariance block of the parameter blocks at offsets a and b (camera_offset / point_offset)."""
+        na, nb = self._block_size(offset_a), self._block_size(offset_b)
+        out = np.zeros((na, nb))
+        _chk(load().rsba_solver_covariance_block(self.h, int(offset_a), int(offset_b), _vp(out)), "rsba_solver_covariance_block")
+        return out
+
+    def point_covariances(self):
+        """P x 3 x 3 marginals of the points, in the problem's point order."""
+        out = np.zeros((self.problem.num_points, 3, 3))
+        _chk(load().rsba_solver_point_covariances(self.h, _vp(out)), "rsba_solver_point_covariances")
+        return out
+
+    def camera_offset(self, camera_idx):
+        return 6 * int(camera_idx)
+
+    def point_offset(self, point_idx):
+        return 6 * self.problem.num_cameras + 3 * int(point_idx)
+
+    def time_offset(self, time_idx):
+        return 6 * (self.problem.num_cameras + int(time_idx))
+
+    def marker_offset(self, marker_idx):
+        return 6 * (self.problem.num_cameras + self.problem.num_times + int(marker_idx))
+
+    def _block_size(self, offset):
+        if self.problem.model == MODEL_POINTS and offset >= 6 * self.problem.num_cameras:
+            return 3
+        return 6
 
     def final_costs(self):
         c, ss = C.c_double(), C.c_double()

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "ba_comm.hpp"
+#include "ba_covariance.hpp"
 #include "ba_marker_kernels.hpp"
 #include "ba_marker_schur.hpp"
 #include "ba_point_kernels.hpp"
@@ -304,6 +305,18 @@ struct rsba_solver {
   MarkerDevice marker;
   MarkerSchurDevice marker_schur;   // time blocks eliminated: the marker-chain model at scale
   bool eliminate_times = false;
+
+  // ---- covariance (rsba_solver_covariance_compute, ba_covariance.hpp): buffers of its own, the LM state is not touched
+  bool cov_valid = false;
+  int cov_n = 0;
+  std::vector<int> cov_pos;                    // per camera (point model) / per block of [C | T | M] (marker chain): 6 x its index in the
+                                               // covariance system, -1: constant, unreferenced or eliminated
+  std::vector<uint8_t> cov_ref_cam, cov_ref_pt;   // referenced by a residual (marker chain: cov_ref_cam per block of [C | T | M])
+  double* cov_sinv = nullptr;                  // cov_n x cov_n, full symmetric
+  size_t cov_sinv_cap = 0;
+  double* cov_pts = nullptr;                   // P x 9, the problem's point order
+  char* cov_arena = nullptr;                   // scratch of the computation, kept between calls (grows only)
+  size_t cov_arena_cap = 0;
 };
 
 namespace rsba {
@@ -902,7 +915,7 @@ static void FreeSolver(rsba_solver* s) {
   s->timer.Reset();
   void* ptrs[] = {s->obs_u, s->obs_v, s->intr, s->obs_cam, s->pt_ptr, s->sl_row_ptr, s->sl_cam, s->sl_uv, s->cam[0], s->cam[1], s->pts[0], s->pts[1], s->camc[0], s->camc[1],
                   s->cam0, s->pts0, s->scale_c, s->scale_p, s->red, s->A, s->W, s->chol_ok, s->S_copy, s->rhs_copy, s->dcam, s->block_scal,
-                  s->block_part, s->small_red, s->gmax, s->res, s->dec, s->cam_backup, s->red_tri, s->cam_free, s->pt_const, s->mc_flags, s->mc_dg, s->tc_flags, s->tc_map, s->tc_hand, s->tc_xs, s->tc_ys};
+                  s->block_part, s->small_red, s->gmax, s->res, s->dec, s->cam_backup, s->red_tri, s->cam_free, s->pt_const, s->mc_flags, s->mc_dg, s->tc_flags, s->tc_map, s->tc_hand, s->tc_xs, s->tc_ys, s->cov_sinv, s->cov_pts, s->cov_arena};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   s->tiled.Free();
   s->marker.Free();
@@ -2465,6 +2478,182 @@ static int MinimizeLoop(rsba_solver* s, rsba_summary* sum, StepFn step, AcceptFn
   }
 }
 
+// Scratch of one covariance computation, carved out of one device allocation that the solver keeps (it grows only: no hipFree — a
+// device-wide synchronisation — on a repeated call).  Two passes over the same sequence of take()s: the first sizes, the second hands out.
+struct CovCarve {
+  char* base = nullptr;
+  size_t off = 0;
+  template <typename T>
+  T* take(size_t n) {
+    off = (off + 255) & ~(size_t)255;
+    T* q = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += std::max<size_t>(n, 1) * sizeof(T);
+    return q;
+  }
+};
+template <typename T>
+static int CovGrow(T** p, size_t* cap, size_t n) {
+  if (*p && *cap >= n) return RSBA_OK;
+  if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
+  if (hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) { *p = nullptr; return RSBA_ERR_HIP; }
+  *cap = n;
+  return RSBA_OK;
+}
+
+struct CovSystem {   // the reduced system's buffers (carved) and its size
+  int n = 0, np = 0;
+  double *S = nullptr, *A = nullptr, *dsc = nullptr, *piv = nullptr, *panel = nullptr;
+  int* flags = nullptr;
+  void Carve(CovCarve& cv) {
+    S = cv.take<double>((size_t)n * n); A = cv.take<double>((size_t)np * np); dsc = cv.take<double>(np);
+    piv = cv.take<double>(RSBA_COV_NB * RSBA_COV_NB); panel = cv.take<double>((size_t)np * RSBA_COV_NB); flags = cv.take<int>(COV_FLAG_WORDS);
+  }
+};
+
+// S^-1 into s->cov_sinv: Jacobi scaling, the 16-wide block sweep (rank test in the pivots), unscaling with the mirrored upper triangle
+static void CovInvert(rsba_solver* s, const CovSystem& y, double rcond, hipStream_t st) {
+  const int n = y.n, np = y.np;
+  if (n == 0) return;
+  const size_t nA = (size_t)np * np, nS = (size_t)n * n;
+  k_cov_scale<<<(int)std::min<size_t>((nA + 255) / 256, 8192), 256, 0, st>>>(n, np, y.S, y.A, y.dsc, y.flags);
+  const int nb = np / RSBA_COV_NB;
+  for (int kb = 0; kb < nb; ++kb) {
+    k_cov_pivot<<<1, 64, 0, st>>>(np, kb, y.A, y.piv, y.panel, rcond, y.flags);
+    k_cov_sweep<<<nb * nb, 64, 0, st>>>(np, kb, y.A, y.piv, y.panel);
+  }
+  k_cov_unscale<<<(int)std::min<size_t>((nS + 255) / 256, 8192), 256, 0, st>>>(n, np, y.A, y.dsc, s->cov_sinv);
+}
+
+// ceres::Covariance::Compute (ba_covariance.hpp): the system's size from the free referenced blocks, scratch, then `launch` queues the
+// linearisation into y.S; the inverse and the flags follow.  Everything on the solver's stream, nothing the LM loop reads is written.
+template <typename Extra, typename Launch>
+static int CovRun(rsba_solver* s, int n, double rcond, Extra&& extra, Launch&& launch) {
+  hipStream_t st = s->stream;
+  s->cov_n = n;
+  CovSystem y;
+  y.n = n; y.np = std::max(RSBA_COV_NB, (n + RSBA_COV_NB - 1) / RSBA_COV_NB * RSBA_COV_NB);
+  CovCarve sizing;
+  y.Carve(sizing); extra(sizing);
+  int rc;
+  if ((rc = CovGrow(&s->cov_arena, &s->cov_arena_cap, sizing.off)) || (rc = CovGrow(&s->cov_sinv, &s->cov_sinv_cap, (size_t)n * n))) return rc;
+  CovCarve cv;
+  cv.base = s->cov_arena;
+  y.Carve(cv); extra(cv);
+  rc = RSBA_OK;
+  auto hip = [&](hipError_t e) { if (e != hipSuccess && rc == RSBA_OK) rc = RSBA_ERR_HIP; };
+  hip(hipMemsetAsync(y.flags, 0, COV_FLAG_WORDS * sizeof(int), st));
+  hip(hipMemsetAsync(y.S, 0, std::max<size_t>((size_t)n * n, 1) * sizeof(double), st));
+  launch(y, hip);
+  CovInvert(s, y, rcond, st);
+  hip(hipGetLastError());
+  int fl[COV_FLAG_WORDS] = {0, 0};
+  hip(hipMemcpyAsync(fl, y.flags, sizeof(fl), hipMemcpyDeviceToHost, st));
+  hip(hipStreamSynchronize(st));
+  if (rc != RSBA_OK) return rc;
+  if (fl[COV_FLAG_SYSTEM] || fl[COV_FLAG_POINT]) return RSBA_ERR_RANK_DEFICIENT;
+  s->cov_valid = true;
+  return RSBA_OK;
+}
+
+// Point model: S^-1 of the free referenced cameras and the 3 x 3 marginal of every point, at the solver's current device state.
+static int CovariancePoints(rsba_solver* s, const rsba_covariance_options& co) {
+  const rsba_problem& p = *s->prob;
+  const int C = s->C, P = s->P;
+  s->cov_ref_cam.assign(C, 0);
+  s->cov_ref_pt.assign(P, 0);
+  for (int64_t i = 0; i < s->N; ++i) { s->cov_ref_cam[p.camera_index[i]] = 1; s->cov_ref_pt[p.point_index[i]] = 1; }
+  s->cov_pos.assign(C, -1);
+  int n = 0;
+  for (int c = 0; c < C; ++c) {
+    const bool constant = c < (int)p.camera_constant.size() && p.camera_constant[c];
+    if (s->cov_ref_cam[c] && !constant) { s->cov_pos[c] = n; n += 6; }
+  }
+  if (!s->cov_pts) { int rc = DevAlloc(&s->cov_pts, 9 * (size_t)P); if (rc) return rc; }
+  double* camc = nullptr;
+  int *pos = nullptr, *perm = nullptr;
+  auto extra = [&](CovCarve& cv) { camc = cv.take<double>((size_t)CC_STRIDE * C); pos = cv.take<int>(C); perm = s->pt_perm.empty() ? nullptr : cv.take<int>(P); };
+  // the current device state: the last run's accepted point, or the uploaded start before the first run
+  const double* cam = s->has_run ? s->cam[s->cur] : s->cam0;
+  const double* pts = s->has_run ? s->pts[s->cur] : s->pts0;
+  const double loss = !co.apply_loss_function || !(s->opt.huber_delta > 0.0) ? 0.0 : (s->opt.loss_type == RSBA_LOSS_CAUCHY ? -s->opt.huber_delta : s->opt.huber_delta);
+  const double rcond = co.min_reciprocal_condition_number;
+  const int grid_pts = std::max(1, std::min((P + 3) / 4, 8192));
+  hipStream_t st = s->stream;
+  int rc = CovRun(s, n, rcond, extra, [&](CovSystem& y, auto& hip) {
+    hip(hipMemcpyAsync(pos, s->cov_pos.data(), C * sizeof(int), hipMemcpyHostToDevice, st));
+    if (perm) hip(hipMemcpyAsync(perm, s->pt_perm.data(), P * sizeof(int), hipMemcpyHostToDevice, st));
+    k_camera_constants<<<(C + 63) / 64, 64, 0, st>>>(C, cam, s->intr, camc);
+    k_cov_lin<<<grid_pts, 256, 0, st>>>(P, s->obs_u, s->obs_v, s->obs_cam, s->pt_ptr, camc, pts, pos, s->pt_const, loss, rcond, y.n, y.S, y.flags);
+  });
+  if (rc != RSBA_OK || !s->cov_valid) return rc;
+  s->cov_valid = false;
+  k_cov_points<<<grid_pts, 256, 0, st>>>(P, s->obs_u, s->obs_v, s->obs_cam, s->pt_ptr, camc, pts, pos, s->pt_const, perm, loss, rcond, n,
+                                         s->cov_sinv, s->cov_pts);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return RSBA_ERR_HIP;
+  s->cov_valid = true;
+  return RSBA_OK;
+}
+
+// Marker-chain models: S^-1 of the free referenced camera / marker blocks.  The dense path keeps the free time blocks in the system
+// (the inverse of its whole active system); the time-eliminating path eliminates them first, as its solve does.  No loss.
+static int CovarianceMarker(rsba_solver* s, const rsba_covariance_options& co) {
+  const rsba_problem& p = *s->prob;
+  const int C = p.num_cameras, T = p.num_times, M = p.num_markers, nb = C + T + M;
+  const int64_t N = p.num_observations;
+  const bool elim_path = s->eliminate_times;
+  s->cov_ref_cam.assign(nb, 0);
+  for (int64_t i = 0; i < N; ++i) {
+    if (p.uses_camera(i)) s->cov_ref_cam[p.camera_block(i)] = 1;
+    s->cov_ref_cam[p.time_block(i)] = 1;
+    if (p.uses_marker(i)) s->cov_ref_cam[p.marker_block(i)] = 1;
+  }
+  auto is_free = [&](int b) { return s->cov_ref_cam[b] && !(b < (int)p.block_constant.size() && p.block_constant[b]); };
+  s->cov_pos.assign(nb, -1);
+  std::vector<unsigned char> elim(std::max(T, 1), 0);
+  int n = 0;
+  for (int b = 0; b < nb; ++b) {
+    const bool time = b >= C && b < C + T;
+    if (!is_free(b)) continue;
+    if (time && elim_path) { elim[b - C] = 1; continue; }
+    s->cov_pos[b] = n; n += 6;
+  }
+  // rows in time order
+  std::vector<int> tptr(T + 1, 0);
+  for (int64_t i = 0; i < N; ++i) tptr[p.time_index[i] + 1]++;
+  for (int t = 0; t < T; ++t) tptr[t + 1] += tptr[t];
+  std::vector<int> fill(tptr.begin(), tptr.end() - 1);
+  std::vector<CovMcRow> rows(std::max<int64_t>(N, 1));
+  std::vector<double> obs(8 * (size_t)std::max<int64_t>(N, 1));
+  for (int64_t i = 0; i < N; ++i) {
+    const int q = fill[p.time_index[i]]++;
+    rows[q] = CovMcRow{p.uses_camera(i) ? p.camera_block(i) : -1, p.time_block(i), p.uses_marker(i) ? p.marker_block(i) : -1, p.camera_index[i]};
+    for (int e = 0; e < 8; ++e) obs[8 * (size_t)q + e] = p.observations[8 * i + e];
+  }
+  double *pc = nullptr, *obs_d = nullptr, *intr = nullptr;
+  int *pos = nullptr, *tptr_d = nullptr;
+  CovMcRow* rows_d = nullptr;
+  unsigned char* elim_d = nullptr;
+  auto extra = [&](CovCarve& cv) {
+    pc = cv.take<double>((size_t)CC_STRIDE * nb); obs_d = cv.take<double>(obs.size()); intr = cv.take<double>(p.intrinsics.size());
+    pos = cv.take<int>(nb); tptr_d = cv.take<int>(T + 1); rows_d = cv.take<CovMcRow>(rows.size()); elim_d = cv.take<unsigned char>(elim.size());
+  };
+  const double* params = elim_path ? (s->has_run ? s->marker_schur.params[s->marker_schur.cur] : s->marker_schur.params0)
+                                   : (s->has_run ? s->marker.params[s->marker.cur] : s->marker.params0);
+  const double rcond = co.min_reciprocal_condition_number;
+  hipStream_t st = s->stream;
+  return CovRun(s, n, rcond, extra, [&](CovSystem& y, auto& hip) {
+    hip(hipMemcpyAsync(obs_d, obs.data(), obs.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    hip(hipMemcpyAsync(intr, p.intrinsics.data(), p.intrinsics.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    hip(hipMemcpyAsync(pos, s->cov_pos.data(), nb * sizeof(int), hipMemcpyHostToDevice, st));
+    hip(hipMemcpyAsync(tptr_d, tptr.data(), (T + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+    hip(hipMemcpyAsync(rows_d, rows.data(), rows.size() * sizeof(CovMcRow), hipMemcpyHostToDevice, st));
+    hip(hipMemcpyAsync(elim_d, elim.data(), elim.size(), hipMemcpyHostToDevice, st));
+    k_cov_pose_constants<<<(nb + 255) / 256, 256, 0, st>>>(nb, params, pc);
+    k_cov_mc_lin<<<std::max(1, std::min(T, 4096)), 64, 0, st>>>(T, tptr_d, rows_d, obs_d, intr, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags);
+    // (the host vectors outlive CovRun, which synchronises the stream before it returns)
+  });
+}
+
 }  // namespace rsba
 
 // ================================================================================================
@@ -2837,6 +3026,81 @@ int rsba_solve(rsba_problem* p, const rsba_options* o, rsba_summary* summary) {
   if (rc == RSBA_OK) rc = rsba_solver_download(s);
   rsba_solver_destroy(s);
   return rc;
+}
+
+void rsba_covariance_options_default(rsba_covariance_options* o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  o->min_reciprocal_condition_number = 1e-14; o->apply_loss_function = 1;
+}
+
+int rsba_solver_covariance_compute(rsba_solver* s, const rsba_covariance_options* o) {
+  if (!s) return RSBA_ERR_ARG;
+  rsba_covariance_options co;
+  if (o) co = *o; else rsba_covariance_options_default(&co);
+  if (!(co.min_reciprocal_condition_number >= 0.0)) return RSBA_ERR_ARG;
+  s->cov_valid = false;
+  // (several ranks: no collective is issued, every rank returns here)
+  if (s->opt.world_size > 1 || s->comm) return RSBA_ERR_UNSUPPORTED;
+  if (hipSetDevice(s->device) != hipSuccess) return RSBA_ERR_HIP;
+  if (hipStreamSynchronize(s->stream) != hipSuccess) return RSBA_ERR_HIP;
+  return s->prob->model == RSBA_MODEL_POINTS ? rsba::CovariancePoints(s, co) : rsba::CovarianceMarker(s, co);
+}
+
+int rsba_solver_covariance_block(const rsba_solver* s, int64_t offset_a, int64_t offset_b, double* out) {
+  if (!s || !out) return RSBA_ERR_ARG;
+  if (!s->cov_valid) return RSBA_ERR_ARG;
+  const size_t n = (size_t)s->cov_n;
+  auto copy6 = [&](int pa, int pb) {
+    if (pa < 0 || pb < 0) { memset(out, 0, 36 * sizeof(double)); return RSBA_OK; }   // a constant block
+    if (hipSetDevice(s->device) != hipSuccess) return RSBA_ERR_HIP;
+    return hipMemcpy2D(out, 6 * sizeof(double), s->cov_sinv + (size_t)pa * n + pb, n * sizeof(double), 6 * sizeof(double), 6, hipMemcpyDeviceToHost) == hipSuccess
+               ? RSBA_OK : RSBA_ERR_HIP;
+  };
+  if (s->prob->model != RSBA_MODEL_POINTS) {
+    // [C | T | M] x 6: camera and marker blocks; time blocks are not offered (eliminated on one path)
+    const rsba_problem& p = *s->prob;
+    const int C = p.num_cameras, T = p.num_times, nb = C + T + p.num_markers;
+    int blk[2];
+    const int64_t offs[2] = {offset_a, offset_b};
+    for (int e = 0; e < 2; ++e) {
+      if (offs[e] < 0 || offs[e] >= 6LL * nb || offs[e] % 6) return RSBA_ERR_ARG;
+      blk[e] = (int)(offs[e] / 6);
+    }
+    for (int e = 0; e < 2; ++e) if (blk[e] >= C && blk[e] < C + T) return RSBA_ERR_UNSUPPORTED;
+    for (int e = 0; e < 2; ++e) if (!s->cov_ref_cam[blk[e]]) return RSBA_ERR_ARG;
+    return copy6(s->cov_pos[blk[0]], s->cov_pos[blk[1]]);
+  }
+  const rsba_problem& p = *s->prob;
+  const int64_t cam_end = 6LL * s->C, end = cam_end + 3LL * s->P;
+  // -> (is camera, index); RSBA_ERR_ARG for an offset that starts no block or names a block no residual references
+  auto block = [&](int64_t off, bool* is_cam, int* idx) {
+    if (off < 0 || off >= end) return RSBA_ERR_ARG;
+    if (off < cam_end) {
+      if (off % 6) return RSBA_ERR_ARG;
+      *is_cam = true; *idx = (int)(off / 6);
+      return s->cov_ref_cam[*idx] ? RSBA_OK : RSBA_ERR_ARG;
+    }
+    if ((off - cam_end) % 3) return RSBA_ERR_ARG;
+    *is_cam = false; *idx = (int)((off - cam_end) / 3);
+    return s->cov_ref_pt[*idx] ? RSBA_OK : RSBA_ERR_ARG;
+  };
+  bool ca = false, cb = false;
+  int ia = 0, ib = 0, rc;
+  if ((rc = block(offset_a, &ca, &ia)) != RSBA_OK || (rc = block(offset_b, &cb, &ib)) != RSBA_OK) return rc;
+  if (hipSetDevice(s->device) != hipSuccess) return RSBA_ERR_HIP;
+  if (ca && cb) return copy6(s->cov_pos[ia], s->cov_pos[ib]);
+  if (ca || cb || ia != ib) return RSBA_ERR_UNSUPPORTED;   // camera x point and cross-point blocks
+  // (a constant point's marginal is written as zeros by k_cov_points)
+  return hipMemcpy(out, s->cov_pts + 9 * (size_t)ia, 9 * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess ? RSBA_OK : RSBA_ERR_HIP;
+}
+
+int rsba_solver_point_covariances(const rsba_solver* s, double* out) {
+  if (!s || !out) return RSBA_ERR_ARG;
+  if (s->prob->model != RSBA_MODEL_POINTS) return RSBA_ERR_UNSUPPORTED;
+  if (!s->cov_valid) return RSBA_ERR_ARG;
+  if (hipSetDevice(s->device) != hipSuccess) return RSBA_ERR_HIP;
+  return hipMemcpy(out, s->cov_pts, 9 * (size_t)s->P * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess ? RSBA_OK : RSBA_ERR_HIP;
 }
 
 int rsba_points_linearize_and_step(rsba_problem* p, const rsba_options* o, double radius, double* S, double* rhs, double* delta, double* scalars) {

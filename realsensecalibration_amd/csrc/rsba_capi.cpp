@@ -21,6 +21,7 @@ const char* rsba_error_string(int code) {
     case RSBA_ERR_NO_DEVICE: return "no HIP device (this library has no CPU path)";
     case RSBA_ERR_COMM: return "RCCL error";
     case RSBA_ERR_UNSUPPORTED: return "unsupported configuration";
+    case RSBA_ERR_RANK_DEFICIENT: return "rank deficient: the covariance does not exist";
     default: return "unknown error";
   }
 }
