@@ -23,7 +23,7 @@
 //   * stores are wave 4's business in workgroup 0 (L11 / T the moment the block is factored, the two newest X blocks, their
 //     acknowledgements, the flags tdone and strip_ready); nobody on the chain waits for a store.
 //
-// STATUS (round 2): the default for 32 to 64 cameras, on six workgroups (RSBA_CHOL_DIAG=0 selects the round-robin kernel):
+// STATUS (round 2): the default for 32 to 64 cameras, on six workgroups (against the round-robin kernel it superseded):
 // 0.465 - 0.470 against 0.479 ms per LM iteration at 64 cameras, 184 against 221 us alone.  A panel of workgroup 0 takes 11 - 13 us when the next block is
 // there (factorisation 6.3, update waves' data 4 - 5 us after they ask + 2 - 4 us of matrix cores, tail 2.2), but the row
 // workgroups need 13 - 15 us per panel (every global round trip costs 2.3 - 8 us beside the Schur kernel), so it waits for
@@ -416,7 +416,7 @@ k_reduced_system_solve_diag(int C, double* __restrict__ red, RedLayout L, double
                             const double* __restrict__ cam_x, double* __restrict__ cam_c, const double* __restrict__ intr,
                             double* __restrict__ camc_c, double* __restrict__ dcam, const double* __restrict__ gmax_p,
                             double* __restrict__ res, IterParams ip, int* __restrict__ chol_ok, StageGate gate, DiagCholFlags f, int tag,
-                            long long* __restrict__ mtrace /* diagnostic: [G][16][8] wall-clock stamps, or nullptr */, AheadSel ahead = AheadSel{},
+                            long long* __restrict__ mtrace /* diagnostic: [G][16][8] wall-clock stamps, or nullptr */,
                             int border_cols = 0 /* > 0: the leading system's columns (a multiple of 96); the last camera group is the border, formed by the launch's last workgroup (ba_cholesky_border.hpp) */) {
   extern __shared__ __attribute__((aligned(16))) double lds[];   // (16: the strip image is read and written 16 bytes at a time)
   const int ld = L.nc;                                          // columns of S in memory
@@ -444,30 +444,6 @@ k_reduced_system_solve_diag(int C, double* __restrict__ red, RedLayout L, double
   if (gate.trace && tid == 0 && w == 0) gate.trace[0] = wall_clock64();
   AnnounceResident(gate);
   bool stalled = false;
-  if (RSBA_EXP(ahead.dec != nullptr)) {
-    // launched ahead: the previous step's decision (see AheadSel).  One lane polls, asleep in between; never hang.
-    __shared__ int s_dec_ok;
-    if (tid == 0) {
-      const long long t0 = wall_clock64();
-      int ok = 1;
-      while (__hip_atomic_load(ahead.dec + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != ahead.seq) {
-        __builtin_amdgcn_s_sleep(32);
-        if (wall_clock64() - t0 > budget) { ok = 0; break; }
-      }
-      s_dec_ok = ok;
-    }
-    __syncthreads();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    if (s_dec_ok == 0) stalled = true;
-    if (__hip_atomic_load(ahead.dec + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0.0) {
-      const double* t = cam_x; cam_x = cam_c; cam_c = const_cast<double*>(t); camc_c = ahead.camc_x;
-      if (w == 0) {   // (see AheadSel: what the candidate will overwrite at the end of this kernel)
-        for (int i = tid; i < 6 * C; i += nt) ahead.cam_backup[i] = cam_c[i];
-        for (int i = tid; i < C * CC_STRIDE; i += nt) ahead.camc_backup[i] = camc_c[i];
-      }
-    }
-    ip.radius = __hip_atomic_load(ahead.dec + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
   const double* S = red + L.S();
   const double inv_radius = 1.0 / ip.radius;
   const int mi = lane & 15, kk = lane >> 4;

@@ -203,7 +203,7 @@ struct rsba_solver {
                              // (0.436 against 0.449 ms per step).  Opt-in because its roundings are not the pipelined schedule's kernel's: the two
                              // schedules — and a step repeated sequentially after a stall — would no longer add the same bits.
   int chol_wgs = 1;          // > 1: the reduced system is factored by this many workgroups (ba_cholesky_multi.hpp)
-  bool chol_diag = false;    // ... with the diagonal chain in workgroup 0 (ba_cholesky_diag.hpp; RSBA_CHOL_DIAG=0: blocks dealt round-robin, ba_cholesky_multi.hpp)
+  bool chol_diag = false;    // ... with the diagonal chain in workgroup 0 (ba_cholesky_diag.hpp)
   int border_cols = 0;       // > 0 (RSBA_BORDER=1; 33 .. 64 cameras, no communicator): the diagonal-chain kernel factors the leading 96 B columns and one more
                              // workgroup forms the last camera group as their border (ba_cholesky_border.hpp); both schedules, so that they add the same bits
   int* mc_flags = nullptr;   // tdone[16] | strip_ready[16] | wg_done[8] | error (error[12]: the leading system is through)
@@ -223,7 +223,6 @@ struct rsba_solver {
   bool pipelined_mg = false;
   bool pipe_serial = false;            // RSBA_PIPELINE=2: the pipelined schedule's kernels launched one after the other (counter collection)
   hipEvent_t ev_serial[2] = {nullptr, nullptr};
-  hipEvent_t ev_tiles = nullptr;       // tile pipeline (more than 64 cameras): the side stream's solve -> the main stream's back-substitution
   size_t tc_nflags = 0, tc_hand_doubles = 0, tc_xs_doubles = 0, tc_ys_doubles = 0;   // sizes of the tiled factorisation's flags and hand-over buffers (reset after a stall)
   hipStream_t sR = nullptr;
   int* ready_global = nullptr;
@@ -235,16 +234,6 @@ struct rsba_solver {
   double lm_decrease_factor = 2.0;
   double* dec = nullptr;
   bool dec_step = false;
-  // Launch-ahead (single GPU, pipelined, up to 64 cameras): the NEXT step's factorisation and Schur kernel are queued behind this
-  // step's back-substitution and the damping kernel, on the device's decision, before the host has this step's result (see
-  // launch_ahead in PointsStep).  ahead_ok: MinimizeLoop says another step may follow (the iteration limit is not reached);
-  // ahead_inflight / ahead_tag: such a pair is queued, with that step tag; ahead_state / ahead_radius: what the device decided
-  // (from the result block): the next PointsStep uses the pair if that is what the host asks for, else waits for it and
-  // launches its own.
-  bool ahead_ok = false, ahead_inflight = false;
-  int ahead_tag = 0, ahead_state = 0, ahead_x = 0;   // ahead_x: which buffers held x when the pair was launched
-  double ahead_radius = 0.0;
-  double* cam_backup = nullptr;    // [6 C + C x CC_STRIDE]: see AheadSel
   // pipelined schedule: steps that timed out (the step is repeated sequentially; the third time-out ends the pipelined
   // schedule for this solver), and "the next pipelined step waits until the factorisation is resident" (first step of a
   // run, first step after a time-out)
@@ -915,13 +904,12 @@ static void FreeSolver(rsba_solver* s) {
   s->timer.Reset();
   void* ptrs[] = {s->obs_u, s->obs_v, s->intr, s->obs_cam, s->pt_ptr, s->sl_row_ptr, s->sl_cam, s->sl_uv, s->cam[0], s->cam[1], s->pts[0], s->pts[1], s->camc[0], s->camc[1],
                   s->cam0, s->pts0, s->scale_c, s->scale_p, s->red, s->A, s->W, s->chol_ok, s->S_copy, s->rhs_copy, s->dcam, s->block_scal,
-                  s->block_part, s->small_red, s->gmax, s->res, s->dec, s->cam_backup, s->red_tri, s->cam_free, s->pt_const, s->mc_flags, s->mc_dg, s->tc_flags, s->tc_map, s->tc_hand, s->tc_xs, s->tc_ys, s->cov_sinv, s->cov_pts, s->cov_arena};
+                  s->block_part, s->small_red, s->gmax, s->res, s->dec, s->red_tri, s->cam_free, s->pt_const, s->mc_flags, s->mc_dg, s->tc_flags, s->tc_map, s->tc_hand, s->tc_xs, s->tc_ys, s->cov_sinv, s->cov_pts, s->cov_arena};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   s->tiled.Free();
   s->marker.Free();
   s->marker_schur.Free();
   for (hipEvent_t e : s->ev_serial) if (e) (void)hipEventDestroy(e);
-  if (s->ev_tiles) (void)hipEventDestroy(s->ev_tiles);
   if (s->res_host) (void)hipHostFree(s->res_host);
   if (s->trace_base) (void)hipFree(s->trace_base);
   if (s->wg_trace) (void)hipFree(s->wg_trace);
@@ -1044,25 +1032,9 @@ static bool SetupPipeline(rsba_solver* s) {
   if (s->C <= RSBA_TG) return false;        // one camera group: nothing to overlap
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, s->device) != hipSuccess) return false;
-  if (s->nc > RSBA_CHOL_MAXN) {
-    // More than 64 cameras (round 4): the persistent TILED factorisation beside the Schur kernel — OPT-IN (RSBA_PIPELINE_TILES=1),
-    // because it is slower than the sequential schedule: 1.04 against 0.955 ms per iteration at 256 cameras x 62.5k points.  One
-    // resident workgroup per 64 x 64 tile is 325 of the chip's 512 workgroup slots from the first panel on; the elimination runs on
-    // the 187 left (a hit loop alone on its SIMDs is as fast as two, so that is ~73 % of its rate, and the holes retiring tiles
-    // leave only fit a Schur workgroup since the tiles ask for as much LDS), its stages come at 160 / 250 / 290 ... us instead of
-    // 60 / 100 / ..., and the chain of tile columns, which needs ~18 us per column alone, needs ~27 beside the hit loops: the
-    // factorisation ends ~250 us behind the last stage (HISTORY.md, round 4).  What an overlap above 64 cameras needs is a
-    // factorisation with a small resident footprint (left-looking, a tile column at a time).  One process / one GPU only, every
-    // tile resident at once, at most RSBA_MAX_STAGES camera groups to gate on.
-#ifdef RSBA_EXPERIMENTAL
-    const char* et = getenv("RSBA_PIPELINE_TILES");
-#else
-    const char* et = nullptr;   // (-DRSBA_EXPERIMENTAL builds only: slower than the sequential step, and it hung one run of the suite)
-#endif
-    const char* ec = getenv("RSBA_CHOL_TILES");
-    const int m = MultiCholPadded(s->nc), nrt = (m + 1 + 63) / 64, ntiles = nrt * (nrt + 1) / 2;
-    if (mg || !(et && atoi(et) == 1) || (ec && atoi(ec) == 0) || ntiles > 2 * prop.multiProcessorCount || (s->C + RSBA_TG - 1) / RSBA_TG > RSBA_MAX_STAGES) return false;
-  }
+  // More than 64 cameras: the sequential schedule.  (A persistent tiled factorisation gated beside the Schur kernel was slower
+  // than it: one resident workgroup per 64 x 64 tile leaves the elimination too few workgroup slots — HISTORY.md, round 4.)
+  if (s->nc > RSBA_CHOL_MAXN) return false;
   const int cus = prop.multiProcessorCount, words = (cus + 31) / 32;
   std::vector<uint32_t> mask(words, 0xffffffffu);
   // A side stream with a hardware queue of its own (hipExtStreamCreateWithCUMask, all CUs) that passes `probe`; a few attempts:
@@ -1085,7 +1057,6 @@ static bool SetupPipeline(rsba_solver* s) {
   bool ok = side_stream(&s->sB, [&](hipStream_t c) { return s->pipe_serial || StreamsRunConcurrently(c, s->stream); });
   if (!ok && getenv("RSBA_DEBUG")) fprintf(stderr, "rsba: the side stream does not run beside the main stream, solve not pipelined\n");
   ok = ok && hipMalloc((void**)&s->chol_waited, 2 * sizeof(long long)) == hipSuccess && hipMemset(s->chol_waited, 0, 2 * sizeof(long long)) == hipSuccess;
-  if (ok && s->nc > RSBA_CHOL_MAXN) ok = hipEventCreateWithFlags(&s->ev_tiles, hipEventDisableTiming) == hipSuccess;
   if (ok && mg) {
     // The communication stream carries kernels that WAIT (k_wait_stage, for the Schur kernel on the main stream) and kernels
     // others wait for (k_set_flag, for the factorisation on sB): it must run beside both, probed in every direction that
@@ -1219,8 +1190,7 @@ static int UploadPoints(rsba_solver* s) {
       (rc = DevAlloc(&s->scale_p, 3 * (size_t)P)) || (rc = DevAlloc(&s->red, s->L.size())) || (rc = DevAlloc(&s->A, (size_t)(MultiCholPadded(s->nc) + 2) * MultiCholPadded(s->nc) + (size_t)6 * RSBA_TG * s->nc /* the border's rows of L behind a smaller leading factor, ba_cholesky_border.hpp */)) || (rc = DevAlloc(&s->W, (s->nc > RSBA_CHOL_MAXN || s->tiles_small) ? (size_t)(s->nc + 1) * s->nc : 1)) ||
       (rc = DevAlloc(&s->chol_ok, 3)) ||
       (rc = DevAlloc(&s->S_copy, (size_t)s->nc * s->nc)) || (rc = DevAlloc(&s->rhs_copy, s->nc)) || (rc = DevAlloc(&s->dcam, s->nc)) ||
-      (rc = DevAlloc(&s->small_red, 8)) || (rc = DevAlloc(&s->gmax, 2)) || (rc = DevAlloc(&s->res, RES_SIZE)) || (rc = DevAlloc(&s->dec, 4)) ||
-      (rc = DevAlloc(&s->cam_backup, (size_t)s->C * (6 + CC_STRIDE))))
+      (rc = DevAlloc(&s->small_red, 8)) || (rc = DevAlloc(&s->gmax, 2)) || (rc = DevAlloc(&s->res, RES_SIZE)) || (rc = DevAlloc(&s->dec, 4)))
     return rc;
   if (s->comm) {
     // triangular all-reduce payload: by default where bytes bound the collective (more than 64 cameras), RSBA_TRI_PAYLOAD=1 / 0 forces / disables it
@@ -1270,14 +1240,8 @@ static int UploadPoints(rsba_solver* s) {
   {
     // several workgroups for the reduced system: 32 to 64 cameras (padded to whole 32-wide panels), full symmetric S
     // (the diagonal-chain kernel, one workgroup for the diagonal + five for the rows below by default: 0.469 against 0.474 ms per
-    //  LM iteration with three row workgroups — fewer blocks per workgroup, more K slices per block; up to 8; the round-robin kernel
-    //  RSBA_CHOL_DIAG=0: four, up to RSBA_MC_MAXG)
+    //  LM iteration with three row workgroups — fewer blocks per workgroup, more K slices per block; up to 8)
     const char* e = getenv("RSBA_CHOL_WGS");
-#ifdef RSBA_EXPERIMENTAL
-    const bool want_diag = !(getenv("RSBA_CHOL_DIAG") && atoi(getenv("RSBA_CHOL_DIAG")) == 0);
-#else
-    const bool want_diag = true;   // (the round-robin kernel, RSBA_CHOL_DIAG=0, exists in -DRSBA_EXPERIMENTAL builds only)
-#endif
     // (the last camera group as a border — three camera groups or more, the tiled Schur kernel, one rank; RSBA_BORDER=0: every camera group
     //  through the diagonal-chain kernel — leaves that kernel nine panels instead of twelve at 64 cameras: ONE diagonal and THREE row
     //  workgroups then (round 6; six alternating runs on one box: 0.3452 - 0.3470 ms per step against 0.3489 - 0.3513 with five row
@@ -1285,22 +1249,17 @@ static int UploadPoints(rsba_solver* s) {
     //  the factorisation holds a CU's whole LDS for the length of the step, and the row workgroups' traffic shares the Schur kernel's paths))
     static const bool border_env = !(getenv("RSBA_BORDER") && atoi(getenv("RSBA_BORDER")) == 0);
     const int ngroups_c = (C + RSBA_TG - 1) / RSBA_TG;
-    const bool border_ok = border_env && want_diag && !s->comm && ngroups_c >= 3;
-    const int want = e ? atoi(e) : (want_diag ? (border_ok ? 3 : 6) : 4);
+    const bool border_ok = border_env && !s->comm && ngroups_c >= 3;
+    const int want = e ? atoi(e) : (border_ok ? 3 : 6);
     if (want > 1 && s->opt.schur_impl != 0 && s->nc >= 6 * RSBA_PB && s->nc <= RSBA_CHOL_MAXN) {
-      s->chol_wgs = std::min(want, want_diag ? 8 : RSBA_MC_MAXG);
+      s->chol_wgs = std::min(want, 8);
       if ((rc = DevAlloc(&s->mc_flags, 64))) return rc;
       HIPCHK(hipMemset(s->mc_flags, 0, 64 * sizeof(int)));
-      // RSBA_CHOL_DIAG=0: round-robin kernel.  A row workgroup of the diagonal-chain kernel keeps the look-ahead sums of at
-      // most four blocks
+      // a row workgroup of the diagonal-chain kernel keeps the look-ahead sums of at most four blocks
       const int np_d = MultiCholPadded(s->nc) / RSBA_PB;
       const int np_rule = border_ok ? 3 * (ngroups_c - 1) : np_d;   // panels of the system the diagonal-chain kernel factors (the border's workgroup has the rest)
-      s->chol_diag = want_diag && s->chol_wgs >= 2 && (np_rule - 2 + s->chol_wgs - 2) / (s->chol_wgs - 1) <= 4;
-#ifdef RSBA_EXPERIMENTAL
-      if (!s->chol_diag) s->chol_wgs = std::min(s->chol_wgs, RSBA_MC_MAXG);
-#else
+      s->chol_diag = s->chol_wgs >= 2 && (np_rule - 2 + s->chol_wgs - 2) / (s->chol_wgs - 1) <= 4;
       if (!s->chol_diag) s->chol_wgs = 1;   // (more blocks per row workgroup than the diagonal-chain kernel keeps sums for: one workgroup)
-#endif
       if (s->chol_diag && (rc = DevAlloc(&s->mc_dg, (size_t)2 * (np_d + 1) * 1024))) return rc;   // look-ahead sums | blocks as handed over
       {
         // the last camera group as a border: three camera groups or more, the tiled Schur kernel, one rank
@@ -1312,10 +1271,6 @@ static int UploadPoints(rsba_solver* s) {
                                  (int)(DiagCholLdsDoubles(s->nc) * sizeof(double))));
       // (RSBA_CHOL_WGS allows eight workgroups, and the border's is one more: nine rows of [16][8] stamps)
       if (getenv("RSBA_MC_TRACE")) { if ((rc = DevAlloc(&s->mc_trace, kMcTraceWords))) return rc; HIPCHK(hipMemset(s->mc_trace, 0, kMcTraceWords * sizeof(long long))); }
-#ifdef RSBA_EXPERIMENTAL
-      HIPCHK(hipFuncSetAttribute((const void*)k_reduced_system_solve_multi, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)(MultiCholLdsDoubles(s->nc) * sizeof(double))));
-#endif
     }
     // more than 64 cameras: one resident workgroup per 64 x 64 tile, if they all fit on the chip at once
     const char* e2 = getenv("RSBA_CHOL_TILES");
@@ -1362,7 +1317,6 @@ static int UploadPoints(rsba_solver* s) {
       }
     }
   }
-  if (s->pipelined && s->nc > RSBA_CHOL_MAXN && s->tc_tiles == 0) s->pipelined = false;   // (the persistent tiles did not fit after all)
   if (s->opt.schur_impl != 0) {
     rc = s->tiled.Build(C, P, ptr, cam, u, v, sl_q, s->pipelined, s->border_cols > 0);
     if (rc != RSBA_OK) return rc;
@@ -1510,16 +1464,10 @@ static SchurArgs MakeSchurArgs(TiledSchur& ts, rsba_solver* s, int tag) {
   return a;
 }
 
-void TiledSchur::LaunchTiles(rsba_solver* s, const IterParams& ip, KernelTimer& T, hipStream_t st, int tag, bool first_staged, bool ahead, long long* ahead_trace) {
+void TiledSchur::LaunchTiles(rsba_solver* s, const IterParams& ip, KernelTimer& T, hipStream_t st, int tag, bool first_staged) {
   RoctxRange rr("K2+K3 camera-side rows + Schur elimination into the reduced system");
   SchurArgs a = MakeSchurArgs(*this, s, tag);
   if (first_staged) { a.segs_ordered = segs_ordered_first; a.all_self = 1; }
-  if (ahead) {
-    // the NEXT step's elimination, queued before this step's outcome is known: state by the device's decision (SchurArgs::dec)
-    const int c = 1 - s->cur;
-    a.dec = s->dec; a.camc_alt = s->camc[c]; a.sq_cm_alt = sq_cm2[c];
-    a.trace = ahead_trace; a.wg_trace = nullptr;
-  }
   const bool sparse = a.hits != nullptr;   // (resident workgroups: as many as the chip holds, each drawing tickets until the list is through)
   const int grid = SchurGrid(nblocks, sparse);
   a.total = nblocks; a.ticket_base = ticket_base; ticket_base += (unsigned)(nblocks + ((sparse || RSBA_RESIDENT != 0) ? grid : 0));
@@ -1611,25 +1559,6 @@ static int WaitResult(rsba_solver* s, hipStream_t posting) {
 
 // One "solve at radius": linearise at x, reduce, factor, back-substitute, evaluate the candidate.
 // On return res_host holds the RES_* block (host has synchronised).
-// A factorisation + Schur kernel launched ahead that nobody will consume (the host stopped, or asks for something else): they
-// run to their end on the device's decision — the step tag they used is skipped.
-static int DrainAhead(rsba_solver* s) {
-  if (!s->ahead_inflight) return RSBA_OK;
-  HIPCHK(hipStreamSynchronize(s->stream));
-  if (s->sB) HIPCHK(hipStreamSynchronize(s->sB));
-  ++s->step_tag;
-  s->ahead_inflight = false;
-  if (s->ahead_state != s->ahead_x && s->cur == s->ahead_x) {
-    // the device had accepted the step, the host has not (it stopped on a tolerance or the time limit, which the device does not
-    // test): the factorisation launched ahead has written its candidate where x is — x's cameras and constants back (AheadSel)
-    const size_t nc6 = 6 * (size_t)s->C, ncc = (size_t)s->C * CC_STRIDE;
-    HIPCHK(hipMemcpyAsync(s->cam[s->ahead_x], s->cam_backup, nc6 * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
-    HIPCHK(hipMemcpyAsync(s->camc[s->ahead_x], s->cam_backup + nc6, ncc * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-  }
-  return RSBA_OK;
-}
-
 static int PointsStep(rsba_solver* s, double radius, bool first, bool keep_system_copy) {
   const int C = s->C, P = s->P, x = s->cur, c = 1 - s->cur;
   hipStream_t st = s->stream;
@@ -1651,47 +1580,7 @@ static int PointsStep(rsba_solver* s, double radius, bool first, bool keep_syste
     T.End(st);
   }
   DebugSync(st, "k_camera_constants");
-  // (above 64 cameras the pipelined schedule needs the resident tiles building their own entries of the system, the chain
-  //  back-substitution, and — on the first step of a run — the work list that runs every self tile first)
-  static const int fuse_env = getenv("RSBA_SYS_FUSED") ? atoi(getenv("RSBA_SYS_FUSED")) : 1;
-  static const int bsm = getenv("RSBA_BACKSUB_MULTI") ? atoi(getenv("RSBA_BACKSUB_MULTI")) : 2;
-  static const bool first_staged_env = !(getenv("RSBA_FIRST_STAGED") && atoi(getenv("RSBA_FIRST_STAGED")) == 0);
-  const bool tiles_ok = s->nc <= RSBA_CHOL_MAXN ||
-                        (s->tc_tiles > 0 && fuse_env != 0 && bsm >= 2 && s->tc_xs != nullptr && s->ev_tiles != nullptr &&
-                         (!first || (first_staged_env && s->tiled.has_first_order)));
-  const bool pipe = s->pipelined && s->opt.schur_impl != 0 && !keep_system_copy && tiles_ok;
-  const bool pipe_tiles = pipe && s->nc > RSBA_CHOL_MAXN;
-  // the persistent tiled factorisation and the chain back-substitution behind it (more than 64 cameras), on stream sx
-  auto launch_tile_solve = [&](hipStream_t sx, const TileGate& gate) {
-    const int n = s->nc;
-    TileSysSource src;
-    src.fused = 1; src.red = s->red; src.L = s->L; src.scale_c = s->scale_c; src.ip = ip; src.sym_full = s->opt.schur_impl != 0 ? 1 : 0;
-    // (gated: a tile asks for as much LDS as a Schur workgroup — 81 KB instead of its 76 — so that the hole a retiring tile leaves is
-    //  one a Schur workgroup fits into: LDS is allocated contiguously, and behind 76 KB tiles the elimination ran on the 187 slots
-    //  the tiles had left it from the first block to the last, 710 us instead of 340)
-    const size_t tile_lds = gate.ready != nullptr ? std::max(TileCholLdsDoubles() * sizeof(double), (size_t)RSBA_SCHUR_LDS_BYTES + 64) : TileCholLdsDoubles() * sizeof(double);
-    T.Begin("k_chol_tiles_persistent", sx);
-    k_chol_tiles_persistent<<<s->tc_tiles, 256, tile_lds, sx>>>(
-        n, s->W, s->A, s->chol_ok, TileCholFlags{s->tc_flags, s->tc_flags + s->tc_np, s->tc_flags + (size_t)s->tc_np * (s->tc_nrt + 1), s->tc_nrt, s->tc_hand, s->tc_launches++ & 1, s->test_stall == 3 ? 1 : 0, s->tc_map, s->mc_trace},
-        s->step_tag, s->res, src, gate);
-    T.End(sx);
-    const int nblk = s->tc_np, H = (nblk + 2) / 3;
-    int* fl = s->tc_flags + (size_t)s->tc_np * (s->tc_nrt + 1);   // [error | xdone ...]
-    T.Begin("k_backsub_chain", sx);
-    k_backsub_chain<<<1 + H, 256, 0, sx>>>(
-        C, s->red, s->L, s->A, s->tc_xs, s->scale_c, s->cam[x], s->cam[c], s->intr, s->camc[c], s->dcam, s->gmax, s->res, s->chol_ok, s->cam_free,
-        s->tc_ys, fl, s->tc_bs_launches++ & 1);
-    T.End(sx);
-  };
-  // the factorisation + Schur kernel the previous step launched ahead (launch_ahead, below): they are this step's if they are what
-  // it would launch — the state and radius of the device's decision are the host's — else they run out unused
-  bool ahead_hit = false;
-  if (s->ahead_inflight) {
-    ahead_hit = pipe && !pipe_tiles && !first && !s->pipelined_mg && !s->pipe_serial && s->ahead_state == x && s->ahead_radius == radius &&
-                s->ahead_tag == s->step_tag + 1;
-    if (!ahead_hit) { const int rcd = DrainAhead(s); if (rcd != RSBA_OK) return rcd; }
-    s->ahead_inflight = false;
-  }
+  const bool pipe = s->pipelined && s->opt.schur_impl != 0 && !keep_system_copy;
   ++s->step_tag;
   if (s->trace_ring) {
     if (s->trace_ring_first_tag == 0) s->trace_ring_first_tag = s->step_tag;
@@ -1718,59 +1607,6 @@ static int PointsStep(rsba_solver* s, double radius, bool first, bool keep_syste
   } else if (!pipe) {
     int rc = s->tiled.Launch(s, ip, T);
     if (rc != RSBA_OK) return rc;
-  } else if (pipe_tiles) {
-    // Pipelined above 64 cameras (round 4).  The persistent tiled factorisation goes out FIRST on the side stream — one resident
-    // workgroup per 64 x 64 tile, 76 KB of LDS and one wavefront per SIMD each, so that a Schur workgroup (81 KB, one wavefront
-    // per SIMD) fits beside every one of them — and every tile sleeps until the Schur kernel, launched behind it on the main
-    // stream with the stage-ordered work list, has published the camera group(s) of its columns (TileGate).  A sleeping tile
-    // issues nothing; a hit loop alone on its SIMDs runs at 98 % of what two of them reach together (tools/probes/hit_probe.hip),
-    // so the elimination loses little, and the factorisation — a latency chain of ~18 us per tile column — ends a few tile
-    // columns behind the last stage instead of starting there.  The chain back-substitution follows it on the side stream; the
-    // point back-substitution waits for both behind a stream event.
-    TiledSchur& ts = s->tiled;
-    const int tag = s->step_tag;
-    LaunchPointSide(ts, s, ip, T, st);
-    if (s->trace) s->host_t[1] = std::chrono::steady_clock::now();
-    RoctxRange rr_k4("K4 reduced camera system: tiled Cholesky + solve (launched ahead, gated on the Schur stages)");
-    const bool first_staged = ip.first;   // (tiles_ok: the first-step work list exists)
-    int* resident_word = (ip.first || s->pipe_check_resident) ? reinterpret_cast<int*>(s->res_host + RES_SIZE) : nullptr;
-    s->pipe_check_resident = false;
-    TileGate gate;
-    gate.ready = ts.ready; gate.tag = (s->test_stall == 1 || (s->test_stall == 4 && s->pipe_stalls == 0)) ? tag + 1 : tag; gate.cols = 6 * RSBA_TG;
-    gate.all_diag = first_staged ? ts.ready + RSBA_READY_ALLDIAG : nullptr;
-    gate.started_cnt = ts.ready + RSBA_READY_STARTED; gate.started_host = resident_word; gate.started_need = s->tc_tiles;
-    gate.waited = T.all_kernels() ? s->chol_waited : nullptr;
-    if (s->pipe_serial) {
-      // RSBA_PIPELINE=2: the same kernels one after the other (counter collection)
-      ts.LaunchTiles(s, ip, T, st, tag, first_staged);
-      HIPCHK(hipEventRecord(s->ev_serial[0], st));
-      HIPCHK(hipStreamWaitEvent(s->sB, s->ev_serial[0], 0));
-      gate.started_host = nullptr;
-      launch_tile_solve(s->sB, gate);
-    } else {
-      // The tiles go out BEHIND the point side (a stream event, no host wait).  Launched beside it — as the 64-camera factorisation is —
-      // the first step of every run but a solver's first deadlocked: with all 325 tiles resident and asleep, the point pass on the
-      // main stream did not complete (and the Schur kernel queued behind it never started) until the tiles' waits ran out, 0.5 s
-      // later; in a solver's very first step the side stream's first launch starts ~150 us late, i.e. behind the point pass anyway.
-      // (Measured with device stamps: first Schur block 500 001 us after tile (0, 0)'s start; with the event: no stall in 3 x 5 runs.)
-      HIPCHK(hipEventRecord(s->ev_tiles, st));
-      HIPCHK(hipStreamWaitEvent(s->sB, s->ev_tiles, 0));
-      launch_tile_solve(s->sB, gate);
-      if (resident_word != nullptr) {
-        volatile int* w = resident_word;
-        const auto t_res = std::chrono::steady_clock::now();
-        while (*w != gate.tag && std::chrono::steady_clock::now() - t_res < std::chrono::milliseconds(20)) __builtin_ia32_pause();
-      }
-      hp(1);
-      ts.LaunchTiles(s, ip, T, st, tag, first_staged);
-      hp(2);
-    }
-    HIPCHK(hipEventRecord(s->ev_tiles, s->sB));
-    HIPCHK(hipStreamWaitEvent(st, s->ev_tiles, 0));
-    rr_k4.End();
-  } else if (ahead_hit) {
-    // launched by the previous step (launch_ahead): damping kernel, factorisation (side stream) and Schur kernel are queued or running
-    hp(1); hp(2);
   } else {
     // Pipelined.  Camera group g's columns of the reduced system are complete once the pair tiles (g, g' >= g) are
     // reduced, and the left-looking Cholesky needs nothing else for its panels 3g..3g+2.  The Cholesky kernel goes out
@@ -1821,15 +1657,8 @@ static int PointsStep(rsba_solver* s, double radius, bool first, bool keep_syste
         if (mg) k_reduced_system_solve_diag<true><<<s->chol_wgs, 512, DiagCholLdsDoubles(n) * sizeof(double), s->sB>>>(
             C, s->red, s->L, s->A, s->scale_c, s->cam[x], s->cam[c], s->intr, s->camc[c], s->dcam, s->gmax, s->res, ip, s->chol_ok, sg, df, tag, s->mc_trace);
         else k_reduced_system_solve_diag<false><<<wgs, 512, lds_d, s->sB>>>(
-            C, s->red, s->L, s->A, s->scale_c, s->cam[x], s->cam[c], s->intr, s->camc[c], s->dcam, s->gmax, s->res, ip, s->chol_ok, sg, df, tag, s->mc_trace, AheadSel{}, s->border_cols);
+            C, s->red, s->L, s->A, s->scale_c, s->cam[x], s->cam[c], s->intr, s->camc[c], s->dcam, s->gmax, s->res, ip, s->chol_ok, sg, df, tag, s->mc_trace, s->border_cols);
       }
-#ifdef RSBA_EXPERIMENTAL
-      else if (s->chol_wgs > 1 && !mg)   // (the round-robin kernel has no transposed source: multi-GPU, it is the one-workgroup kernel)
-        k_reduced_system_solve_multi<<<s->chol_wgs, 512, MultiCholLdsDoubles(n) * sizeof(double), s->sB>>>(
-            C, s->red, s->L, s->A, s->scale_c, s->cam[x], s->cam[c], s->intr, s->camc[c], s->dcam, s->gmax, s->res, ip, s->chol_ok,
-            StageGate{gate_ready, gate_tag, 6 * RSBA_TG, ts.ready + RSBA_READY_SOLVED, T.all_kernels() ? s->chol_waited : nullptr, s->trace, gate_budget, ts.ready + RSBA_READY_STARTED, resident_word, s->chol_wgs},
-            MultiCholFlags{s->mc_flags, s->mc_flags + 16, s->mc_flags + 32, s->mc_flags + 48}, tag, s->mc_trace);
-#endif
       else
       k_reduced_system_solve<<<1, 512, lds_c, s->sB>>>(C, s->red, s->L, s->A, nullptr, nullptr, s->scale_c, s->cam[x], s->cam[c], s->intr,
                                                        s->camc[c], s->dcam, s->gmax, s->res, ip, mg ? 2 : 1,
@@ -1916,14 +1745,7 @@ static int PointsStep(rsba_solver* s, double radius, bool first, bool keep_syste
                                            (s->border_cols > 0 ? std::max(DiagCholLdsDoubles(s->border_cols), BorderLdsDoubles(s->nc)) : DiagCholLdsDoubles(s->nc)) * sizeof(double), st>>>(
           C, s->red, s->L, s->A, s->scale_c, s->cam[x], s->cam[c], s->intr, s->camc[c], s->dcam, s->gmax, s->res, ip, s->chol_ok,
           StageGate{nullptr, 0, 0, nullptr, nullptr, nullptr, 0}, DiagCholFlags{s->mc_flags, s->mc_flags + 16, s->mc_flags + 32, s->mc_flags + 48, s->mc_dg, s->mc_dg + (size_t)(MultiCholPadded(s->nc) / RSBA_PB + 1) * 1024},
-          s->step_tag, s->mc_trace, AheadSel{}, s->border_cols);
-#ifdef RSBA_EXPERIMENTAL
-    else if (s->chol_wgs > 1 && !keep_system_copy)
-      k_reduced_system_solve_multi<<<s->chol_wgs, 512, MultiCholLdsDoubles(s->nc) * sizeof(double), st>>>(
-          C, s->red, s->L, s->A, s->scale_c, s->cam[x], s->cam[c], s->intr, s->camc[c], s->dcam, s->gmax, s->res, ip, s->chol_ok,
-          StageGate{nullptr, 0, 0, nullptr, nullptr, nullptr, 0}, MultiCholFlags{s->mc_flags, s->mc_flags + 16, s->mc_flags + 32, s->mc_flags + 48},
-          s->step_tag, s->mc_trace);
-#endif
+          s->step_tag, s->mc_trace, s->border_cols);
     else
     k_reduced_system_solve<<<1, 512, lds_c, st>>>(C, s->red, s->L, s->A, keep_system_copy ? s->S_copy : nullptr,
                                                   keep_system_copy ? s->rhs_copy : nullptr, s->scale_c, s->cam[x], s->cam[c], s->intr,
@@ -1935,6 +1757,7 @@ static int PointsStep(rsba_solver* s, double radius, bool first, bool keep_syste
     const int n = s->nc;
     // the resident tiles build their entries of the system themselves (TileSysSource); k_sys_build only where its output is
     // wanted for itself (the copies of the system a caller asked for) or the multi-launch factorisation reads it
+    static const int fuse_env = getenv("RSBA_SYS_FUSED") ? atoi(getenv("RSBA_SYS_FUSED")) : 1;
     const bool fused = s->tc_tiles > 0 && !keep_system_copy && fuse_env != 0;
     if (!fused) {
       T.Begin("k_sys_build", st);
@@ -1948,7 +1771,7 @@ static int PointsStep(rsba_solver* s, double radius, bool first, bool keep_syste
       T.Begin("k_chol_tiles_persistent", st);
       k_chol_tiles_persistent<<<s->tc_tiles, 256, TileCholLdsDoubles() * sizeof(double), st>>>(
           n, s->W, s->A, s->chol_ok, TileCholFlags{s->tc_flags, s->tc_flags + s->tc_np, s->tc_flags + (size_t)s->tc_np * (s->tc_nrt + 1), s->tc_nrt, s->tc_hand, s->tc_launches++ & 1, s->test_stall == 3 ? 1 : 0, s->tc_map, s->mc_trace},
-          s->step_tag, s->res, src, TileGate{});
+          s->step_tag, s->res, src);
       T.End(st);
     } else {
     const size_t lds_s = CholStepLdsDoubles() * sizeof(double);
@@ -1962,6 +1785,7 @@ static int PointsStep(rsba_solver* s, double radius, bool first, bool keep_syste
     }
     // RSBA_BACKSUB_MULTI: 2 (default) the chain in one workgroup with helpers for the far strips (k_backsub_chain), 1 the chain
     // passed from owner to owner (k_backsub_multi, round 2), 0 one workgroup for everything (k_chol_finish)
+    static const int bsm = getenv("RSBA_BACKSUB_MULTI") ? atoi(getenv("RSBA_BACKSUB_MULTI")) : 2;
     if (s->tc_tiles > 0 && bsm >= 2 && s->tc_xs != nullptr) {
       const int nblk = s->tc_np, H = (nblk + 2) / 3;
       int* fl = s->tc_flags + (size_t)s->tc_np * (s->tc_nrt + 1);   // [error | xdone ...]
@@ -2011,7 +1835,7 @@ static int PointsStep(rsba_solver* s, double radius, bool first, bool keep_syste
     const FusedLin fl0 = fused ? FusedLin{s->tiled.lin2[x], s->tiled.lin2[c], s->tiled.cm_pos, s->tiled.sq_cm2[c], s->trace} : FusedLin{nullptr, nullptr, nullptr, nullptr, s->trace};
     FusedLin fl0b = fl0; fl0b.bs_wg = s->bs_wg;
     const FusedLin& fl = fl0b;
-    const int* solve_done = pipe && !pipe_tiles ? s->tiled.ready + RSBA_READY_SOLVED : nullptr;   // (tile pipeline: a stream event orders the back-substitution behind the solve)
+    const int* solve_done = pipe ? s->tiled.ready + RSBA_READY_SOLVED : nullptr;
     const int solve_tag = (s->test_stall && (s->test_stall != 4 || s->pipe_stalls == 0)) ? s->step_tag + s->test_stall * s->test_stall : s->step_tag;
     long long* waited = pipe && T.all_kernels() ? s->chol_waited + 1 : nullptr;
 #define RSBA_BACKSUB_ARGS C, P, s->sliced(), s->camc[x], s->camc[c], s->dcam, s->pts[x], s->pts[c], s->scale_p, s->block_part, ip, fin_cnt, s->small_red, \
@@ -2084,46 +1908,10 @@ static int PointsStep(rsba_solver* s, double radius, bool first, bool keep_syste
     T.End(st);
     ts.pt_valid = false;   // (until the decision is in: below)
   };
-  // Launch-ahead.  Between the result of one step and the first Schur workgroup of the next lay the host: the result's trip over
-  // PCIe, the decision, two launches — 23 us of a 390 us step at 64 cameras, the chip idle but for the damping kernel.  The device
-  // takes the decision itself (DecideStep, the host's arithmetic), so the NEXT step's factorisation (side stream: resident and asleep
-  // until the decision is in, AheadSel) and Schur kernel (main stream, behind the damping kernel; state by SchurArgs::dec) are queued
-  // right here, before this step's result exists.  The host takes the same decision from the same numbers and, in the next
-  // PointsStep, finds its launches done (ahead_hit) — or stops (a tolerance, the time limit) and lets them run out (DrainAhead); the
-  // step that reaches the iteration limit launches nothing ahead (MinimizeLoop: ahead_ok).
-  // OPT-IN (RSBA_LAUNCH_AHEAD=1).  Measured at 64 cameras (round 4, device stamps, 99 steps): result posted -> first Schur workgroup
-  // 13.1 us without, 12.1 us with — the host's share was already hidden behind the damping kernel (7.3 us) it queues on the device's
-  // decision, what is left is that kernel and the dispatch behind it; 0.3885 vs 0.3890 ms per step, inside the run-to-run spread.
-  // Round 5, with the border factorisation: 14.2 -> 13.2 us, 0.3523 - 0.3531 against 0.3516 - 0.3529 ms per step.
-  // Against that microsecond per step stands a whole unused elimination (0.26 ms) at the end of every run a tolerance ends.
-#ifdef RSBA_EXPERIMENTAL
-  static const bool ahead_env = getenv("RSBA_LAUNCH_AHEAD") && atoi(getenv("RSBA_LAUNCH_AHEAD")) != 0;
-#else
-  static const bool ahead_env = false;   // (-DRSBA_EXPERIMENTAL builds only: worth 1 us a step, costs an unused elimination at the end of a run)
-#endif
-  auto launch_ahead = [&]() {
-    TiledSchur& ts = s->tiled;
-    const int n = s->nc, atag = s->step_tag + 1;
-    IterParams ipn = ip; ipn.first = 0;
-    long long* tr = s->trace_ring ? s->trace_base + 64 * (size_t)(atag % s->trace_ring) : nullptr;
-    const StageGate sg{ts.ready, atag, 6 * RSBA_TG, ts.ready + RSBA_READY_SOLVED, nullptr, tr, 0, ts.ready + RSBA_READY_STARTED, nullptr, s->chol_wgs + (s->border_cols > 0 ? 1 : 0), nullptr, 0};
-    const DiagCholFlags df{s->mc_flags, s->mc_flags + 16, s->mc_flags + 32, s->mc_flags + 48, s->mc_dg, s->mc_dg + (size_t)(MultiCholPadded(s->nc) / RSBA_PB + 1) * 1024};
-    AheadSel ah; ah.dec = s->dec; ah.seq = s->res_seq + 1.0; ah.camc_x = s->camc[x]; ah.cam_backup = s->cam_backup; ah.camc_backup = s->cam_backup + 6 * (size_t)C;
-    T.Begin("k_reduced_system_solve", s->sB);
-    const int wgs = s->chol_wgs + (s->border_cols > 0 ? 1 : 0);   // (with the border's workgroup: ba_cholesky_border.hpp)
-    const size_t lds_d = (s->border_cols > 0 ? std::max(DiagCholLdsDoubles(s->border_cols), BorderLdsDoubles(n)) : DiagCholLdsDoubles(n)) * sizeof(double);
-    k_reduced_system_solve_diag<false><<<wgs, 512, lds_d, s->sB>>>(
-        C, s->red, s->L, s->A, s->scale_c, s->cam[x], s->cam[c], s->intr, s->camc[c], s->dcam, s->gmax, s->res, ipn, s->chol_ok, sg, df, atag, s->mc_trace, ah, s->border_cols);
-    T.End(s->sB);
-    ts.LaunchTiles(s, ipn, T, st, atag, false, true, tr);
-    s->ahead_inflight = true; s->ahead_tag = atag; s->ahead_x = x;
-  };
-  if (s->dec_step && !comm_tail) {
-    queue_damping();
-    if (ahead_env && s->ahead_ok && pipe && !pipe_tiles && !s->pipelined_mg && !s->pipe_serial && s->chol_wgs > 1 && s->chol_diag && !keep_system_copy &&
-        !T.all_kernels() && !(s->trace && !s->trace_ring) && !s->wg_trace && !s->test_stall)
-      launch_ahead();
-  }
+  // The device takes the step's decision itself (DecideStep, the host's arithmetic), so the next step's damping kernel is queued
+  // right here, before this step's result has reached the host.  (Queueing the next step's factorisation and Schur kernel here
+  // too was measured worth ~1 us a step, against an unused elimination at the end of every run a tolerance ends: HISTORY.md.)
+  if (s->dec_step && !comm_tail) queue_damping();
   rr_k5.End();
   DebugSync(st, "k_backsub_candidate");
   if (comm_tail) {
@@ -2162,14 +1950,13 @@ static int PointsStep(rsba_solver* s, double radius, bool first, bool keep_syste
     TiledSchur& ts = s->tiled;
     const double* r = s->res_host;
     ts.pt_valid = r[RES_DEC_GO] != 0.0; ts.pt_state = r[RES_DEC_ACCEPT] != 0.0 ? c : x; ts.pt_radius = r[RES_DEC_RADIUS]; ts.scal_blocks = ts.grid_pp;
-    s->ahead_state = ts.pt_state; s->ahead_radius = ts.pt_radius;
     s->dec_step = false;
   }
   if (pipe && T.all_kernels()) {
     // the Cholesky's event span includes the time it slept on the ready flags: record that separately
     long long w[2] = {0, 0};
     HIPCHK(hipMemcpy(w, s->chol_waited, sizeof(w), hipMemcpyDeviceToHost));
-    T.Add(pipe_tiles ? "k_chol_tiles_persistent:waiting" : "k_reduced_system_solve:waiting", (w[0] - s->chol_waited_seen) * 1e-5);
+    T.Add("k_reduced_system_solve:waiting", (w[0] - s->chol_waited_seen) * 1e-5);
     T.Add("k_backsub_candidate:waiting", (w[1] - s->backsub_waited_seen) * 1e-5);
     s->chol_waited_seen = w[0]; s->backsub_waited_seen = w[1];
   }
@@ -2297,7 +2084,6 @@ static int PointsGradient(rsba_solver* s, double radius) {
   ip.pt_const = s->pt_const;
   KernelTimer& T = s->timer;
   T.NextStep();
-  { const int rcd = DrainAhead(s); if (rcd != RSBA_OK) return rcd; }
   if (s->opt.schur_impl == 0) {
     HIPCHK(hipMemsetAsync(s->red, 0, s->L.size() * sizeof(double), st));
     const bool stage = (size_t)C * (RSBA_ACC_PER_CAM + RSBA_CC_LDS) * sizeof(double) <= 96 * 1024;
@@ -2409,8 +2195,6 @@ static int MinimizeLoop(rsba_solver* s, rsba_summary* sum, StepFn step, AcceptFn
       if (radius < o.min_trust_region_radius) return finish(RSBA_CONVERGENCE, RSBA_STOP_MIN_RADIUS);
     }
     s->lm_decrease_factor = decrease_factor;
-    // (another step may follow this one unless it reaches the iteration limit: PointsStep may launch its head ahead)
-    s->ahead_ok = (first ? 1 : s->iters.back().iteration + 1) < o.max_num_iterations;
     if (s->share_clock) s->time_up = (o.rank == 0 && clock_says()) ? 1.0 : 0.0;
     int rc = step(radius, first);
     if (rc != RSBA_OK) return rc;
@@ -2778,7 +2562,6 @@ int rsba_solver_run(rsba_solver* s, rsba_summary* sum_out) {
     double cur_radius = s->opt.initial_trust_region_radius;
     rc = rsba::MinimizeLoop(s, &sum, [&](double radius, bool first) { cur_radius = radius; return rsba::PointsStep(s, radius, first, false); },
                             [&]() { s->cur = 1 - s->cur; }, [&]() { return rsba::PointsGradient(s, cur_radius); });
-    if (rc == RSBA_OK) rc = rsba::DrainAhead(s);   // (a run that a tolerance ended: the step launched ahead runs out)
     sum.minimizer_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (getenv("RSBA_RUNPROF")) {
       auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };

@@ -48,15 +48,6 @@ SETTINGS = [
 ]
 
 
-# Experimental paths — the step launched ahead on the device's decision (RSBA_LAUNCH_AHEAD), the tiled factorisation gated beside the
-# Schur kernel above 64 cameras (RSBA_PIPELINE_TILES), the round-robin factorisation (RSBA_CHOL_DIAG=0) — exist only in libraries built
-# with -DRSBA_EXPERIMENTAL (tools/build_variant.sh exp -DRSBA_EXPERIMENTAL; RSBA_LIB points the tests at such a build):
-# RSBA_TEST_EXPERIMENTAL=1 adds their settings.
-if os.environ.get("RSBA_TEST_EXPERIMENTAL") == "1":
-    SETTINGS += [({"RSBA_PIPELINE_TILES": "1"}, ["c70_huber", "c130", "c240"]), ({"RSBA_CHOL_DIAG": "0"}, ["c40", "c64_huber"]),
-                 ({"RSBA_LAUNCH_AHEAD": "1"}, ["c40", "c64_huber", "c8_dense"])]
-
-
 @pytest.mark.parametrize("env,cases", SETTINGS, ids=[" ".join("%s=%s" % kv for kv in e.items()) or "defaults" for e, _ in SETTINGS])
 def test_switch_selects_a_path_that_matches_the_oracle(env, cases):
     child_env = dict(os.environ)
@@ -73,28 +64,6 @@ def test_switch_selects_a_path_that_matches_the_oracle(env, cases):
     assert "stalled" not in out.stderr, out.stderr[-2000:]
 
 
-@pytest.mark.skipif(os.environ.get("RSBA_TEST_EXPERIMENTAL") != "1", reason="launch-ahead exists in -DRSBA_EXPERIMENTAL builds only")
-def test_steps_launched_ahead_add_the_same_bits(tmp_path):
-    """Up to 64 cameras on one GPU the NEXT step's factorisation and Schur kernel can be queued on the device's decision before the
-    host has the step's result (launch_ahead in PointsStep, RSBA_LAUNCH_AHEAD=1; default: the host launches them once it has decided).
-    The same kernels on the same state either way: whole solves — accepted and rejected steps, runs a tolerance ends with a
-    step launched ahead still queued, runs the iteration limit ends — agree bit for bit, and so does a second run of the same
-    solver (the worker's reproducibility check) behind a step that ran out unused."""
-    cases = ["c40", "c64_huber", "c8_dense", "c33_long", "c64_dense_huber"]
-    files = []
-    for ahead in ("0", "1"):
-        env = dict(os.environ, RSBA_LAUNCH_AHEAD=ahead)
-        f = str(tmp_path / ("ahead%s.npz" % ahead))
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "switch_worker.py"), "--dump", f] + cases, env=env, capture_output=True, text=True, timeout=900)
-        assert out.returncode == 0, out.stderr[-2000:]
-        assert "stalled" not in out.stderr, out.stderr[-2000:]
-        files.append(f)
-    import numpy as np
-    a, b = np.load(files[0]), np.load(files[1])
-    for name in a.files:
-        assert np.array_equal(a[name], b[name]), name
-
-
 def test_thousands_of_pipelined_steps_add_the_same_bits_as_the_sequential_schedule(tmp_path):
     """The in-kernel hand-overs (stage flags between the Schur kernel and the factorisation beside it, the tiled factorisation's
     data-as-flag transfers above 64 cameras) are ordered by agent-scope stores awaited before a counter or flag moves, one release
@@ -105,9 +74,7 @@ def test_thousands_of_pipelined_steps_add_the_same_bits_as_the_sequential_schedu
     for pipe, steps in (("1", "3000"), ("0", "3000")):
         # (the same segments in both schedules — the sequential one cuts four per CU by default, the pipelined one eight — so that
         #  both add in the same order)
-        # (the pipelined run with every step's head launched ahead on the device's decision, RSBA_LAUNCH_AHEAD: 3000 hand-overs of
-        #  the decision block to a factorisation that is already resident)
-        env = dict(os.environ, RSBA_PIPELINE=pipe, SWITCH_FORCED_STEPS=steps, RSBA_SEG_PER_CU="8", RSBA_LAUNCH_AHEAD=pipe)
+        env = dict(os.environ, RSBA_PIPELINE=pipe, SWITCH_FORCED_STEPS=steps, RSBA_SEG_PER_CU="8")
         f = str(tmp_path / ("pipe%s.npz" % pipe))
         out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "switch_worker.py"), "--dump", f, "c64_long"], env=env, capture_output=True, text=True, timeout=900)
         assert out.returncode == 0, out.stderr[-2000:]

@@ -1,7 +1,8 @@
-# build/variants/librsba_<name>.so: the library with extra compiler flags (-D switches of an experiment), for tools/ab_variants.sh.
+# build/variants/librsba_<name>.so: the library with extra compiler flags (-D overrides of the #ifndef tuning constants in
+# realsensecalibration_amd/csrc, e.g. -DRSBA_CHUNK=...), for tools/ab_variants.sh; RSBA_LIB=<path> loads it in place of the packaged one.
 # usage: tools/build_variant.sh <name> [flags...]
 set -e
-R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
+cd "$(dirname "$0")/.."
 name=$1; shift
 mkdir -p build/variants build/obj
 python __graft_entry__.py >/dev/null
