@@ -93,6 +93,8 @@ typedef struct rsba_options {
   int32_t loss_type;       /* with huber_delta = a > 0: RSBA_LOSS_HUBER (0) = ceres::HuberLoss(a),       */
                            /* RSBA_LOSS_CAUCHY (1) = ceres::CauchyLoss(a); both have rho'' <= 0, so the  */
                            /* corrector scales residual and Jacobians by sqrt(rho') (corrector.cc)      */
+                           /* per residual block: a point's 2 residuals, a marker-chain observation's 8   */
+                           /* (both marker-chain paths: dense and time-eliminating)                     */
   const void* comm_unique_id; /* world_size > 1: the 128-byte id from rsba_comm_unique_id (rank 0's) */
   void* stream;               /* hipStream_t to run on, NULL = a private stream                    */
   double max_solver_time_in_seconds; /* 1e9 (Ceres' default; Solver::Options, left alone by bundle_adjustment_manager.cpp:90-92): checked
@@ -272,7 +274,8 @@ void rsba_solver_destroy(rsba_solver* s);
  *
  * Point model: every camera x camera block (6 x 6) and the 3 x 3 marginal of every point; camera x point and cross-point blocks
  * are RSBA_ERR_UNSUPPORTED.  Marker-chain models (dense and time-eliminating paths alike): every camera / marker x camera / marker
- * block (6 x 6); time blocks are RSBA_ERR_UNSUPPORTED; no loss (the marker-chain solve applies none).  world_size > 1 returns
+ * block (6 x 6); time blocks are RSBA_ERR_UNSUPPORTED.  apply_loss_function applies the solve's corrector in both models (the
+ * marker chain: sqrt(rho') of each observation's 8 residuals).  world_size > 1 returns
  * RSBA_ERR_UNSUPPORTED on every rank without issuing a collective. */
 typedef struct rsba_covariance_options { /* ceres::Covariance::Options, Ceres 1.14 defaults */
   double min_reciprocal_condition_number; /* 1e-14: a Cholesky pivot of the Jacobi-scaled reduced system (or of a point block)

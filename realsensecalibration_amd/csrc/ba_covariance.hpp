@@ -11,7 +11,8 @@
 //   k_cov_unscale  S^-1 = -D A D, mirrored from the upper triangle, so that block (b, a) is block (a, b)' bit for bit
 //   k_cov_mc_lin   marker-chain models: the normal matrix of the free camera / marker blocks (and, on the dense path, time blocks),
 //                  one wavefront per time block; on the time-eliminating path every free time block is eliminated as a point is
-//                  (S -= W_t V_t^-1 W_t'), no loss (the marker-chain solve applies none)
+//                  (S -= W_t V_t^-1 W_t'); with a loss (kLoss) every row's J through the solve's corrector, sqrt(rho'(s)) with s
+//                  over the residual block's 8 residuals
 //   k_cov_points   per point j: V_j^-1 + sum_{a,b} (W_a V_j^-1)' (S^-1)_{c_a c_b} (W_b V_j^-1), the 2x6 / 2x3 blocks recomputed
 //                  in registers from the observations, written in the problem's own point order
 #pragma once
@@ -487,10 +488,12 @@ __device__ __forceinline__ bool CovSym6Inverse(const double U[21], double rcond,
 // Normal matrix of the marker-chain problem into S (n x n, zeroed by the caller, upper blocks): one wavefront per time block,
 // one lane per row (chunks of 64).  pos[block] = 6 x compact index or -1 (constant / unreferenced / eliminated).  elim[t] != 0:
 // time block t is eliminated — S -= W_x V_t^-1 W_y' over the pairs of its rows' camera / marker blocks, W_x = sum J_x'J_t.
+// kLoss: J of a row scaled by sqrt(rho'(s)) (loss: LossAndScale's signed parameter), s taken over its four corners first.
+template <bool kLoss>
 __global__ void __launch_bounds__(64)
 k_cov_mc_lin(int T, const int* __restrict__ tptr, const CovMcRow* __restrict__ rows, const double* __restrict__ obs8, const double* __restrict__ intr,
              const double* __restrict__ pc, const int* __restrict__ pos, const unsigned char* __restrict__ elim, double half_side, double rcond,
-             int n, double* __restrict__ S, int* __restrict__ flags) {
+             int n, double* __restrict__ S, int* __restrict__ flags, double loss = 0.0) {
   __shared__ double Wl[64 * RSBA_COV_MC_LDS];
   __shared__ int Pl[64][2];
   const int lane = threadIdx.x;
@@ -502,9 +505,22 @@ k_cov_mc_lin(int T, const int* __restrict__ tptr, const CovMcRow* __restrict__ r
     const double* o8 = obs8 + 8 * (size_t)q;
     const double* pcc = rw.cam_block >= 0 ? pc + (size_t)rw.cam_block * CC_STRIDE : nullptr;
     const double* pcm = rw.marker_block >= 0 ? pc + (size_t)rw.marker_block * CC_STRIDE : nullptr;
+    double sq = 1.0;
+    if constexpr (kLoss) {
+      double ss = 0.0;
+      for (int k = 0; k < 4; ++k) {
+        double r[2], J[36];
+        MarkerCornerResidualJacobian(pcc, pc + (size_t)rw.time_block * CC_STRIDE, pcm, intr + 4 * rw.camera, cx[k], cy[k], o8[2 * k], o8[2 * k + 1], r, J);
+        ss += r[0] * r[0] + r[1] * r[1];
+      }
+      (void)LossAndScale(loss, ss, &sq);
+    }
     for (int k = 0; k < 4; ++k) {
       double r[2], J[36];
       MarkerCornerResidualJacobian(pcc, pc + (size_t)rw.time_block * CC_STRIDE, pcm, intr + 4 * rw.camera, cx[k], cy[k], o8[2 * k], o8[2 * k + 1], r, J);
+      if constexpr (kLoss) {
+        for (int e = 0; e < 36; ++e) J[e] *= sq;
+      }
       f(J);
     }
   };

@@ -84,10 +84,14 @@ struct MarkerObs {
 };
 
 // Evaluate residual blocks.  with_jacobian: J (8 x 18, columns camera|time|marker) and r (8) are stored.
+// kLoss: the residual block (one observation, 8 residuals) is robustified as Ceres' corrector does it for rho'' <= 0 (Huber,
+// Cauchy): s = |r|^2 over the 8 residuals, J and r stored scaled by sqrt(rho'(s)), rho(s) (the cost) into rho_per_obs;
+// sumsq_per_obs keeps the raw s (the RMS metric).  loss: the signed parameter of LossAndScale.
+template <bool kLoss>
 __global__ void __launch_bounds__(64) k_marker_eval(int N, const MarkerObs* __restrict__ mo, const double* __restrict__ obs8,
                               const double* __restrict__ params, const double* __restrict__ intr, double half_side,
                               int with_jacobian, double* __restrict__ Jbuf, double* __restrict__ rbuf,
-                              double* __restrict__ sumsq_per_obs) {
+                              double* __restrict__ sumsq_per_obs, double loss = 0.0, double* __restrict__ rho_per_obs = nullptr) {
   // Jacobian rows leave through LDS: a thread's 36 doubles per corner would otherwise be 64 scattered 288-byte pieces per
   // store instruction (1152 B between neighbouring lanes); staged, consecutive lanes write consecutive words
   __shared__ double stage[64 * 37];
@@ -135,6 +139,26 @@ __global__ void __launch_bounds__(64) k_marker_eval(int N, const MarkerObs* __re
       __syncthreads();
       ss += r0 * r0 + r1 * r1;
     }
+    if constexpr (kLoss) {
+      // s is known only after the fourth corner: the block's stored rows are scaled in place (its r by the thread that wrote
+      // them; its J through the same coalesced walk that stored it, sqrt(rho') handed over in the staging row's unused word).
+      // Scaling before the store would need s first, i.e. a value pass over the corners ahead of the dual-number one; the
+      // re-read of the block's 1152 bytes is the cheaper of the two on this one-workgroup-system path.
+      double sq;
+      const double rho = LossAndScale(loss, ss, &sq);
+      if (live) {
+        rho_per_obs[i] = rho;
+        for (int e = 0; e < 8; ++e) rbuf[8 * (size_t)i + e] *= sq;
+      }
+      stage[threadIdx.x * 37 + 36] = sq;
+      __threadfence_block();
+      __syncthreads();
+      const int nlive = min(64, N - i0);
+      for (int e = threadIdx.x; e < nlive * 144; e += 64) Jbuf[(size_t)i0 * 144 + e] *= stage[(e / 144) * 37 + 36];
+    }
+  }
+  if constexpr (kLoss) {
+    if (!with_jacobian && live) { double sq; rho_per_obs[i] = LossAndScale(loss, ss, &sq); }
   }
   if (live) sumsq_per_obs[i] = ss;
 }
@@ -224,13 +248,16 @@ k_marker_system(int N, int n, const MarkerObs* __restrict__ mo, const double* __
   }
 }
 
-// Model cost change -(J d).(r + J d / 2) and candidate cost, one workgroup, fixed order.
+// Model cost change -(J d).(r + J d / 2) and candidate cost, one workgroup, fixed order.  kLoss: J and r are the corrected ones
+// (k_marker_eval<true>), the cost is 1/2 sum rho(s_c) (rho_c) and the raw sum of squares stays the RMS metric's.
+template <bool kLoss>
 __global__ void __launch_bounds__(256)
 k_marker_candidate(int N, const MarkerObs* __restrict__ mo, const double* __restrict__ Jbuf, const double* __restrict__ rbuf,
-                   const double* __restrict__ delta_act, const double* __restrict__ sumsq_c, double* __restrict__ res) {
-  __shared__ double s[2][256];
+                   const double* __restrict__ delta_act, const double* __restrict__ sumsq_c, double* __restrict__ res,
+                   const double* __restrict__ rho_c = nullptr) {
+  __shared__ double s[kLoss ? 3 : 2][256];
   const int tid = threadIdx.x;
-  double mcc = 0, cc = 0;
+  double mcc = 0, cc = 0, rc = 0;
   for (int i = tid; i < N; i += blockDim.x) {
     const MarkerObs o = mo[i];
     for (int r = 0; r < 8; ++r) {
@@ -242,13 +269,18 @@ k_marker_candidate(int N, const MarkerObs* __restrict__ mo, const double* __rest
       mcc -= mr * (rbuf[8 * (size_t)i + r] + 0.5 * mr);
     }
     cc += sumsq_c[i];
+    if constexpr (kLoss) rc += rho_c[i];
   }
   s[0][tid] = mcc; s[1][tid] = cc;
+  if constexpr (kLoss) s[2][tid] = rc;
   __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) { if (tid < off) { s[0][tid] += s[0][tid + off]; s[1][tid] += s[1][tid + off]; } __syncthreads(); }
+  for (int off = 128; off > 0; off >>= 1) {
+    if (tid < off) { s[0][tid] += s[0][tid + off]; s[1][tid] += s[1][tid + off]; if constexpr (kLoss) s[2][tid] += s[2][tid + off]; }
+    __syncthreads();
+  }
   if (tid == 0) {
     res[RES_MCC] = s[0][0];
-    double c = 0.5 * s[1][0];
+    double c = 0.5 * s[kLoss ? 2 : 1][0];
     if (!(c == c) || !(fabs(c) <= DBL_MAX)) c = DBL_MAX;
     res[RES_COST_C] = c; res[RES_SUMSQ_C] = s[1][0];
   }
@@ -263,11 +295,12 @@ struct MarkerDevice {
   double *obs8 = nullptr, *intr = nullptr, *params[2] = {nullptr, nullptr}, *params0 = nullptr;
   double *Jbuf = nullptr, *rbuf = nullptr, *ss_x = nullptr, *ss_c = nullptr, *A = nullptr, *scale = nullptr, *grad = nullptr,
          *delta = nullptr, *res = nullptr;
+  double *rho_x = nullptr, *rho_c = nullptr;   // rho(s) per residual block at x / at the candidate (a robust loss only)
   int* act_to_full = nullptr;
   int cur = 0;
 
   void Free() {
-    void* ptrs[] = {mo, obs8, intr, params[0], params[1], params0, Jbuf, rbuf, ss_x, ss_c, A, scale, grad, delta, res, act_to_full};
+    void* ptrs[] = {mo, obs8, intr, params[0], params[1], params0, Jbuf, rbuf, ss_x, ss_c, A, scale, grad, delta, res, act_to_full, rho_x, rho_c};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     mo = nullptr;
   }
@@ -297,7 +330,7 @@ struct MarkerDevice {
         !al((void**)&params[0], nfull * 8) || !al((void**)&params[1], nfull * 8) || !al((void**)&params0, nfull * 8) ||
         !al((void**)&Jbuf, (size_t)N * 8 * 18 * 8) || !al((void**)&rbuf, (size_t)N * 8 * 8) || !al((void**)&ss_x, N * 8) || !al((void**)&ss_c, N * 8) ||
         !al((void**)&A, (size_t)(n + 2) * n * 8) || !al((void**)&scale, n * 8) || !al((void**)&grad, n * 8) || !al((void**)&delta, n * 8) ||
-        !al((void**)&res, RES_SIZE * 8) || !al((void**)&act_to_full, n * sizeof(int)))
+        !al((void**)&res, RES_SIZE * 8) || !al((void**)&act_to_full, n * sizeof(int)) || !al((void**)&rho_x, N * 8) || !al((void**)&rho_c, N * 8))
       return RSBA_ERR_HIP;
     if (hipMemcpy(mo, h.data(), N * sizeof(MarkerObs), hipMemcpyHostToDevice) != hipSuccess) return RSBA_ERR_HIP;
     if (hipMemcpy(obs8, p.observations.data(), 8 * (size_t)N * 8, hipMemcpyHostToDevice) != hipSuccess) return RSBA_ERR_HIP;
@@ -318,6 +351,8 @@ struct MarkerDevice {
     IterParams ip;
     ip.radius = radius; ip.min_lm_diagonal = o.min_lm_diagonal; ip.max_lm_diagonal = o.max_lm_diagonal; ip.huber_delta = 0.0;
     ip.first = first ? 1 : 0; ip.jacobi_scaling = o.jacobi_scaling;
+    // the robust loss, read as the point model reads it (signed: see LossAndScale); the instances without one are untouched
+    const double loss = o.huber_delta > 0.0 ? (o.loss_type == RSBA_LOSS_CAUCHY ? -o.huber_delta : o.huber_delta) : 0.0;
     const int x = cur, c = 1 - cur;
     // the candidate array must carry the untouched blocks too
     if (hipMemcpyAsync(params[c], params[x], nfull * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return RSBA_ERR_HIP;
@@ -328,25 +363,29 @@ struct MarkerDevice {
     };
     if (!chk("(before marker step)")) return RSBA_ERR_HIP;
     T.Begin("k_marker_eval", st);
-    k_marker_eval<<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[x], intr, half_side, 1, Jbuf, rbuf, ss_x);
+    if (loss != 0.0) k_marker_eval<true><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[x], intr, half_side, 1, Jbuf, rbuf, ss_x, loss, rho_x);
+    else k_marker_eval<false><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[x], intr, half_side, 1, Jbuf, rbuf, ss_x);
     T.End(st);
     if (!chk("k_marker_eval")) return RSBA_ERR_HIP;
     size_t lds = (size_t)std::max(2 * RSBA_TB * (RSBA_NB + 1) + RSBA_NB * (RSBA_NB + 1), 5 * 1024) * sizeof(double);
     if (n <= RSBA_CHOL_MAXN) lds = std::max(lds, CholeskyLdsDoubles(n) * sizeof(double));
+    const double* cost_x = loss != 0.0 ? rho_x : ss_x;   // what k_marker_system sums into the cost at x
     T.Begin("k_marker_system", st);
     if (n <= RSBA_CHOL_MAXN) {
       if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k_marker_system<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      k_marker_system<512><<<1, 512, lds, st>>>(N, n, mo, Jbuf, rbuf, ss_x, A, scale, grad, act_to_full, params[x], params[c], delta, res, ip);
+      k_marker_system<512><<<1, 512, lds, st>>>(N, n, mo, Jbuf, rbuf, cost_x, A, scale, grad, act_to_full, params[x], params[c], delta, res, ip);
     } else {
-      k_marker_system<1024><<<1, 1024, lds, st>>>(N, n, mo, Jbuf, rbuf, ss_x, A, scale, grad, act_to_full, params[x], params[c], delta, res, ip);
+      k_marker_system<1024><<<1, 1024, lds, st>>>(N, n, mo, Jbuf, rbuf, cost_x, A, scale, grad, act_to_full, params[x], params[c], delta, res, ip);
     }
     T.End(st);
     if (!chk("k_marker_system")) return RSBA_ERR_HIP;
     T.Begin("k_marker_eval", st);
-    k_marker_eval<<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[c], intr, half_side, 0, nullptr, nullptr, ss_c);
+    if (loss != 0.0) k_marker_eval<true><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[c], intr, half_side, 0, nullptr, nullptr, ss_c, loss, rho_c);
+    else k_marker_eval<false><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[c], intr, half_side, 0, nullptr, nullptr, ss_c);
     T.End(st);
     T.Begin("k_marker_candidate", st);
-    k_marker_candidate<<<1, 256, 0, st>>>(N, mo, Jbuf, rbuf, delta, ss_c, res);
+    if (loss != 0.0) k_marker_candidate<true><<<1, 256, 0, st>>>(N, mo, Jbuf, rbuf, delta, ss_c, res, rho_c);
+    else k_marker_candidate<false><<<1, 256, 0, st>>>(N, mo, Jbuf, rbuf, delta, ss_c, res);
     T.End(st);
     if (!chk("k_marker_candidate")) return RSBA_ERR_HIP;
     if (hipMemcpyAsync(res_host, res, RES_SIZE * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess) return RSBA_ERR_HIP;
@@ -355,7 +394,7 @@ struct MarkerDevice {
   }
   int SumSquares(hipStream_t st, double* out) {
     if (Reset(st) != RSBA_OK) return RSBA_ERR_HIP;
-    k_marker_eval<<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[0], intr, half_side, 0, nullptr, nullptr, ss_x);
+    k_marker_eval<false><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[0], intr, half_side, 0, nullptr, nullptr, ss_x);
     std::vector<double> h(N);
     if (hipMemcpyAsync(h.data(), ss_x, N * 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return RSBA_ERR_HIP;
     double s = 0; for (double v : h) s += v;

@@ -782,16 +782,21 @@ k_marker_chol_finish(int nr, const double* __restrict__ red, double* __restrict_
 //   pass 2  the same residual blocks again (their Jacobians are still in the L2): the model cost change
 //           -(J d).(r + J d / 2) and the squared residuals of the candidate (four corners through the three candidate poses).
 // Per workgroup (four times): |delta_t|^2, |x_t + delta_t|^2, model cost change, candidate sum of squares.
+// kLoss: the rows scaled by sqrt(rho') at x (wsq, k_mc_block_weight); the candidate's raw sum as without a loss, the workgroup's
+// rho(s_c) - s_c to drho_c[blockIdx.x] (k_marker_schur_finish<true>).
+template <bool kLoss>
 __global__ void __launch_bounds__(256)
 k_time_backsub_terms(int T, const int* __restrict__ time_ptr, const int* __restrict__ time_full, const TimeSlots* __restrict__ ts,
                      const MarkerObs* __restrict__ mo, const double* __restrict__ obs8, const double* __restrict__ intr, double half_side,
                      const double* __restrict__ posec /* pose constants at x */, const double* __restrict__ tdata,
                      const double* __restrict__ delta_r, const double* __restrict__ params_x, double* __restrict__ params_c,
-                     double* __restrict__ delta_t, double* __restrict__ bpart /* gridDim.x x 4 */) {
+                     double* __restrict__ delta_t, double* __restrict__ bpart /* gridDim.x x 4 */, double loss = 0.0,
+                     const double* __restrict__ wsq = nullptr, double* __restrict__ drho_c = nullptr) {
   __shared__ double s_part[4][4];
+  __shared__ double s_dcc[kLoss ? 4 : 1];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int t = blockIdx.x * 4 + wave;
-  double d2 = 0, xc2 = 0, mcc = 0, cc = 0;
+  double d2 = 0, xc2 = 0, mcc = 0, cc = 0, dcc = 0;
   if (t < T) {
     const int o0 = time_ptr[t], o1 = time_ptr[t + 1], tf = time_full[t];
     double h[6] = {0, 0, 0, 0, 0, 0};
@@ -810,6 +815,11 @@ k_time_backsub_terms(int T, const int* __restrict__ time_ptr, const int* __restr
         double rr[2], Jc[36];
         MarkerCornerResidualJacobian(pcc, pct, pcm, intr + 4 * o.camera, (k == 0 || k == 3) ? -half_side : half_side, k < 2 ? half_side : -half_side,
                                      obs8[8 * (size_t)i + 2 * k], obs8[8 * (size_t)i + 2 * k + 1], rr, Jc);
+        if constexpr (kLoss) {
+          const double w = wsq[i];
+#pragma unroll
+          for (int e = 0; e < 36; ++e) Jc[e] *= w;
+        }
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
           double m = 0.0;
@@ -864,6 +874,12 @@ k_time_backsub_terms(int T, const int* __restrict__ time_ptr, const int* __restr
           double rr[2], Jc[36];
           MarkerCornerResidualJacobian(pcc, pct, pcm, intr + 4 * o.camera, (k == 0 || k == 3) ? -half_side : half_side, k < 2 ? half_side : -half_side,
                                        obs8[8 * (size_t)i + 2 * k], obs8[8 * (size_t)i + 2 * k + 1], rr, Jc);
+          if constexpr (kLoss) {
+            const double w = wsq[i];
+            rr[0] *= w; rr[1] *= w;
+#pragma unroll
+            for (int e = 0; e < 36; ++e) Jc[e] *= w;
+          }
 #pragma unroll
           for (int q = 0; q < 2; ++q) {
             double m = 0.0;
@@ -875,6 +891,7 @@ k_time_backsub_terms(int T, const int* __restrict__ time_ptr, const int* __restr
       }
       // candidate residuals: cameras and markers of the candidate are in params_c already (reduced solve), the time here
       const double fx = intr[4 * o.camera], fy = intr[4 * o.camera + 1], ppx = intr[4 * o.camera + 2], ppy = intr[4 * o.camera + 3];
+      double sb = 0.0;   // (kLoss: the block's s_c)
       for (int k = 0; k < 4; ++k) {
         double pt[3] = {cx[k], cy[k], 0.0};
         if (o.full_marker >= 0) { const double* m = params_c + o.full_marker; RotateD(m, pt); pt[0] += m[3]; pt[1] += m[4]; pt[2] += m[5]; }
@@ -883,16 +900,25 @@ k_time_backsub_terms(int T, const int* __restrict__ time_ptr, const int* __restr
         const double r0 = fx * pt[0] / pt[2] + ppx - obs8[8 * (size_t)i + 2 * k];
         const double r1 = fy * pt[1] / pt[2] + ppy - obs8[8 * (size_t)i + 2 * k + 1];
         cc += r0 * r0 + r1 * r1;
+        if constexpr (kLoss) sb += r0 * r0 + r1 * r1;
       }
+      if constexpr (kLoss) { double sq; dcc += LossAndScale(loss, sb, &sq) - sb; }
     }
   }
   // the lanes' sums in a fixed tree, then the four times of the workgroup in wave order
   for (int off = 32; off > 0; off >>= 1) { mcc += __shfl_down(mcc, off, 64); cc += __shfl_down(cc, off, 64); }
   if (lane == 0) { s_part[wave][0] = d2; s_part[wave][1] = xc2; s_part[wave][2] = mcc; s_part[wave][3] = cc; }
+  if constexpr (kLoss) {
+    for (int off = 32; off > 0; off >>= 1) dcc += __shfl_down(dcc, off, 64);
+    if (lane == 0) s_dcc[wave] = dcc;
+  }
   __syncthreads();
   if (threadIdx.x < 4) {
     const int k = threadIdx.x;
     bpart[4 * blockIdx.x + k] = ((s_part[0][k] + s_part[1][k]) + s_part[2][k]) + s_part[3][k];
+  }
+  if constexpr (kLoss) {
+    if (threadIdx.x == 0) drho_c[blockIdx.x] = ((s_dcc[0] + s_dcc[1]) + s_dcc[2]) + s_dcc[3];
   }
 }
 
@@ -1090,12 +1116,15 @@ k_time_backsub_wg(int T, const int* __restrict__ time_ptr, const int* __restrict
 // (1024 threads, an entry = 32 bytes in two 16-byte loads, four entries in flight a thread, the lanes by butterfly and the sixteen
 //  wavefronts in order: 256 threads walking 27 entries each, one dependent trip to memory after the other, and a tree of eight
 //  barriers were 11 us for 200 KB)
+// kLoss: the candidate's cost is 1/2 (sum r_c^2 + sum of drho_c [nd], the workgroups' sums of rho(s_c) - s_c); its raw sum of squares as
+// without a loss.
+template <bool kLoss>
 __global__ void __launch_bounds__(1024)
 k_marker_schur_finish(int nb_time, const double* __restrict__ bp_time, const double* __restrict__ red_scal,
-                      const double* __restrict__ solve_out, double* __restrict__ res) {
-  __shared__ double s[4][16];
+                      const double* __restrict__ solve_out, double* __restrict__ res, int nd = 0, const double* __restrict__ drho_c = nullptr) {
+  __shared__ double s[kLoss ? 5 : 4][16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  double v[4] = {0, 0, 0, 0};
+  double v[kLoss ? 5 : 4] = {};
   const double2* __restrict__ bp2 = reinterpret_cast<const double2*>(bp_time);
   for (int b0 = tid; b0 < nb_time; b0 += 4 * 1024) {
     double2 lo[4], hi[4];
@@ -1104,14 +1133,16 @@ k_marker_schur_finish(int nb_time, const double* __restrict__ bp_time, const dou
 #pragma unroll
     for (int u = 0; u < 4; ++u) if (b0 + 1024 * u < nb_time) { v[0] += lo[u].x; v[1] += lo[u].y; v[2] += hi[u].x; v[3] += hi[u].y; }
   }
+  if constexpr (kLoss) for (int i = tid; i < nd; i += 1024) v[4] += drho_c[i];
+  constexpr int kV = kLoss ? 5 : 4;
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1)
 #pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] += __shfl_xor(v[k], off, 64);
-  if (lane == 0) for (int k = 0; k < 4; ++k) s[k][wave] = v[k];
+    for (int k = 0; k < kV; ++k) v[k] += __shfl_xor(v[k], off, 64);
+  if (lane == 0) for (int k = 0; k < kV; ++k) s[k][wave] = v[k];
   __syncthreads();
   if (tid == 0) {
-    for (int k = 0; k < 4; ++k) { double t = s[k][0]; for (int w = 1; w < 16; ++w) t += s[k][w]; s[k][0] = t; }
+    for (int k = 0; k < kV; ++k) { double t = s[k][0]; for (int w = 1; w < 16; ++w) t += s[k][w]; s[k][0] = t; }
     res[RES_COST_X] = 0.5 * red_scal[0];
     res[RES_GMAX] = fmax(red_scal[3], solve_out[3]);
     res[RES_XNORM2] = red_scal[1] + solve_out[1];
@@ -1120,7 +1151,7 @@ k_marker_schur_finish(int nb_time, const double* __restrict__ bp_time, const dou
     res[RES_STEP2] = solve_out[0] + s[0][0];
     res[RES_XCNORM2] = solve_out[2] + s[1][0];
     res[RES_MCC] = s[2][0];
-    double c = 0.5 * s[3][0];
+    double c = 0.5 * (kLoss ? s[3][0] + s[4][0] : s[3][0]);
     if (!(c == c) || !(fabs(c) <= DBL_MAX)) c = DBL_MAX;
     res[RES_COST_C] = c;
     res[RES_SUMSQ_C] = s[3][0];
@@ -1152,6 +1183,9 @@ struct MarkerSchurDevice {
   hipEvent_t fork_ev[3] = {nullptr, nullptr, nullptr};
   bool backsub_wg = false;   // k_time_backsub_wg instead of k_time_backsub_terms
   double* posec_c = nullptr; // pose constants of the candidate's cameras and markers
+  bool with_loss = false;    // a robust loss (Upload): the kLoss instances, the split elimination and the wavefront-per-time or split back-substitution
+  double *wsq = nullptr, *drho = nullptr, *drho_c = nullptr;   // [N] each: sqrt(rho'), rho(s) - s at x (k_mc_block_weight); per candidate
+                                                                 // workgroup (at most N): its blocks' rho(s_c) - s_c
   double half_side = 0;
   MarkerObs* mo = nullptr;
   TimeSlots* ts = nullptr;
@@ -1172,7 +1206,7 @@ struct MarkerSchurDevice {
   void Free() {
     void* ptrs[] = {mo, ts, chunk_ptr, time_ptr, slot_ptr, slot_col, time_full, col_full, ok_flag, obs8, intr, params[0], params[1],
                     params0, posec, posec_c, ss_x, scale_t, scale_r, tdata, part, red, A, Wm, delta_r, delta_t, bp_time, solve_out, res, tc_flags, tc_hand, tc_map,
-                    slot_order, slot_time, sb_ptr, sb_blk, xi_ptr, xi_blk, xi_cc, xi_cm, xc_ptr, sp, xout, tscal, blk_time, x_order};
+                    slot_order, slot_time, sb_ptr, sb_blk, xi_ptr, xi_blk, xi_cc, xi_cm, xc_ptr, sp, xout, tscal, blk_time, x_order, wsq, drho, drho_c};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     mo = nullptr; ts = nullptr;
     for (auto& q : fork_s) if (q) { (void)hipStreamDestroy(q); q = nullptr; }
@@ -1187,7 +1221,11 @@ struct MarkerSchurDevice {
     return 6 * nblocks > RSBA_CHOL_MAXN;
   }
 
-  int Upload(const rsba_problem& p) {
+  // loss: a robust loss is set.  Its rows are formed by the split kernels only (round 4's k_time_eliminate and k_time_backsub_wg spread a
+  // residual block's corners over lanes and have no block-wide s): RSBA_MT_SPLIT=0 and RSBA_MT_BACKSUB_WG are not taken then, and a problem
+  // whose times are too wide for the split accumulation returns RSBA_ERR_UNSUPPORTED (the solver takes the dense path).
+  int Upload(const rsba_problem& p, bool loss = false) {
+    with_loss = loss;
     N = (int)p.num_observations; nfull = (int)p.parameters.size(); half_side = p.marker_side / 2;
     if (N <= 0) return RSBA_ERR_ARG;
     const int C = p.num_cameras, Tn = p.num_times, M = p.num_markers;
@@ -1268,7 +1306,7 @@ struct MarkerSchurDevice {
     lds_s = lds_elim + (PL.packed() + 3 * (size_t)nr) * sizeof(double) <= 156 * 1024;
     if (lds_s) lds_elim += (PL.packed() + 3 * (size_t)nr) * sizeof(double);
     const bool lds_s_elim = lds_s;   // (k_time_eliminate's own choice, should the split kernels not take the problem)
-    split = !(getenv("RSBA_MT_SPLIT") && atoi(getenv("RSBA_MT_SPLIT")) == 0);
+    split = with_loss || !(getenv("RSBA_MT_SPLIT") && atoi(getenv("RSBA_MT_SPLIT")) == 0);
     if (split) {
       const int per_wave = (AccMfmaTiles(nr) + 15) / 16;
       acc_tiles = (per_wave <= 8 && !(getenv("RSBA_MT_ACC_MFMA") && atoi(getenv("RSBA_MT_ACC_MFMA")) == 0)) ? (per_wave <= 3 ? 3 : 8) : 0;
@@ -1283,6 +1321,7 @@ struct MarkerSchurDevice {
       if (lds_acc > 156 * 1024) {
         // times that touch more blocks than the accumulation's double-buffered records hold in LDS (~110 of the 170 the model allows):
         // round 4's kernel, which stages 32 residual blocks at a time whatever the width
+        if (with_loss) return RSBA_ERR_UNSUPPORTED;
         split = false; acc_tiles = 0; lds_s = lds_s_elim;
       }
     }
@@ -1375,7 +1414,7 @@ struct MarkerSchurDevice {
       }
     }
     // (k_time_backsub_wg: a corner of a residual block per lane, two per lane at most; wider times take the wavefront-per-time kernel)
-    { int widest = 0; for (int t = 0; t < T; ++t) widest = std::max(widest, tptr[t + 1] - tptr[t]); backsub_wg = widest <= 128 /* 4 x 128 corners = 512 lanes */ && !(getenv("RSBA_MT_BACKSUB_WG") && atoi(getenv("RSBA_MT_BACKSUB_WG")) == 0); }
+    { int widest = 0; for (int t = 0; t < T; ++t) widest = std::max(widest, tptr[t + 1] - tptr[t]); backsub_wg = !with_loss && widest <= 128 /* 4 x 128 corners = 512 lanes */ && !(getenv("RSBA_MT_BACKSUB_WG") && atoi(getenv("RSBA_MT_BACKSUB_WG")) == 0); }
     nb_time = backsub_wg ? T : (T + 3) / 4;
     split_backsub = split && !(getenv("RSBA_MT_SPLIT_BACKSUB") && atoi(getenv("RSBA_MT_SPLIT_BACKSUB")) == 0);
     if (split_backsub) { ncand_wg = (N + 255) / 256; nb_time = T + ncand_wg; }
@@ -1391,7 +1430,8 @@ struct MarkerSchurDevice {
         !al((void**)&scale_r, nr * 8) || !al((void**)&tdata, 48 * (size_t)T * 8) || !al((void**)&part, (size_t)G * PL.size() * 8) ||
         !al((void**)&red, RL.size() * 8) || !al((void**)&A, nA * 8) || (nr > RSBA_CHOL_MAXN && !al((void**)&Wm, nA * 8)) ||
         !al((void**)&delta_r, nr * 8) || !al((void**)&delta_t, 6 * (size_t)T * 8) || !al((void**)&bp_time, 4 * (size_t)nb_time * 8) ||
-        !al((void**)&solve_out, 8 * 8) || !al((void**)&res, RES_SIZE * 8))
+        !al((void**)&solve_out, 8 * 8) || !al((void**)&res, RES_SIZE * 8) ||
+        (with_loss && (!al((void**)&wsq, N * 8) || !al((void**)&drho, N * 8) || !al((void**)&drho_c, N * 8))))
       return RSBA_ERR_HIP;
     auto up = [](void* d, const void* h, size_t bytes) { return bytes == 0 || hipMemcpy(d, h, bytes, hipMemcpyHostToDevice) == hipSuccess; };
     if (!up(mo, hmo.data(), N * sizeof(MarkerObs)) || !up(ts, hts.data(), N * sizeof(TimeSlots)) || !up(chunk_ptr, cptr.data(), (G + 1) * 4) ||
@@ -1478,6 +1518,8 @@ struct MarkerSchurDevice {
     IterParams ip;
     ip.radius = radius; ip.min_lm_diagonal = o.min_lm_diagonal; ip.max_lm_diagonal = o.max_lm_diagonal; ip.huber_delta = 0.0;
     ip.first = first ? 1 : 0; ip.jacobi_scaling = o.jacobi_scaling;
+    // the robust loss, read as the point model reads it (signed: see LossAndScale); Upload was told whether there is one
+    const double loss = with_loss ? (o.loss_type == RSBA_LOSS_CAUCHY ? -o.huber_delta : o.huber_delta) : 0.0;
     const int x = cur, c = 1 - cur;
     if (hipMemcpyAsync(params[c], params[x], nfull * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return RSBA_ERR_HIP;
     auto chk = [&](const char* what) {
@@ -1493,7 +1535,13 @@ struct MarkerSchurDevice {
     ElimArgs ea{nr, dmax, (int)N, chunk_ptr, time_ptr, slot_ptr, slot_col, time_full, col_full, ts, mo, obs8, intr, posec, half_side, params[x], scale_t, tdata, part, ip};
     if (split) {
       SplitArgs sa{nslots, T, nx, ncam_cols, nx_threads, slot_order, x_order, slot_time, slot_col, sb_ptr, sb_blk, time_ptr, time_full, col_full, ts, mo, obs8, intr, posec, half_side,
-                   xi_ptr, xi_blk, xi_cc, xi_cm, sp, xout};
+                   xi_ptr, xi_blk, xi_cc, xi_cm, sp, xout, wsq, drho};
+      if (with_loss) {
+        // the corrector's weights at x, wanted by all three product kernels
+        Tm.Begin("k_mc_block_weight", st);
+        k_mc_block_weight<<<(N + 255) / 256, 256, 0, st>>>(N, ts, mo, obs8, intr, half_side, posec, loss, wsq, drho);
+        Tm.End(st);
+      }
       // the three product kernels are independent and none fills the chip: side by side on three streams (one after the other
       // when every kernel is timed)
       const bool fork = fork_s[0] != nullptr && !Tm.enabled();
@@ -1503,14 +1551,17 @@ struct MarkerSchurDevice {
             hipStreamWaitEvent(s_cross, fork_ev[0], 0) != hipSuccess) return RSBA_ERR_HIP;
       }
       Tm.Begin("k_mc_slot_products", st);
-      k_mc_slot_products<<<(nslots + 255) / 256, 256, 0, st>>>(sa);
+      if (with_loss) k_mc_slot_products<true><<<(nslots + 255) / 256, 256, 0, st>>>(sa);
+      else k_mc_slot_products<false><<<(nslots + 255) / 256, 256, 0, st>>>(sa);
       Tm.End(st);
       Tm.Begin("k_mc_time_products", st);
-      k_mc_time_products<<<(T + 3) / 4, 256, 0, s_time>>>(sa, ip, params[x], scale_t, tdata, tscal);
+      if (with_loss) k_mc_time_products<true><<<(T + 3) / 4, 256, 0, s_time>>>(sa, ip, params[x], scale_t, tdata, tscal);
+      else k_mc_time_products<false><<<(T + 3) / 4, 256, 0, s_time>>>(sa, ip, params[x], scale_t, tdata, tscal);
       Tm.End(st);
       if (nx > 0) {
         Tm.Begin("k_mc_cross", st);
-        k_mc_cross<<<(nx_threads + 255) / 256, 256, 0, s_cross>>>(sa);
+        if (with_loss) k_mc_cross<true><<<(nx_threads + 255) / 256, 256, 0, s_cross>>>(sa);
+        else k_mc_cross<false><<<(nx_threads + 255) / 256, 256, 0, s_cross>>>(sa);
         Tm.End(st);
       }
       if (fork) {
@@ -1576,8 +1627,13 @@ struct MarkerSchurDevice {
       const bool fork2 = fork_s[0] != nullptr && !Tm.enabled();
       hipStream_t s_cost = fork2 ? fork_s[0] : st;
       if (fork2 && (hipEventRecord(fork_ev[0], st) != hipSuccess || hipStreamWaitEvent(s_cost, fork_ev[0], 0) != hipSuccess)) return RSBA_ERR_HIP;
-      k_mc_candidate<0><<<ncand_wg, 256, 0, st>>>(N, T, ts, mo, obs8, intr, half_side, posec, posec_c, delta_r, delta_t, blk_time, bp_time);
-      k_mc_candidate<1><<<ncand_wg, 256, 0, s_cost>>>(N, T, ts, mo, obs8, intr, half_side, posec, posec_c, delta_r, delta_t, blk_time, bp_time);
+      if (with_loss) {
+        k_mc_candidate<0, true><<<ncand_wg, 256, 0, st>>>(N, T, ts, mo, obs8, intr, half_side, posec, posec_c, delta_r, delta_t, blk_time, bp_time, loss, wsq, drho_c);
+        k_mc_candidate<1, true><<<ncand_wg, 256, 0, s_cost>>>(N, T, ts, mo, obs8, intr, half_side, posec, posec_c, delta_r, delta_t, blk_time, bp_time, loss, wsq, drho_c);
+      } else {
+        k_mc_candidate<0, false><<<ncand_wg, 256, 0, st>>>(N, T, ts, mo, obs8, intr, half_side, posec, posec_c, delta_r, delta_t, blk_time, bp_time);
+        k_mc_candidate<1, false><<<ncand_wg, 256, 0, s_cost>>>(N, T, ts, mo, obs8, intr, half_side, posec, posec_c, delta_r, delta_t, blk_time, bp_time);
+      }
       if (fork2 && (hipEventRecord(fork_ev[1], s_cost) != hipSuccess || hipStreamWaitEvent(st, fork_ev[1], 0) != hipSuccess)) return RSBA_ERR_HIP;
     } else if (backsub_wg) {
       k_pose_constants_reduced<<<(nr / 6 + 63) / 64, 64, 0, st>>>(nr / 6, col_full, params[c], posec_c);
@@ -1585,12 +1641,17 @@ struct MarkerSchurDevice {
       k_time_backsub_wg<2, 256><<<T, 256, lds_bw, st>>>(T, time_ptr, time_full, ts, mo, obs8, intr, half_side, posec, posec_c, tdata, delta_r, params[x],
                                                    params[c], delta_t, bp_time, slot_ptr, slot_col, col_full);
     } else {
-      k_time_backsub_terms<<<nb_time, 256, 0, st>>>(T, time_ptr, time_full, ts, mo, obs8, intr, half_side, posec, tdata, delta_r, params[x],
-                                                    params[c], delta_t, bp_time);
+      if (with_loss)
+        k_time_backsub_terms<true><<<nb_time, 256, 0, st>>>(T, time_ptr, time_full, ts, mo, obs8, intr, half_side, posec, tdata, delta_r, params[x],
+                                                            params[c], delta_t, bp_time, loss, wsq, drho_c);
+      else
+        k_time_backsub_terms<false><<<nb_time, 256, 0, st>>>(T, time_ptr, time_full, ts, mo, obs8, intr, half_side, posec, tdata, delta_r, params[x],
+                                                             params[c], delta_t, bp_time);
     }
     Tm.End(st);
     Tm.Begin("k_marker_schur_finish", st);
-    k_marker_schur_finish<<<1, 1024, 0, st>>>(nb_time, bp_time, red + RL.scal(), solve_out, res);
+    if (with_loss) k_marker_schur_finish<true><<<1, 1024, 0, st>>>(nb_time, bp_time, red + RL.scal(), solve_out, res, split_backsub ? ncand_wg : nb_time, drho_c);
+    else k_marker_schur_finish<false><<<1, 1024, 0, st>>>(nb_time, bp_time, red + RL.scal(), solve_out, res);
     Tm.End(st);
     if (!chk("k_marker_schur_finish")) return RSBA_ERR_HIP;
     if (hipMemcpyAsync(res_host, res, RES_SIZE * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess) return RSBA_ERR_HIP;
@@ -1606,7 +1667,7 @@ struct MarkerSchurDevice {
   }
   int SumSquares(hipStream_t st, double* out) {
     if (Reset(st) != RSBA_OK) return RSBA_ERR_HIP;
-    k_marker_eval<<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[0], intr, half_side, 0, nullptr, nullptr, ss_x);
+    k_marker_eval<false><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[0], intr, half_side, 0, nullptr, nullptr, ss_x);
     std::vector<double> h(N);
     if (hipMemcpyAsync(h.data(), ss_x, N * 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return RSBA_ERR_HIP;
     double s = 0; for (double v : h) s += v;

@@ -134,9 +134,51 @@ struct SplitArgs {
   const int* __restrict__ xi_cm;
   double* __restrict__ sp;              // [nslots][RSBA_SP_STRIDE]
   double* __restrict__ xout;            // [nx][36]: U_cm, marker row qm, camera column qc at 6 qm + qc
+  const double* __restrict__ wsq;       // [N] with a robust loss (kLoss instances): sqrt(rho'(s)) of each residual block at x ...
+  const double* __restrict__ drho;      // [N] ... and rho(s) - s (k_mc_block_weight)
 };
 
-template <bool kCam>
+// With a robust loss: per residual block (thread per block, the device's time order) s = |r|^2 over its 8 residuals at x, the corrector's
+// sqrt(rho'(s)), which every kLoss kernel below applies to the rows it forms (r and J scaled, Ceres' corrector for rho'' <= 0), and
+// rho(s) - s.  The costs keep the loss-free sum of r^2 corner by corner and add the blocks' rho(s) - s beside it: a block inside
+// Huber's threshold adds an exact zero, so a loss no block reaches gives the loss-free bits.  The corners through the rotation matrices
+// and translations of k_pose_constants, as CornerRows forms them.
+__global__ void __launch_bounds__(256) k_mc_block_weight(int N, const TimeSlots* __restrict__ ts, const MarkerObs* __restrict__ mo, const double* __restrict__ obs8,
+                                                         const double* __restrict__ intr, double half_side, const double* __restrict__ posec, double loss,
+                                                         double* __restrict__ wsq, double* __restrict__ drho) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= N) return;
+  const MarkerObs o = mo[k];
+  const double* in = intr + 4 * ts[k].camera;
+  const double fx = in[0], fy = in[1], ppx = in[2], ppy = in[3];
+  const PoseC cam = LoadPose<false>(posec, o.full_cam >= 0 ? o.full_cam / 6 : -1);
+  const PoseC tim = LoadPose<false>(posec, o.full_time / 6);
+  const PoseC mar = LoadPose<false>(posec, o.full_marker >= 0 ? o.full_marker / 6 : -1);
+  const double* ob = obs8 + 8 * (size_t)k;
+  double ss = 0.0;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    double r[2];
+    CornerRows<false, false, false>(cam, tim, mar, fx, fy, ppx, ppy, CornerX(c, half_side), CornerY(c, half_side), ob[2 * c], ob[2 * c + 1], r, nullptr, nullptr, nullptr);
+    ss = fma(r[0], r[0], ss);
+    ss = fma(r[1], r[1], ss);
+  }
+  double sq;
+  drho[k] = LossAndScale(loss, ss, &sq) - ss;
+  wsq[k] = sq;
+}
+
+// the corrector on one corner's residuals and the 2 x 6 blocks formed of its rows (nullptr: not formed)
+__device__ __forceinline__ void ScaleCorner(double w, double r[2], double (*Ja)[6], double (*Jb)[6]) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    r[i] *= w;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) { if (Ja) Ja[i][q] *= w; if (Jb) Jb[i][q] *= w; }
+  }
+}
+
+template <bool kCam, bool kLoss>
 __device__ __forceinline__ void SlotProducts(const SplitArgs& a, int S, const PoseC& own, const PoseC& tim) {
   double W[36], gs[6], U[21];
 #pragma unroll
@@ -149,9 +191,10 @@ __device__ __forceinline__ void SlotProducts(const SplitArgs& a, int S, const Po
   // What a residual block's rows need from memory — the other block's pose, the observed corners, the intrinsics — is asked for ONE ENTRY AHEAD,
   // and the entry's own record two ahead: as block -> slots -> column -> pose -> constants it was four dependent trips to memory per entry, on one
   // wavefront a SIMD with nothing to run meanwhile (5 us an entry; the arithmetic is 1.2).
-  struct Fetched { PoseC oth; double ob[8], in[4]; };
+  struct Fetched { PoseC oth; double ob[8], in[4], w; };
   auto fetch = [&](const int4 r, Fetched& f) {
     f.oth = LoadPose<false>(a.posec, r.y);
+    f.w = kLoss ? a.wsq[r.x] : 1.0;
     const double* ob = a.obs8 + 8 * (size_t)r.x;
 #pragma unroll
     for (int i = 0; i < 8; ++i) f.ob[i] = ob[i];
@@ -180,6 +223,7 @@ __device__ __forceinline__ void SlotProducts(const SplitArgs& a, int S, const Po
       double r[2], Jo[2][6], Jt[2][6];
       if (kCam) CornerRows<true, true, false>(own, tim, oth, fx, fy, ppx, ppy, CornerX(c, hs), CornerY(c, hs), ou, ov, r, Jo, Jt, nullptr);
       else CornerRows<false, true, true>(oth, tim, own, fx, fy, ppx, ppy, CornerX(c, hs), CornerY(c, hs), ou, ov, r, nullptr, Jt, Jo);
+      if constexpr (kLoss) ScaleCorner(cur.w, r, Jo, Jt);
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
 #pragma unroll
@@ -207,17 +251,20 @@ __device__ __forceinline__ void SlotProducts(const SplitArgs& a, int S, const Po
   out[63] = 0.0;
 }
 
+template <bool kLoss>
 __global__ void __launch_bounds__(256) k_mc_slot_products(SplitArgs a) {
   const int g = blockIdx.x * 256 + threadIdx.x;
   if (g >= a.nslots) return;
   const int S = a.slot_order[g], col = a.slot_col[S];
   const PoseC own = LoadPose<true>(a.posec, a.col_full[col] / 6);
   const PoseC tim = LoadPose<true>(a.posec, a.time_full[a.slot_time[S]] / 6);
-  if (col < a.ncam_cols) SlotProducts<true>(a, S, own, tim);
-  else SlotProducts<false>(a, S, own, tim);
+  if (col < a.ncam_cols) SlotProducts<true, kLoss>(a, S, own, tim);
+  else SlotProducts<false, kLoss>(a, S, own, tim);
 }
 
-// Wavefront per time.  tdata[t]: E (36) | g_t (6) | E g_t (6); tscal[t]: sum r^2, |x_t|^2, 1.0 if V + D is not positive definite, max |g_t|.
+// Wavefront per time.  tdata[t]: E (36) | g_t (6) | E g_t (6); tscal[t]: sum r^2 (kLoss: + sum (rho(s) - s)), |x_t|^2, 1.0 if V + D is not
+// positive definite, max |g_t|.  kLoss: V, g_t and so the time's Jacobi scale from the corrected rows.
+template <bool kLoss>
 __global__ void __launch_bounds__(256) k_mc_time_products(SplitArgs a, IterParams ip, const double* __restrict__ params_x, double* __restrict__ scale_t,
                                                           double* __restrict__ tdata, double* __restrict__ tscal) {
   __shared__ double s_v[4][3 * 36 + 8];
@@ -225,7 +272,7 @@ __global__ void __launch_bounds__(256) k_mc_time_products(SplitArgs a, IterParam
   const int t = blockIdx.x * 4 + wave;
   if (t >= a.T) return;   // (whole wavefronts; no workgroup barrier below)
   const PoseC tim = LoadPose<true>(a.posec, a.time_full[t] / 6);
-  double V[21], g[6], ss = 0.0;
+  double V[21], g[6], ss = 0.0, corr = 0.0;
 #pragma unroll
   for (int i = 0; i < 21; ++i) V[i] = 0.0;
 #pragma unroll
@@ -238,10 +285,15 @@ __global__ void __launch_bounds__(256) k_mc_time_products(SplitArgs a, IterParam
     const double* in = a.intr + 4 * s.camera;
     const double fx = in[0], fy = in[1], ppx = in[2], ppy = in[3];
     const double* ob = a.obs8 + 8 * (size_t)k;
+    double w = 1.0;
+    if constexpr (kLoss) { w = a.wsq[k]; corr += a.drho[k]; }
 #pragma unroll 1
     for (int c = 0; c < 4; ++c) {
       double r[2], Jt[2][6];
       CornerRows<false, true, false>(cam, tim, mar, fx, fy, ppx, ppy, CornerX(c, hs), CornerY(c, hs), ob[2 * c], ob[2 * c + 1], r, nullptr, Jt, nullptr);
+#pragma unroll
+      for (int i = 0; i < 2; ++i) ss = fma(r[i], r[i], ss);   // (the raw residuals)
+      if constexpr (kLoss) ScaleCorner(w, r, Jt, nullptr);
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
 #pragma unroll
@@ -250,7 +302,6 @@ __global__ void __launch_bounds__(256) k_mc_time_products(SplitArgs a, IterParam
 #pragma unroll
           for (int p = 0; p <= q; ++p) V[q * (q + 1) / 2 + p] = fma(Jt[i][q], Jt[i][p], V[q * (q + 1) / 2 + p]);
         }
-        ss = fma(r[i], r[i], ss);
       }
     }
   }
@@ -262,7 +313,9 @@ __global__ void __launch_bounds__(256) k_mc_time_products(SplitArgs a, IterParam
 #pragma unroll
     for (int i = 0; i < 6; ++i) g[i] += __shfl_xor(g[i], off, 64);
     ss += __shfl_xor(ss, off, 64);
+    if constexpr (kLoss) corr += __shfl_xor(corr, off, 64);
   }
+  if constexpr (kLoss) ss += corr;
   double* Vd = s_v[wave];        // V + D, row-major
   double* Mx = Vd + 36;          // scratch of the inverse
   double* E = Mx + 36;           // (V + D)^-1
@@ -307,6 +360,7 @@ __global__ void __launch_bounds__(256) k_mc_time_products(SplitArgs a, IterParam
   if (lane == 0) { tscal[4 * (size_t)t] = ss; tscal[4 * (size_t)t + 1] = xn2; tscal[4 * (size_t)t + 2] = ok ? 0.0 : 1.0; tscal[4 * (size_t)t + 3] = gmax; }
 }
 
+template <bool kLoss>
 __global__ void __launch_bounds__(256) k_mc_cross(SplitArgs a) {
   const int g = blockIdx.x * 256 + threadIdx.x;
   if (g >= a.nx_threads) return;
@@ -321,9 +375,10 @@ __global__ void __launch_bounds__(256) k_mc_cross(SplitArgs a) {
   for (int i = 0; i < 36; ++i) X[i] = 0.0;
   const double hs = a.half_side;
   // (the time's pose, the corners and the intrinsics one entry ahead, the entry's record two: see SlotProducts)
-  struct Fetched { PoseC tim; double ob[8], in[4]; };
+  struct Fetched { PoseC tim; double ob[8], in[4], w; };
   auto fetch = [&](const int4 r, Fetched& f) {
     f.tim = LoadPose<false>(a.posec, r.y);
+    f.w = kLoss ? a.wsq[r.x] : 1.0;
     const double* ob = a.obs8 + 8 * (size_t)r.x;
 #pragma unroll
     for (int i = 0; i < 8; ++i) f.ob[i] = ob[i];
@@ -350,6 +405,7 @@ __global__ void __launch_bounds__(256) k_mc_cross(SplitArgs a) {
       const double ov = c == 0 ? cur.ob[1] : (c == 1 ? cur.ob[3] : (c == 2 ? cur.ob[5] : cur.ob[7]));
       double r[2], Jc[2][6], Jm[2][6];
       CornerRows<true, false, true>(cam, tim, mar, fx, fy, ppx, ppy, CornerX(c, hs), CornerY(c, hs), ou, ov, r, Jc, nullptr, Jm);
+      if constexpr (kLoss) ScaleCorner(cur.w, r, Jc, Jm);
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -755,14 +811,17 @@ __global__ void __launch_bounds__(256) k_mc_time_step(int T, const int* __restri
 
 // kPart 0: the model cost change (the block's rows at x: 340 registers, one wavefront a SIMD); 1: the candidate's residuals (rotation
 // matrices and translations only: four wavefronts a SIMD) — two launches side by side instead of one kernel with the registers of both.
-template <int kPart>
+// kLoss: part 0 from the corrected rows (wsq: sqrt(rho') at x); part 1 sums the raw r_c^2 as without a loss and the workgroup's
+// rho(s_c) - s_c into drho_c[blockIdx.x] (k_marker_schur_finish<true> adds them to the cost).
+template <int kPart, bool kLoss>
 __global__ void __launch_bounds__(256) k_mc_candidate(int N, int T, const TimeSlots* __restrict__ ts, const MarkerObs* __restrict__ mo, const double* __restrict__ obs8,
                                                       const double* __restrict__ intr, double half_side, const double* __restrict__ posec,
                                                       const double* __restrict__ posec_c, const double* __restrict__ delta_r, const double* __restrict__ delta_t,
-                                                      const int* __restrict__ blk_time, double* __restrict__ bp_time) {
-  __shared__ double s_w[4];
+                                                      const int* __restrict__ blk_time, double* __restrict__ bp_time, double loss = 0.0,
+                                                      const double* __restrict__ wsq = nullptr, double* __restrict__ drho_c = nullptr) {
+  __shared__ double s_w[kLoss && kPart == 1 ? 8 : 4];
   const int k = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  double sum = 0.0;
+  double sum = 0.0, dsum = 0.0;
   if (k < N) {
     const TimeSlots s = ts[k];
     const MarkerObs o = mo[k];
@@ -775,6 +834,7 @@ __global__ void __launch_bounds__(256) k_mc_candidate(int N, int T, const TimeSl
       const PoseC mar = LoadPose<true>(posec, o.full_marker >= 0 ? o.full_marker / 6 : -1);
       double dl[18];
       const int t = blk_time[k];
+      const double w = kLoss ? wsq[k] : 1.0;
 #pragma unroll
       for (int x = 0; x < 6; ++x) {
         dl[x] = s.col_cam >= 0 ? delta_r[s.col_cam + x] : 0.0;
@@ -790,6 +850,13 @@ __global__ void __launch_bounds__(256) k_mc_candidate(int N, int T, const TimeSl
 #pragma unroll
           for (int q = 0; q < 6; ++q) Jc[i][q] = 0.0;   // (an absent camera transform: CornerRows leaves the block alone)
         CornerRows<true, true, true>(cam, tim, mar, fx, fy, ppx, ppy, cx, cy, u, v, r, Jc, Jt, Jm);
+        if constexpr (kLoss) {
+          ScaleCorner(w, r, Jc, Jt);
+#pragma unroll
+          for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int q = 0; q < 6; ++q) Jm[i][q] *= w;
+        }
         // (an absent marker transform: its block is formed from the stand-in pose's constants and meets dl[12..17] = 0)
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -808,6 +875,7 @@ __global__ void __launch_bounds__(256) k_mc_candidate(int N, int T, const TimeSl
       const PoseC ccam = LoadPose<false>(posec_c, o.full_cam >= 0 ? o.full_cam / 6 : -1);
       const PoseC ctim = LoadPose<false>(posec_c, o.full_time / 6);
       const PoseC cmar = LoadPose<false>(posec_c, o.full_marker >= 0 ? o.full_marker / 6 : -1);
+      double sb = 0.0;   // (kLoss: the block's s_c)
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         const double u = ob[2 * c], v = ob[2 * c + 1];
@@ -821,17 +889,24 @@ __global__ void __launch_bounds__(256) k_mc_candidate(int N, int T, const TimeSl
         if (ccam.on) apply(ccam);
         const double r0 = fx * pt[0] / pt[2] + ppx - u, r1 = fy * pt[1] / pt[2] + ppy - v;
         sum += r0 * r0 + r1 * r1;
+        if constexpr (kLoss) sb += r0 * r0 + r1 * r1;
       }
+      if constexpr (kLoss) { double sq; dsum = LossAndScale(loss, sb, &sq) - sb; }
     }
   }
   for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
   if (lane == 0) s_w[wave] = sum;
+  if constexpr (kLoss && kPart == 1) {
+    for (int off = 32; off > 0; off >>= 1) dsum += __shfl_down(dsum, off, 64);
+    if (lane == 0) s_w[4 + wave] = dsum;
+  }
   __syncthreads();
   if (threadIdx.x == 0) {
     double* out = bp_time + 4 * ((size_t)T + blockIdx.x);
     const double tot = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
     if (kPart == 0) { out[0] = 0.0; out[1] = 0.0; out[2] = tot; }
     else out[3] = tot;
+    if constexpr (kLoss && kPart == 1) drho_c[blockIdx.x] = ((s_w[4] + s_w[5]) + s_w[6]) + s_w[7];
   }
 }
 

@@ -2379,7 +2379,8 @@ static int CovariancePoints(rsba_solver* s, const rsba_covariance_options& co) {
 }
 
 // Marker-chain models: S^-1 of the free referenced camera / marker blocks.  The dense path keeps the free time blocks in the system
-// (the inverse of its whole active system); the time-eliminating path eliminates them first, as its solve does.  No loss.
+// (the inverse of its whole active system); the time-eliminating path eliminates them first, as its solve does.  The solve's loss
+// corrector with apply_loss_function, on both paths (the eliminated time blocks included).
 static int CovarianceMarker(rsba_solver* s, const rsba_covariance_options& co) {
   const rsba_problem& p = *s->prob;
   const int C = p.num_cameras, T = p.num_times, M = p.num_markers, nb = C + T + M;
@@ -2424,6 +2425,7 @@ static int CovarianceMarker(rsba_solver* s, const rsba_covariance_options& co) {
   const double* params = elim_path ? (s->has_run ? s->marker_schur.params[s->marker_schur.cur] : s->marker_schur.params0)
                                    : (s->has_run ? s->marker.params[s->marker.cur] : s->marker.params0);
   const double rcond = co.min_reciprocal_condition_number;
+  const double loss = !co.apply_loss_function || !(s->opt.huber_delta > 0.0) ? 0.0 : (s->opt.loss_type == RSBA_LOSS_CAUCHY ? -s->opt.huber_delta : s->opt.huber_delta);
   hipStream_t st = s->stream;
   return CovRun(s, n, rcond, extra, [&](CovSystem& y, auto& hip) {
     hip(hipMemcpyAsync(obs_d, obs.data(), obs.size() * sizeof(double), hipMemcpyHostToDevice, st));
@@ -2433,7 +2435,10 @@ static int CovarianceMarker(rsba_solver* s, const rsba_covariance_options& co) {
     hip(hipMemcpyAsync(rows_d, rows.data(), rows.size() * sizeof(CovMcRow), hipMemcpyHostToDevice, st));
     hip(hipMemcpyAsync(elim_d, elim.data(), elim.size(), hipMemcpyHostToDevice, st));
     k_cov_pose_constants<<<(nb + 255) / 256, 256, 0, st>>>(nb, params, pc);
-    k_cov_mc_lin<<<std::max(1, std::min(T, 4096)), 64, 0, st>>>(T, tptr_d, rows_d, obs_d, intr, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags);
+    if (loss != 0.0)
+      k_cov_mc_lin<true><<<std::max(1, std::min(T, 4096)), 64, 0, st>>>(T, tptr_d, rows_d, obs_d, intr, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags, loss);
+    else
+      k_cov_mc_lin<false><<<std::max(1, std::min(T, 4096)), 64, 0, st>>>(T, tptr_d, rows_d, obs_d, intr, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags);
     // (the host vectors outlive CovRun, which synchronises the stream before it returns)
   });
 }
@@ -2529,7 +2534,7 @@ int rsba_solver_create(rsba_problem* p, const rsba_options* o, rsba_solver** out
   } else {
     const bool any_const_block = std::find(p->block_constant.begin(), p->block_constant.end(), (uint8_t)1) != p->block_constant.end();
     s->eliminate_times = !any_const_block && rsba::MarkerSchurDevice::Wanted(*p, opt.schur_impl);   // (constant blocks: the dense path)
-    rc = s->eliminate_times ? s->marker_schur.Upload(*p) : s->marker.Upload(*p);
+    rc = s->eliminate_times ? s->marker_schur.Upload(*p, opt.huber_delta > 0.0) : s->marker.Upload(*p);
     if (s->eliminate_times && rc == RSBA_ERR_UNSUPPORTED) {
       // duplicate detections, no camera / marker block at all, or a time wider than the kernel's LDS: the dense path is general
       s->marker_schur.Free();

@@ -1,6 +1,6 @@
 """Marker-chain model at scale on the GPU: per-kernel times of the time-elimination path.
 
-    python tools/marker_chain_scale.py [C T M]        default 8 5000 16
+    python tools/marker_chain_scale.py [C T M [huber|cauchy a]]        default 8 5000 16, no loss
 """
 import json
 import os
@@ -13,19 +13,21 @@ import numpy as np  # noqa: E402
 from realsensecalibration_amd import capi, synthetic  # noqa: E402
 
 C_, T_, M_ = (int(v) for v in sys.argv[1:4]) if len(sys.argv) >= 4 else (8, 5000, 16)
+LOSS, LOSS_A = (sys.argv[4], float(sys.argv[5])) if len(sys.argv) >= 6 else ("none", 0.0)
+LOSS_KW = {} if LOSS == "none" else {"huber_delta": LOSS_A, "loss_type": 1 if LOSS == "cauchy" else 0}
 t0 = time.time()
 prob = synthetic.make_marker_chain(C_, T_, M_, seed=11)
 gen = time.time() - t0
 p = capi.Problem.marker_chain(prob)
 out = {}
 for mode in (0, 1):
-    s = capi.Solver(p, capi.default_options(profile_kernels=mode))
+    s = capi.Solver(p, capi.default_options(profile_kernels=mode, **LOSS_KW))
     s.run()            # warm-up: code objects, allocations
     for _ in range(int(os.environ.get("MC_RUNS", "3")) - 1):   # (the kernel statistics include the warm-up's first launches: amortised)
         s.run()
     sm = s.run()
     if mode == 0:
-        out.update({"cameras": C_, "times": T_, "markers": M_, "residual_blocks": int(prob["N"]), "generate_s": round(gen, 2),
+        out.update({"cameras": C_, "times": T_, "markers": M_, "residual_blocks": int(prob["N"]), "generate_s": round(gen, 2), "loss": LOSS, "loss_scale": LOSS_A,
                     "iterations": sm.num_iterations, "initial_cost": sm.initial_cost, "final_cost": sm.final_cost,
                     "minimizer_ms": 1e3 * sm.minimizer_seconds,
                     "ms_per_iteration": 1e3 * sm.minimizer_seconds / max(1, sm.num_iterations + 1)})
