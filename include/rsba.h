@@ -182,9 +182,11 @@ int rsba_problem_set_camera_constant(rsba_problem* p, int32_t camera_idx, int32_
 int rsba_problem_set_point_constant(rsba_problem* p, int32_t point_idx, int32_t constant);
 /* ceres::Problem::SetParameterBlockConstant(values) as the reference would call it — with the block's place in the parameter array
  * (`parameter_offset` = values - parameters_: a multiple of 6 for a pose block, 6 C + 3 j for point j of the point model).  Point model: the
- * two calls above.  Marker-chain models (round 6): any camera / time / marker block of [C | T | M] (bundle_adjustment.cpp:64-87) — the
- * block keeps its transform in every residual that names it and leaves the program; the solve then runs the dense path (the
- * time-eliminating one does not know constant blocks). */
+ * two calls above.  Marker-chain models: any camera / time / marker block of [C | T | M] (bundle_adjustment.cpp:64-87) — the
+ * block keeps its transform in every residual that names it and leaves the program (no columns, no step, out of the norms and the
+ * Jacobi scaling; residuals with no free block count in the cost only).  Both paths take constant blocks: the time-eliminating one
+ * gives constant cameras and markers no reduced column and eliminates a constant time with E = 0; with every camera and marker
+ * constant only the time blocks are solved, each on its own (rsba_solver_time_elimination tells which path a solver runs). */
 int rsba_problem_set_parameter_block_constant(rsba_problem* p, int64_t parameter_offset, int32_t constant);
 
 /* Test1 file "two_cam_data.txt": `C P`, P rows `cam pt u v` (one observation per point,
@@ -337,6 +339,11 @@ int rsba_solver_comm_nranks(const rsba_solver* s);
 /* The schedule in effect and the stalls / fallbacks so far (rsba_schedule_info).  The reference has no counterpart: Ceres runs
  * one thread (bundle_adjustment_manager.cpp:90-92). */
 int rsba_solver_schedule_info(const rsba_solver* s, rsba_schedule_info* out);
+/* Marker-chain models: which path the solver runs.  *eliminates_times = 1 when the time blocks are eliminated (rsba_options.schur_impl 2,
+ * or 1 above RSBA_CHOL_MAXN unknowns), 0 on the dense one-workgroup path — the choice falls back to it silently for duplicate
+ * detections, a time that touches more than 170 camera / marker blocks, or a robust loss with times too wide for the split
+ * accumulation.  RSBA_ERR_UNSUPPORTED for the point model, RSBA_ERR_ARG for NULL. */
+int rsba_solver_time_elimination(const rsba_solver* s, int32_t* eliminates_times);
 
 /* ------------------------------------------------------------------ files either side of the path */
 /* IO::GetIntrinsics (my_io.cpp:5-31) without OpenCV: reads <intrinsics> 3x3 from an OpenCV

@@ -30,6 +30,7 @@ EXPORTS = [
     "rsba_problem_initial_camera_poses", "rsba_problem_set_camera_constant", "rsba_problem_set_point_constant", "rsba_problem_set_parameter_block_constant", "rsba_solver_full_report", "rsba_solver_configure_run",
     "rsba_solver_comm_nranks", "rsba_solver_schedule_info", "rsba_comm_shm_id", "rsba_comm_finalize",
     "rsba_covariance_options_default", "rsba_solver_covariance_compute", "rsba_solver_covariance_block", "rsba_solver_point_covariances",
+    "rsba_solver_time_elimination",
 ]
 
 
@@ -128,6 +129,7 @@ def load():
     lib.rsba_solver_destroy.argtypes = [C.c_void_p]
     lib.rsba_solver_comm_nranks.argtypes = [C.c_void_p]
     lib.rsba_solver_schedule_info.argtypes = [C.c_void_p, C.c_void_p]
+    lib.rsba_solver_time_elimination.argtypes = [C.c_void_p, C.c_void_p]
     lib.rsba_comm_shm_id.argtypes = [C.c_char_p, C.c_void_p]
     lib.rsba_points_linearize_and_step.argtypes = [C.c_void_p, C.c_void_p, C.c_double] + [C.c_void_p] * 4
     lib.rsba_points_linearize_payload.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int64, C.c_void_p]
@@ -327,6 +329,12 @@ class Solver:
         return {"schedule": ("sequential", "pipelined", "pipelined_mg")[i.schedule], "stalls": int(i.stalls), "fallbacks": int(i.fallbacks),
                 "comm_nranks": int(i.comm_nranks), "chol_workgroups": int(i.chol_workgroups), "schur_impl": int(i.schur_impl),
                 "comm_kind": i.comm_kind.decode()}
+
+    def eliminates_times(self):
+        """Marker-chain models: 1 when this solver eliminates the time blocks, 0 on the dense path (rsba_solver_time_elimination)."""
+        v = C.c_int32()
+        _chk(load().rsba_solver_time_elimination(self.h, C.byref(v)), "rsba_solver_time_elimination")
+        return int(v.value)
 
     def full_report(self):
         n = load().rsba_solver_full_report(self.h, None, 0)

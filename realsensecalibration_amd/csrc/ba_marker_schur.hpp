@@ -64,7 +64,8 @@ struct PartLayout {
 };
 
 struct TimeSlots {  // per residual block, in time order: where its camera / marker block sits
-  int slot_cam, slot_marker;   // index in its time's slot list (-1: block not part of the residual)
+  int slot_cam, slot_marker;   // index in its time's slot list (-1: block not part of the residual; -2 - j: a constant block, the
+                               // time's j-th pose-only slot, ConstSlotPose)
   int col_cam, col_marker;     // first column in the reduced system (-1)
   int camera, pad;             // camera index of the detection (its intrinsics), whether or not the camera pose is a parameter
 };
@@ -157,6 +158,11 @@ struct ElimArgs {
   double* __restrict__ tdata;          // [T][48]: E (36), g_t (6)
   double* __restrict__ part;           // [G][RedLayout(nr).size()]; S lower triangle only
   IterParams ip;
+  // kConst instances only: the times' pose-only slots (full offsets of their constant camera / marker blocks) and constant flags
+  const int* __restrict__ cs_ptr;      // [T + 1]
+  const int* __restrict__ cs_full;
+  const int* __restrict__ tconst;      // [T]
+  int pmax;                            // the widest pose cache (free + pose-only slots); dmax stays the widest free part
 };
 
 #ifdef RSBA_PROFILE_PHASES
@@ -171,7 +177,12 @@ __device__ long long g_mt_cycles[16];
 
 __device__ __forceinline__ int LocalColumn(int slot, int q, int sc, int sm) { return slot == sc ? q : (slot == sm ? 12 + q : -1); }
 
-template <bool kLdsS>
+// Constant camera / marker blocks have no column but their transform is applied: a time's constant blocks get pose-only slots
+// behind its nslot free ones (slot -2 - j in TimeSlots -> pose-cache entry nslot + j, ConstSlotPose).  A time's constant flag
+// eliminates it with E = 0 (infinitely stiff): no step, no W'EW, its rows still add U and g_r.
+__device__ __forceinline__ int ConstSlotPose(int slot, int nslot) { return nslot - 2 - slot; }
+
+template <bool kLdsS, bool kConst = false>
 __global__ void __launch_bounds__(RSBA_MT_THREADS)
 k_time_eliminate(ElimArgs a) {
   extern __shared__ double lds[];
@@ -191,8 +202,8 @@ k_time_eliminate(ElimArgs a) {
   int* kb = mk + dmax / 6 + 1;            //   where the slot's block sits in a residual's Jacobian: column 0 (camera) or 12 (marker)
   // the chunk's sum of S (packed lower triangle) and of the three vectors: in LDS when they fit, else straight in the workgroup's partial system
   // pose constants of the current time: the time pose, then one per slot (camera / marker block of the time)
-  double* pcl = (double*)(sl + ((2 * RSBA_MT_TILE + 3 * (dmax / 6 + 1) + 1) & ~1));   // [dmax / 6 + 2][CC_STRIDE]
-  double* Sl = pcl + (size_t)(dmax / 6 + 2) * CC_STRIDE;
+  double* pcl = (double*)(sl + ((2 * RSBA_MT_TILE + 3 * (dmax / 6 + 1) + 1) & ~1));   // [dmax / 6 + 2][CC_STRIDE] (kConst: pmax + 2)
+  double* Sl = pcl + (size_t)((kConst ? a.pmax : dmax / 6) + 2) * CC_STRIDE;
   double* P = a.part + (size_t)blockIdx.x * RL.size();
   double* Sacc = kLdsS ? Sl : P + RL.S();
   const size_t nacc = RL.packed() + 3 * (size_t)nr;   // S, then the three vectors behind it (PartLayout): all of them in LDS or none
@@ -226,10 +237,19 @@ k_time_eliminate(ElimArgs a) {
     for (int e = tid; e < d; e += RSBA_MT_THREADS) Gr[e] = 0.0;
     if (tid < 43) Vs[tid] = 0.0;
     for (int e = tid; e < nslot; e += RSBA_MT_THREADS) scol[e] = a.slot_col[s0 + e];
-    for (int e = tid; e < (nslot + 1) * CC_STRIDE; e += RSBA_MT_THREADS) {
-      const int ps = e / CC_STRIDE, q = e - ps * CC_STRIDE;
-      const int pose = (ps == 0 ? a.time_full[t] : a.col_full[a.slot_col[s0 + ps - 1]]) / 6;
-      pcl[e] = a.posec[(size_t)pose * CC_STRIDE + q];
+    if constexpr (kConst) {
+      const int c0 = a.cs_ptr[t], npose = nslot + a.cs_ptr[t + 1] - c0;
+      for (int e = tid; e < (npose + 1) * CC_STRIDE; e += RSBA_MT_THREADS) {
+        const int ps = e / CC_STRIDE, q = e - ps * CC_STRIDE;
+        const int pose = (ps == 0 ? a.time_full[t] : (ps <= nslot ? a.col_full[a.slot_col[s0 + ps - 1]] : a.cs_full[c0 + ps - 1 - nslot])) / 6;
+        pcl[e] = a.posec[(size_t)pose * CC_STRIDE + q];
+      }
+    } else {
+      for (int e = tid; e < (nslot + 1) * CC_STRIDE; e += RSBA_MT_THREADS) {
+        const int ps = e / CC_STRIDE, q = e - ps * CC_STRIDE;
+        const int pose = (ps == 0 ? a.time_full[t] : a.col_full[a.slot_col[s0 + ps - 1]]) / 6;
+        pcl[e] = a.posec[(size_t)pose * CC_STRIDE + q];
+      }
     }
     const int ntile = (nobs + RSBA_MT_TILE - 1) / RSBA_MT_TILE;
     auto stage = [&](int tile) {
@@ -247,8 +267,12 @@ k_time_eliminate(ElimArgs a) {
         if (sb_i < RSBA_ABL_STAGE * nb) {
           const double hs = a.half_side;
           const double cx = (sk == 0 || sk == 3) ? -hs : hs, cy = sk < 2 ? hs : -hs;
-          MarkerCornerJacobianPart(sp, slot_cam >= 0 ? pcl + (size_t)(1 + slot_cam) * CC_STRIDE : nullptr, pcl,
-                                   slot_marker >= 0 ? pcl + (size_t)(1 + slot_marker) * CC_STRIDE : nullptr,
+          auto pose_of = [&](int slot) -> const double* {
+            if (slot >= 0) return pcl + (size_t)(1 + slot) * CC_STRIDE;
+            if (kConst && slot <= -2) return pcl + (size_t)(1 + ConstSlotPose(slot, nslot)) * CC_STRIDE;
+            return nullptr;
+          };
+          MarkerCornerJacobianPart(sp, pose_of(slot_cam), pcl, pose_of(slot_marker),
                                    fx, fy, ppx, ppy, cx, cy, u, v, rt + sb_i * 8 + 2 * sk, Jt + sb_i * RSBA_MT_JLD + 36 * sk);
           if (sp == 0 && sk == 0) { sl[2 * sb_i] = slot_cam; sl[2 * sb_i + 1] = slot_marker; }
         }
@@ -381,7 +405,13 @@ k_time_eliminate(ElimArgs a) {
     __syncthreads();
     RSBA_MT_STAMP(2);
     // ---- E = (V + D)^-1, E g_t: the first wavefront (the residual blocks' products are dead: the damped block and the inverse's scratch)
-    if (tid < 64) {
+    const bool tcon = kConst && a.tconst[t] != 0;
+    if (kConst && tcon) {
+      // a constant time: E = 0, E g_t = 0 (so Y = 0 and no correction below); only its cost counts
+      if (tid < 36) { Vs[48 + tid] = 0.0; a.tdata[(size_t)t * 48 + tid] = 0.0; }
+      if (tid < 6) { Vs[84 + tid] = 0.0; a.tdata[(size_t)t * 48 + 36 + tid] = Vs[36 + tid]; }
+      cost += Vs[42];
+    } else if (tid < 64) {
       double* Vd = PA + 36;
       double sc = 1.0;
       if (tid < 6) {
@@ -784,14 +814,15 @@ k_marker_chol_finish(int nr, const double* __restrict__ red, double* __restrict_
 // Per workgroup (four times): |delta_t|^2, |x_t + delta_t|^2, model cost change, candidate sum of squares.
 // kLoss: the rows scaled by sqrt(rho') at x (wsq, k_mc_block_weight); the candidate's raw sum as without a loss, the workgroup's
 // rho(s_c) - s_c to drho_c[blockIdx.x] (k_marker_schur_finish<true>).
-template <bool kLoss>
+// kConst: a constant time (tconst[t]) takes a zero step (E = 0) and its |x_t|^2 stays out of the candidate's norm.
+template <bool kLoss, bool kConst = false>
 __global__ void __launch_bounds__(256)
 k_time_backsub_terms(int T, const int* __restrict__ time_ptr, const int* __restrict__ time_full, const TimeSlots* __restrict__ ts,
                      const MarkerObs* __restrict__ mo, const double* __restrict__ obs8, const double* __restrict__ intr, double half_side,
                      const double* __restrict__ posec /* pose constants at x */, const double* __restrict__ tdata,
                      const double* __restrict__ delta_r, const double* __restrict__ params_x, double* __restrict__ params_c,
                      double* __restrict__ delta_t, double* __restrict__ bpart /* gridDim.x x 4 */, double loss = 0.0,
-                     const double* __restrict__ wsq = nullptr, double* __restrict__ drho_c = nullptr) {
+                     const double* __restrict__ wsq = nullptr, double* __restrict__ drho_c = nullptr, const int* __restrict__ tconst = nullptr) {
   __shared__ double s_part[4][4];
   __shared__ double s_dcc[kLoss ? 4 : 1];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -845,6 +876,7 @@ k_time_backsub_terms(int T, const int* __restrict__ time_ptr, const int* __restr
       tc[a] = params_x[tf + a] + dt[a];
       d2 += dt[a] * dt[a]; xc2 += tc[a] * tc[a];   // identical in every lane; lane 0's copy is used
     }
+    if constexpr (kConst) { if (tconst[t]) xc2 = 0.0; }
     if (lane < 6) {
       double dsel = dt[0], csel = tc[0];
 #pragma unroll
@@ -944,14 +976,17 @@ __global__ void __launch_bounds__(64) k_pose_constants_reduced(int nred_poses, c
 // registers — J_r delta_r, the residual and the time block's two rows: 16 doubles a corner — so the rows are formed once; the
 // candidate's cameras and markers come as rotation matrices (k_pose_constants_reduced), the time's own is formed once per lane.
 // Sums in a fixed order: lanes by butterfly, the four wavefronts in order.  bpart: one entry (4 doubles) per time.
-template <int kPer, int kThreads>
+// kConst: the time's constant camera / marker blocks as pose-only slots behind the free ones (cs_ptr / cs_full: ElimArgs); their
+// candidate is their pose at x.
+template <int kPer, int kThreads, bool kConst = false>
 __global__ void __launch_bounds__(kThreads)
 k_time_backsub_wg(int T, const int* __restrict__ time_ptr, const int* __restrict__ time_full, const TimeSlots* __restrict__ ts,
                   const MarkerObs* __restrict__ mo, const double* __restrict__ obs8, const double* __restrict__ intr, double half_side,
                   const double* __restrict__ posec /* pose constants at x */, const double* __restrict__ posec_c /* candidate: cameras, markers */,
                   const double* __restrict__ tdata, const double* __restrict__ delta_r, const double* __restrict__ params_x,
                   double* __restrict__ params_c, double* __restrict__ delta_t, double* __restrict__ bpart /* T x 4 */,
-                  const int* __restrict__ slot_ptr, const int* __restrict__ slot_col, const int* __restrict__ col_full) {
+                  const int* __restrict__ slot_ptr, const int* __restrict__ slot_col, const int* __restrict__ col_full,
+                  const int* __restrict__ cs_ptr = nullptr, const int* __restrict__ cs_full = nullptr, const int* __restrict__ tconst = nullptr) {
   constexpr int kWaves = kThreads / 64;
   __shared__ double s_h[kWaves][8];
   extern __shared__ double s_tab[];
@@ -962,18 +997,33 @@ k_time_backsub_wg(int T, const int* __restrict__ time_ptr, const int* __restrict
   // pose constants at x of the time (row 0) and of its slots' cameras / markers, the candidate's rotation and translation of
   // the slots, the slots' part of delta_r
   const int s0 = slot_ptr[t], nslot = slot_ptr[t + 1] - s0;
-  double* s_pc = s_tab;                                  // [(nslot + 1)][CC_STRIDE]
-  double* s_cd = s_pc + (size_t)(nslot + 1) * CC_STRIDE;   // [nslot][12]
-  double* s_dr = s_cd + (size_t)nslot * 12;               // [nslot][6]
-  for (int e = tid; e < (nslot + 1) * CC_STRIDE; e += kThreads) {
-    const int ps = e / CC_STRIDE, q = e - ps * CC_STRIDE;
-    const int pose = (ps == 0 ? tf : col_full[slot_col[s0 + ps - 1]]) / 6;
-    s_pc[e] = posec[(size_t)pose * CC_STRIDE + q];
-  }
-  for (int e = tid; e < nslot * 12; e += kThreads) {
-    const int ps = e / 12, q = e - 12 * ps;
-    const int pose = col_full[slot_col[s0 + ps]] / 6;
-    s_cd[e] = posec_c[(size_t)pose * CC_STRIDE + (q < 9 ? CC_R + q : CC_T + q - 9)];
+  const int c0 = kConst ? cs_ptr[t] : 0, npose = kConst ? nslot + cs_ptr[t + 1] - c0 : nslot;   // (kConst: the pose-only slots behind)
+  double* s_pc = s_tab;                                  // [(npose + 1)][CC_STRIDE]
+  double* s_cd = s_pc + (size_t)(npose + 1) * CC_STRIDE;   // [npose][12]
+  double* s_dr = s_cd + (size_t)npose * 12;               // [nslot][6]
+  if constexpr (kConst) {
+    for (int e = tid; e < (npose + 1) * CC_STRIDE; e += kThreads) {
+      const int ps = e / CC_STRIDE, q = e - ps * CC_STRIDE;
+      const int pose = (ps == 0 ? tf : (ps <= nslot ? col_full[slot_col[s0 + ps - 1]] : cs_full[c0 + ps - 1 - nslot])) / 6;
+      s_pc[e] = posec[(size_t)pose * CC_STRIDE + q];
+    }
+    for (int e = tid; e < npose * 12; e += kThreads) {
+      const int ps = e / 12, q = e - 12 * ps;
+      const bool fr = ps < nslot;
+      const int pose = (fr ? col_full[slot_col[s0 + ps]] : cs_full[c0 + ps - nslot]) / 6;
+      s_cd[e] = (fr ? posec_c : posec)[(size_t)pose * CC_STRIDE + (q < 9 ? CC_R + q : CC_T + q - 9)];
+    }
+  } else {
+    for (int e = tid; e < (nslot + 1) * CC_STRIDE; e += kThreads) {
+      const int ps = e / CC_STRIDE, q = e - ps * CC_STRIDE;
+      const int pose = (ps == 0 ? tf : col_full[slot_col[s0 + ps - 1]]) / 6;
+      s_pc[e] = posec[(size_t)pose * CC_STRIDE + q];
+    }
+    for (int e = tid; e < nslot * 12; e += kThreads) {
+      const int ps = e / 12, q = e - 12 * ps;
+      const int pose = col_full[slot_col[s0 + ps]] / 6;
+      s_cd[e] = posec_c[(size_t)pose * CC_STRIDE + (q < 9 ? CC_R + q : CC_T + q - 9)];
+    }
   }
   for (int e = tid; e < nslot * 6; e += kThreads) { const int ps = e / 6; s_dr[e] = delta_r[slot_col[s0 + ps] + (e - 6 * ps)]; }
   // (lanes 0..5: their row of E, g_t and the time's parameters, wanted between the passes)
@@ -1001,9 +1051,11 @@ k_time_backsub_wg(int T, const int* __restrict__ time_ptr, const int* __restrict
       double dc[6], dm[6];
 #pragma unroll
       for (int x = 0; x < 6; ++x) { dc[x] = sl.slot_cam >= 0 ? s_dr[6 * sl.slot_cam + x] : 0.0; dm[x] = sl.slot_marker >= 0 ? s_dr[6 * sl.slot_marker + x] : 0.0; }
-      const double* pcc = sl.slot_cam >= 0 ? s_pc + (size_t)(1 + sl.slot_cam) * CC_STRIDE : nullptr;
+      const double* pcc = sl.slot_cam >= 0 ? s_pc + (size_t)(1 + sl.slot_cam) * CC_STRIDE
+                          : (kConst && sl.slot_cam <= -2 ? s_pc + (size_t)(1 + ConstSlotPose(sl.slot_cam, nslot)) * CC_STRIDE : nullptr);
       const double* pct = s_pc;
-      const double* pcm = sl.slot_marker >= 0 ? s_pc + (size_t)(1 + sl.slot_marker) * CC_STRIDE : nullptr;
+      const double* pcm = sl.slot_marker >= 0 ? s_pc + (size_t)(1 + sl.slot_marker) * CC_STRIDE
+                          : (kConst && sl.slot_marker <= -2 ? s_pc + (size_t)(1 + ConstSlotPose(sl.slot_marker, nslot)) * CC_STRIDE : nullptr);
       double rr[2], Jc[36];
       MarkerCornerResidualJacobian(pcc, pct, pcm, intr + 4 * sl.camera, (k == 0 || k == 3) ? -half_side : half_side, k < 2 ? half_side : -half_side,
                                    obs8[8 * (size_t)i + 2 * k], obs8[8 * (size_t)i + 2 * k + 1], rr, Jc);
@@ -1058,7 +1110,7 @@ k_time_backsub_wg(int T, const int* __restrict__ time_ptr, const int* __restrict
     double d2 = 0.0, xc2 = 0.0;
 #pragma unroll
     for (int a = 0; a < 6; ++a) { d2 += dt[a] * dt[a]; xc2 += tc[a] * tc[a]; }
-    s_n2[0] = d2; s_n2[1] = xc2;
+    s_n2[0] = d2; s_n2[1] = (kConst && tconst[t]) ? 0.0 : xc2;
   }
   // pass 2: the model cost change from what the lane kept (while one lane forms the candidate's rotation matrix), then the
   // candidate's residuals with the candidate's rotation matrices
@@ -1093,8 +1145,10 @@ k_time_backsub_wg(int T, const int* __restrict__ time_ptr, const int* __restrict
         pt[0] = a0 + tr[0]; pt[1] = a1 + tr[1]; pt[2] = a2 + tr[2];
       };
       if (sl.slot_marker >= 0) { const double* pc = s_cd + 12 * sl.slot_marker; apply(pc, pc + 9); }
+      else if (kConst && sl.slot_marker <= -2) { const double* pc = s_cd + 12 * ConstSlotPose(sl.slot_marker, nslot); apply(pc, pc + 9); }
       apply(Rt, tc + 3);
       if (sl.slot_cam >= 0) { const double* pc = s_cd + 12 * sl.slot_cam; apply(pc, pc + 9); }
+      else if (kConst && sl.slot_cam <= -2) { const double* pc = s_cd + 12 * ConstSlotPose(sl.slot_cam, nslot); apply(pc, pc + 9); }
       const double r0 = fx * pt[0] / pt[2] + ppx - obs8[8 * (size_t)i + 2 * k];
       const double r1 = fy * pt[1] / pt[2] + ppy - obs8[8 * (size_t)i + 2 * k + 1];
       cc += r0 * r0 + r1 * r1;
@@ -1202,11 +1256,17 @@ struct MarkerSchurDevice {
   int tc_np = 0, tc_nrt = 0, tc_tiles = 0, tc_tag = 0;
   size_t lds_elim = 0;
   bool lds_s = false;   // the chunk sums of S live in LDS
+  // constant blocks (Upload): the kConst instances run when a residual names a constant camera, marker or time block
+  bool has_const = false;
+  int pmax = 0;         // widest pose cache of a time: its free slots and its pose-only (constant) slots
+  int ncpose = 0;       // constant camera / marker poses some residual applies
+  int *cs_ptr = nullptr, *cs_full = nullptr, *tconst = nullptr, *cpose_full = nullptr;
 
   void Free() {
     void* ptrs[] = {mo, ts, chunk_ptr, time_ptr, slot_ptr, slot_col, time_full, col_full, ok_flag, obs8, intr, params[0], params[1],
                     params0, posec, posec_c, ss_x, scale_t, scale_r, tdata, part, red, A, Wm, delta_r, delta_t, bp_time, solve_out, res, tc_flags, tc_hand, tc_map,
-                    slot_order, slot_time, sb_ptr, sb_blk, xi_ptr, xi_blk, xi_cc, xi_cm, xc_ptr, sp, xout, tscal, blk_time, x_order, wsq, drho, drho_c};
+                    slot_order, slot_time, sb_ptr, sb_blk, xi_ptr, xi_blk, xi_cc, xi_cm, xc_ptr, sp, xout, tscal, blk_time, x_order, wsq, drho, drho_c,
+                    cs_ptr, cs_full, tconst, cpose_full};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     mo = nullptr; ts = nullptr;
     for (auto& q : fork_s) if (q) { (void)hipStreamDestroy(q); q = nullptr; }
@@ -1221,6 +1281,11 @@ struct MarkerSchurDevice {
     return 6 * nblocks > RSBA_CHOL_MAXN;
   }
 
+  // Constant blocks (block_constant, Ceres' SetParameterBlockConstant): a constant camera or marker has no reduced column; a time's
+  // constant cameras and markers are its pose-only slots, behind its free slots (ConstSlotPose).  The width rule: a time's pose cache —
+  // its distinct camera and marker blocks, free or constant — holds at most RSBA_MT_MAXD / 6 = 170 entries; the split accumulation's
+  // LDS bound counts the free ones (columns) only.  A constant time is eliminated with E = 0.  No free camera or marker at all (n_r = 0):
+  // every time is eliminated on its own and the reduced solve is skipped.
   // loss: a robust loss is set.  Its rows are formed by the split kernels only (round 4's k_time_eliminate and k_time_backsub_wg spread a
   // residual block's corners over lanes and have no block-wide s): RSBA_MT_SPLIT=0 and RSBA_MT_BACKSUB_WG are not taken then, and a problem
   // whose times are too wide for the split accumulation returns RSBA_ERR_UNSUPPORTED (the solver takes the dense path).
@@ -1229,7 +1294,8 @@ struct MarkerSchurDevice {
     N = (int)p.num_observations; nfull = (int)p.parameters.size(); half_side = p.marker_side / 2;
     if (N <= 0) return RSBA_ERR_ARG;
     const int C = p.num_cameras, Tn = p.num_times, M = p.num_markers;
-    // reduced blocks: the cameras and markers some residual uses, cameras first
+    auto is_const = [&](int block) { return block < (int)p.block_constant.size() && p.block_constant[block] != 0; };
+    // reduced blocks: the free cameras and markers some residual uses, cameras first
     std::vector<int> red_col(C + M, -1);
     std::vector<char> used(C + M, 0), tused(Tn, 0);
     for (int i = 0; i < N; ++i) {
@@ -1239,16 +1305,15 @@ struct MarkerSchurDevice {
     }
     std::vector<int> cf;
     int K = 0;
-    for (int b = 0; b < C + M; ++b) if (used[b]) {
+    for (int b = 0; b < C + M; ++b) if (used[b] && !is_const(b < C ? b : Tn + b)) {
       red_col[b] = 6 * K++;
       const int full = 6 * (b < C ? b : Tn + b);   // [C | T | M] x 6
       for (int q = 0; q < 6; ++q) cf.push_back(full + q);
     }
-    nr = 6 * K;
-    if (nr == 0) return RSBA_ERR_UNSUPPORTED;   // nothing but time blocks: the dense path handles it
-    std::vector<int> tid_of(Tn, -1), tfull;
+    nr = 6 * K;   // (0: nothing but time blocks are free)
+    std::vector<int> tid_of(Tn, -1), tfull, htc;
     T = 0;
-    for (int t = 0; t < Tn; ++t) if (tused[t]) { tid_of[t] = T++; tfull.push_back(6 * (C + t)); }
+    for (int t = 0; t < Tn; ++t) if (tused[t]) { tid_of[t] = T++; tfull.push_back(6 * (C + t)); htc.push_back(is_const(C + t) ? 1 : 0); }
     // residual blocks in time order (stable)
     std::vector<int> order(N);
     for (int i = 0; i < N; ++i) order[i] = i;
@@ -1259,17 +1324,30 @@ struct MarkerSchurDevice {
     std::vector<double> hobs(8 * (size_t)N);
     for (int k = 0; k < N; ++k) tptr[tid_of[p.time_index[order[k]]] + 1]++;
     for (int t = 0; t < T; ++t) tptr[t + 1] += tptr[t];
-    dmax = 0;
+    dmax = 0; pmax = 0;
     std::vector<double> work(T);
+    std::vector<int> csptr(T + 1, 0), csfull;
+    std::vector<char> cpose_seen(C + M, 0);
+    std::vector<int> hcpose;
     for (int t = 0; t < T; ++t) {
-      std::vector<int> cols;
+      std::vector<int> cols, cfl;   // the time's free slots (reduced columns) and pose-only slots (full offsets of constant blocks)
       for (int k = tptr[t]; k < tptr[t + 1]; ++k) {
         const int i = order[k];
-        if (p.uses_camera(i)) cols.push_back(red_col[p.camera_index[i]]);
-        if (p.uses_marker(i)) cols.push_back(red_col[C + p.marker_index[i]]);
+        if (p.uses_camera(i)) {
+          const int b = p.camera_index[i];
+          if (red_col[b] >= 0) cols.push_back(red_col[b]);
+          else { cfl.push_back(6 * p.camera_block(i)); if (!cpose_seen[b]) { cpose_seen[b] = 1; hcpose.push_back(6 * p.camera_block(i)); } }
+        }
+        if (p.uses_marker(i)) {
+          const int b = C + p.marker_index[i];
+          if (red_col[b] >= 0) cols.push_back(red_col[b]);
+          else { cfl.push_back(6 * p.marker_block(i)); if (!cpose_seen[b]) { cpose_seen[b] = 1; hcpose.push_back(6 * p.marker_block(i)); } }
+        }
       }
       std::sort(cols.begin(), cols.end());
       cols.erase(std::unique(cols.begin(), cols.end()), cols.end());
+      std::sort(cfl.begin(), cfl.end());
+      cfl.erase(std::unique(cfl.begin(), cfl.end()), cfl.end());
       {
         // the kernel relies on one residual block per (time, camera, marker); the same detection listed twice goes to
         // the dense path
@@ -1288,21 +1366,29 @@ struct MarkerSchurDevice {
         s.col_cam = p.uses_camera(i) ? red_col[p.camera_index[i]] : -1;
         s.col_marker = p.uses_marker(i) ? red_col[C + p.marker_index[i]] : -1;
         s.camera = p.camera_index[i]; s.pad = 0;
-        s.slot_cam = s.col_cam >= 0 ? (int)(std::lower_bound(cols.begin(), cols.end(), s.col_cam) - cols.begin()) : -1;
-        s.slot_marker = s.col_marker >= 0 ? (int)(std::lower_bound(cols.begin(), cols.end(), s.col_marker) - cols.begin()) : -1;
+        auto const_slot = [&](int full) { return -2 - (int)(std::lower_bound(cfl.begin(), cfl.end(), full) - cfl.begin()); };
+        s.slot_cam = s.col_cam >= 0 ? (int)(std::lower_bound(cols.begin(), cols.end(), s.col_cam) - cols.begin()) : (o.full_cam >= 0 ? const_slot(o.full_cam) : -1);
+        s.slot_marker = s.col_marker >= 0 ? (int)(std::lower_bound(cols.begin(), cols.end(), s.col_marker) - cols.begin())
+                                          : (o.full_marker >= 0 ? const_slot(o.full_marker) : -1);
         memcpy(&hobs[8 * (size_t)k], &p.observations[8 * (size_t)i], 8 * sizeof(double));
       }
       sptr[t + 1] = sptr[t] + (int)cols.size();
       scol.insert(scol.end(), cols.begin(), cols.end());
+      csptr[t + 1] = csptr[t] + (int)cfl.size();
+      csfull.insert(csfull.end(), cfl.begin(), cfl.end());
       const int d = 6 * (int)cols.size();
       dmax = std::max(dmax, d);
+      pmax = std::max(pmax, (int)(cols.size() + cfl.size()));
       work[t] = (double)d * d * (1.0 + 0.25 * (tptr[t + 1] - tptr[t])) + 2000.0;
     }
-    if (dmax > RSBA_MT_MAXD) return RSBA_ERR_UNSUPPORTED;
+    if (6 * pmax > RSBA_MT_MAXD) return RSBA_ERR_UNSUPPORTED;
+    ncpose = (int)hcpose.size();
+    has_const = ncpose > 0 || std::find(htc.begin(), htc.end(), 1) != htc.end();
+    const int npc = has_const ? pmax : dmax / 6;   // k_time_eliminate's pose cache holds the pose-only slots too; its other tables are the free columns'
     // chunks of consecutive times, balanced by work; the partial systems together stay below 2 GB
     const RedLayout RL{nr};
     const PartLayout PL{nr};
-    lds_elim = (size_t)(13 * dmax + 96 + RSBA_MT_TILE * (RSBA_MT_JLD + 9) + (dmax / 6 + 2) * CC_STRIDE) * sizeof(double) + (size_t)(2 * RSBA_MT_TILE + 3 * (dmax / 6 + 1) + 2) * sizeof(int);
+    lds_elim = (size_t)(13 * dmax + 96 + RSBA_MT_TILE * (RSBA_MT_JLD + 9) + (npc + 2) * CC_STRIDE) * sizeof(double) + (size_t)(2 * RSBA_MT_TILE + 3 * (dmax / 6 + 1) + 2) * sizeof(int);
     lds_s = lds_elim + (PL.packed() + 3 * (size_t)nr) * sizeof(double) <= 156 * 1024;
     if (lds_s) lds_elim += (PL.packed() + 3 * (size_t)nr) * sizeof(double);
     const bool lds_s_elim = lds_s;   // (k_time_eliminate's own choice, should the split kernels not take the problem)
@@ -1352,12 +1438,12 @@ struct MarkerSchurDevice {
     // the split elimination's tables: a (time, slot)'s residual blocks, the thread order, the camera-marker pairs of every chunk
     std::vector<int> h_slot_time, h_sb_ptr, h_order, h_xi_ptr, h_xi_cc, h_xi_cm, h_xc_ptr, h_xorder;
     std::vector<int4> h_sb_blk, h_xi_blk;
-    auto pose_of_col = [&](int col) { return col >= 0 ? cf[col] / 6 : -1; };   // reduced column -> pose in the parameter array
+    auto pose_of_full = [](int full) { return full >= 0 ? full / 6 : -1; };   // full offset -> pose in the parameter array
     const int kShareFrom = 10;   // an item of k_mc_cross with this many residual blocks or more runs on two neighbouring lanes
     if (split) {
       nslots = (int)scol.size();
       ncam_cols = 0;
-      for (int b = 0; b < C; ++b) if (used[b]) ncam_cols += 6;
+      for (int b = 0; b < C; ++b) if (red_col[b] >= 0) ncam_cols += 6;   // (the free cameras: the reduced columns below the markers')
       h_slot_time.resize(nslots);
       h_sb_ptr.assign(nslots + 1, 0);
       for (int t = 0; t < T; ++t) {
@@ -1373,8 +1459,9 @@ struct MarkerSchurDevice {
         std::vector<int> fill(h_sb_ptr.begin(), h_sb_ptr.end() - 1);
         for (int t = 0; t < T; ++t)
           for (int k = tptr[t]; k < tptr[t + 1]; ++k) {
-            if (hts[k].slot_cam >= 0) h_sb_blk[fill[sptr[t] + hts[k].slot_cam]++] = int4{k, pose_of_col(hts[k].col_marker), hts[k].camera, 0};
-            if (hts[k].slot_marker >= 0) h_sb_blk[fill[sptr[t] + hts[k].slot_marker]++] = int4{k, pose_of_col(hts[k].col_cam), hts[k].camera, 0};
+            // (the other block's pose whether it is free or constant)
+            if (hts[k].slot_cam >= 0) h_sb_blk[fill[sptr[t] + hts[k].slot_cam]++] = int4{k, pose_of_full(hmo[k].full_marker), hts[k].camera, 0};
+            if (hts[k].slot_marker >= 0) h_sb_blk[fill[sptr[t] + hts[k].slot_marker]++] = int4{k, pose_of_full(hmo[k].full_cam), hts[k].camera, 0};
           }
       }
       h_order.resize(nslots);
@@ -1441,6 +1528,19 @@ struct MarkerSchurDevice {
         !up(params0, p.parameters.data(), nfull * 8))
       return RSBA_ERR_HIP;
     if (hipMemset(res, 0, RES_SIZE * 8) != hipSuccess) return RSBA_ERR_HIP;
+    if (has_const) {
+      std::vector<int> cpf(6 * (size_t)ncpose, 0);   // (k_pose_constants_reduced's layout: a pose's offset at every sixth entry)
+      for (int k = 0; k < ncpose; ++k) cpf[6 * (size_t)k] = hcpose[k];
+      if (!al((void**)&cs_ptr, (T + 1) * 4) || !al((void**)&cs_full, csfull.size() * 4) || !al((void**)&tconst, T * 4) || !al((void**)&cpose_full, cpf.size() * 4) ||
+          !up(cs_ptr, csptr.data(), (T + 1) * 4) || !up(cs_full, csfull.data(), csfull.size() * 4) || !up(tconst, htc.data(), T * 4) ||
+          !up(cpose_full, cpf.data(), cpf.size() * 4))
+        return RSBA_ERR_HIP;
+    }
+    if (nr == 0) {
+      // no reduced system: the solve's result block is that of an empty one, once
+      const double empty[5] = {0.0, 0.0, 0.0, 0.0, 1.0};
+      if (!up(solve_out, empty, sizeof(empty))) return RSBA_ERR_HIP;
+    }
     if (split) {
       if (!al((void**)&slot_order, (size_t)nslots * 4) || !al((void**)&x_order, (size_t)nx_threads * 4) || !al((void**)&slot_time, (size_t)nslots * 4) || !al((void**)&sb_ptr, ((size_t)nslots + 1) * 4) ||
           !al((void**)&sb_blk, h_sb_blk.size() * sizeof(int4)) || !al((void**)&xi_ptr, ((size_t)nx + 1) * 4) || !al((void**)&xi_blk, h_xi_blk.size() * sizeof(int4)) ||
@@ -1468,13 +1568,17 @@ struct MarkerSchurDevice {
       }
     }
     if (backsub_wg) {
-      const size_t lds_bw = (size_t)(dmax / 6 + 1) * (CC_STRIDE + 12 + 6) * sizeof(double);
-      if (lds_bw > 48 * 1024 && hipFuncSetAttribute((const void*)k_time_backsub_wg<2, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bw) != hipSuccess) return RSBA_ERR_HIP;
+      const size_t lds_bw = (size_t)(pmax + 1) * (CC_STRIDE + 12 + 6) * sizeof(double);
+      if (lds_bw > 48 * 1024 && hipFuncSetAttribute(has_const ? (const void*)k_time_backsub_wg<2, 256, true> : (const void*)k_time_backsub_wg<2, 256>,
+                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bw) != hipSuccess) return RSBA_ERR_HIP;
     }
     if (!split && lds_elim > 48 * 1024 &&
-        hipFuncSetAttribute(lds_s ? (const void*)k_time_eliminate<true> : (const void*)k_time_eliminate<false>,
+        hipFuncSetAttribute(has_const ? (lds_s ? (const void*)k_time_eliminate<true, true> : (const void*)k_time_eliminate<false, true>)
+                                      : (lds_s ? (const void*)k_time_eliminate<true> : (const void*)k_time_eliminate<false>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_elim) != hipSuccess) return RSBA_ERR_HIP;
-    if (nr <= RSBA_CHOL_MAXN) {
+    if (nr == 0) {
+      // (no reduced solve)
+    } else if (nr <= RSBA_CHOL_MAXN) {
       const size_t lds_c = std::max((size_t)4 * 1024, CholeskyLdsDoubles(nr)) * sizeof(double);
       if (lds_c > 48 * 1024 &&
           hipFuncSetAttribute((const void*)k_marker_reduced_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c) != hipSuccess) return RSBA_ERR_HIP;
@@ -1508,6 +1612,11 @@ struct MarkerSchurDevice {
   int Reset(hipStream_t st) {
     if (hipMemcpyAsync(params[0], params0, nfull * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return RSBA_ERR_HIP;
     if (hipMemcpyAsync(params[1], params0, nfull * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return RSBA_ERR_HIP;
+    if (ncpose > 0) {
+      // the constant cameras' and markers' candidate pose constants are those at x, for the whole run
+      k_pose_constants_reduced<<<(ncpose + 63) / 64, 64, 0, st>>>(ncpose, cpose_full, params0, posec_c);
+      if (hipGetLastError() != hipSuccess) return RSBA_ERR_HIP;
+    }
     cur = 0;
     return RSBA_OK;
   }
@@ -1532,7 +1641,8 @@ struct MarkerSchurDevice {
     Tm.Begin("k_pose_constants", st);
     k_pose_constants<<<(nfull / 6 + 255) / 256, 256, 0, st>>>(nfull / 6, params[x], posec);
     Tm.End(st);
-    ElimArgs ea{nr, dmax, (int)N, chunk_ptr, time_ptr, slot_ptr, slot_col, time_full, col_full, ts, mo, obs8, intr, posec, half_side, params[x], scale_t, tdata, part, ip};
+    ElimArgs ea{nr, dmax, (int)N, chunk_ptr, time_ptr, slot_ptr, slot_col, time_full, col_full, ts, mo, obs8, intr, posec, half_side, params[x], scale_t, tdata, part, ip,
+                cs_ptr, cs_full, tconst, pmax};
     if (split) {
       SplitArgs sa{nslots, T, nx, ncam_cols, nx_threads, slot_order, x_order, slot_time, slot_col, sb_ptr, sb_blk, time_ptr, time_full, col_full, ts, mo, obs8, intr, posec, half_side,
                    xi_ptr, xi_blk, xi_cc, xi_cm, sp, xout, wsq, drho};
@@ -1550,13 +1660,20 @@ struct MarkerSchurDevice {
         if (hipEventRecord(fork_ev[0], st) != hipSuccess || hipStreamWaitEvent(s_time, fork_ev[0], 0) != hipSuccess ||
             hipStreamWaitEvent(s_cross, fork_ev[0], 0) != hipSuccess) return RSBA_ERR_HIP;
       }
-      Tm.Begin("k_mc_slot_products", st);
-      if (with_loss) k_mc_slot_products<true><<<(nslots + 255) / 256, 256, 0, st>>>(sa);
-      else k_mc_slot_products<false><<<(nslots + 255) / 256, 256, 0, st>>>(sa);
-      Tm.End(st);
+      if (nslots > 0) {   // (none: n_r = 0)
+        Tm.Begin("k_mc_slot_products", st);
+        if (with_loss) k_mc_slot_products<true><<<(nslots + 255) / 256, 256, 0, st>>>(sa);
+        else k_mc_slot_products<false><<<(nslots + 255) / 256, 256, 0, st>>>(sa);
+        Tm.End(st);
+      }
       Tm.Begin("k_mc_time_products", st);
-      if (with_loss) k_mc_time_products<true><<<(T + 3) / 4, 256, 0, s_time>>>(sa, ip, params[x], scale_t, tdata, tscal);
-      else k_mc_time_products<false><<<(T + 3) / 4, 256, 0, s_time>>>(sa, ip, params[x], scale_t, tdata, tscal);
+      if (has_const) {
+        if (with_loss) k_mc_time_products<true, true><<<(T + 3) / 4, 256, 0, s_time>>>(sa, ip, params[x], scale_t, tdata, tscal, tconst);
+        else k_mc_time_products<false, true><<<(T + 3) / 4, 256, 0, s_time>>>(sa, ip, params[x], scale_t, tdata, tscal, tconst);
+      } else {
+        if (with_loss) k_mc_time_products<true><<<(T + 3) / 4, 256, 0, s_time>>>(sa, ip, params[x], scale_t, tdata, tscal);
+        else k_mc_time_products<false><<<(T + 3) / 4, 256, 0, s_time>>>(sa, ip, params[x], scale_t, tdata, tscal);
+      }
       Tm.End(st);
       if (nx > 0) {
         Tm.Begin("k_mc_cross", st);
@@ -1579,7 +1696,10 @@ struct MarkerSchurDevice {
       if (!chk("split elimination")) return RSBA_ERR_HIP;
     } else {
       Tm.Begin("k_time_eliminate", st);
-      if (lds_s) k_time_eliminate<true><<<G, RSBA_MT_THREADS, lds_elim, st>>>(ea);
+      if (has_const) {
+        if (lds_s) k_time_eliminate<true, true><<<G, RSBA_MT_THREADS, lds_elim, st>>>(ea);
+        else k_time_eliminate<false, true><<<G, RSBA_MT_THREADS, lds_elim, st>>>(ea);
+      } else if (lds_s) k_time_eliminate<true><<<G, RSBA_MT_THREADS, lds_elim, st>>>(ea);
       else k_time_eliminate<false><<<G, RSBA_MT_THREADS, lds_elim, st>>>(ea);
       Tm.End(st);
       if (!chk("k_time_eliminate")) return RSBA_ERR_HIP;
@@ -1587,7 +1707,9 @@ struct MarkerSchurDevice {
     Tm.Begin("k_marker_reduce", st);
     k_marker_reduce<<<(unsigned)((PartLayout{nr}.size() + 63) / 64), 512, 0, st>>>(nr, G, part, red);
     Tm.End(st);
-    if (nr <= RSBA_CHOL_MAXN) {
+    if (nr == 0) {
+      // nothing but time blocks are free: solve_out holds the empty system's result (Upload)
+    } else if (nr <= RSBA_CHOL_MAXN) {
       const size_t lds_c = std::max((size_t)4 * 1024, CholeskyLdsDoubles(nr)) * sizeof(double);
       Tm.Begin("k_marker_reduced_solve", st);
       if (solve_lds) k_marker_reduced_solve_lds<<<1, 512, MarkerSolveLdsDoubles(nr) * sizeof(double), st>>>(nr, red, A, scale_r, col_full, params[x], params[c], delta_r, solve_out, ip);
@@ -1621,8 +1743,9 @@ struct MarkerSchurDevice {
     if (!chk("reduced solve")) return RSBA_ERR_HIP;
     Tm.Begin("k_time_backsub_terms", st);
     if (split_backsub) {
-      k_pose_constants_reduced<<<(nr / 6 + 63) / 64, 64, 0, st>>>(nr / 6, col_full, params[c], posec_c);
-      k_mc_time_step<<<(8 * T + 255) / 256, 256, 0, st>>>(T, slot_ptr, slot_col, time_full, sp, tdata, delta_r, params[x], params[c], delta_t, posec_c, bp_time);
+      if (nr > 0) k_pose_constants_reduced<<<(nr / 6 + 63) / 64, 64, 0, st>>>(nr / 6, col_full, params[c], posec_c);
+      if (has_const) k_mc_time_step<true><<<(8 * T + 255) / 256, 256, 0, st>>>(T, slot_ptr, slot_col, time_full, sp, tdata, delta_r, params[x], params[c], delta_t, posec_c, bp_time, tconst);
+      else k_mc_time_step<<<(8 * T + 255) / 256, 256, 0, st>>>(T, slot_ptr, slot_col, time_full, sp, tdata, delta_r, params[x], params[c], delta_t, posec_c, bp_time);
       // the two halves of the candidate's evaluation side by side (one after the other when every kernel is timed)
       const bool fork2 = fork_s[0] != nullptr && !Tm.enabled();
       hipStream_t s_cost = fork2 ? fork_s[0] : st;
@@ -1636,14 +1759,24 @@ struct MarkerSchurDevice {
       }
       if (fork2 && (hipEventRecord(fork_ev[1], s_cost) != hipSuccess || hipStreamWaitEvent(st, fork_ev[1], 0) != hipSuccess)) return RSBA_ERR_HIP;
     } else if (backsub_wg) {
-      k_pose_constants_reduced<<<(nr / 6 + 63) / 64, 64, 0, st>>>(nr / 6, col_full, params[c], posec_c);
-      const size_t lds_bw = (size_t)(dmax / 6 + 1) * (CC_STRIDE + 12 + 6) * sizeof(double);   // the shot's tables (k_time_backsub_wg)
-      k_time_backsub_wg<2, 256><<<T, 256, lds_bw, st>>>(T, time_ptr, time_full, ts, mo, obs8, intr, half_side, posec, posec_c, tdata, delta_r, params[x],
-                                                   params[c], delta_t, bp_time, slot_ptr, slot_col, col_full);
+      if (nr > 0) k_pose_constants_reduced<<<(nr / 6 + 63) / 64, 64, 0, st>>>(nr / 6, col_full, params[c], posec_c);
+      const size_t lds_bw = (size_t)(pmax + 1) * (CC_STRIDE + 12 + 6) * sizeof(double);   // the shot's tables (k_time_backsub_wg)
+      if (has_const)
+        k_time_backsub_wg<2, 256, true><<<T, 256, lds_bw, st>>>(T, time_ptr, time_full, ts, mo, obs8, intr, half_side, posec, posec_c, tdata, delta_r, params[x],
+                                                           params[c], delta_t, bp_time, slot_ptr, slot_col, col_full, cs_ptr, cs_full, tconst);
+      else
+        k_time_backsub_wg<2, 256><<<T, 256, lds_bw, st>>>(T, time_ptr, time_full, ts, mo, obs8, intr, half_side, posec, posec_c, tdata, delta_r, params[x],
+                                                     params[c], delta_t, bp_time, slot_ptr, slot_col, col_full);
     } else {
-      if (with_loss)
+      if (with_loss && has_const)
+        k_time_backsub_terms<true, true><<<nb_time, 256, 0, st>>>(T, time_ptr, time_full, ts, mo, obs8, intr, half_side, posec, tdata, delta_r, params[x],
+                                                                  params[c], delta_t, bp_time, loss, wsq, drho_c, tconst);
+      else if (with_loss)
         k_time_backsub_terms<true><<<nb_time, 256, 0, st>>>(T, time_ptr, time_full, ts, mo, obs8, intr, half_side, posec, tdata, delta_r, params[x],
                                                             params[c], delta_t, bp_time, loss, wsq, drho_c);
+      else if (has_const)
+        k_time_backsub_terms<false, true><<<nb_time, 256, 0, st>>>(T, time_ptr, time_full, ts, mo, obs8, intr, half_side, posec, tdata, delta_r, params[x],
+                                                                   params[c], delta_t, bp_time, 0.0, nullptr, nullptr, tconst);
       else
         k_time_backsub_terms<false><<<nb_time, 256, 0, st>>>(T, time_ptr, time_full, ts, mo, obs8, intr, half_side, posec, tdata, delta_r, params[x],
                                                              params[c], delta_t, bp_time);

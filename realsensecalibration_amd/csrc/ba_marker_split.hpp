@@ -263,10 +263,12 @@ __global__ void __launch_bounds__(256) k_mc_slot_products(SplitArgs a) {
 }
 
 // Wavefront per time.  tdata[t]: E (36) | g_t (6) | E g_t (6); tscal[t]: sum r^2 (kLoss: + sum (rho(s) - s)), |x_t|^2, 1.0 if V + D is not
-// positive definite, max |g_t|.  kLoss: V, g_t and so the time's Jacobi scale from the corrected rows.
-template <bool kLoss>
+// positive definite, max |g_t|.  kLoss: V, g_t and so the time's Jacobi scale from the corrected rows.  kConst: the camera and marker
+// poses through the residual blocks' full offsets (a constant block has no column); a constant time (tconst[t] = 1) gets E = 0 and only
+// its cost.
+template <bool kLoss, bool kConst = false>
 __global__ void __launch_bounds__(256) k_mc_time_products(SplitArgs a, IterParams ip, const double* __restrict__ params_x, double* __restrict__ scale_t,
-                                                          double* __restrict__ tdata, double* __restrict__ tscal) {
+                                                          double* __restrict__ tdata, double* __restrict__ tscal, const int* __restrict__ tconst = nullptr) {
   __shared__ double s_v[4][3 * 36 + 8];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int t = blockIdx.x * 4 + wave;
@@ -280,8 +282,8 @@ __global__ void __launch_bounds__(256) k_mc_time_products(SplitArgs a, IterParam
   const double hs = a.half_side;
   for (int k = a.time_ptr[t] + lane; k < a.time_ptr[t + 1]; k += 64) {
     const TimeSlots s = a.ts[k];
-    const PoseC cam = LoadPose<false>(a.posec, s.col_cam >= 0 ? a.col_full[s.col_cam] / 6 : -1);
-    const PoseC mar = LoadPose<false>(a.posec, s.col_marker >= 0 ? a.col_full[s.col_marker] / 6 : -1);
+    const PoseC cam = LoadPose<false>(a.posec, kConst ? (a.mo[k].full_cam >= 0 ? a.mo[k].full_cam / 6 : -1) : (s.col_cam >= 0 ? a.col_full[s.col_cam] / 6 : -1));
+    const PoseC mar = LoadPose<false>(a.posec, kConst ? (a.mo[k].full_marker >= 0 ? a.mo[k].full_marker / 6 : -1) : (s.col_marker >= 0 ? a.col_full[s.col_marker] / 6 : -1));
     const double* in = a.intr + 4 * s.camera;
     const double fx = in[0], fy = in[1], ppx = in[2], ppy = in[3];
     const double* ob = a.obs8 + 8 * (size_t)k;
@@ -316,6 +318,16 @@ __global__ void __launch_bounds__(256) k_mc_time_products(SplitArgs a, IterParam
     if constexpr (kLoss) corr += __shfl_xor(corr, off, 64);
   }
   if constexpr (kLoss) ss += corr;
+  if constexpr (kConst) {
+    if (tconst[t]) {   // (wave-uniform)
+      double* td = tdata + (size_t)t * 48;
+      if (lane < 36) td[lane] = 0.0;
+#pragma unroll
+      for (int q = 0; q < 6; ++q) if (lane == q) { td[36 + q] = g[q]; td[42 + q] = 0.0; }
+      if (lane == 0) { tscal[4 * (size_t)t] = ss; tscal[4 * (size_t)t + 1] = 0.0; tscal[4 * (size_t)t + 2] = 0.0; tscal[4 * (size_t)t + 3] = 0.0; }
+      return;
+    }
+  }
   double* Vd = s_v[wave];        // V + D, row-major
   double* Mx = Vd + 36;          // scratch of the inverse
   double* E = Mx + 36;           // (V + D)^-1
@@ -758,10 +770,12 @@ __global__ void __launch_bounds__(RSBA_MT_THREADS) k_mc_accumulate_mfma(AccArgs 
 //   k_mc_candidate   thread per residual block: its rows once more for the model cost change -(J d).(r + J d / 2), the candidate's corners
 //                    through the candidate's rotation matrices; a workgroup's sums in a fixed order -> one entry of bp_time
 // bp_time: [T] (|delta_t|^2, |x_t + delta_t|^2, 0, 0), then one entry per workgroup of k_mc_candidate (0, 0, model cost change, sum r_c^2).
+// kConst: a constant time (tconst[t]; E = 0, a zero step) keeps its |x_t|^2 out of the candidate's norm.
+template <bool kConst = false>
 __global__ void __launch_bounds__(256) k_mc_time_step(int T, const int* __restrict__ slot_ptr, const int* __restrict__ slot_col, const int* __restrict__ time_full,
                                                       const double* __restrict__ sp, const double* __restrict__ tdata, const double* __restrict__ delta_r,
                                                       const double* __restrict__ params_x, double* __restrict__ params_c, double* __restrict__ delta_t,
-                                                      double* __restrict__ posec_c, double* __restrict__ bp_time) {
+                                                      double* __restrict__ posec_c, double* __restrict__ bp_time, const int* __restrict__ tconst = nullptr) {
   const int g = blockIdx.x * 256 + threadIdx.x, t = g >> 3, l = g & 7;
   if (t >= T) return;   // (whole groups of eight lanes)
   double h[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -806,7 +820,7 @@ __global__ void __launch_bounds__(256) k_mc_time_step(int T, const int* __restri
   for (int q = 0; q < 9; ++q) pc[CC_R + q] = cct[CC_R + q];
 #pragma unroll
   for (int q = 0; q < 3; ++q) pc[CC_T + q] = cct[CC_T + q];
-  bp_time[4 * (size_t)t] = d2; bp_time[4 * (size_t)t + 1] = xc2; bp_time[4 * (size_t)t + 2] = 0.0; bp_time[4 * (size_t)t + 3] = 0.0;
+  bp_time[4 * (size_t)t] = d2; bp_time[4 * (size_t)t + 1] = (kConst && tconst[t]) ? 0.0 : xc2; bp_time[4 * (size_t)t + 2] = 0.0; bp_time[4 * (size_t)t + 3] = 0.0;
 }
 
 // kPart 0: the model cost change (the block's rows at x: 340 registers, one wavefront a SIMD); 1: the candidate's residuals (rotation

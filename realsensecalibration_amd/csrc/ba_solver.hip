@@ -2491,6 +2491,13 @@ int rsba_solver_schedule_info(const rsba_solver* s, rsba_schedule_info* out) {
   return RSBA_OK;
 }
 
+int rsba_solver_time_elimination(const rsba_solver* s, int32_t* eliminates_times) {
+  if (!s || !eliminates_times) return RSBA_ERR_ARG;
+  if (s->prob->model == RSBA_MODEL_POINTS) return RSBA_ERR_UNSUPPORTED;
+  *eliminates_times = s->eliminate_times ? 1 : 0;
+  return RSBA_OK;
+}
+
 int rsba_solver_create(rsba_problem* p, const rsba_options* o, rsba_solver** out) {
   if (!p || !out) return RSBA_ERR_ARG;
   if (rsba::DeviceCount() <= 0) return RSBA_ERR_NO_DEVICE;
@@ -2532,11 +2539,10 @@ int rsba_solver_create(rsba_problem* p, const rsba_options* o, rsba_solver** out
     rc = rsba::UploadPoints(s);
     if (rc == RSBA_OK && s->tiled.tree_error) s->tiled.error_flag = reinterpret_cast<int*>(s->res_host + RES_SIZE + 4);   // (zeroed above)
   } else {
-    const bool any_const_block = std::find(p->block_constant.begin(), p->block_constant.end(), (uint8_t)1) != p->block_constant.end();
-    s->eliminate_times = !any_const_block && rsba::MarkerSchurDevice::Wanted(*p, opt.schur_impl);   // (constant blocks: the dense path)
+    s->eliminate_times = rsba::MarkerSchurDevice::Wanted(*p, opt.schur_impl);
     rc = s->eliminate_times ? s->marker_schur.Upload(*p, opt.huber_delta > 0.0) : s->marker.Upload(*p);
     if (s->eliminate_times && rc == RSBA_ERR_UNSUPPORTED) {
-      // duplicate detections, no camera / marker block at all, or a time wider than the kernel's LDS: the dense path is general
+      // duplicate detections, or a time wider than the kernels' LDS: the dense path is general
       s->marker_schur.Free();
       s->eliminate_times = false;
       rc = s->marker.Upload(*p);

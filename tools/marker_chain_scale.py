@@ -1,6 +1,9 @@
 """Marker-chain model at scale on the GPU: per-kernel times of the time-elimination path.
 
-    python tools/marker_chain_scale.py [C T M [huber|cauchy a]]        default 8 5000 16, no loss
+    python tools/marker_chain_scale.py [C T M [huber|cauchy a]] [const=SET] [schur_impl=K] [dump=PATH]
+        default 8 5000 16, no loss; SET: markers | cameras:K (cameras 1..K) | times:K (every T/K-th time) | rig (every camera
+        and marker: only the times are free), joined by '+' (e.g. cameras:2+times:100); dump=PATH writes the final parameters
+        and the iteration log (.npz) of the last unprofiled run
 """
 import json
 import os
@@ -12,21 +15,50 @@ import numpy as np  # noqa: E402
 
 from realsensecalibration_amd import capi, synthetic  # noqa: E402
 
-C_, T_, M_ = (int(v) for v in sys.argv[1:4]) if len(sys.argv) >= 4 else (8, 5000, 16)
-LOSS, LOSS_A = (sys.argv[4], float(sys.argv[5])) if len(sys.argv) >= 6 else ("none", 0.0)
+KW = dict(a.split("=", 1) for a in sys.argv[1:] if "=" in a)
+ARGS = [a for a in sys.argv[1:] if "=" not in a]
+C_, T_, M_ = (int(v) for v in ARGS[0:3]) if len(ARGS) >= 3 else (8, 5000, 16)
+LOSS, LOSS_A = (ARGS[3], float(ARGS[4])) if len(ARGS) >= 5 else ("none", 0.0)
+
+
+def constant_blocks(spec):
+    out = set()
+    for part in filter(None, spec.split("+")):
+        kind, _, k = part.partition(":")
+        if kind == "markers":
+            out |= {C_ + T_ + m for m in range(1, M_)}
+        elif kind == "cameras":
+            out |= set(range(1, int(k) + 1))
+        elif kind == "times":
+            out |= {C_ + t for t in range(0, T_, max(1, T_ // int(k)))}
+        elif kind == "rig":
+            out |= set(range(1, C_)) | {C_ + T_ + m for m in range(1, M_)}
+        else:
+            raise SystemExit("unknown constant set %r" % part)
+    return sorted(out)
+
+
+CONST = constant_blocks(KW.get("const", ""))
 LOSS_KW = {} if LOSS == "none" else {"huber_delta": LOSS_A, "loss_type": 1 if LOSS == "cauchy" else 0}
 t0 = time.time()
 prob = synthetic.make_marker_chain(C_, T_, M_, seed=11)
 gen = time.time() - t0
 p = capi.Problem.marker_chain(prob)
+for b in CONST:
+    p.set_parameter_block_constant(6 * b)
 out = {}
 for mode in (0, 1):
-    s = capi.Solver(p, capi.default_options(profile_kernels=mode, **LOSS_KW))
+    s = capi.Solver(p, capi.default_options(profile_kernels=mode, schur_impl=int(KW.get("schur_impl", 1)), **LOSS_KW))
     s.run()            # warm-up: code objects, allocations
     for _ in range(int(os.environ.get("MC_RUNS", "3")) - 1):   # (the kernel statistics include the warm-up's first launches: amortised)
         s.run()
     sm = s.run()
     if mode == 0:
+        out["constant_blocks"] = len(CONST)
+        out["eliminates_times"] = s.eliminates_times()
+        if "dump" in KW:
+            s.download()
+            np.savez(KW["dump"], params=p.params.copy(), iterations=s.iterations())
         out.update({"cameras": C_, "times": T_, "markers": M_, "residual_blocks": int(prob["N"]), "generate_s": round(gen, 2), "loss": LOSS, "loss_scale": LOSS_A,
                     "iterations": sm.num_iterations, "initial_cost": sm.initial_cost, "final_cost": sm.final_cost,
                     "minimizer_ms": 1e3 * sm.minimizer_seconds,
