@@ -305,6 +305,22 @@ int rsba_solver_point_covariances(const rsba_solver* s, double* out);
 int rsba_points_linearize_and_step(rsba_problem* p, const rsba_options* o, double radius, double* S,
                                    double* rhs, double* delta, double* scalars /* 8 */);
 
+/* Stage-level entry (tests): the first step rsba_solver_run would take on this problem, with these options and the RSBA_*
+ * environment — its schedule, factorisation and back-substitution — at the given radius.  Any output may be NULL.
+ *   S, rhs    as in rsba_points_linearize_and_step, formed again after the step from the reduced system the factorisation read
+ *   dcam      6C: the camera step as the kernels wrote it (= -scale_c * y, y the solution of S y = rhs)
+ *   scale_c   6C: the Jacobi scale of the step
+ *   delta     6C + 3P: x_candidate - x
+ *   scalars   [0..7] as in rsba_points_linearize_and_step, [7] the candidate's sum of squares;
+ *             [8] 1 pipelined schedule, 0 sequential; [9] factorisation: 0 one workgroup, 1 diagonal chain, 2 diagonal chain +
+ *             border, 3 persistent tiles at 64 cameras or fewer (RSBA_TILES_SMALL), 4 persistent tiles, 5 one launch per panel;
+ *             [10] its workgroups (5: of the first panel's launch); [11] the border's first column (2 only); [12] resident tiles; [13] back-substitution:
+ *             0 inside the factorisation, 1 one workgroup, 2 block owners, 3 chain with helpers; [14] 1: the tiles built the
+ *             system themselves; [15] stalls during the step; [16] fallbacks taken */
+#define RSBA_SOLVE_STAGE_SCALARS 17
+int rsba_points_solve_stage(rsba_problem* p, const rsba_options* o, double radius, double* S, double* rhs, double* dcam,
+                            double* scale_c, double* delta, double* scalars /* RSBA_SOLVE_STAGE_SCALARS */);
+
 /* Stage-level entry (tests): the payload the multi-GPU path all-reduces after one linearisation of this problem
  * (a rank's point shard, or the whole problem): S (6C)^2 unscaled / undamped, full symmetric | g_c (6C) | rhs
  * correction (6C) | diag U (6C) | 8 scalars (cost sum, |points|^2, failed point blocks, ...), followed by the one value

@@ -24,7 +24,7 @@ EXPORTS = [
     "rsba_problem_marker_idx", "rsba_problem_camera_parameters", "rsba_problem_marker_transform",
     "rsba_problem_point3d_coordinates", "rsba_options_default", "rsba_solve", "rsba_solver_create", "rsba_solver_run",
     "rsba_solver_download", "rsba_solver_iterations", "rsba_solver_kernel_stats", "rsba_solver_final_costs",
-    "rsba_solver_destroy", "rsba_points_linearize_and_step", "rsba_points_linearize_payload", "rsba_comm_unique_id", "rsba_comm_loopback_id", "rsba_read_intrinsics_xml",
+    "rsba_solver_destroy", "rsba_points_linearize_and_step", "rsba_points_solve_stage", "rsba_points_linearize_payload", "rsba_comm_unique_id", "rsba_comm_loopback_id", "rsba_read_intrinsics_xml",
     "rsba_write_outputs", "rsba_reprojection_error", "rsba_reprojection_check_files",
     "rsba_base_pose_from_marker_detection", "rsba_marker_pose_in_camera", "rsba_marker_corners_in_camera", "rsba_solve_pnp_epnp",
     "rsba_problem_initial_camera_poses", "rsba_problem_set_camera_constant", "rsba_problem_set_point_constant", "rsba_problem_set_parameter_block_constant", "rsba_solver_full_report", "rsba_solver_configure_run",
@@ -132,6 +132,7 @@ def load():
     lib.rsba_solver_time_elimination.argtypes = [C.c_void_p, C.c_void_p]
     lib.rsba_comm_shm_id.argtypes = [C.c_char_p, C.c_void_p]
     lib.rsba_points_linearize_and_step.argtypes = [C.c_void_p, C.c_void_p, C.c_double] + [C.c_void_p] * 4
+    lib.rsba_points_solve_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_double] + [C.c_void_p] * 6
     lib.rsba_points_linearize_payload.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int64, C.c_void_p]
     lib.rsba_comm_unique_id.argtypes = [C.c_void_p]
     lib.rsba_comm_loopback_id.argtypes = [C.c_void_p]
@@ -428,6 +429,31 @@ def points_linearize_and_step(prob, radius, opts=None):
         p.close()
     return dict(S=S, rhs=rhs, delta=delta, cost=scal[0], model_cost_change=scal[1], gradient_max_norm=scal[2],
                 solve_ok=bool(scal[3]), cost_candidate=scal[4], step_norm=scal[5], x_norm=scal[6])
+
+
+# rsba_points_solve_stage's path scalars (include/rsba.h)
+STAGE_FACTORISATIONS = ("one_wg", "diag", "diag_border", "tiles_small", "tiled", "multi_launch")
+STAGE_BACKSUBS = ("in_kernel", "one_wg", "multi", "chain")
+
+
+def points_solve_stage(prob, radius, opts=None):
+    """The first step rsba_solver_run takes on this problem (its own schedule and factorisation): S, rhs, dcam, scale_c, delta,
+    the step's scalars and the path that ran."""
+    p = Problem.points(prob)
+    nc, n = 6 * prob["C"], 6 * prob["C"] + 3 * prob["P"]
+    S, rhs, dcam, scale_c, delta, scal = np.zeros((nc, nc)), np.zeros(nc), np.zeros(nc), np.zeros(nc), np.zeros(n), np.zeros(17)
+    o = opts or default_options()
+    try:
+        _chk(load().rsba_points_solve_stage(p.h, C.byref(o), radius, _vp(S), _vp(rhs), _vp(dcam), _vp(scale_c), _vp(delta), _vp(scal)),
+             "rsba_points_solve_stage")
+    finally:
+        p.close()
+    path = dict(schedule="pipelined" if scal[8] else "sequential", factorisation=STAGE_FACTORISATIONS[int(scal[9])],
+                workgroups=int(scal[10]), border_cols=int(scal[11]), tiles=int(scal[12]), backsub=STAGE_BACKSUBS[int(scal[13])],
+                sys_fused=bool(scal[14]), stalls=int(scal[15]), fallbacks=int(scal[16]))
+    return dict(S=S, rhs=rhs, dcam=dcam, scale_c=scale_c, delta=delta, cost=scal[0], model_cost_change=scal[1],
+                gradient_max_norm=scal[2], solve_ok=bool(scal[3]), cost_candidate=scal[4], step_norm=scal[5], x_norm=scal[6],
+                path=path)
 
 
 def points_linearize_payload(prob, radius, opts=None):

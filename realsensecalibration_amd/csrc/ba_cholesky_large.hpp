@@ -2,7 +2,9 @@
 // 256-camera configuration): the matrix no longer fits one workgroup's LDS, so the factorisation is right-looking and
 // spread over the whole chip, one launch per 32-wide panel:
 //
-//   k_sys_build   <<<n+1 rows>>>   W = scaled, damped, mirrored system + rhs row (and the optional copies)
+//   k_sys_build   <<<n+1 rows>>>   W = scaled, damped, mirrored system + rhs row (and the optional copies); W == nullptr with
+//                                  ip.first == 0 and ok_flag == nullptr: the copies alone, from the scale already in
+//                                  scale_c and without touching the Cholesky status (rsba_points_solve_stage)
 //   k_chol_step   <<<tiles>>>      per panel kb: every workgroup factors the 32 x 32 diagonal block itself (redundantly:
 //                                  9 us of one wavefront, cheaper than another launch and a round trip through HBM),
 //                                  solves its own two 64-row strips of the panel against it on the matrix cores
@@ -28,12 +30,12 @@ k_sys_build(const double* __restrict__ red, RedLayout L, double* __restrict__ W 
   const int n = L.nc, tid = threadIdx.x;
   // at the first iteration the scale is defined here (from diagU) and nobody may read scale_c yet
   auto sc = [&](int i) { return ip.first ? (ip.jacobi_scaling ? 1.0 / (1.0 + sqrt(red[L.diagU() + i])) : 1.0) : scale_c[i]; };
-  if (blockIdx.x == 0 && tid == 0) *ok_flag = 1;
+  if (blockIdx.x == 0 && tid == 0 && ok_flag) *ok_flag = 1;
   for (int i = blockIdx.x; i <= n; i += gridDim.x) {
     if (i == n) {
       for (int j = tid; j < n; j += blockDim.x) {
         const double v = sc(j) * (red[L.gc() + j] + red[L.corr() + j]);
-        W[(size_t)n * n + j] = v;
+        if (W) W[(size_t)n * n + j] = v;
         if (rhs_copy) rhs_copy[j] = v;
       }
       continue;
@@ -47,7 +49,7 @@ k_sys_build(const double* __restrict__ red, RedLayout L, double* __restrict__ W 
       const double raw = upper ? red[L.S() + (size_t)i * n + j] : red[L.S() + (size_t)j * n + i];
       double v = raw * (si * sc(j));
       if (i == j) v += fmin(fmax(si * si * red[L.diagU() + i], ip.min_lm_diagonal), ip.max_lm_diagonal) / ip.radius;
-      W[(size_t)i * n + j] = v;
+      if (W) W[(size_t)i * n + j] = v;
       if (S_copy) S_copy[(size_t)i * n + j] = v;
     }
   }

@@ -240,6 +240,8 @@ struct rsba_solver {
   int pipe_stalls = 0;
   int other_stalls = 0;      // stalls of the multi-workgroup / tiled factorisation in the sequential schedule (each is a permanent fallback)
   bool pipe_check_resident = false;
+  // what the last PointsStep ran (a step repeated after a stall overwrites it): rsba_points_solve_stage reports it
+  struct StepPath { int pipelined = 0, fact = 0, workgroups = 0, backsub = 0, sys_fused = 0; } path;
   long long* trace = nullptr;   // RSBA_TRACE=1: 64 wall-clock stamps of the pipelined step
   // RSBA_TRACE=3: the stamps of the last 256 steps in a ring (trace points at the current step's 64 slots), nothing is
   // copied or printed per step — the step's own timing is not disturbed; TraceRingDump prints the gaps at the end of a run
@@ -1581,6 +1583,8 @@ static int PointsStep(rsba_solver* s, double radius, bool first, bool keep_syste
   }
   DebugSync(st, "k_camera_constants");
   const bool pipe = s->pipelined && s->opt.schur_impl != 0 && !keep_system_copy;
+  s->path = rsba_solver::StepPath{};
+  s->path.pipelined = pipe ? 1 : 0;
   ++s->step_tag;
   if (s->trace_ring) {
     if (s->trace_ring_first_tag == 0) s->trace_ring_first_tag = s->step_tag;
@@ -1651,6 +1655,7 @@ static int PointsStep(rsba_solver* s, double radius, bool first, bool keep_syste
       const long long gate_budget = mg ? 10 * RSBA_STALL_TICKS : 0;
       if (s->chol_wgs > 1 && s->chol_diag) {
         const int wgs = s->chol_wgs + (s->border_cols > 0 ? 1 : 0);   // (the border's workgroup is the launch's last)
+        s->path.fact = s->border_cols > 0 && !mg ? 2 : 1; s->path.workgroups = mg ? s->chol_wgs : wgs;
         const size_t lds_d = (s->border_cols > 0 ? std::max(DiagCholLdsDoubles(s->border_cols), BorderLdsDoubles(n)) : DiagCholLdsDoubles(n)) * sizeof(double);
         const StageGate sg{gate_ready, gate_tag, 6 * RSBA_TG, ts.ready + RSBA_READY_SOLVED, T.all_kernels() ? s->chol_waited : nullptr, s->trace, gate_budget, ts.ready + RSBA_READY_STARTED, resident_word, wgs, all_diag, mg ? 1 : 0};
         const DiagCholFlags df{s->mc_flags, s->mc_flags + 16, s->mc_flags + 32, s->mc_flags + 48, s->mc_dg, s->mc_dg + (size_t)(MultiCholPadded(s->nc) / RSBA_PB + 1) * 1024};
@@ -1659,12 +1664,14 @@ static int PointsStep(rsba_solver* s, double radius, bool first, bool keep_syste
         else k_reduced_system_solve_diag<false><<<wgs, 512, lds_d, s->sB>>>(
             C, s->red, s->L, s->A, s->scale_c, s->cam[x], s->cam[c], s->intr, s->camc[c], s->dcam, s->gmax, s->res, ip, s->chol_ok, sg, df, tag, s->mc_trace, s->border_cols);
       }
-      else
+      else {
+      s->path.fact = 0; s->path.workgroups = 1;
       k_reduced_system_solve<<<1, 512, lds_c, s->sB>>>(C, s->red, s->L, s->A, nullptr, nullptr, s->scale_c, s->cam[x], s->cam[c], s->intr,
                                                        s->camc[c], s->dcam, s->gmax, s->res, ip, mg ? 2 : 1,
                                                        s->chol_ok, StageGate{gate_ready, gate_tag, 6 * RSBA_TG, ts.ready + RSBA_READY_SOLVED,
                                                                              T.all_kernels() ? s->chol_waited : nullptr, s->trace, gate_budget,
                                                                              ts.ready + RSBA_READY_STARTED, resident_word, 1});
+      }
       T.End(s->sB);
       rr_k4.End();
       if (resident_word != nullptr) {
@@ -1740,7 +1747,10 @@ static int PointsStep(rsba_solver* s, double radius, bool first, bool keep_syste
   } else if (s->nc <= RSBA_CHOL_MAXN && !(s->tiles_small && s->tc_tiles > 0 && !keep_system_copy)) {
     const size_t lds_c = std::max((size_t)4 * 1024, CholeskyLdsDoubles(s->nc)) * sizeof(double);
     T.Begin("k_reduced_system_solve", st);
-    if (s->chol_wgs > 1 && !keep_system_copy && s->chol_diag)
+    const bool diag = s->chol_wgs > 1 && !keep_system_copy && s->chol_diag;
+    s->path.fact = diag ? (s->border_cols > 0 ? 2 : 1) : 0;
+    s->path.workgroups = diag ? s->chol_wgs + (s->border_cols > 0 ? 1 : 0) : 1;
+    if (diag)
       k_reduced_system_solve_diag<false><<<s->chol_wgs + (s->border_cols > 0 ? 1 : 0), 512,
                                            (s->border_cols > 0 ? std::max(DiagCholLdsDoubles(s->border_cols), BorderLdsDoubles(s->nc)) : DiagCholLdsDoubles(s->nc)) * sizeof(double), st>>>(
           C, s->red, s->L, s->A, s->scale_c, s->cam[x], s->cam[c], s->intr, s->camc[c], s->dcam, s->gmax, s->res, ip, s->chol_ok,
@@ -1759,6 +1769,7 @@ static int PointsStep(rsba_solver* s, double radius, bool first, bool keep_syste
     // wanted for itself (the copies of the system a caller asked for) or the multi-launch factorisation reads it
     static const int fuse_env = getenv("RSBA_SYS_FUSED") ? atoi(getenv("RSBA_SYS_FUSED")) : 1;
     const bool fused = s->tc_tiles > 0 && !keep_system_copy && fuse_env != 0;
+    s->path.sys_fused = fused ? 1 : 0;
     if (!fused) {
       T.Begin("k_sys_build", st);
       k_sys_build<<<n + 1, 256, 0, st>>>(s->red, s->L, s->W, keep_system_copy ? s->S_copy : nullptr, keep_system_copy ? s->rhs_copy : nullptr,
@@ -1766,6 +1777,7 @@ static int PointsStep(rsba_solver* s, double radius, bool first, bool keep_syste
       T.End(st);
     }
     if (s->tc_tiles > 0) {
+      s->path.fact = n <= RSBA_CHOL_MAXN ? 3 : 4; s->path.workgroups = s->tc_tiles;
       TileSysSource src;
       if (fused) { src.fused = 1; src.red = s->red; src.L = s->L; src.scale_c = s->scale_c; src.ip = ip; src.sym_full = s->opt.schur_impl != 0 ? 1 : 0; }
       T.Begin("k_chol_tiles_persistent", st);
@@ -1775,6 +1787,7 @@ static int PointsStep(rsba_solver* s, double radius, bool first, bool keep_syste
       T.End(st);
     } else {
     const size_t lds_s = CholStepLdsDoubles() * sizeof(double);
+    { const int nrt = (n + 1 - std::min(RSBA_PB, n) + RSBA_CT - 1) / RSBA_CT; s->path.fact = 5; s->path.workgroups = nrt * (nrt + 1) / 2; }
     T.Begin("k_chol_step(all panels)", st);
     for (int kb = 0; kb < n; kb += RSBA_PB) {
       const int r0 = kb + std::min(RSBA_PB, n - kb);
@@ -1789,6 +1802,7 @@ static int PointsStep(rsba_solver* s, double radius, bool first, bool keep_syste
     if (s->tc_tiles > 0 && bsm >= 2 && s->tc_xs != nullptr) {
       const int nblk = s->tc_np, H = (nblk + 2) / 3;
       int* fl = s->tc_flags + (size_t)s->tc_np * (s->tc_nrt + 1);   // [error | xdone ...]
+      s->path.backsub = 3;
       T.Begin("k_backsub_chain", st);
       k_backsub_chain<<<1 + H, 256, 0, st>>>(
           C, s->red, s->L, s->A, s->tc_xs, s->scale_c, s->cam[x], s->cam[c], s->intr, s->camc[c], s->dcam, s->gmax, s->res, s->chol_ok, s->cam_free,
@@ -1798,12 +1812,14 @@ static int PointsStep(rsba_solver* s, double radius, bool first, bool keep_syste
       // block back-substitution on several workgroups (three 32-column blocks each); x goes to row n of W (free by now)
       const int nblk = s->tc_np, G = (nblk + RSBA_BSM_BPG - 1) / RSBA_BSM_BPG;
       int* fl = s->tc_flags + (size_t)s->tc_np * (s->tc_nrt + 1);   // [error | xdone ...]
+      s->path.backsub = 2;
       T.Begin("k_backsub_multi", st);
       k_backsub_multi<<<G, 256, 0, st>>>(C, s->red, s->L, s->A, s->W + (size_t)n * n, s->scale_c, s->cam[x], s->cam[c], s->intr, s->camc[c], s->dcam,
                                          s->gmax, s->res, s->chol_ok, s->cam_free, fl + 1, fl, s->step_tag);
       T.End(st);
     } else {
     const size_t lds_f = std::max((size_t)4 * 1024, (size_t)((n + 63) & ~63) + 3 * RSBA_PB * RSBA_PLD + 64) * sizeof(double);
+    s->path.backsub = 1;
     T.Begin("k_chol_finish", st);
     k_chol_finish<<<1, 1024, lds_f, st>>>(C, s->red, s->L, s->A, s->scale_c, s->cam[x], s->cam[c], s->intr, s->camc[c], s->dcam, s->gmax, s->res,
                                           s->chol_ok, s->cam_free);
@@ -2918,6 +2934,50 @@ int rsba_points_linearize_and_step(rsba_problem* p, const rsba_options* o, doubl
       const double* r = s->res_host;
       scalars[0] = r[RES_COST_X]; scalars[1] = r[RES_MCC]; scalars[2] = r[RES_GMAX]; scalars[3] = r[RES_CHOL_OK];
       scalars[4] = r[RES_COST_C]; scalars[5] = std::sqrt(r[RES_STEP2]); scalars[6] = std::sqrt(r[RES_XNORM2]); scalars[7] = r[RES_SUMSQ_C];
+    }
+  }
+  rsba_solver_destroy(s);
+  return rc;
+}
+
+int rsba_points_solve_stage(rsba_problem* p, const rsba_options* o, double radius, double* S, double* rhs, double* dcam, double* scale_c,
+                            double* delta, double* scalars) {
+  if (!p || p->model != RSBA_MODEL_POINTS) return RSBA_ERR_ARG;
+  rsba_solver* s = nullptr;
+  int rc = rsba_solver_create(p, o, &s);
+  if (rc != RSBA_OK) return rc;
+  rc = rsba::ResetPoints(s);
+  // the step rsba_solver_run would take first: its schedule, factorisation and back-substitution
+  if (rc == RSBA_OK) rc = rsba::PointsStep(s, radius, true, false);
+  if (rc == RSBA_OK) rc = rsba::SyncSolver(s);
+  if (rc == RSBA_OK && (S || rhs)) {
+    // S and rhs formed again from `red`, apart from the factorisation (which scaled and damped its own copy): nothing behind the
+    // Schur kernel writes `red`, the scale is the one the step left in scale_c (first = 0: read, not written), and neither W nor
+    // the Cholesky status is touched
+    rsba::IterParams ip = rsba::MakeIterParams(s->opt, radius, false);
+    rsba::k_sys_build<<<s->nc + 1, 256, 0, s->stream>>>(s->red, s->L, nullptr, s->S_copy, s->rhs_copy, s->scale_c, ip,
+                                                        s->opt.schur_impl != 0 ? 1 : 0, nullptr);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s->stream) != hipSuccess) rc = RSBA_ERR_HIP;
+  }
+  if (rc == RSBA_OK) {
+    const int nc = s->nc;
+    if (S && hipMemcpy(S, s->S_copy, (size_t)nc * nc * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = RSBA_ERR_HIP;
+    if (rhs && hipMemcpy(rhs, s->rhs_copy, nc * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = RSBA_ERR_HIP;
+    if (dcam && hipMemcpy(dcam, s->dcam, nc * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = RSBA_ERR_HIP;
+    if (scale_c && hipMemcpy(scale_c, s->scale_c, nc * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = RSBA_ERR_HIP;
+    if (delta) {
+      std::vector<double> xc(6 * s->C + 3 * (size_t)s->P);
+      if (hipMemcpy(xc.data(), s->cam[1 - s->cur], 6 * s->C * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = RSBA_ERR_HIP;
+      if (rsba::DownloadPoints(s, s->pts[1 - s->cur], xc.data() + 6 * s->C) != RSBA_OK) rc = RSBA_ERR_HIP;
+      for (size_t i = 0; i < xc.size(); ++i) delta[i] = xc[i] - p->parameters[i];
+    }
+    if (scalars) {
+      const double* r = s->res_host;
+      scalars[0] = r[RES_COST_X]; scalars[1] = r[RES_MCC]; scalars[2] = r[RES_GMAX]; scalars[3] = r[RES_CHOL_OK];
+      scalars[4] = r[RES_COST_C]; scalars[5] = std::sqrt(r[RES_STEP2]); scalars[6] = std::sqrt(r[RES_XNORM2]); scalars[7] = r[RES_SUMSQ_C];
+      scalars[8] = s->path.pipelined; scalars[9] = s->path.fact; scalars[10] = s->path.workgroups; scalars[11] = s->path.fact == 2 ? s->border_cols : 0;
+      scalars[12] = s->path.fact == 3 || s->path.fact == 4 ? s->tc_tiles : 0; scalars[13] = s->path.backsub; scalars[14] = s->path.sys_fused;
+      scalars[15] = s->pipe_stalls + s->other_stalls; scalars[16] = (s->pipe_stalls >= 3 ? 1 : 0) + s->other_stalls;
     }
   }
   rsba_solver_destroy(s);
