@@ -22,9 +22,10 @@
 
 #include <cfloat>
 
+#include "ba_schur_plan.hpp"   // RSBA_CHOL_MAXN (the planner cuts the work list by it as well)
+
 namespace rsba {
 
-#define RSBA_CHOL_MAXN 384
 #define RSBA_PB 32                       // panel width
 #define RSBA_PLD (RSBA_PB + 1)           // LDS leading dimension (bank-conflict padding)
 

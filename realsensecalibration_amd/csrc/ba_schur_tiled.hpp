@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "ba_point_kernels.hpp"
+#include "ba_schur_plan.hpp"   // SchurSeg, SchurPlan and the constants the planner shares with the kernels (RSBA_TG, RSBA_CHUNK, ...)
 
 struct rsba_solver;
 
@@ -46,9 +47,7 @@ namespace rsba {
 
 class KernelTimer;
 
-#define RSBA_TG 16          // cameras per group
 // Flags of a step in TiledSchur::ready (64 ints): [1 + g] stage g published (g < RSBA_MAX_STAGES), then the three below.
-#define RSBA_MAX_STAGES 32        // camera groups a pipelined solve can gate on (512 cameras)
 #define RSBA_READY_ALLDIAG 40     // = tag once every self tile is finished (first step of a run: every camera's diag U)
 #define RSBA_READY_SOLVED 41      // = tag when the reduced system is solved (the back-substitution waits for it inside the kernel)
 #define RSBA_READY_STARTED 42     // arrival counter of the factorisation's workgroups ("all resident")
@@ -64,10 +63,6 @@ class KernelTimer;
 #else
 #define RSBA_PRIO_HITS(stage) RSBA_PRIO(0)
 #endif
-#ifndef RSBA_CHUNK
-#define RSBA_CHUNK 512      // points per LDS chunk (-DRSBA_CHUNK=256 builds and runs: measured only together with three workgroups per CU, HISTORY.md round 5)
-#endif
-#define RSBA_CW (RSBA_CHUNK / 64)
 // A point's record in the chunk's LDS copy: RSBA_PT_STRIDE (12) doubles at a stride of RSBA_PT_LDS.  Every lane of a hit loop reads the record
 // of ITS OWN hit — 64 random points per instruction, four 16-byte reads and an 8-byte one.  At a stride of 12 doubles (24 banks) the
 // records start on 8 of the 64 banks; at 14 (-DRSBA_PT_LDS=14: 28 banks, still 16-byte aligned, 80 KB of LDS a workgroup) on 16 —
@@ -91,15 +86,6 @@ struct PtLdsCursor {
 // (RSBA_PT_STRIDE, the record of a point — X(3) Vinv(6) y(3) — is defined in ba_point_kernels.hpp, whose back-substitution writes it too)
 #define RSBA_PART 42        // 36 block + 6 corr
 
-// A segment is a range of 64-point mask words of one tile (not necessarily chunk-aligned: small problems get as many
-// workgroups as they have words).
-struct SchurSeg {
-  int ga, gb, word_begin, word_end, self;
-  // in-kernel reduction tree of the pair tiles: segment -> group of RSBA_GRP consecutive segments -> tile -> stage
-  int tile, grp, grp_seg0, grp_nseg, tile_grp0, tile_ngrp, stage, stage_ntiles, nred, index, pad2;
-  // index: the entry's own number (segs_ordered, the copy in launch order, is what the kernel reads: one load per ticket)
-  // self: 0 pair segment, 1 self segment, 2 / 3 reducer of a pair / self tile (word_begin..word_end = its components)
-};
 // An entry of the work list, field by field into scalar registers.  (Copied as a struct, the entry went through vector
 // registers into SCRATCH and were read back from there field by field — and a kernel that uses scratch at all pays for it in
 // the launch latency of every workgroup: end of an entry -> start of the next on its slot 7.6 instead of 6.1 us.)
@@ -111,10 +97,6 @@ __device__ __forceinline__ SchurSeg LoadSeg(const SchurSeg* __restrict__ p) {
 #undef RSBA_F
   return s;
 }
-#define RSBA_GRP 8          // segments per reduction group (more than 64 cameras)
-#define RSBA_GRP_SMALL 4    // ... up to 64 cameras
-#define RSBA_SELF_SETS 6      // reducers of a self tile: the sets of its 42 components that the K factors do not couple (ReducerSelfSet)
-#define RSBA_DIRECT_GROUPS 4  // tiles with at most this many groups are finished by their last group, without reducers
 
 struct TiledSchur {
   int C = 0, P = 0, ngroups = 0, nwords = 0, nchunks = 0, nseg = 0, nseg_pair = 0, grid_pp = 0;
@@ -162,9 +144,9 @@ struct TiledSchur {
   int* hit_trips = nullptr;
   size_t hit_entries = 0;
 
-  int Build(int C, int P, const std::vector<int>& pt_ptr, const std::vector<int>& obs_cam, const std::vector<double>& u, const std::vector<double>& v,
-            const std::vector<int>& sliced_q /* sliced slot -> CSR position, -1 pads */, bool staged, bool bordered = false);
-  // stages of the pipelined solve (TiledSchur::Build: stage_of): camera groups, or 2 B + 1 with the last group as a border
+  // allocates the kernel's buffers and uploads the plan (BuildSchurPlan, ba_schur_plan.hpp)
+  int Build(const SchurPlan& plan, int cus);
+  // stages of the pipelined solve (PlanSegments: stage_of): camera groups, or 2 B + 1 with the last group as a border
   int nstages = 0;
   int Launch(rsba_solver* s, const IterParams& ip, KernelTimer& T);
   void LaunchPointPass(rsba_solver* s, const IterParams& ip, KernelTimer& T, hipStream_t st);
@@ -950,7 +932,7 @@ __device__ __forceinline__ void PairSegment(const SchurArgs& a, const SchurSeg& 
 // masked search above finds 3 hits in a 512-point chunk, a wave runs as many trips as its busiest lane (~8), and every
 // workgroup stages every chunk (48 KB) to find them — the kernel spent its time staging and searching (680 us for 2.9 GFLOP,
 // 5 % of the fp64 peak, round 2).  Which points a pair shares never changes, so the lists are built ONCE at set-up
-// (TiledSchur::BuildHitLists): per pair segment and wavefront, lane-interleaved — entry n of lane l at [n * 64 + l], as many
+// (PlanHitLists, ba_schur_plan.cpp): per pair segment and wavefront, lane-interleaved — entry n of lane l at [n * 64 + l], as many
 // trips as the longest of the 64 lists (one segment is ~1/8 of the points: ~48 hits per lane, busiest lane ~60) — each entry
 // the point and the two observations' places in the camera-major arrays (sqrt(rho')).  The point record (X, damped inverse
 // block: 72 bytes) is gathered from ptdata one trip ahead of the arithmetic, the entries two.  No chunk staging, no barrier, no
@@ -963,7 +945,6 @@ __device__ __forceinline__ void PairSegment(const SchurArgs& a, const SchurSeg& 
 // A diagonal tile's 120 pairs sit in both halves of the workgroup as above; the halves split the hits by the parity of the
 // point's 64-point word.
 // ------------------------------------------------------------------------------------------------
-#define RSBA_HIT_NONE 0xffffffffu
 template <bool kLoss, bool kSmall>
 __device__ __forceinline__ void PairSegmentSparse(const SchurArgs& a, const SchurSeg& sg, int seg_index, int ticket, double* pt, double* sc) {
   const int C = a.C;
