@@ -295,6 +295,44 @@ int rsba_solver_covariance_block(const rsba_solver* s, int64_t offset_a, int64_t
 /* Point model: P x 3 x 3 marginals in the problem's point order (zeros for constant and unreferenced points); RSBA_ERR_UNSUPPORTED otherwise. */
 int rsba_solver_point_covariances(const rsba_solver* s, double* out);
 
+/* ------------------------------------------------------------------ evaluate and re-solve (ceres::Problem::Evaluate; values changed in place)
+ * Not used by the reference, which looks at its residuals by eye (ReprojectionCheck::Reproject draws every reprojected corner beside its
+ * detection, reprojection_check.cpp:68-88).  rsba_solver_evaluate is Problem::Evaluate without the Jacobian, at the solver's current
+ * device parameters — after rsba_solver_run: the solution; before it: the uploaded start, or what rsba_solver_set_parameters set.
+ * Any output may be NULL (all three: RSBA_OK, nothing is launched).
+ *   residuals  rsba_solver_num_residuals doubles in the PROBLEM's observation order (the arrays given to rsba_problem_create_*, the rows
+ *              of the loaded file): observation i owns [2i, 2i+1] = (u, v) on the point model, [8i .. 8i+7] = 4 corners x (u, v), top-left,
+ *              top-right, bottom-right, bottom-left, on the marker-chain models; projected minus detected.  With apply_loss_function and a
+ *              loss configured (rsba_options.huber_delta > 0) every residual block is multiplied by sqrt(rho'(s)), s its squared norm — the
+ *              corrector the solve applies; raw otherwise.
+ *   cost       1/2 sum rho(s_i) with the loss applied, 1/2 sum s_i without, over EVERY residual block (those all of whose parameter
+ *              blocks are constant included).
+ *   gradient   rsba_problem_num_parameters doubles in the problem's parameter layout: J'r of the (corrected) residuals, unscaled (no
+ *              Jacobi scale, no damping).  Exactly 0.0 in the slots of constant blocks, of blocks no residual references and of the fixed
+ *              base blocks of the marker-chain models (camera 0 and marker 0 of RSBA_MODEL_MARKER_CHAIN, camera 0 of _TEST2): Ceres'
+ *              ProgramEvaluator leaves such blocks out in the same way.
+ * The solver's parameters, scales, kept linearisation, iteration log, schedule and covariance result are left untouched: run ->
+ * evaluate -> run gives the bits of run -> run, and two consecutive calls return the same bits in every output (every sum is taken in a
+ * fixed order).  Scratch is kept by the solver and only grows.  The Jacobian is not offered (it is never formed in memory);
+ * world_size > 1 returns RSBA_ERR_UNSUPPORTED on every rank without issuing a collective. */
+typedef struct rsba_evaluate_options { /* ceres::Problem::EvaluateOptions */
+  int32_t apply_loss_function;         /* 1 */
+  int32_t reserved;
+} rsba_evaluate_options;
+
+void rsba_evaluate_options_default(rsba_evaluate_options* o);
+/* 2 N (point model), 8 N (marker-chain models); for a NULL solver the negative code -RSBA_ERR_ARG, which is no count. */
+int64_t rsba_solver_num_residuals(const rsba_solver* s);
+int rsba_solver_evaluate(rsba_solver* s, const rsba_evaluate_options* o /* NULL = defaults */, double* cost, double* residuals, double* gradient);
+/* Ceres keeps the values in the caller's arrays: change them and Solve again, the Problem is not rebuilt.  Here: rsba_problem_num_parameters
+ * new values into the solver's start state (what rsba_solver_run restarts from), which also become the current state that
+ * rsba_solver_evaluate, rsba_solver_covariance_compute and rsba_solver_download read.  Nothing is planned or allocated again — the
+ * plan depends on the index arrays alone.  Constant and unreferenced blocks take the new values too (constant during a solve, not
+ * immutable).  The problem's own parameter array is not touched until rsba_solver_download; a covariance result is dropped (block
+ * queries: RSBA_ERR_ARG until the next compute); the iteration log and last summary stay until the next run.  A non-finite value:
+ * RSBA_ERR_ARG, nothing changes.  world_size > 1: RSBA_ERR_UNSUPPORTED. */
+int rsba_solver_set_parameters(rsba_solver* s, const double* parameters);
+
 /* Stage-level entry (tests): one linearisation of the point model at the current parameters with a
  * given trust-region radius.  Any output may be NULL.
  *   S       (6C)^2 reduced camera matrix, Jacobi-scaled, LM-damped, full symmetric, row-major

@@ -31,6 +31,7 @@ EXPORTS = [
     "rsba_solver_comm_nranks", "rsba_solver_schedule_info", "rsba_comm_shm_id", "rsba_comm_finalize",
     "rsba_covariance_options_default", "rsba_solver_covariance_compute", "rsba_solver_covariance_block", "rsba_solver_point_covariances",
     "rsba_solver_time_elimination",
+    "rsba_evaluate_options_default", "rsba_solver_num_residuals", "rsba_solver_evaluate", "rsba_solver_set_parameters",
 ]
 
 
@@ -72,6 +73,10 @@ class ScheduleInfo(C.Structure):
 
 class CovarianceOptions(C.Structure):
     _fields_ = [("min_reciprocal_condition_number", C.c_double), ("apply_loss_function", C.c_int32), ("reserved", C.c_int32)]
+
+
+class EvaluateOptions(C.Structure):
+    _fields_ = [("apply_loss_function", C.c_int32), ("reserved", C.c_int32)]
 
 
 class RsbaError(RuntimeError):
@@ -152,6 +157,11 @@ def load():
     lib.rsba_solver_covariance_compute.argtypes = [C.c_void_p, C.c_void_p]
     lib.rsba_solver_covariance_block.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
     lib.rsba_solver_point_covariances.argtypes = [C.c_void_p, C.c_void_p]
+    lib.rsba_evaluate_options_default.argtypes = [C.c_void_p]
+    lib.rsba_solver_num_residuals.argtypes = [C.c_void_p]
+    lib.rsba_solver_num_residuals.restype = C.c_int64
+    lib.rsba_solver_evaluate.argtypes = [C.c_void_p] * 5
+    lib.rsba_solver_set_parameters.argtypes = [C.c_void_p, C.c_void_p]
     _LIB = lib
     return lib
 
@@ -384,6 +394,32 @@ class Solver:
         if self.problem.model == MODEL_POINTS and offset >= 6 * self.problem.num_cameras:
             return 3
         return 6
+
+    # ---- ceres::Problem::Evaluate (no Jacobian) and values changed in place
+    @property
+    def num_residuals(self):
+        return int(load().rsba_solver_num_residuals(self.h))
+
+    def evaluate(self, residuals=True, gradient=True, apply_loss_function=True):
+        """(cost, residuals, gradient) at the solver's current parameters; None for an output not asked for.  Residuals in the
+        problem's observation order, the gradient in its parameter layout (0.0 for constant, unreferenced and base blocks)."""
+        o = EvaluateOptions()
+        load().rsba_evaluate_options_default(C.byref(o))
+        o.apply_loss_function = 1 if apply_loss_function else 0
+        cost = C.c_double()
+        r = np.zeros(self.num_residuals) if residuals else None
+        g = np.zeros(self.problem.num_parameters) if gradient else None
+        _chk(load().rsba_solver_evaluate(self.h, C.byref(o), C.byref(cost), _vp(r) if residuals else None, _vp(g) if gradient else None),
+             "rsba_solver_evaluate")
+        return cost.value, r, g
+
+    def set_parameters(self, x):
+        """New values for every parameter (the problem's layout): the start of the next run() and the current state that
+        evaluate(), covariance_compute() and download() read.  Nothing is planned again."""
+        x = np.ascontiguousarray(x, np.float64)
+        if x.shape != (self.problem.num_parameters,):
+            raise ValueError("set_parameters: %d values expected" % self.problem.num_parameters)
+        _chk(load().rsba_solver_set_parameters(self.h, _vp(x)), "rsba_solver_set_parameters")
 
     def final_costs(self):
         c, ss = C.c_double(), C.c_double()

@@ -1,0 +1,49 @@
+// Host-side planning of rsba_solver_evaluate (ba_evaluate.hpp): the index structures its gradient kernels need beyond what the
+// solver keeps.  Plain C++ without HIP, vectors in and vectors out (the pattern of ba_schur_plan.hpp): ba_solver.hip allocates and
+// copies, tests/evaluate_plan_driver.cpp checks the contracts under the host sanitizers.
+//
+// Every gradient slot is the sum of its block's observations IN A FIXED ORDER, so that two calls return the same bits.  The kernels
+// get that order from lists that name, block by block, the observations that reference the block, ascending:
+//   point model    the camera-major index over the solver's point-major observation slots (the points need none: a point's
+//                  observations are contiguous in pt_ptr)
+//   marker chain   per block of [C | T | M] the (observation, slot) pairs, slot = 0 camera, 1 time, 2 marker: where the block's six
+//                  values sit in the observation's J'r (18 values, camera | time | marker)
+// and from the mask of the blocks whose slots are 0.0 by definition: constant blocks, blocks no residual references, and the fixed
+// base blocks of the marker-chain models (which no residual references as parameters).
+#pragma once
+#include <cstdint>
+#include <vector>
+
+namespace rsba {
+
+// Which blocks' gradient slots are computed (1) and which are 0.0 by definition (0: constant or referenced by no residual).  Point
+// model: the C cameras, then the P points in the problem's order.  camera_constant / point_constant may be shorter than C / P
+// (missing entries: free), as rsba_problem keeps them.  The kernels place block b themselves: camera c at 6 c, point j at 6 C + 3 j.
+std::vector<unsigned char> EvalPointLive(int C, int P, int64_t N, const int32_t* camera_index, const int32_t* point_index,
+                                         const std::vector<uint8_t>& camera_constant, const std::vector<uint8_t>& point_constant);
+
+// Camera-major index over the solver's observation slots.  `order[s]` is the problem observation in slot s (the solver's `order`),
+// `pt_perm` the solver's point order (device position -> problem point; empty: identity).  Camera c owns entries
+// [ptr[c], ptr[c + 1]): `slot` ascending, `point` the DEVICE position of the slot's point.
+struct EvalCameraIndex {
+  std::vector<int> ptr, slot, point;
+};
+EvalCameraIndex BuildEvalCameraIndex(int C, int P, const std::vector<int64_t>& order, const int32_t* camera_index,
+                                     const int32_t* point_index, const std::vector<int>& pt_perm);
+
+// Marker-chain models: one row per observation in the problem's order, the blocks of [C | T | M] it names as PARAMETERS (-1: the
+// functor has no such block — camera 0, and marker 0 of RSBA_MODEL_MARKER_CHAIN) and the camera whose intrinsics project it.
+// (The fields of ba_covariance.hpp's CovMcRow; that header is device code, and this unit compiles without HIP.)
+struct EvalMarkerRow {
+  int cam_block, time_block, marker_block, camera;
+};
+// Block b owns entries [ptr[b], ptr[b + 1]): `obs` ascending; `slot` 0 / 1 / 2.  An observation is in the list of every block it names.
+struct EvalMarkerLists {
+  std::vector<int> ptr, obs;
+  std::vector<unsigned char> slot;
+};
+EvalMarkerLists BuildEvalMarkerLists(int num_blocks, const std::vector<EvalMarkerRow>& rows);
+// ... and the live mask of the blocks of [C | T | M] (block b sits at 6 b).  block_constant may be shorter than num_blocks.
+std::vector<unsigned char> EvalMarkerLive(int num_blocks, const std::vector<EvalMarkerRow>& rows, const std::vector<uint8_t>& block_constant);
+
+}  // namespace rsba

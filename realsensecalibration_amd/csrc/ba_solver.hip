@@ -29,6 +29,7 @@
 
 #include "ba_comm.hpp"
 #include "ba_covariance.hpp"
+#include "ba_evaluate.hpp"
 #include "ba_marker_kernels.hpp"
 #include "ba_marker_schur.hpp"
 #include "ba_point_kernels.hpp"
@@ -306,6 +307,10 @@ struct rsba_solver {
   double* cov_pts = nullptr;                   // P x 9, the problem's point order
   char* cov_arena = nullptr;                   // scratch of the computation, kept between calls (grows only)
   size_t cov_arena_cap = 0;
+
+  // ---- evaluate (rsba_solver_evaluate, ba_evaluate.hpp): tables and arena of its own, the LM state is not touched
+  EvalDevice eval;
+  std::vector<uint8_t> eval_const_cam, eval_const_pt, eval_const_block;   // the problem's constant flags as they were at create
 };
 
 namespace rsba {
@@ -409,6 +414,7 @@ static void FreeSolver(rsba_solver* s) {
   s->tiled.Free();
   s->marker.Free();
   s->marker_schur.Free();
+  s->eval.Free();
   for (hipEvent_t e : s->ev_serial) if (e) (void)hipEventDestroy(e);
   if (s->res_host) (void)hipHostFree(s->res_host);
   if (s->trace_base) (void)hipFree(s->trace_base);
@@ -1921,6 +1927,150 @@ static int CovarianceMarker(rsba_solver* s, const rsba_covariance_options& co) {
   });
 }
 
+// ------------------------------------------------------------------------------------------------
+// ceres::Problem::Evaluate without the Jacobian (rsba_solver_evaluate; kernels: ba_evaluate.hpp, index tables: ba_evaluate_plan.cpp)
+// ------------------------------------------------------------------------------------------------
+template <typename T>
+static int EvalUpload(T** dst, const std::vector<T>& v) {
+  int rc = DevAlloc(dst, v.size());
+  if (rc != RSBA_OK) return rc;
+  if (!v.empty() && hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return RSBA_ERR_HIP;
+  return RSBA_OK;
+}
+
+static std::vector<EvalMarkerRow> EvalMarkerRows(const rsba_problem& p) {
+  std::vector<EvalMarkerRow> rows((size_t)p.num_observations);
+  for (int64_t i = 0; i < p.num_observations; ++i)
+    rows[i] = EvalMarkerRow{p.uses_camera(i) ? p.camera_block(i) : -1, p.time_block(i), p.uses_marker(i) ? p.marker_block(i) : -1, p.camera_index[i]};
+  return rows;
+}
+
+// The tables of the first call.  They depend on the problem's index arrays and on the constant flags AS THE SOLVER TOOK THEM at
+// create (eval_const_*: flags changed on the problem afterwards change neither the solve nor this mask), so they outlive every
+// rsba_solver_set_parameters.  A failure half way frees what was uploaded: the next call starts over.
+static int EvalBuildTables(rsba_solver* s) {
+  EvalDevice& e = s->eval;
+  const rsba_problem& p = *s->prob;
+  int rc;
+  if (p.model == RSBA_MODEL_POINTS) {
+    if (s->N > INT32_MAX) return RSBA_ERR_UNSUPPORTED;   // (the observation slots are ints, as pt_ptr's)
+    const EvalCameraIndex idx = BuildEvalCameraIndex(s->C, s->P, s->order, p.camera_index.data(), p.point_index.data(), s->pt_perm);
+    const std::vector<unsigned char> live = EvalPointLive(s->C, s->P, s->N, p.camera_index.data(), p.point_index.data(), s->eval_const_cam, s->eval_const_pt);
+    const std::vector<int> order32(s->order.begin(), s->order.end());
+    if ((rc = EvalUpload(&e.cam_ptr, idx.ptr)) || (rc = EvalUpload(&e.cam_slot, idx.slot)) || (rc = EvalUpload(&e.cam_point, idx.point)) ||
+        (rc = EvalUpload(&e.order, order32)) || (rc = EvalUpload(&e.live, live)))
+      return rc;
+    if (!s->pt_perm.empty() && (rc = EvalUpload(&e.pt_perm, s->pt_perm))) return rc;
+  } else {
+    const int nb = p.num_cameras + p.num_times + p.num_markers;
+    const std::vector<EvalMarkerRow> rows = EvalMarkerRows(p);
+    const EvalMarkerLists lists = BuildEvalMarkerLists(nb, rows);
+    const std::vector<unsigned char> live = EvalMarkerLive(nb, rows, s->eval_const_block);
+    if ((rc = EvalUpload(&e.rows, rows)) || (rc = EvalUpload(&e.obs8, p.observations)) || (rc = EvalUpload(&e.intr, p.intrinsics)) ||
+        (rc = EvalUpload(&e.list_ptr, lists.ptr)) || (rc = EvalUpload(&e.list_obs, lists.obs)) || (rc = EvalUpload(&e.list_slot, lists.slot)) ||
+        (rc = EvalUpload(&e.live, live)))
+      return rc;
+  }
+  return RSBA_OK;
+}
+
+static int EvalBuild(rsba_solver* s) {
+  if (s->eval.built) return RSBA_OK;
+  const int rc = EvalBuildTables(s);
+  if (rc != RSBA_OK) { s->eval.Free(); return rc; }
+  s->eval.built = true;
+  return RSBA_OK;
+}
+
+static int EvaluateOnDevice(rsba_solver* s, bool apply_loss, double* cost, double* residuals, double* gradient) {
+  const rsba_problem& p = *s->prob;
+  EvalDevice& e = s->eval;
+  int rc = EvalBuild(s);
+  if (rc != RSBA_OK) return rc;
+  const bool points = p.model == RSBA_MODEL_POINTS;
+  const size_t N = (size_t)p.num_observations, nres = (size_t)p.obs_dim() * N, npar = p.parameters.size();
+  const int C = p.num_cameras, nb = points ? 0 : C + p.num_times + p.num_markers;
+  const int grid = points ? std::max(1, std::min((s->P + 3) / 4, 8192)) : (int)std::max<size_t>(1, (N + 63) / 64);   // = the cost's partials
+  const double loss = !apply_loss || !(s->opt.huber_delta > 0.0) ? 0.0 : (s->opt.loss_type == RSBA_LOSS_CAUCHY ? -s->opt.huber_delta : s->opt.huber_delta);
+  double *posec = nullptr, *res_d = nullptr, *grad_d = nullptr, *work = nullptr, *cost_parts = nullptr, *cost_d = nullptr;
+  auto carve = [&](CovCarve& cv) {
+    posec = cv.take<double>((size_t)CC_STRIDE * (points ? C : nb));
+    res_d = residuals ? cv.take<double>(nres) : nullptr;
+    grad_d = gradient ? cv.take<double>(npar) : nullptr;
+    // the camera gradient's segment sums / every observation's J'r
+    work = gradient ? cv.take<double>(points ? (size_t)C * RSBA_EVAL_CAM_SEGS * 6 : 18 * N) : nullptr;
+    cost_parts = cv.take<double>(grid);
+    cost_d = cv.take<double>(1);
+  };
+  CovCarve sizing;
+  carve(sizing);
+  if ((rc = CovGrow(&e.arena, &e.arena_cap, sizing.off))) return rc;
+  CovCarve cv;
+  cv.base = e.arena;
+  carve(cv);
+  hipStream_t st = s->stream;
+  // the current device state: the last run's accepted point, or the uploaded / set start before any run
+  if (points) {
+    const double* cam = s->has_run ? s->cam[s->cur] : s->cam0;
+    const double* pts = s->has_run ? s->pts[s->cur] : s->pts0;
+    k_camera_constants<<<(C + 63) / 64, 64, 0, st>>>(C, cam, s->intr, posec);
+    if (gradient) {
+      k_eval_points<true><<<grid, 256, 0, st>>>(s->P, C, s->obs_u, s->obs_v, s->obs_cam, s->pt_ptr, posec, pts, e.order, e.pt_perm, e.live, loss, res_d, grad_d, cost_parts);
+      k_eval_cam_grad<<<C * RSBA_EVAL_CAM_SEGS, 256, 0, st>>>(e.cam_ptr, e.cam_slot, e.cam_point, s->obs_u, s->obs_v, posec, pts, loss, work);
+      k_eval_cam_sum<<<(6 * C + 255) / 256, 256, 0, st>>>(C, work, e.live, grad_d);
+    } else {
+      k_eval_points<false><<<grid, 256, 0, st>>>(s->P, C, s->obs_u, s->obs_v, s->obs_cam, s->pt_ptr, posec, pts, e.order, e.pt_perm, e.live, loss, res_d, nullptr, cost_parts);
+    }
+  } else {
+    const double* params = s->eliminate_times ? (s->has_run ? s->marker_schur.params[s->marker_schur.cur] : s->marker_schur.params0)
+                                              : (s->has_run ? s->marker.params[s->marker.cur] : s->marker.params0);
+    k_cov_pose_constants<<<(nb + 255) / 256, 256, 0, st>>>(nb, params, posec);
+    if (gradient) {
+      k_eval_marker<true><<<grid, 64, 0, st>>>((int)N, e.rows, e.obs8, e.intr, posec, p.marker_side / 2, loss, res_d, work, cost_parts);
+      k_eval_marker_block_sum<<<nb, 256, 0, st>>>(e.list_ptr, e.list_obs, e.list_slot, work, e.live, grad_d);
+    } else {
+      k_eval_marker<false><<<grid, 64, 0, st>>>((int)N, e.rows, e.obs8, e.intr, posec, p.marker_side / 2, loss, res_d, nullptr, cost_parts);
+    }
+  }
+  k_eval_cost<<<1, 256, 0, st>>>(grid, cost_parts, cost_d);
+  rc = RSBA_OK;
+  auto hip = [&](hipError_t err) { if (err != hipSuccess && rc == RSBA_OK) rc = RSBA_ERR_HIP; };
+  hip(hipGetLastError());
+  if (cost) hip(hipMemcpyAsync(cost, cost_d, sizeof(double), hipMemcpyDeviceToHost, st));
+  if (residuals && nres > 0) hip(hipMemcpyAsync(residuals, res_d, nres * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (gradient && npar > 0) hip(hipMemcpyAsync(gradient, grad_d, npar * sizeof(double), hipMemcpyDeviceToHost, st));
+  hip(hipStreamSynchronize(st));
+  return rc;
+}
+
+// New values into the start state and the current state; no plan, table or allocation depends on them.
+static int SetParametersOnDevice(rsba_solver* s, const double* x) {
+  const rsba_problem& p = *s->prob;
+  hipStream_t st = s->stream;
+  if (p.model == RSBA_MODEL_POINTS) {
+    const int C = s->C, P = s->P;
+    HIPCHK(hipMemcpy(s->cam0, x, 6 * (size_t)C * sizeof(double), hipMemcpyHostToDevice));
+    const double* src = x + 6 * (size_t)C;
+    if (s->pt_perm.empty()) {
+      HIPCHK(hipMemcpy(s->pts0, src, 3 * (size_t)P * sizeof(double), hipMemcpyHostToDevice));
+    } else {
+      std::vector<double> xp(3 * (size_t)P);
+      for (int jn = 0; jn < P; ++jn) { const size_t o = 3 * (size_t)s->pt_perm[jn]; xp[3 * (size_t)jn] = src[o]; xp[3 * (size_t)jn + 1] = src[o + 1]; xp[3 * (size_t)jn + 2] = src[o + 2]; }
+      HIPCHK(hipMemcpy(s->pts0, xp.data(), xp.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    // the working state, the kept linearisation's validity (the camera constants are formed again by the first step of a run)
+    int rc = ResetPoints(s);
+    if (rc != RSBA_OK) return rc;
+  } else {
+    double* params0 = s->eliminate_times ? s->marker_schur.params0 : s->marker.params0;
+    HIPCHK(hipMemcpy(params0, x, p.parameters.size() * sizeof(double), hipMemcpyHostToDevice));
+    int rc = s->eliminate_times ? s->marker_schur.Reset(st) : s->marker.Reset(st);
+    if (rc != RSBA_OK) return rc;
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  return RSBA_OK;
+}
+
 }  // namespace rsba
 
 // ================================================================================================
@@ -2026,6 +2176,7 @@ int rsba_solver_create(rsba_problem* p, const rsba_options* o, rsba_solver** out
       rc = s->marker.Upload(*p);
     }
   }
+  s->eval_const_cam = p->camera_constant; s->eval_const_pt = p->point_constant; s->eval_const_block = p->block_constant;
   if (rc == RSBA_OK && hipDeviceSynchronize() != hipSuccess) rc = RSBA_ERR_HIP;
   if (rc != RSBA_OK) { if (comm_keep) comm_keep->Abort(); rsba::FreeSolver(s); return rc; }
   s->setup_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -2373,6 +2524,33 @@ int rsba_solver_point_covariances(const rsba_solver* s, double* out) {
   if (!s->cov_valid) return RSBA_ERR_ARG;
   if (hipSetDevice(s->device) != hipSuccess) return RSBA_ERR_HIP;
   return hipMemcpy(out, s->cov_pts, 9 * (size_t)s->P * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess ? RSBA_OK : RSBA_ERR_HIP;
+}
+
+int64_t rsba_solver_num_residuals(const rsba_solver* s) {
+  if (!s) return -(int64_t)RSBA_ERR_ARG;
+  return (int64_t)s->prob->obs_dim() * s->prob->num_observations;
+}
+
+int rsba_solver_evaluate(rsba_solver* s, const rsba_evaluate_options* o, double* cost, double* residuals, double* gradient) {
+  if (!s) return RSBA_ERR_ARG;
+  rsba_evaluate_options eo;
+  if (o) eo = *o; else rsba_evaluate_options_default(&eo);
+  // (several ranks: no collective is issued, every rank returns here)
+  if (s->opt.world_size > 1 || s->comm) return RSBA_ERR_UNSUPPORTED;
+  if (!cost && !residuals && !gradient) return RSBA_OK;
+  if (hipSetDevice(s->device) != hipSuccess) return RSBA_ERR_HIP;
+  return rsba::EvaluateOnDevice(s, eo.apply_loss_function != 0, cost, residuals, gradient);
+}
+
+int rsba_solver_set_parameters(rsba_solver* s, const double* parameters) {
+  if (!s || !parameters) return RSBA_ERR_ARG;
+  if (s->opt.world_size > 1 || s->comm) return RSBA_ERR_UNSUPPORTED;
+  const size_t n = s->prob->parameters.size();
+  for (size_t i = 0; i < n; ++i) if (!std::isfinite(parameters[i])) return RSBA_ERR_ARG;
+  if (hipSetDevice(s->device) != hipSuccess) return RSBA_ERR_HIP;
+  if (hipStreamSynchronize(s->stream) != hipSuccess) return RSBA_ERR_HIP;
+  s->cov_valid = false;   // the covariance was that of the old values
+  return rsba::SetParametersOnDevice(s, parameters);
 }
 
 int rsba_points_linearize_and_step(rsba_problem* p, const rsba_options* o, double radius, double* S, double* rhs, double* delta, double* scalars) {

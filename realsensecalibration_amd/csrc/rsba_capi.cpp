@@ -156,6 +156,12 @@ void rsba_options_default(rsba_options* o) {
   o->max_solver_time_in_seconds = 1e9;
 }
 
+void rsba_evaluate_options_default(rsba_evaluate_options* o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  o->apply_loss_function = 1;
+}
+
 int rsba_read_intrinsics_xml(const char* path, double* out4) { return rsba::ReadIntrinsicsXml(path, out4); }
 int rsba_write_outputs(rsba_problem* p, const char* xml, const char* dir, const char* p3d) {
   if (!p) return RSBA_ERR_ARG;

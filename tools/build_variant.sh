@@ -10,6 +10,6 @@ python __graft_entry__.py >/dev/null
 # (the host-side planner shares the tuning constants with the kernels: it is rebuilt with the same -D overrides)
 defs=""; for f in "$@"; do case "$f" in -D*) defs="$defs $f";; esac; done
 g++ -O3 -std=c++17 -fPIC -pthread $defs -I include -c realsensecalibration_amd/csrc/ba_schur_plan.cpp -o build/variants/p_$name.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o build/variants/librsba_$name.so build/variants/s_$name.o build/variants/p_$name.o build/obj/ba_problem.cpp.o build/obj/ba_initial_guess.cpp.o build/obj/rsba_capi.cpp.o -L/opt/rocm/lib -lrccl -pthread -Wl,-rpath,/opt/rocm/lib
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o build/variants/librsba_$name.so build/variants/s_$name.o build/variants/p_$name.o build/obj/ba_evaluate_plan.cpp.o build/obj/ba_problem.cpp.o build/obj/ba_initial_guess.cpp.o build/obj/rsba_capi.cpp.o -L/opt/rocm/lib -lrccl -pthread -Wl,-rpath,/opt/rocm/lib
 rm -f build/variants/s_$name.o build/variants/p_$name.o
 echo built build/variants/librsba_$name.so
