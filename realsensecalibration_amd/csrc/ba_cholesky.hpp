@@ -26,7 +26,7 @@
 
 namespace rsba {
 
-#define RSBA_PB 32                       // panel width
+// (RSBA_PB, the panel width: ba_schur_plan.hpp)
 #define RSBA_PLD (RSBA_PB + 1)           // LDS leading dimension (bank-conflict padding)
 
 typedef double d4_t __attribute__((ext_vector_type(4)));
@@ -82,7 +82,7 @@ struct StageGate {
   long long budget;   // ticks a wait may last before the kernel gives up (0: RSBA_STALL_TICKS); the multi-GPU pipeline waits
                       // for other ranks' collectives and gets ten times as long
   // "every workgroup of this kernel is resident": the last one to start writes `tag` into the host's pinned word.  The host
-  // waits for it before it launches the Schur kernel on the first step of a run (see PointsStep): the first launch on the
+  // waits for it before it launches the Schur kernel on the first step of a run (LaunchGatedFactorisation, ba_solver.hip): the first launch on the
   // side stream was measured to start ~150 us late, and a factorisation that is not resident when the chip fills up does
   // not get a CU with enough LDS until the back-substitution — which waits for it — has left.
   int* started_cnt = nullptr;    // device

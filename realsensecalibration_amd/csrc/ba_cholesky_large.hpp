@@ -22,7 +22,7 @@
 
 namespace rsba {
 
-#define RSBA_CT 64   // trailing-update tile
+// (RSBA_CT, the trailing-update tile: ba_schur_plan.hpp)
 
 __global__ void __launch_bounds__(256)
 k_sys_build(const double* __restrict__ red, RedLayout L, double* __restrict__ W /* (n+1) x n */, double* __restrict__ S_copy,

@@ -137,7 +137,6 @@ __device__ __forceinline__ double* BackSubstituteBlocksWaves(int n, double* __re
   return xs;
 }
 
-// n = the padded dimension
-__host__ __device__ inline int MultiCholPadded(int nc) { return (nc + RSBA_PB - 1) / RSBA_PB * RSBA_PB; }
+// (MultiCholPadded, the padded dimension: ba_schur_plan.hpp)
 
 }  // namespace rsba

@@ -55,7 +55,7 @@ struct TileCholFlags {
   long long* trace = nullptr;   // RSBA_MC_TRACE=1: [nrt][24] stamps of the diagonal tiles' chain (wall clock, 10 ns)
 };
 
-constexpr int kTileHandT2 = 0, kTileHandAH = 1024, kTileHandS1 = 3072, kTileHandXH = 5120, kTileHandDoubles = 7168;
+constexpr int kTileHandT2 = 0, kTileHandAH = 1024, kTileHandS1 = 3072, kTileHandXH = 5120;   // of kTileHandDoubles (ba_schur_plan.hpp)
 
 __device__ __forceinline__ double* TileHandSlot(const TileCholFlags& f, int parity, int idx) { return f.hand + ((size_t)parity * f.nrt + idx) * kTileHandDoubles; }
 __device__ __forceinline__ bool HandThere(double v) { return __double_as_longlong(v) != -1LL; }   // the sentinel: all bits set (hipMemset 0xff)
@@ -663,7 +663,7 @@ k_chol_tiles_persistent(int n, const double* __restrict__ W /* (n + 1) x n: scal
 // (32 doubles + a flag); every workgroup with columns below b subtracts L[b, own columns]' x_b from its part of y — the strip
 // it needs is loaded one block ahead (its addresses do not depend on x).  The chain is T'y + a hop only where the owner
 // changes; workgroup 0 ends with block 0, has seen every flag, and runs the camera-step epilogue.
-#define RSBA_BSM_BPG 3   // blocks per workgroup (96 columns)
+// (RSBA_BSM_BPG blocks per workgroup, 96 columns: ba_schur_plan.hpp)
 __global__ void __launch_bounds__(256)
 k_backsub_multi(int C, const double* __restrict__ red, RedLayout L, const double* __restrict__ F, double* __restrict__ xsol,
                 const double* __restrict__ scale_c, const double* __restrict__ cam_x, double* __restrict__ cam_c,

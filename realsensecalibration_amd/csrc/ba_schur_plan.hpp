@@ -25,6 +25,12 @@ namespace rsba {
 #define RSBA_DIRECT_GROUPS 4  // tiles with at most this many groups are finished by their last group, without reducers
 #define RSBA_HIT_NONE 0xffffffffu   // an empty entry of a sparse hit list (PairSegmentSparse)
 #define RSBA_CHOL_MAXN 384  // largest reduced system the one-launch factorisations take (64 cameras)
+#define RSBA_PB 32          // panel width of the factorisations
+#define RSBA_CT 64          // trailing-update tile of the multi-launch factorisation (ba_cholesky_large.hpp)
+#define RSBA_BSM_BPG 3      // k_backsub_multi: blocks per workgroup (96 columns)
+constexpr int kTileHandDoubles = 7168;   // doubles of one hand-over buffer of the tiled factorisation's diagonal chain (ba_cholesky_tiles.hpp)
+// the reduced system's dimension padded to whole panels (constexpr: host and device)
+constexpr int MultiCholPadded(int nc) { return (nc + RSBA_PB - 1) / RSBA_PB * RSBA_PB; }
 
 // A segment is a range of 64-point mask words of one tile (not necessarily chunk-aligned: small problems get as many
 // workgroups as they have words).
