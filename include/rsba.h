@@ -277,8 +277,17 @@ void rsba_solver_destroy(rsba_solver* s);
  * Point model: every camera x camera block (6 x 6) and the 3 x 3 marginal of every point; camera x point and cross-point blocks
  * are RSBA_ERR_UNSUPPORTED.  Marker-chain models (dense and time-eliminating paths alike): every camera / marker x camera / marker
  * block (6 x 6); time blocks are RSBA_ERR_UNSUPPORTED.  apply_loss_function applies the solve's corrector in both models (the
- * marker chain: sqrt(rho') of each observation's 8 residuals).  world_size > 1 returns
- * RSBA_ERR_UNSUPPORTED on every rank without issuing a collective. */
+ * marker chain: sqrt(rho') of each observation's 8 residuals).
+ *
+ * A solver with a communicator (point model; world_size > 1, or the one-rank communicator of RSBA_FORCE_COMM):
+ * rsba_solver_covariance_compute is COLLECTIVE (the collective contract below).  Every rank linearises its shard into its part of
+ * U - sum W V^-1 W' over one column map — the free cameras SOME rank references, from all-reduced flags, so the layout is the
+ * same everywhere —, the upper triangles are summed over the ranks in one all-reduce (with them the shards' rank-deficient point
+ * flags: a positive total is RSBA_ERR_RANK_DEFICIENT on every rank), every rank inverts the identical sum (so the pivot test fires
+ * identically everywhere) and forms the marginals of its own points against it.  The block queries are local: camera x camera
+ * blocks on every rank (a camera another shard alone observes included), bit-identical across the ranks of a loopback or
+ * shared-memory group; point blocks on the owning rank, by that rank's offsets.  The constant flags of the cameras must be the
+ * same on every rank, as for the solve. */
 typedef struct rsba_covariance_options { /* ceres::Covariance::Options, Ceres 1.14 defaults */
   double min_reciprocal_condition_number; /* 1e-14: a Cholesky pivot of the Jacobi-scaled reduced system (or of a point block)
                                              at or below this -> RSBA_ERR_RANK_DEFICIENT */
@@ -313,8 +322,32 @@ int rsba_solver_point_covariances(const rsba_solver* s, double* out);
  *              ProgramEvaluator leaves such blocks out in the same way.
  * The solver's parameters, scales, kept linearisation, iteration log, schedule and covariance result are left untouched: run ->
  * evaluate -> run gives the bits of run -> run, and two consecutive calls return the same bits in every output (every sum is taken in a
- * fixed order).  Scratch is kept by the solver and only grows.  The Jacobian is not offered (it is never formed in memory);
- * world_size > 1 returns RSBA_ERR_UNSUPPORTED on every rank without issuing a collective. */
+ * fixed order).  Scratch is kept by the solver and only grows.  The Jacobian is not offered (it is never formed in memory).
+ *
+ * A solver with a communicator (point model): a call with cost or gradient non-NULL is COLLECTIVE (the contract below); one that
+ * asks for residuals alone is local and issues no collective.
+ *   residuals  this rank's shard, in this rank's problem's observation order.
+ *   cost       the all-ranks total: each rank's cost as above, then one sum over the ranks.
+ *   gradient   rsba_problem_num_parameters doubles of THIS rank's problem.  The point slots are this rank's own.  The 6C camera
+ *              slots are the all-ranks sum of the shards' sums; cost, camera slots and the cameras' "referenced" flags travel in one
+ *              group of all-reduces (6C + 1 + C doubles).  A camera slot is exactly 0.0 when the camera is constant or NO rank
+ *              references it — the mask comes from the summed flags: a camera this shard never observes but another does carries
+ *              the other ranks' sum.
+ * On loopback and shared-memory groups the partials are added in rank order: two consecutive calls return identical bits on every
+ * rank, and cost and camera slots are bit-identical across the ranks.  Over RCCL cost and camera slots are identical across the ranks
+ * as well (one all-reduce result) and repeatable as far as RCCL's choice of algorithm is.
+ *
+ * THE COLLECTIVE CONTRACT of rsba_solver_evaluate (cost or gradient asked for), rsba_solver_set_parameters and
+ * rsba_solver_covariance_compute on a solver with a communicator.  Every rank of the group calls the entry point, in the same order
+ * relative to its other collective calls (rsba_solver_run included); the call takes the device as rsba_solver_run does (a loopback
+ * rank launches on its turn only).  rsba_solver_covariance_block and rsba_solver_point_covariances are local.  Each collective call
+ * opens with one small all-reduce, the request word: which entry point, which of cost / gradient are wanted, apply_loss_function,
+ * min_reciprocal_condition_number, and a "bad" flag for an argument error only one rank can see (a NULL pointer or a non-finite
+ * value in rsba_solver_set_parameters, a negative min_reciprocal_condition_number).  Every value travels beside its negation under
+ * one max, so disagreement is detected on EVERY rank: all ranks then return RSBA_ERR_ARG, nothing has changed on any of them and no
+ * further collective is issued (the next matching call succeeds).  A HIP error or a failed collective aborts the communicator
+ * before it returns, as rsba_solver_create does: the other ranks leave their waits with RSBA_ERR_COMM.  No path returns early on
+ * one rank while the others enter a collective.  A solver WITHOUT a communicator runs none of this. */
 typedef struct rsba_evaluate_options { /* ceres::Problem::EvaluateOptions */
   int32_t apply_loss_function;         /* 1 */
   int32_t reserved;
@@ -330,7 +363,12 @@ int rsba_solver_evaluate(rsba_solver* s, const rsba_evaluate_options* o /* NULL 
  * plan depends on the index arrays alone.  Constant and unreferenced blocks take the new values too (constant during a solve, not
  * immutable).  The problem's own parameter array is not touched until rsba_solver_download; a covariance result is dropped (block
  * queries: RSBA_ERR_ARG until the next compute); the iteration log and last summary stay until the next run.  A non-finite value:
- * RSBA_ERR_ARG, nothing changes.  world_size > 1: RSBA_ERR_UNSUPPORTED. */
+ * RSBA_ERR_ARG, nothing changes.
+ *
+ * A solver with a communicator (point model): COLLECTIVE (the contract above).  Each rank passes its own problem's layout — the
+ * shared cameras, then its own points.  Behind the request word the ranks verify that all of them passed the same camera blocks
+ * (one max over [cameras, -cameras], 12C doubles, compared as values); a mismatch is RSBA_ERR_ARG on every rank with nothing
+ * changed.  A sharded group set to x1 then runs the bits of a group created at x1. */
 int rsba_solver_set_parameters(rsba_solver* s, const double* parameters);
 
 /* Stage-level entry (tests): one linearisation of the point model at the current parameters with a
@@ -390,6 +428,10 @@ void rsba_comm_finalize(void);
 /* ncclCommCount of the solver's communicator: the number of ranks its all-reduces really span (1 without a
  * communicator).  bench.py prints it as `rccl_nranks` and refuses to report a line when it differs from --gpus. */
 int rsba_solver_comm_nranks(const rsba_solver* s);
+/* A rank that gives up OUTSIDE the library (its host code failed between two collective calls) says so here, so that the ranks
+ * already waiting for it in a collective leave with RSBA_ERR_COMM instead of waiting out the time limit.  The communicator is
+ * unusable afterwards, as after any failed collective.  No-op without a communicator; may be called from any thread. */
+int rsba_solver_comm_abort(rsba_solver* s);
 /* The schedule in effect and the stalls / fallbacks so far (rsba_schedule_info).  The reference has no counterpart: Ceres runs
  * one thread (bundle_adjustment_manager.cpp:90-92). */
 int rsba_solver_schedule_info(const rsba_solver* s, rsba_schedule_info* out);

@@ -32,6 +32,7 @@ EXPORTS = [
     "rsba_covariance_options_default", "rsba_solver_covariance_compute", "rsba_solver_covariance_block", "rsba_solver_point_covariances",
     "rsba_solver_time_elimination",
     "rsba_evaluate_options_default", "rsba_solver_num_residuals", "rsba_solver_evaluate", "rsba_solver_set_parameters",
+    "rsba_solver_comm_abort",
 ]
 
 
@@ -162,6 +163,7 @@ def load():
     lib.rsba_solver_num_residuals.restype = C.c_int64
     lib.rsba_solver_evaluate.argtypes = [C.c_void_p] * 5
     lib.rsba_solver_set_parameters.argtypes = [C.c_void_p, C.c_void_p]
+    lib.rsba_solver_comm_abort.argtypes = [C.c_void_p]
     _LIB = lib
     return lib
 
@@ -564,6 +566,91 @@ def solve_points_sharded_loopback(shards, opts_kw=None, max_iterations=None):
         if e is not None:
             raise RuntimeError("loopback rank %d failed: %s" % (r, e))
     return out
+
+
+class ShardedLoopbackGroup:
+    """A loopback group that stays alive between calls: shard r of `shards` is rank r, its problem and solver created, used and
+    closed by ONE host thread of its own, as one process per GPU would.  `prepare(r, problem)` runs before rank r's solver is
+    created (constant blocks).  `run(fn)` calls fn(r, solver, problem) on every rank's thread against the live solver and returns
+    the per-rank results in rank order — what the collective entry points (run, evaluate, set_parameters, covariance_compute)
+    need: every rank calling, in the same order.  If fn raises on a rank, that rank aborts the group's communicator
+    (rsba_solver_comm_abort), so no other rank is left waiting in a collective, and run() re-raises in the caller; the group is
+    then good for close() only.  An error code that the ranks share (RSBA_ERR_ARG after a refused request) is no reason to raise:
+    let fn catch it and return the code.  Use as a context manager, or call close()."""
+
+    def __init__(self, shards, opts_kw=None, prepare=None):
+        import queue
+        import threading
+        self.world = len(shards)
+        self.solvers, self.problems = [None] * self.world, [None] * self.world
+        self._uid = C.create_string_buffer(comm_loopback_id(), 128)
+        self._jobs = [queue.Queue() for _ in range(self.world)]
+        self._done = queue.Queue()
+        self._failed = False
+        self._threads = [threading.Thread(target=self._rank_main, args=(r, shards[r], dict(opts_kw or {}), prepare)) for r in range(self.world)]
+        for t in self._threads:
+            t.start()
+        try:
+            self._collect()
+        except Exception:
+            self.close()
+            raise
+
+    def _create(self, r, shard, opts_kw, prepare):
+        o = default_options(rank=r, world_size=self.world, **opts_kw)
+        o.comm_unique_id = C.cast(self._uid, C.c_void_p)
+        self.problems[r] = Problem.points(shard)
+        if prepare is not None:
+            prepare(r, self.problems[r])
+        self.solvers[r] = Solver(self.problems[r], o)
+
+    def _rank_main(self, r, shard, opts_kw, prepare):
+        fn = lambda *_: self._create(r, shard, opts_kw, prepare)  # noqa: E731
+        while fn is not None:
+            try:
+                self._done.put((r, fn(r, self.solvers[r], self.problems[r]), None))
+            except Exception as e:  # noqa: BLE001 (re-raised by the caller's thread)
+                if self.solvers[r] is not None:
+                    load().rsba_solver_comm_abort(self.solvers[r].h)
+                self._done.put((r, None, e))
+            fn = self._jobs[r].get()
+        for h in (self.solvers[r], self.problems[r]):
+            if h is not None:
+                h.close()
+
+    def _collect(self):
+        out, err = [None] * self.world, [None] * self.world
+        for _ in range(self.world):
+            r, res, e = self._done.get()
+            out[r], err[r] = res, e
+        bad = [(r, e) for r, e in enumerate(err) if e is not None]
+        if bad:
+            self._failed = True
+            # the rank that gave up first, not the ones its abort released (RSBA_ERR_COMM)
+            bad.sort(key=lambda re: isinstance(re[1], RsbaError) and re[1].code == ERR_COMM)
+            raise RuntimeError("loopback rank %d failed: %s" % bad[0]) from bad[0][1]
+        return out
+
+    def run(self, fn):
+        if self._failed or self._threads is None:
+            raise RuntimeError("the loopback group has failed or is closed")
+        for q in self._jobs:
+            q.put(fn)
+        return self._collect()
+
+    def close(self):
+        if self._threads is not None:
+            for q in self._jobs:
+                q.put(None)
+            for t in self._threads:
+                t.join()
+            self._threads = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 def read_intrinsics_xml(path):

@@ -182,6 +182,29 @@ k_cov_lin(int P, const double* __restrict__ obs_u, const double* __restrict__ ob
   }
 }
 
+// A sharded solver adds its partial S to the other ranks': the upper triangle row by row, n (n + 1) / 2 values, and behind it one
+// more, 1.0 when a point block of this shard was rank deficient (the all-ranks sum counts the shards that met one).
+__device__ __forceinline__ size_t CovTriIndex(int n, int i, int j) { return (size_t)i * n - (size_t)i * (i - 1) / 2 + (size_t)(j - i); }   // i <= j
+
+__global__ void __launch_bounds__(256) k_cov_tri_pack(int n, const double* __restrict__ S, const int* __restrict__ flags, double* __restrict__ tri) {
+  const size_t nn = (size_t)n * n;
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e <= nn; e += (size_t)gridDim.x * blockDim.x) {
+    if (e == nn) { tri[(size_t)n * (n + 1) / 2] = flags[COV_FLAG_POINT] != 0 ? 1.0 : 0.0; continue; }
+    const int i = (int)(e / n), j = (int)(e - (size_t)i * n);
+    if (i <= j) tri[CovTriIndex(n, i, j)] = S[e];
+  }
+}
+
+// ... and the sums back into the upper triangle of S (all that k_cov_scale reads) and into the point flag.
+__global__ void __launch_bounds__(256) k_cov_tri_unpack(int n, const double* __restrict__ tri, double* __restrict__ S, int* __restrict__ flags) {
+  const size_t nn = (size_t)n * n;
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e <= nn; e += (size_t)gridDim.x * blockDim.x) {
+    if (e == nn) { flags[COV_FLAG_POINT] = tri[(size_t)n * (n + 1) / 2] > 0.0 ? 1 : 0; continue; }
+    const int i = (int)(e / n), j = (int)(e - (size_t)i * n);
+    if (i <= j) S[e] = tri[CovTriIndex(n, i, j)];
+  }
+}
+
 // A (np x np) = D S D from the upper triangle of S, identity in the padding; dscale[i] = S_ii^-1/2.  A zero or negative diagonal is
 // a rank deficiency (flag), the row is then scaled by 1 so that no NaN enters the sweep.
 __global__ void __launch_bounds__(256) k_cov_scale(int n, int np, const double* __restrict__ S, double* __restrict__ A, double* __restrict__ dscale,

@@ -226,6 +226,33 @@ __global__ void __launch_bounds__(256) k_eval_cost(int n, const double* __restri
   if (threadIdx.x == 0) *cost = 0.5 * v[0];
 }
 
+// Point model on a sharded solver: what the ranks add up, [cost | 6C camera gradient | C "some observation of mine references
+// camera c" flags], from this rank's cost and k_eval_cam_sum's output (the shard's own sums; 0.0 where the shard has nothing).
+// grad false: the cost alone.
+__global__ void __launch_bounds__(256)
+k_eval_shard_pack(int C, bool grad, const double* __restrict__ cost, const double* __restrict__ gradient, const int* __restrict__ cam_ptr,
+                  double* __restrict__ pay) {
+  const int n = grad ? 7 * C + 1 : 1;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    if (i == 0) pay[0] = *cost;
+    else if (i <= 6 * C) pay[i] = gradient[i - 1];
+    else { const int c = i - 1 - 6 * C; pay[i] = cam_ptr[c + 1] > cam_ptr[c] ? 1.0 : 0.0; }
+  }
+}
+
+// ... and back from the all-ranks sums: the cost, and the camera slots under the GROUP's zero mask — 0.0 for a constant camera and
+// for one no rank references; a camera this shard never observes but another does carries the other ranks' sum.
+__global__ void __launch_bounds__(256)
+k_eval_shard_unpack(int C, bool grad, const double* __restrict__ pay, const unsigned char* __restrict__ cam_const, double* __restrict__ cost,
+                    double* __restrict__ gradient) {
+  const int n = grad ? 6 * C + 1 : 1;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    if (i == 0) { *cost = pay[0]; continue; }
+    const int c = (i - 1) / 6;
+    gradient[i - 1] = cam_const[c] != 0 || pay[1 + 6 * C + c] == 0.0 ? 0.0 : pay[i];
+  }
+}
+
 // What a solver keeps for rsba_solver_evaluate: the index tables (built on the first call, from the problem's index arrays alone)
 // and the scratch arena (grows only: a repeated call neither allocates nor frees).
 struct EvalDevice {
@@ -238,11 +265,12 @@ struct EvalDevice {
   int *list_ptr = nullptr, *list_obs = nullptr;
   unsigned char* list_slot = nullptr;
   unsigned char* live = nullptr;   // per block of the gradient: != 0 computed, 0 written as 0.0 (EvalPointLive / EvalMarkerLive)
+  unsigned char* cam_const = nullptr;   // point model with a communicator: per camera, != 0 constant (k_eval_shard_unpack)
   char* arena = nullptr;
   size_t arena_cap = 0;
 
   void Free() {
-    void* ptrs[] = {cam_ptr, cam_slot, cam_point, order, pt_perm, rows, obs8, intr, list_ptr, list_obs, list_slot, live, arena};
+    void* ptrs[] = {cam_ptr, cam_slot, cam_point, order, pt_perm, rows, obs8, intr, list_ptr, list_obs, list_slot, live, cam_const, arena};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     *this = EvalDevice();
   }

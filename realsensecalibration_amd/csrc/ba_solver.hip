@@ -284,6 +284,10 @@ struct rsba_solver {
   // ---- evaluate (rsba_solver_evaluate, ba_evaluate.hpp): tables and arena of its own, the LM state is not touched
   EvalDevice eval;
   std::vector<uint8_t> eval_const_cam, eval_const_pt, eval_const_block;   // the problem's constant flags as they were at create
+
+  // ---- the three above on a solver with a communicator (ShardedQuery): the request word and the camera check travel from here
+  double* query_buf = nullptr;                 // device scratch, kept between calls (grows only)
+  size_t query_cap = 0;
 };
 
 namespace rsba {
@@ -379,7 +383,7 @@ static void FreeSolver(rsba_solver* s) {
   s->timer.Reset();
   void* ptrs[] = {s->obs_u, s->obs_v, s->intr, s->obs_cam, s->pt_ptr, s->sl_row_ptr, s->sl_cam, s->sl_uv, s->cam[0], s->cam[1], s->pts[0], s->pts[1], s->camc[0], s->camc[1],
                   s->cam0, s->pts0, s->scale_c, s->scale_p, s->red, s->A, s->W, s->chol_ok, s->S_copy, s->rhs_copy, s->dcam, s->block_scal,
-                  s->block_part, s->small_red, s->gmax, s->res, s->dec, s->red_tri, s->cam_free, s->pt_const, s->mc_flags, s->mc_dg, s->tc_flags, s->tc_map, s->tc_hand, s->tc_xs, s->tc_ys, s->cov_sinv, s->cov_pts, s->cov_arena};
+                  s->block_part, s->small_red, s->gmax, s->res, s->dec, s->red_tri, s->cam_free, s->pt_const, s->mc_flags, s->mc_dg, s->tc_flags, s->tc_map, s->tc_hand, s->tc_xs, s->tc_ys, s->cov_sinv, s->cov_pts, s->cov_arena, s->query_buf};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   s->tiled.Free();
   s->marker.Free();
@@ -1709,6 +1713,70 @@ static int MinimizeLoop(rsba_solver* s, rsba_summary* sum, StepFn step, AcceptFn
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Evaluate, set-parameters and covariance on a solver with a communicator (point model; include/rsba.h, "collective contract")
+// ------------------------------------------------------------------------------------------------
+// Every collective entry point of the three opens with the same small all-reduce, the REQUEST WORD: which entry point this is, which
+// outputs are wanted, apply_loss_function, min_reciprocal_condition_number and a "bad" flag (an argument error that one rank alone
+// can see).  Each value travels beside its negation under one MaxDoubles, so a rank whose value is not the largest sees the
+// difference in the first half and the rank whose value is sees it in the second: disagreement is known to every rank, and so is
+// any rank's bad flag.  The ranks then return RSBA_ERR_ARG together, before any further collective.
+struct ShardedQuery {
+  enum Entry { EVALUATE = 1, SET_PARAMETERS = 2, COVARIANCE = 3 };
+  enum { WORDS = 5 };
+  rsba_solver* s;
+  Comm* comm;
+
+  int Reserve(size_t doubles) {
+    if (s->query_buf && s->query_cap >= doubles) return RSBA_OK;
+    if (s->query_buf) { (void)hipFree(s->query_buf); s->query_buf = nullptr; s->query_cap = 0; }
+    if (hipMalloc((void**)&s->query_buf, doubles * sizeof(double)) != hipSuccess) { s->query_buf = nullptr; return RSBA_ERR_HIP; }
+    s->query_cap = doubles;
+    return RSBA_OK;
+  }
+  // [v, -v] of n host values through one MaxDoubles; out: the 2 n results
+  int MaxWithNegations(const double* v, size_t n, std::vector<double>* out) {
+    hipStream_t st = s->stream;
+    std::vector<double> h(2 * n);
+    for (size_t i = 0; i < n; ++i) { h[i] = v[i]; h[n + i] = -v[i]; }
+    int rc = Reserve(std::max<size_t>(2 * n, 64));
+    if (rc != RSBA_OK) return rc;
+    HIPCHK(hipMemcpyAsync(s->query_buf, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    COMMCHK(comm->MaxDoubles(s->query_buf, h.size(), st));
+    COMMCHK(comm->WaitStream(st));
+    out->resize(h.size());
+    HIPCHK(hipMemcpy(out->data(), s->query_buf, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+    return RSBA_OK;
+  }
+  // RSBA_OK: every rank made this request and none flagged it; RSBA_ERR_ARG: not so, on every rank alike
+  int Agree(Entry entry, int wants, int apply_loss, double rcond, bool bad) {
+    const double w[WORDS] = {(double)entry, (double)wants, (double)apply_loss, rcond, bad ? 1.0 : 0.0};
+    std::vector<double> m;
+    int rc = MaxWithNegations(w, WORDS, &m);
+    if (rc != RSBA_OK) return rc;
+    if (m[WORDS - 1] > 0.0) return RSBA_ERR_ARG;
+    for (int i = 0; i + 1 < WORDS; ++i) if (m[i] != w[i] || m[WORDS + i] != -w[i]) return RSBA_ERR_ARG;
+    return RSBA_OK;
+  }
+  // Every rank passed the same n values (compared as values: 0.0 and -0.0 agree); RSBA_ERR_ARG on every rank alike otherwise
+  int SameOnEveryRank(const double* v, size_t n) {
+    std::vector<double> m;
+    int rc = MaxWithNegations(v, n, &m);
+    if (rc != RSBA_OK) return rc;
+    // (max == min on every element, or some rank differs from one of them; which rank sees which half differ does not matter, the
+    //  two halves are the same on every rank)
+    for (size_t i = 0; i < n; ++i) if (m[i] != -m[n + i]) return RSBA_ERR_ARG;
+    return RSBA_OK;
+  }
+};
+
+// An entry point that issued collectives leaves with a code every rank shares (RSBA_OK, RSBA_ERR_ARG, RSBA_ERR_RANK_DEFICIENT), or
+// it tells the group that it gave up, as rsba_solver_create and rsba_solver_run do: the others then leave their waits with RSBA_ERR_COMM.
+static int ShardedLeave(rsba_solver* s, int rc) {
+  if (rc != RSBA_OK && rc != RSBA_ERR_ARG && rc != RSBA_ERR_RANK_DEFICIENT && s->comm) s->comm->Abort();
+  return rc;
+}
+
 // Scratch of one covariance computation, carved out of one device allocation that the solver keeps (it grows only: no hipFree — a
 // device-wide synchronisation — on a repeated call).  Two passes over the same sequence of take()s: the first sizes, the second hands out.
 struct CovCarve {
@@ -1757,8 +1825,9 @@ static void CovInvert(rsba_solver* s, const CovSystem& y, double rcond, hipStrea
 
 // ceres::Covariance::Compute (ba_covariance.hpp): the system's size from the free referenced blocks, scratch, then `launch` queues the
 // linearisation into y.S; the inverse and the flags follow.  Everything on the solver's stream, nothing the LM loop reads is written.
-template <typename Extra, typename Launch>
-static int CovRun(rsba_solver* s, int n, double rcond, Extra&& extra, Launch&& launch) {
+// `reduce` (a sharded solver: the ranks' partial systems summed, CovariancePoints; nothing otherwise) sits between the two.
+template <typename Extra, typename Launch, typename Reduce>
+static int CovRun(rsba_solver* s, int n, double rcond, Extra&& extra, Launch&& launch, Reduce&& reduce) {
   hipStream_t st = s->stream;
   s->cov_n = n;
   CovSystem y;
@@ -1775,6 +1844,7 @@ static int CovRun(rsba_solver* s, int n, double rcond, Extra&& extra, Launch&& l
   hip(hipMemsetAsync(y.flags, 0, COV_FLAG_WORDS * sizeof(int), st));
   hip(hipMemsetAsync(y.S, 0, std::max<size_t>((size_t)n * n, 1) * sizeof(double), st));
   launch(y, hip);
+  if (int rrc = reduce(y, hip)) return rrc;
   CovInvert(s, y, rcond, st);
   hip(hipGetLastError());
   int fl[COV_FLAG_WORDS] = {0, 0};
@@ -1787,12 +1857,27 @@ static int CovRun(rsba_solver* s, int n, double rcond, Extra&& extra, Launch&& l
 }
 
 // Point model: S^-1 of the free referenced cameras and the 3 x 3 marginal of every point, at the solver's current device state.
-static int CovariancePoints(rsba_solver* s, const rsba_covariance_options& co) {
+// With a communicator (`comm`; the request word has been agreed by then): the column map from the ALL-RANKS referenced flags, so
+// that every rank lays S out alike; the shards' partial systems and their point flags summed in one group; every rank then inverts
+// the identical sum, and forms the marginals of its own points against it.
+static int CovariancePoints(rsba_solver* s, const rsba_covariance_options& co, Comm* comm) {
   const rsba_problem& p = *s->prob;
   const int C = s->C, P = s->P;
   s->cov_ref_cam.assign(C, 0);
   s->cov_ref_pt.assign(P, 0);
   for (int64_t i = 0; i < s->N; ++i) { s->cov_ref_cam[p.camera_index[i]] = 1; s->cov_ref_pt[p.point_index[i]] = 1; }
+  if (comm) {
+    ShardedQuery q{s, comm};
+    std::vector<double> f(std::max(C, 1), 0.0);
+    for (int c = 0; c < C; ++c) f[c] = s->cov_ref_cam[c] ? 1.0 : 0.0;
+    int rc = q.Reserve(f.size());
+    if (rc != RSBA_OK) return rc;
+    HIPCHK(hipMemcpyAsync(s->query_buf, f.data(), f.size() * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    COMMCHK(comm->SumDoubles(s->query_buf, f.size(), s->stream));
+    COMMCHK(comm->WaitStream(s->stream));
+    HIPCHK(hipMemcpy(f.data(), s->query_buf, f.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int c = 0; c < C; ++c) s->cov_ref_cam[c] = f[c] > 0.0;
+  }
   s->cov_pos.assign(C, -1);
   int n = 0;
   for (int c = 0; c < C; ++c) {
@@ -1800,9 +1885,13 @@ static int CovariancePoints(rsba_solver* s, const rsba_covariance_options& co) {
     if (s->cov_ref_cam[c] && !constant) { s->cov_pos[c] = n; n += 6; }
   }
   if (!s->cov_pts) { int rc = DevAlloc(&s->cov_pts, 9 * (size_t)P); if (rc) return rc; }
-  double* camc = nullptr;
+  double *camc = nullptr, *tri = nullptr;
   int *pos = nullptr, *perm = nullptr;
-  auto extra = [&](CovCarve& cv) { camc = cv.take<double>((size_t)CC_STRIDE * C); pos = cv.take<int>(C); perm = s->pt_perm.empty() ? nullptr : cv.take<int>(P); };
+  const size_t ntri = (size_t)n * (n + 1) / 2 + 1;   // the upper triangle of S and the point flag (k_cov_tri_pack)
+  auto extra = [&](CovCarve& cv) {
+    camc = cv.take<double>((size_t)CC_STRIDE * C); pos = cv.take<int>(C); perm = s->pt_perm.empty() ? nullptr : cv.take<int>(P);
+    if (comm) tri = cv.take<double>(ntri);
+  };
   // the current device state: the last run's accepted point, or the uploaded start before the first run
   const double* cam = s->has_run ? s->cam[s->cur] : s->cam0;
   const double* pts = s->has_run ? s->pts[s->cur] : s->pts0;
@@ -1815,6 +1904,16 @@ static int CovariancePoints(rsba_solver* s, const rsba_covariance_options& co) {
     if (perm) hip(hipMemcpyAsync(perm, s->pt_perm.data(), P * sizeof(int), hipMemcpyHostToDevice, st));
     k_camera_constants<<<(C + 63) / 64, 64, 0, st>>>(C, cam, s->intr, camc);
     k_cov_lin<<<grid_pts, 256, 0, st>>>(P, s->obs_u, s->obs_v, s->obs_cam, s->pt_ptr, camc, pts, pos, s->pt_const, loss, rcond, y.n, y.S, y.flags);
+  }, [&](CovSystem& y, auto& hip) -> int {
+    if (!comm) return RSBA_OK;
+    const int grid_tri = (int)std::min<size_t>(((size_t)n * n + 256) / 256, 8192);
+    k_cov_tri_pack<<<grid_tri, 256, 0, st>>>(n, y.S, y.flags, tri);
+    hip(hipGetLastError());
+    COMMCHK(comm->SumDoubles(tri, ntri, st));   // (one payload: the flag rides behind the triangle)
+    k_cov_tri_unpack<<<grid_tri, 256, 0, st>>>(n, tri, y.S, y.flags);
+    hip(hipGetLastError());
+    COMMCHK(comm->WaitStream(st));
+    return RSBA_OK;
   });
   if (rc != RSBA_OK || !s->cov_valid) return rc;
   s->cov_valid = false;
@@ -1887,7 +1986,7 @@ static int CovarianceMarker(rsba_solver* s, const rsba_covariance_options& co) {
     else
       k_cov_mc_lin<false><<<std::max(1, std::min(T, 4096)), 64, 0, st>>>(T, tptr_d, rows_d, obs_d, intr, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags);
     // (the host vectors outlive CovRun, which synchronises the stream before it returns)
-  });
+  }, [](CovSystem&, auto&) { return RSBA_OK; });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1924,6 +2023,11 @@ static int EvalBuildTables(rsba_solver* s) {
         (rc = EvalUpload(&e.order, order32)) || (rc = EvalUpload(&e.live, live)))
       return rc;
     if (!s->pt_perm.empty() && (rc = EvalUpload(&e.pt_perm, s->pt_perm))) return rc;
+    if (s->comm) {   // the group's zero mask (k_eval_shard_unpack) needs the constant cameras apart from the unreferenced ones
+      std::vector<unsigned char> cam_const(std::max(s->C, 1), 0);
+      for (int c = 0; c < s->C && c < (int)s->eval_const_cam.size(); ++c) cam_const[c] = s->eval_const_cam[c] ? 1 : 0;
+      if ((rc = EvalUpload(&e.cam_const, cam_const))) return rc;
+    }
   } else {
     const int nb = p.num_cameras + p.num_times + p.num_markers;
     const std::vector<EvalMarkerRow> rows = EvalMarkerRows(p);
@@ -1945,7 +2049,10 @@ static int EvalBuild(rsba_solver* s) {
   return RSBA_OK;
 }
 
-static int EvaluateOnDevice(rsba_solver* s, bool apply_loss, double* cost, double* residuals, double* gradient) {
+// `comm` (point model; the request word has been agreed by then): cost and camera gradient are the all-ranks sums — the shard's
+// own sums as without one, then [cost | 6C | C referenced flags] added over the ranks under one group and the zero mask taken from
+// the summed flags.  Residuals and point slots are the shard's own.  nullptr: nothing of this is launched.
+static int EvaluateOnDevice(rsba_solver* s, bool apply_loss, double* cost, double* residuals, double* gradient, Comm* comm = nullptr) {
   const rsba_problem& p = *s->prob;
   EvalDevice& e = s->eval;
   int rc = EvalBuild(s);
@@ -1955,7 +2062,7 @@ static int EvaluateOnDevice(rsba_solver* s, bool apply_loss, double* cost, doubl
   const int C = p.num_cameras, nb = points ? 0 : C + p.num_times + p.num_markers;
   const int grid = points ? std::max(1, std::min((s->P + 3) / 4, 8192)) : (int)std::max<size_t>(1, (N + 63) / 64);   // = the cost's partials
   const double loss = !apply_loss || !(s->opt.huber_delta > 0.0) ? 0.0 : (s->opt.loss_type == RSBA_LOSS_CAUCHY ? -s->opt.huber_delta : s->opt.huber_delta);
-  double *posec = nullptr, *res_d = nullptr, *grad_d = nullptr, *work = nullptr, *cost_parts = nullptr, *cost_d = nullptr;
+  double *posec = nullptr, *res_d = nullptr, *grad_d = nullptr, *work = nullptr, *cost_parts = nullptr, *cost_d = nullptr, *pay = nullptr;
   auto carve = [&](CovCarve& cv) {
     posec = cv.take<double>((size_t)CC_STRIDE * (points ? C : nb));
     res_d = residuals ? cv.take<double>(nres) : nullptr;
@@ -1964,6 +2071,7 @@ static int EvaluateOnDevice(rsba_solver* s, bool apply_loss, double* cost, doubl
     work = gradient ? cv.take<double>(points ? (size_t)C * RSBA_EVAL_CAM_SEGS * 6 : 18 * N) : nullptr;
     cost_parts = cv.take<double>(grid);
     cost_d = cv.take<double>(1);
+    if (comm) pay = cv.take<double>(7 * (size_t)C + 1);
   };
   CovCarve sizing;
   carve(sizing);
@@ -1999,6 +2107,22 @@ static int EvaluateOnDevice(rsba_solver* s, bool apply_loss, double* cost, doubl
   rc = RSBA_OK;
   auto hip = [&](hipError_t err) { if (err != hipSuccess && rc == RSBA_OK) rc = RSBA_ERR_HIP; };
   hip(hipGetLastError());
+  if (comm) {
+    const bool grad = gradient != nullptr;
+    const int grid_pay = (7 * C + 1 + 255) / 256;
+    k_eval_shard_pack<<<grid_pay, 256, 0, st>>>(C, grad, cost_d, grad_d, e.cam_ptr, pay);
+    hip(hipGetLastError());
+    COMMCHK(comm->GroupStart());
+    COMMCHK(comm->SumDoubles(pay, 1, st));
+    if (grad && C > 0) {
+      COMMCHK(comm->SumDoubles(pay + 1, 6 * (size_t)C, st));
+      COMMCHK(comm->SumDoubles(pay + 1 + 6 * (size_t)C, (size_t)C, st));
+    }
+    COMMCHK(comm->GroupEnd());
+    k_eval_shard_unpack<<<grid_pay, 256, 0, st>>>(C, grad, pay, e.cam_const, cost_d, grad_d);
+    hip(hipGetLastError());
+    COMMCHK(comm->WaitStream(st));
+  }
   if (cost) hip(hipMemcpyAsync(cost, cost_d, sizeof(double), hipMemcpyDeviceToHost, st));
   if (residuals && nres > 0) hip(hipMemcpyAsync(residuals, res_d, nres * sizeof(double), hipMemcpyDeviceToHost, st));
   if (gradient && npar > 0) hip(hipMemcpyAsync(gradient, grad_d, npar * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -2067,6 +2191,12 @@ int rsba_solver_comm_nranks(const rsba_solver* s) {
   if (!s) return 0;
   if (!s->comm) return 1;
   return s->comm->nranks();
+}
+
+int rsba_solver_comm_abort(rsba_solver* s) {
+  if (!s) return RSBA_ERR_ARG;
+  if (s->comm) s->comm->Abort();
+  return RSBA_OK;
 }
 
 int rsba_solver_schedule_info(const rsba_solver* s, rsba_schedule_info* out) {
@@ -2425,18 +2555,31 @@ int rsba_solver_covariance_compute(rsba_solver* s, const rsba_covariance_options
   if (!s) return RSBA_ERR_ARG;
   rsba_covariance_options co;
   if (o) co = *o; else rsba_covariance_options_default(&co);
-  if (!(co.min_reciprocal_condition_number >= 0.0)) return RSBA_ERR_ARG;
+  const bool bad = !(co.min_reciprocal_condition_number >= 0.0);
+  if (s->comm) {
+    // collective (rsba.h): an argument error of this rank alone travels in the request word, the group refuses together
+    if (s->prob->model != RSBA_MODEL_POINTS) return RSBA_ERR_UNSUPPORTED;   // (a marker-chain solver has one rank: nobody waits)
+    s->cov_valid = false;
+    rsba::CommScope device_turn(s->comm.get());
+    int rc = hipSetDevice(s->device) == hipSuccess && hipStreamSynchronize(s->stream) == hipSuccess ? RSBA_OK : RSBA_ERR_HIP;
+    if (rc == RSBA_OK) {
+      rsba::ShardedQuery q{s, s->comm.get()};
+      rc = q.Agree(rsba::ShardedQuery::COVARIANCE, 0, co.apply_loss_function != 0, bad ? 0.0 : co.min_reciprocal_condition_number, bad);
+    }
+    if (rc == RSBA_OK) rc = rsba::CovariancePoints(s, co, s->comm.get());
+    return rsba::ShardedLeave(s, rc);
+  }
+  if (bad) return RSBA_ERR_ARG;
   s->cov_valid = false;
-  // (several ranks: no collective is issued, every rank returns here)
-  if (s->opt.world_size > 1 || s->comm) return RSBA_ERR_UNSUPPORTED;
   if (hipSetDevice(s->device) != hipSuccess) return RSBA_ERR_HIP;
   if (hipStreamSynchronize(s->stream) != hipSuccess) return RSBA_ERR_HIP;
-  return s->prob->model == RSBA_MODEL_POINTS ? rsba::CovariancePoints(s, co) : rsba::CovarianceMarker(s, co);
+  return s->prob->model == RSBA_MODEL_POINTS ? rsba::CovariancePoints(s, co, nullptr) : rsba::CovarianceMarker(s, co);
 }
 
 int rsba_solver_covariance_block(const rsba_solver* s, int64_t offset_a, int64_t offset_b, double* out) {
   if (!s || !out) return RSBA_ERR_ARG;
   if (!s->cov_valid) return RSBA_ERR_ARG;
+  rsba::CommScope device_turn(s->comm.get());   // (local, no collective; a loopback rank copies on its turn only)
   const size_t n = (size_t)s->cov_n;
   auto copy6 = [&](int pa, int pb) {
     if (pa < 0 || pb < 0) { memset(out, 0, 36 * sizeof(double)); return RSBA_OK; }   // a constant block
@@ -2486,6 +2629,7 @@ int rsba_solver_point_covariances(const rsba_solver* s, double* out) {
   if (!s || !out) return RSBA_ERR_ARG;
   if (s->prob->model != RSBA_MODEL_POINTS) return RSBA_ERR_UNSUPPORTED;
   if (!s->cov_valid) return RSBA_ERR_ARG;
+  rsba::CommScope device_turn(s->comm.get());   // (local, no collective; a loopback rank copies on its turn only)
   if (hipSetDevice(s->device) != hipSuccess) return RSBA_ERR_HIP;
   return hipMemcpy(out, s->cov_pts, 9 * (size_t)s->P * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess ? RSBA_OK : RSBA_ERR_HIP;
 }
@@ -2499,17 +2643,45 @@ int rsba_solver_evaluate(rsba_solver* s, const rsba_evaluate_options* o, double*
   if (!s) return RSBA_ERR_ARG;
   rsba_evaluate_options eo;
   if (o) eo = *o; else rsba_evaluate_options_default(&eo);
-  // (several ranks: no collective is issued, every rank returns here)
-  if (s->opt.world_size > 1 || s->comm) return RSBA_ERR_UNSUPPORTED;
   if (!cost && !residuals && !gradient) return RSBA_OK;
+  if (s->comm) {
+    if (s->prob->model != RSBA_MODEL_POINTS) return RSBA_ERR_UNSUPPORTED;   // (a marker-chain solver has one rank: nobody waits)
+    rsba::CommScope device_turn(s->comm.get());
+    if (!cost && !gradient)   // residuals alone: this rank's shard, local, no collective
+      return hipSetDevice(s->device) == hipSuccess ? rsba::EvaluateOnDevice(s, eo.apply_loss_function != 0, nullptr, residuals, nullptr) : RSBA_ERR_HIP;
+    int rc = hipSetDevice(s->device) == hipSuccess ? RSBA_OK : RSBA_ERR_HIP;
+    if (rc == RSBA_OK) {
+      rsba::ShardedQuery q{s, s->comm.get()};
+      rc = q.Agree(rsba::ShardedQuery::EVALUATE, (cost ? 1 : 0) | (gradient ? 2 : 0), eo.apply_loss_function != 0, 0.0, false);
+    }
+    if (rc == RSBA_OK) rc = rsba::EvaluateOnDevice(s, eo.apply_loss_function != 0, cost, residuals, gradient, s->comm.get());
+    return rsba::ShardedLeave(s, rc);
+  }
   if (hipSetDevice(s->device) != hipSuccess) return RSBA_ERR_HIP;
   return rsba::EvaluateOnDevice(s, eo.apply_loss_function != 0, cost, residuals, gradient);
 }
 
 int rsba_solver_set_parameters(rsba_solver* s, const double* parameters) {
-  if (!s || !parameters) return RSBA_ERR_ARG;
-  if (s->opt.world_size > 1 || s->comm) return RSBA_ERR_UNSUPPORTED;
+  if (!s) return RSBA_ERR_ARG;
   const size_t n = s->prob->parameters.size();
+  if (s->comm) {
+    // collective (rsba.h): NULL or a non-finite value on this rank alone travels in the request word, the group refuses together
+    // and nothing changes on any rank; then every rank must have passed the same camera blocks
+    if (s->prob->model != RSBA_MODEL_POINTS) return RSBA_ERR_UNSUPPORTED;   // (a marker-chain solver has one rank: nobody waits)
+    bool bad = parameters == nullptr;
+    for (size_t i = 0; !bad && i < n; ++i) bad = !std::isfinite(parameters[i]);
+    rsba::CommScope device_turn(s->comm.get());
+    int rc = hipSetDevice(s->device) == hipSuccess && hipStreamSynchronize(s->stream) == hipSuccess ? RSBA_OK : RSBA_ERR_HIP;
+    rsba::ShardedQuery q{s, s->comm.get()};
+    if (rc == RSBA_OK) rc = q.Agree(rsba::ShardedQuery::SET_PARAMETERS, 0, 0, 0.0, bad);
+    if (rc == RSBA_OK) rc = q.SameOnEveryRank(parameters, 6 * (size_t)s->C);
+    if (rc == RSBA_OK) {
+      s->cov_valid = false;
+      rc = rsba::SetParametersOnDevice(s, parameters);
+    }
+    return rsba::ShardedLeave(s, rc);
+  }
+  if (!parameters) return RSBA_ERR_ARG;
   for (size_t i = 0; i < n; ++i) if (!std::isfinite(parameters[i])) return RSBA_ERR_ARG;
   if (hipSetDevice(s->device) != hipSuccess) return RSBA_ERR_HIP;
   if (hipStreamSynchronize(s->stream) != hipSuccess) return RSBA_ERR_HIP;
