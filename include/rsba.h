@@ -306,7 +306,7 @@ int rsba_solver_point_covariances(const rsba_solver* s, double* out);
 
 /* ------------------------------------------------------------------ evaluate and re-solve (ceres::Problem::Evaluate; values changed in place)
  * Not used by the reference, which looks at its residuals by eye (ReprojectionCheck::Reproject draws every reprojected corner beside its
- * detection, reprojection_check.cpp:68-88).  rsba_solver_evaluate is Problem::Evaluate without the Jacobian, at the solver's current
+ * detection, reprojection_check.cpp:68-88).  rsba_solver_evaluate is Problem::Evaluate's cost, residuals and gradient, at the solver's current
  * device parameters — after rsba_solver_run: the solution; before it: the uploaded start, or what rsba_solver_set_parameters set.
  * Any output may be NULL (all three: RSBA_OK, nothing is launched).
  *   residuals  rsba_solver_num_residuals doubles in the PROBLEM's observation order (the arrays given to rsba_problem_create_*, the rows
@@ -322,7 +322,8 @@ int rsba_solver_point_covariances(const rsba_solver* s, double* out);
  *              ProgramEvaluator leaves such blocks out in the same way.
  * The solver's parameters, scales, kept linearisation, iteration log, schedule and covariance result are left untouched: run ->
  * evaluate -> run gives the bits of run -> run, and two consecutive calls return the same bits in every output (every sum is taken in a
- * fixed order).  Scratch is kept by the solver and only grows.  The Jacobian is not offered (it is never formed in memory).
+ * fixed order).  Scratch is kept by the solver and only grows.  The Jacobian, Problem::Evaluate's fourth output, has entry points of its
+ * own below (rsba_solver_jacobian_structure, rsba_solver_evaluate_jacobian): the solve never forms it in memory.
  *
  * A solver with a communicator (point model): a call with cost or gradient non-NULL is COLLECTIVE (the contract below); one that
  * asks for residuals alone is local and issues no collective.
@@ -357,6 +358,32 @@ void rsba_evaluate_options_default(rsba_evaluate_options* o);
 /* 2 N (point model), 8 N (marker-chain models); for a NULL solver the negative code -RSBA_ERR_ARG, which is no count. */
 int64_t rsba_solver_num_residuals(const rsba_solver* s);
 int rsba_solver_evaluate(rsba_solver* s, const rsba_evaluate_options* o /* NULL = defaults */, double* cost, double* residuals, double* gradient);
+/* The Jacobian of the residual vector rsba_solver_evaluate returns, at the same parameters, in compressed-row form (ceres::CRSMatrix):
+ * row r's entries are cols[row_ptr[r] .. row_ptr[r + 1]) and the values at the same positions.
+ *   rows     rsba_solver_num_residuals, in the problem's observation order: observation i owns rows 2i, 2i+1 (point model) or
+ *            8i .. 8i+7 (marker-chain models; the corner order of the residuals).
+ *   columns  rsba_problem_num_parameters, in the problem's parameter layout: column index = parameter offset, the convention of the
+ *            gradient and of rsba_problem_set_parameter_block_constant.  THIS DEPARTS FROM CERES, which renumbers the columns after
+ *            dropping the constant blocks; it is chosen so that J'r is the gradient rsba_solver_evaluate returns, slot for slot.
+ *   nonzeros a row holds all 6 (or 3) columns of every parameter block its observation names as a parameter and that is free, by
+ *            the constant flags the solver took at create: camera then point; camera, time, marker — ascending columns.  Constant
+ *            blocks and the fixed base blocks of the marker-chain models (no parameters of any functor) are left out, not stored as
+ *            zeros: a row whose blocks are all constant is empty.  An entry that happens to be 0.0 is still stored; duplicate
+ *            observations give duplicate rows; the columns of unreferenced blocks have no entries.
+ *   values   with apply_loss_function and a loss configured the rows of a residual block are multiplied by sqrt(rho'(s)) of that
+ *            block, the corrector the solve and the residual output apply; raw otherwise.  No Jacobi scale, no damping.
+ * rsba_solver_jacobian_structure: any output may be NULL (ask for the three counts, then for the arrays: row_ptr num_rows + 1,
+ * cols num_nonzeros).  The structure depends on the index arrays and the constant flags at create alone — the same before and after
+ * a run — and nothing is launched on the device.  rsba_solver_evaluate_jacobian writes num_nonzeros values in the structure's order.
+ * Nothing of the solver's state is written (run -> jacobian -> run gives the bits of run -> run), and no sum is taken anywhere: two
+ * calls return identical bits, and a dense-path and a time-eliminating marker-chain solver agree bit for bit at the same parameters.
+ * Errors, before any device work: NULL solver or NULL values RSBA_ERR_ARG; more than INT32_MAX parameters or observations
+ * RSBA_ERR_UNSUPPORTED.
+ * A solver with a communicator (point model): both calls are LOCAL and issue no collective, like a residuals-only evaluate.  The
+ * matrix is that of this rank's problem: its shard's observations, the shared cameras, then its own points. */
+int rsba_solver_jacobian_structure(rsba_solver* s, int64_t* num_rows, int64_t* num_cols, int64_t* num_nonzeros,
+                                   int64_t* row_ptr /* num_rows + 1, or NULL */, int32_t* cols /* num_nonzeros, or NULL */);
+int rsba_solver_evaluate_jacobian(rsba_solver* s, const rsba_evaluate_options* o /* NULL = defaults */, double* values /* num_nonzeros */);
 /* Ceres keeps the values in the caller's arrays: change them and Solve again, the Problem is not rebuilt.  Here: rsba_problem_num_parameters
  * new values into the solver's start state (what rsba_solver_run restarts from), which also become the current state that
  * rsba_solver_evaluate, rsba_solver_covariance_compute and rsba_solver_download read.  Nothing is planned or allocated again — the

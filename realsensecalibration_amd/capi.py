@@ -32,6 +32,7 @@ EXPORTS = [
     "rsba_covariance_options_default", "rsba_solver_covariance_compute", "rsba_solver_covariance_block", "rsba_solver_point_covariances",
     "rsba_solver_time_elimination",
     "rsba_evaluate_options_default", "rsba_solver_num_residuals", "rsba_solver_evaluate", "rsba_solver_set_parameters",
+    "rsba_solver_jacobian_structure", "rsba_solver_evaluate_jacobian",
     "rsba_solver_comm_abort",
 ]
 
@@ -162,6 +163,8 @@ def load():
     lib.rsba_solver_num_residuals.argtypes = [C.c_void_p]
     lib.rsba_solver_num_residuals.restype = C.c_int64
     lib.rsba_solver_evaluate.argtypes = [C.c_void_p] * 5
+    lib.rsba_solver_jacobian_structure.argtypes = [C.c_void_p] * 6
+    lib.rsba_solver_evaluate_jacobian.argtypes = [C.c_void_p] * 3
     lib.rsba_solver_set_parameters.argtypes = [C.c_void_p, C.c_void_p]
     lib.rsba_solver_comm_abort.argtypes = [C.c_void_p]
     _LIB = lib
@@ -397,7 +400,7 @@ class Solver:
             return 3
         return 6
 
-    # ---- ceres::Problem::Evaluate (no Jacobian) and values changed in place
+    # ---- ceres::Problem::Evaluate (the Jacobian: jacobian_structure / evaluate_jacobian) and values changed in place
     @property
     def num_residuals(self):
         return int(load().rsba_solver_num_residuals(self.h))
@@ -414,6 +417,27 @@ class Solver:
         _chk(load().rsba_solver_evaluate(self.h, C.byref(o), C.byref(cost), _vp(r) if residuals else None, _vp(g) if gradient else None),
              "rsba_solver_evaluate")
         return cost.value, r, g
+
+    def jacobian_structure(self):
+        """((rows, cols), indptr int64, indices int32) of the Jacobian of evaluate()'s residuals: compressed rows in the problem's
+        observation order, column index = parameter offset; constant and base blocks are structurally absent.  The triple
+        (values, indices, indptr) is what a CSR constructor takes."""
+        nr, nc, nnz = C.c_int64(), C.c_int64(), C.c_int64()
+        _chk(load().rsba_solver_jacobian_structure(self.h, C.byref(nr), C.byref(nc), C.byref(nnz), None, None), "rsba_solver_jacobian_structure")
+        indptr, indices = np.zeros(nr.value + 1, np.int64), np.zeros(nnz.value, np.int32)
+        _chk(load().rsba_solver_jacobian_structure(self.h, None, None, None, _vp(indptr), _vp(indices)), "rsba_solver_jacobian_structure")
+        return (int(nr.value), int(nc.value)), indptr, indices
+
+    def evaluate_jacobian(self, apply_loss_function=True):
+        """The values of that matrix at the solver's current parameters, in the structure's order."""
+        o = EvaluateOptions()
+        load().rsba_evaluate_options_default(C.byref(o))
+        o.apply_loss_function = 1 if apply_loss_function else 0
+        nnz = C.c_int64()
+        _chk(load().rsba_solver_jacobian_structure(self.h, None, None, C.byref(nnz), None, None), "rsba_solver_jacobian_structure")
+        values = np.zeros(max(nnz.value, 1))   # (never a NULL pointer: an empty matrix is no argument error)
+        _chk(load().rsba_solver_evaluate_jacobian(self.h, C.byref(o), _vp(values)), "rsba_solver_evaluate_jacobian")
+        return values[:nnz.value]
 
     def set_parameters(self, x):
         """New values for every parameter (the problem's layout): the start of the next run() and the current state that

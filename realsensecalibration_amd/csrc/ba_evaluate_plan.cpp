@@ -3,6 +3,7 @@
 #include "ba_evaluate_plan.hpp"
 
 #include <algorithm>
+#include <utility>
 
 namespace rsba {
 
@@ -71,6 +72,81 @@ std::vector<unsigned char> EvalMarkerLive(int num_blocks, const std::vector<Eval
   const int nconst = (int)std::min<size_t>(block_constant.size(), (size_t)num_blocks);
   for (int b = 0; b < nconst; ++b) if (block_constant[b]) live[b] = 0;
   return live;
+}
+
+static bool IsConstant(const std::vector<uint8_t>& flags, int b) { return b >= 0 && (size_t)b < flags.size() && flags[b] != 0; }
+
+static EvalJacobianLayout FinishLayout(EvalJacobianLayout l, int rows_per_obs) {
+  const size_t N = l.width.size();
+  l.off.resize(N + 1);
+  int64_t at = 0;
+  for (size_t i = 0; i < N; ++i) { l.off[i] = at; at += (int64_t)rows_per_obs * l.width[i]; }
+  l.off[N] = at;
+  return l;
+}
+
+EvalJacobianLayout EvalPointJacobianLayout(int64_t N, const int32_t* camera_index, const int32_t* point_index,
+                                           const std::vector<uint8_t>& camera_constant, const std::vector<uint8_t>& point_constant) {
+  EvalJacobianLayout l;
+  l.width.resize((size_t)N);
+  for (int64_t i = 0; i < N; ++i)
+    l.width[i] = (unsigned char)((IsConstant(camera_constant, camera_index[i]) ? 0 : 6) + (IsConstant(point_constant, point_index[i]) ? 0 : 3));
+  return FinishLayout(std::move(l), 2);
+}
+
+EvalJacobianLayout EvalMarkerJacobianLayout(const std::vector<EvalMarkerRow>& rows, const std::vector<uint8_t>& block_constant) {
+  EvalJacobianLayout l;
+  l.width.resize(rows.size());
+  for (size_t i = 0; i < rows.size(); ++i) {
+    int w = 0;
+    for (int b : {rows[i].cam_block, rows[i].time_block, rows[i].marker_block}) if (b >= 0 && !IsConstant(block_constant, b)) w += 6;
+    l.width[i] = (unsigned char)w;
+  }
+  return FinishLayout(std::move(l), 8);
+}
+
+void EvalJacobianRowPtr(const EvalJacobianLayout& l, int rows_per_obs, int64_t* row_ptr) {
+  if (!row_ptr) return;
+  const size_t N = l.width.size();
+  for (size_t i = 0; i < N; ++i)
+    for (int r = 0; r < rows_per_obs; ++r) row_ptr[(size_t)rows_per_obs * i + r] = l.off[i] + (int64_t)r * l.width[i];
+  row_ptr[(size_t)rows_per_obs * N] = l.off[N];
+}
+
+void EvalPointJacobianCols(const EvalJacobianLayout& l, int C, const int32_t* camera_index, const int32_t* point_index,
+                           const std::vector<uint8_t>& camera_constant, const std::vector<uint8_t>& point_constant, int32_t* cols) {
+  if (!cols) return;
+  const size_t N = l.width.size();
+  for (size_t i = 0; i < N; ++i) {
+    const int w = l.width[i];
+    int32_t* row = cols + l.off[i];
+    int q = 0;
+    if (!IsConstant(camera_constant, camera_index[i])) for (int a = 0; a < 6; ++a) row[q++] = 6 * camera_index[i] + a;
+    if (!IsConstant(point_constant, point_index[i])) for (int a = 0; a < 3; ++a) row[q++] = 6 * C + 3 * point_index[i] + a;
+    for (int a = 0; a < w; ++a) row[w + a] = row[a];
+  }
+}
+
+void EvalMarkerJacobianCols(const EvalJacobianLayout& l, const std::vector<EvalMarkerRow>& rows, const std::vector<uint8_t>& block_constant,
+                            int32_t* cols) {
+  if (!cols) return;
+  for (size_t i = 0; i < rows.size(); ++i) {
+    const int w = l.width[i];
+    int32_t* row = cols + l.off[i];
+    int q = 0;
+    for (int b : {rows[i].cam_block, rows[i].time_block, rows[i].marker_block})
+      if (b >= 0 && !IsConstant(block_constant, b)) for (int a = 0; a < 6; ++a) row[q++] = 6 * b + a;
+    for (int r = 1; r < 8; ++r) for (int a = 0; a < w; ++a) row[r * w + a] = row[a];
+  }
+}
+
+std::vector<EvalJacobianPointRow> EvalJacobianPointRows(int P, int64_t N, const int32_t* camera_index, const int32_t* point_index,
+                                                        const std::vector<int>& pt_perm) {
+  std::vector<int> pos(P);
+  for (int jn = 0; jn < P; ++jn) pos[pt_perm.empty() ? jn : pt_perm[jn]] = jn;
+  std::vector<EvalJacobianPointRow> rows((size_t)N);
+  for (int64_t i = 0; i < N; ++i) rows[i] = EvalJacobianPointRow{camera_index[i], pos[point_index[i]]};
+  return rows;
 }
 
 }  // namespace rsba

@@ -46,4 +46,33 @@ EvalMarkerLists BuildEvalMarkerLists(int num_blocks, const std::vector<EvalMarke
 // ... and the live mask of the blocks of [C | T | M] (block b sits at 6 b).  block_constant may be shorter than num_blocks.
 std::vector<unsigned char> EvalMarkerLive(int num_blocks, const std::vector<EvalMarkerRow>& rows, const std::vector<uint8_t>& block_constant);
 
+// ---- the Jacobian of rsba_solver_evaluate_jacobian, in compressed-row form (ba_evaluate_jacobian.hpp)
+// Rows in the problem's observation order (2 per observation on the point model, 8 on the marker chain), columns = parameter
+// offsets.  A row holds every column of every block its observation names as a parameter and that is not constant — camera, then
+// point / camera, time, marker: ascending offsets — so all rows of an observation have the same width and its values are one
+// contiguous piece, row after row: `off[i]` is where observation i's piece starts (off[N]: the number of nonzeros), `width[i]` the
+// entries per row.  A named block is referenced by definition, so of EvalPointLive / EvalMarkerLive only the constant part applies.
+struct EvalJacobianLayout {
+  std::vector<int64_t> off;           // N + 1
+  std::vector<unsigned char> width;   // N: 0, 3, 6 or 9 (point model); 0, 6, 12 or 18 (marker chain)
+};
+EvalJacobianLayout EvalPointJacobianLayout(int64_t N, const int32_t* camera_index, const int32_t* point_index,
+                                           const std::vector<uint8_t>& camera_constant, const std::vector<uint8_t>& point_constant);
+EvalJacobianLayout EvalMarkerJacobianLayout(const std::vector<EvalMarkerRow>& rows, const std::vector<uint8_t>& block_constant);
+// row_ptr (rows_per_obs N + 1 entries) from the layout alone.  The three fill functions do nothing for a nullptr output.
+void EvalJacobianRowPtr(const EvalJacobianLayout& l, int rows_per_obs, int64_t* row_ptr);
+// cols (off[N] entries) of the two models, the same walk as the layout's.  Written into the caller's array: at two million
+// observations it is 36 million entries, which nobody wants to hold twice.
+void EvalPointJacobianCols(const EvalJacobianLayout& l, int C, const int32_t* camera_index, const int32_t* point_index,
+                           const std::vector<uint8_t>& camera_constant, const std::vector<uint8_t>& point_constant, int32_t* cols);
+void EvalMarkerJacobianCols(const EvalJacobianLayout& l, const std::vector<EvalMarkerRow>& rows, const std::vector<uint8_t>& block_constant,
+                            int32_t* cols);
+// Point model: what the kernel gathers through, one entry per observation in the problem's order — its camera and the DEVICE
+// position of its point (pt_perm: device position -> problem point; empty: identity).
+struct EvalJacobianPointRow {
+  int32_t camera, point;
+};
+std::vector<EvalJacobianPointRow> EvalJacobianPointRows(int P, int64_t N, const int32_t* camera_index, const int32_t* point_index,
+                                                        const std::vector<int>& pt_perm);
+
 }  // namespace rsba

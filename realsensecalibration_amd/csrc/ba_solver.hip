@@ -30,6 +30,7 @@
 #include "ba_comm.hpp"
 #include "ba_covariance.hpp"
 #include "ba_evaluate.hpp"
+#include "ba_evaluate_jacobian.hpp"
 #include "ba_marker_kernels.hpp"
 #include "ba_marker_schur.hpp"
 #include "ba_point_kernels.hpp"
@@ -283,6 +284,7 @@ struct rsba_solver {
 
   // ---- evaluate (rsba_solver_evaluate, ba_evaluate.hpp): tables and arena of its own, the LM state is not touched
   EvalDevice eval;
+  EvalJacobianDevice eval_jac;   // rsba_solver_jacobian_structure / rsba_solver_evaluate_jacobian (ba_evaluate_jacobian.hpp)
   std::vector<uint8_t> eval_const_cam, eval_const_pt, eval_const_block;   // the problem's constant flags as they were at create
 
   // ---- the three above on a solver with a communicator (ShardedQuery): the request word and the camera check travel from here
@@ -389,6 +391,7 @@ static void FreeSolver(rsba_solver* s) {
   s->marker.Free();
   s->marker_schur.Free();
   s->eval.Free();
+  s->eval_jac.Free();
   for (hipEvent_t e : s->ev_serial) if (e) (void)hipEventDestroy(e);
   if (s->res_host) (void)hipHostFree(s->res_host);
   if (s->trace_base) (void)hipFree(s->trace_base);
@@ -2130,6 +2133,111 @@ static int EvaluateOnDevice(rsba_solver* s, bool apply_loss, double* cost, doubl
   return rc;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The Jacobian of Problem::Evaluate as a CRS matrix (rsba_solver_jacobian_structure / rsba_solver_evaluate_jacobian; kernels:
+// ba_evaluate_jacobian.hpp, structure: ba_evaluate_plan.cpp)
+// ------------------------------------------------------------------------------------------------
+// The layout, on the host: from the problem's index arrays and the constant flags the solver took at create, like evaluate's tables.
+static int JacobianPlan(rsba_solver* s) {
+  EvalJacobianDevice& j = s->eval_jac;
+  if (j.planned) return RSBA_OK;
+  const rsba_problem& p = *s->prob;
+  if (p.num_parameters() > INT32_MAX || p.num_observations > INT32_MAX) return RSBA_ERR_UNSUPPORTED;   // (int32 columns; evaluate's N limit)
+  if (p.model == RSBA_MODEL_POINTS)
+    j.layout = EvalPointJacobianLayout(p.num_observations, p.camera_index.data(), p.point_index.data(), s->eval_const_cam, s->eval_const_pt);
+  else
+    j.layout = EvalMarkerJacobianLayout(EvalMarkerRows(p), s->eval_const_block);
+  j.planned = true;
+  return RSBA_OK;
+}
+
+static int JacobianStructure(rsba_solver* s, int64_t* num_rows, int64_t* num_cols, int64_t* num_nonzeros, int64_t* row_ptr, int32_t* cols) {
+  int rc = JacobianPlan(s);
+  if (rc != RSBA_OK) return rc;
+  const rsba_problem& p = *s->prob;
+  const EvalJacobianLayout& l = s->eval_jac.layout;
+  if (num_rows) *num_rows = (int64_t)p.obs_dim() * p.num_observations;
+  if (num_cols) *num_cols = p.num_parameters();
+  if (num_nonzeros) *num_nonzeros = l.off.back();
+  EvalJacobianRowPtr(l, p.obs_dim(), row_ptr);
+  if (cols) {
+    if (p.model == RSBA_MODEL_POINTS)
+      EvalPointJacobianCols(l, p.num_cameras, p.camera_index.data(), p.point_index.data(), s->eval_const_cam, s->eval_const_pt, cols);
+    else
+      EvalMarkerJacobianCols(l, EvalMarkerRows(p), s->eval_const_block, cols);
+  }
+  return RSBA_OK;
+}
+
+// The device tables of the first call that wants values.  A failure half way frees what was uploaded: the next call starts over.
+static int JacobianBuild(rsba_solver* s) {
+  EvalJacobianDevice& j = s->eval_jac;
+  if (j.built) return RSBA_OK;
+  const rsba_problem& p = *s->prob;
+  auto upload = [&]() -> int {
+    int rc = EvalUpload(&j.off, j.layout.off);
+    if (rc != RSBA_OK || p.model != RSBA_MODEL_POINTS) return rc;
+    if ((rc = EvalUpload(&j.rows, EvalJacobianPointRows(s->P, p.num_observations, p.camera_index.data(), p.point_index.data(), s->pt_perm)))) return rc;
+    const size_t N = (size_t)p.num_observations;
+    if ((rc = DevAlloc(&j.obs, N))) return rc;
+    if (N > 0 && hipMemcpy(j.obs, p.observations.data(), N * sizeof(double2), hipMemcpyHostToDevice) != hipSuccess) return RSBA_ERR_HIP;
+    return RSBA_OK;
+  };
+  const int rc = upload();
+  if (rc != RSBA_OK) {
+    void* ptrs[] = {j.off, j.rows, j.obs};
+    for (void* q : ptrs) if (q) (void)hipFree(q);
+    j.off = nullptr; j.rows = nullptr; j.obs = nullptr;
+    return rc;
+  }
+  j.built = true;
+  return RSBA_OK;
+}
+
+// Local on every solver: no sum, so nothing for a group to add up.  Reads the current device state as EvaluateOnDevice does.
+static int JacobianOnDevice(rsba_solver* s, bool apply_loss, double* values) {
+  const rsba_problem& p = *s->prob;
+  int rc;
+  if ((rc = JacobianPlan(s)) || (rc = EvalBuild(s)) || (rc = JacobianBuild(s))) return rc;
+  EvalDevice& e = s->eval;
+  EvalJacobianDevice& j = s->eval_jac;
+  const bool points = p.model == RSBA_MODEL_POINTS;
+  const int N = (int)p.num_observations;
+  const size_t nnz = (size_t)j.layout.off.back();
+  if (nnz == 0) return RSBA_OK;
+  const int C = p.num_cameras, nb = points ? 0 : C + p.num_times + p.num_markers;
+  const double loss = !apply_loss || !(s->opt.huber_delta > 0.0) ? 0.0 : (s->opt.loss_type == RSBA_LOSS_CAUCHY ? -s->opt.huber_delta : s->opt.huber_delta);
+  double *posec = nullptr, *values_d = nullptr;
+  auto carve = [&](CovCarve& cv) {
+    posec = cv.take<double>((size_t)CC_STRIDE * (points ? C : nb));
+    values_d = cv.take<double>(nnz);
+  };
+  CovCarve sizing;
+  carve(sizing);
+  if ((rc = CovGrow(&e.arena, &e.arena_cap, sizing.off))) return rc;
+  CovCarve cv;
+  cv.base = e.arena;
+  carve(cv);
+  hipStream_t st = s->stream;
+  if (points) {
+    const double* cam = s->has_run ? s->cam[s->cur] : s->cam0;
+    const double* pts = s->has_run ? s->pts[s->cur] : s->pts0;
+    k_camera_constants<<<(C + 63) / 64, 64, 0, st>>>(C, cam, s->intr, posec);
+    k_eval_jacobian_points<<<(N + RSBA_JAC_OBS - 1) / RSBA_JAC_OBS, RSBA_JAC_OBS, 0, st>>>(N, j.rows, j.obs, j.off, posec, pts, loss, values_d);
+  } else {
+    const double* params = s->eliminate_times ? (s->has_run ? s->marker_schur.params[s->marker_schur.cur] : s->marker_schur.params0)
+                                              : (s->has_run ? s->marker.params[s->marker.cur] : s->marker.params0);
+    k_cov_pose_constants<<<(nb + 255) / 256, 256, 0, st>>>(nb, params, posec);
+    k_eval_jacobian_marker<<<(N + 63) / 64, 64, 0, st>>>(N, e.rows, e.obs8, e.intr, posec, j.off, e.live, p.marker_side / 2, loss, values_d);
+  }
+  rc = RSBA_OK;
+  auto hip = [&](hipError_t err) { if (err != hipSuccess && rc == RSBA_OK) rc = RSBA_ERR_HIP; };
+  hip(hipGetLastError());
+  hip(hipMemcpyAsync(values, values_d, nnz * sizeof(double), hipMemcpyDeviceToHost, st));
+  hip(hipStreamSynchronize(st));
+  return rc;
+}
+
 // New values into the start state and the current state; no plan, table or allocation depends on them.
 static int SetParametersOnDevice(rsba_solver* s, const double* x) {
   const rsba_problem& p = *s->prob;
@@ -2659,6 +2767,21 @@ int rsba_solver_evaluate(rsba_solver* s, const rsba_evaluate_options* o, double*
   }
   if (hipSetDevice(s->device) != hipSuccess) return RSBA_ERR_HIP;
   return rsba::EvaluateOnDevice(s, eo.apply_loss_function != 0, cost, residuals, gradient);
+}
+
+int rsba_solver_jacobian_structure(rsba_solver* s, int64_t* num_rows, int64_t* num_cols, int64_t* num_nonzeros, int64_t* row_ptr, int32_t* cols) {
+  if (!s) return RSBA_ERR_ARG;
+  return rsba::JacobianStructure(s, num_rows, num_cols, num_nonzeros, row_ptr, cols);   // (host only: no device turn to take)
+}
+
+int rsba_solver_evaluate_jacobian(rsba_solver* s, const rsba_evaluate_options* o, double* values) {
+  if (!s || !values) return RSBA_ERR_ARG;
+  rsba_evaluate_options eo;
+  if (o) eo = *o; else rsba_evaluate_options_default(&eo);
+  if (s->comm && s->prob->model != RSBA_MODEL_POINTS) return RSBA_ERR_UNSUPPORTED;   // (as rsba_solver_evaluate)
+  rsba::CommScope device_turn(s->comm.get());   // (local, no collective; a loopback rank launches on its turn only)
+  if (hipSetDevice(s->device) != hipSuccess) return RSBA_ERR_HIP;
+  return rsba::JacobianOnDevice(s, eo.apply_loss_function != 0, values);
 }
 
 int rsba_solver_set_parameters(rsba_solver* s, const double* parameters) {
