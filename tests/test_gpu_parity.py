@@ -654,7 +654,8 @@ def test_marker_chain_time_elimination_matches_oracle(oracle, shape, env, monkey
     """The split elimination (csrc/ba_marker_split.hpp, round 6) in its variants — the chunk's sum of W'Y on the matrix cores in the
     wavefronts' registers (up to 144 reduced columns: three tiles a wavefront; up to 240: eight — the (12, 40, 20) shape, 180 columns),
     the VALU accumulation in LDS (wider systems; forced here), the three product kernels on one stream — and round 4's k_time_eliminate; the
-    reduced solve with the whole triangle in LDS (up to 160 columns: 48, 108, 30 here; 180 takes the panel solver) or the panel solver forced."""
+    reduced solve with the whole triangle in LDS (up to 160 columns: 48, 108, 30 here; 180 takes the panel solver) or the panel solver forced.
+    These are whole solves; one step of every variant is held as a linear solve, to a backward-error bar, in tests/test_gpu_marker_step.py."""
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     C_, T_, M_ = shape
@@ -700,7 +701,8 @@ def test_marker_chain_at_its_benchmarked_size_matches_the_sparse_oracle(oracle, 
 @pytest.mark.parametrize("chunks", ["1", "7", "1000"])
 def test_marker_chain_chunk_count_does_not_change_the_answer(oracle, chunks):
     """RSBA_MT_CHUNKS: how many workgroups share the times of the elimination (one partial system each, summed in chunk order).
-    One chunk, a number that does not divide the times, more chunks than times: the oracle's solution each time."""
+    One chunk, a number that does not divide the times, more chunks than times: the oracle's solution each time (whole solves; the
+    partial systems' sum itself is held per step in tests/test_gpu_marker_step.py)."""
     prob = syn.make_marker_chain(8, 120, 12, seed=140)
     os.environ["RSBA_MT_CHUNKS"] = chunks
     try:
@@ -717,7 +719,8 @@ def test_marker_chain_both_back_substitution_kernels_match_the_oracle(oracle, wg
     """The shots' back-substitution: round 6's split form (k_mc_time_step from the slots' records + k_mc_candidate, a thread per
     residual block: the default), a workgroup per shot with a corner of a residual block per lane (k_time_backsub_wg, shots of
     at most 128 residual blocks) or a wavefront per shot (k_time_backsub_terms, any width; RSBA_MT_BACKSUB_WG=0 forces it).  All
-    against the oracle, on a shape with all cameras x markers in a shot (96 residual blocks) and on one with few."""
+    against the oracle, on a shape with all cameras x markers in a shot (96 residual blocks) and on one with few (whole solves; one step of
+    each kernel is held as a linear solve in tests/test_gpu_marker_step.py)."""
     if wg != "split":
         monkeypatch.setenv("RSBA_MT_SPLIT_BACKSUB", "0")
     os.environ["RSBA_MT_BACKSUB_WG"] = "1" if wg == "split" else wg
@@ -753,7 +756,8 @@ def test_marker_chain_automatic_choice_and_dense_cross_check(oracle):
 
 
 def test_marker_chain_large_reduced_system(oracle):
-    """More than 64 camera + marker blocks: the reduced system goes through the multi-launch Cholesky."""
+    """More than 64 camera + marker blocks: the reduced system goes through the multi-launch Cholesky (a whole solve; the step itself, on both
+    sides of the 384-column hand-over, is held in tests/test_gpu_marker_step.py)."""
     prob = syn.make_marker_chain(36, 24, 36, seed=5, keep=0.5)
     assert 6 * (35 + 35) > 384
     ref, s_ref, got, s = _solve_marker_chain_both(oracle, prob, 1)
@@ -779,7 +783,7 @@ def test_marker_chain_times_wider_than_the_split_kernels_hold(oracle):
     """A shot that touches more camera / marker blocks than the split accumulation's double-buffered records fit in LDS (~110 of the 170 the
     model allows): the library takes round 4's k_time_eliminate for it (32 residual blocks staged at a time, whatever the width) — 60 cameras
     x 60 markers all seen in every shot (118 blocks, 3 481 residual blocks a shot: the split kernels with the chunk sums in memory), 62 x 62
-    (122 blocks: k_time_eliminate)."""
+    (122 blocks: k_time_eliminate).  Whole solves; one step of both is held as a linear solve in tests/test_gpu_marker_step.py."""
     for C_, T_, M_ in ((60, 5, 60), (62, 4, 62)):
         prob = syn.make_marker_chain(C_, T_, M_, seed=21, keep=1.0)
         ref, s_ref, got, s = _solve_marker_chain_both(oracle, prob, 2)
