@@ -189,6 +189,26 @@ int rsba_problem_set_point_constant(rsba_problem* p, int32_t point_idx, int32_t 
  * constant only the time blocks are solved, each on its own (rsba_solver_time_elimination tells which path a solver runs). */
 int rsba_problem_set_parameter_block_constant(rsba_problem* p, int64_t parameter_offset, int32_t constant);
 
+/* Per-observation weights on the marker-chain models: what `new ceres::ScaledLoss(loss_or_NULL, a_i, TAKE_OWNERSHIP)` around each
+ * residual block's loss does (Ceres 1.14 loss_function.h, corrector.cc).  One weight a_i >= 0 per residual block (one detected
+ * marker, 8 residuals), in the problem's observation order.  With s_i = |r_i|^2 over the block's 8 residuals and rho the
+ * configured loss (Huber or Cauchy; rho(s) = s when huber_delta == 0):
+ *   - block i contributes 1/2 a_i rho(s_i) to the cost;
+ *   - rho'' <= 0 still holds, so the corrector scales the block's residuals and Jacobian rows by sqrt(a_i rho'(s_i)); gradient, Jacobi
+ *     scales, J'J, model cost change and candidate cost all come from the corrected rows, as with a loss alone;
+ *   - the raw sum of squares is never weighted: the RMS metric, rsba_solver_final_costs' second output, rsba_reprojection_error;
+ *   - apply_loss_function = 0 (evaluate, Jacobian, covariance) ignores the weights together with the loss, as Ceres ignores the
+ *     whole LossFunction.
+ * A weight of 0 is legal and leaves the block's rows zero (dropping a detection without a new problem).  A free pose block all of
+ * whose observations have weight 0 stays in the program — zero diagonal, damping from min_lm_diagonal, a zero step, its bits
+ * unchanged, as in Ceres — and rsba_solver_covariance_compute then returns RSBA_ERR_RANK_DEFICIENT.
+ * Host only; the array is copied; NULL removes the weights.  A negative or non-finite value: RSBA_ERR_ARG, nothing changes.  The point
+ * model: RSBA_ERR_UNSUPPORTED.  rsba_solve and rsba_solver_create honour the problem's weights; a problem that carries weights (all
+ * ones included) also makes its solvers accept rsba_solver_set_observation_weights. */
+int rsba_problem_set_observation_weights(rsba_problem* p, const double* weights /* num_observations, or NULL */);
+/* the problem's copy of the weights; NULL when it has none */
+const double* rsba_problem_observation_weights(const rsba_problem* p);
+
 /* Test1 file "two_cam_data.txt": `C P`, P rows `cam pt u v` (one observation per point,
  * bundle_adjustmenter.cpp:62-64), C x (rvec row, tvec row), P rows xyz.  Also accepts the extended
  * first line `C P N` with N observation rows.  One intrinsics 4-vector is used for every
@@ -397,6 +417,18 @@ int rsba_solver_evaluate_jacobian(rsba_solver* s, const rsba_evaluate_options* o
  * (one max over [cameras, -cameras], 12C doubles, compared as values); a mismatch is RSBA_ERR_ARG on every rank with nothing
  * changed.  A sharded group set to x1 then runs the bits of a group created at x1. */
 int rsba_solver_set_parameters(rsba_solver* s, const double* parameters);
+/* New observation weights (rsba_problem_set_observation_weights: semantics and validation) on a resident marker-chain solver, the way
+ * rsba_solver_set_parameters changes values: they take effect with the next run, evaluate, Jacobian or covariance call.  Nothing is
+ * planned or allocated again; parameters, iteration log and last summary stay; a covariance result is dropped.  The problem's own copy
+ * is not touched.  The intended loop: solve with Huber, evaluate raw residuals (apply_loss_function = 0), set the offenders' weights
+ * to 0, run again on the same solver.
+ * Which solvers take weights is decided once, at create, with the kernels the solver runs: those created with a robust loss
+ * (huber_delta > 0; they start from all ones) and those whose problem carried weights at create (all ones counts: that is how a
+ * caller asks for the capability without a loss).  Such a solver runs the loss instances of the marker-chain kernels, with every
+ * consequence the robust loss has for the path (rsba_solver_time_elimination keeps reporting it).  Any other marker-chain solver, and
+ * every point-model solver: RSBA_ERR_UNSUPPORTED, nothing changes.  NULL weights, a negative or non-finite value: RSBA_ERR_ARG, nothing
+ * changes. */
+int rsba_solver_set_observation_weights(rsba_solver* s, const double* weights /* num_observations */);
 
 /* Stage-level entry (tests): one linearisation of the point model at the current parameters with a
  * given trust-region radius.  Any output may be NULL.

@@ -59,6 +59,10 @@ class BALProblem {
   double* mutable_camera_transform_from_base_camera(int i) { return rsba_problem_parameters(p_) + 6 * rsba_problem_camera_idx(p_, i); }
   double* mutable_base_marker_transform_from_base_camera(int i) { return rsba_problem_parameters(p_) + 6 * num_cameras() + 6 * rsba_problem_time_idx(p_, i); }
   double* mutable_marker_transform_from_base_marker(int i) { return rsba_problem_parameters(p_) + 6 * num_cameras() + 6 * num_times() + 6 * rsba_problem_marker_idx(p_, i); }
+  // per-observation weights (ceres::ScaledLoss around each residual block's loss; rsba_problem_set_observation_weights): one
+  // a_i >= 0 per observation, nullptr removes them / none set
+  bool set_observation_weights(const double* weights) { return rsba_problem_set_observation_weights(p_, weights) == RSBA_OK; }
+  const double* observation_weights() const { return rsba_problem_observation_weights(p_); }
   // Test1 accessors
   double* mutable_cameras() { return rsba_problem_parameters(p_); }
   double* mutable_points() { return rsba_problem_parameters(p_) + 6 * num_cameras(); }

@@ -34,6 +34,7 @@ EXPORTS = [
     "rsba_evaluate_options_default", "rsba_solver_num_residuals", "rsba_solver_evaluate", "rsba_solver_set_parameters",
     "rsba_solver_jacobian_structure", "rsba_solver_evaluate_jacobian",
     "rsba_solver_comm_abort",
+    "rsba_problem_set_observation_weights", "rsba_problem_observation_weights", "rsba_solver_set_observation_weights",
 ]
 
 
@@ -167,6 +168,10 @@ def load():
     lib.rsba_solver_evaluate_jacobian.argtypes = [C.c_void_p] * 3
     lib.rsba_solver_set_parameters.argtypes = [C.c_void_p, C.c_void_p]
     lib.rsba_solver_comm_abort.argtypes = [C.c_void_p]
+    lib.rsba_problem_set_observation_weights.argtypes = [C.c_void_p, C.c_void_p]
+    lib.rsba_problem_observation_weights.argtypes = [C.c_void_p]
+    lib.rsba_problem_observation_weights.restype = C.POINTER(C.c_double)
+    lib.rsba_solver_set_observation_weights.argtypes = [C.c_void_p, C.c_void_p]
     _LIB = lib
     return lib
 
@@ -275,6 +280,23 @@ class Problem:
 
     def set_parameter_block_constant(self, parameter_offset, constant=True):
         _chk(load().rsba_problem_set_parameter_block_constant(self.h, parameter_offset, 1 if constant else 0), "rsba_problem_set_parameter_block_constant")
+
+    def set_observation_weights(self, w):
+        """Marker-chain models: one weight a_i >= 0 per residual block (ceres::ScaledLoss), the problem's observation order; None
+        removes them.  A solver created from a problem that carries weights takes new ones later (Solver.set_observation_weights)."""
+        if w is None:
+            _chk(load().rsba_problem_set_observation_weights(self.h, None), "rsba_problem_set_observation_weights")
+            return
+        w = np.ascontiguousarray(w, np.float64)
+        if w.shape != (self.num_observations,):
+            raise ValueError("set_observation_weights: %d values expected" % self.num_observations)
+        _chk(load().rsba_problem_set_observation_weights(self.h, _vp(w)), "rsba_problem_set_observation_weights")
+
+    @property
+    def observation_weights(self):
+        """A copy of the problem's weights, or None when it has none."""
+        q = load().rsba_problem_observation_weights(self.h)
+        return np.ctypeslib.as_array(q, shape=(self.num_observations,)).copy() if q else None
 
     def initial_camera_poses(self):
         _chk(load().rsba_problem_initial_camera_poses(self.h), "rsba_problem_initial_camera_poses")
@@ -446,6 +468,14 @@ class Solver:
         if x.shape != (self.problem.num_parameters,):
             raise ValueError("set_parameters: %d values expected" % self.problem.num_parameters)
         _chk(load().rsba_solver_set_parameters(self.h, _vp(x)), "rsba_solver_set_parameters")
+
+    def set_observation_weights(self, w):
+        """New weights (one per residual block, >= 0) for the next run(), evaluate() or covariance_compute() of a marker-chain
+        solver that was created with a robust loss or from a problem that carried weights; parameters, log and summary stay."""
+        w = np.ascontiguousarray(w, np.float64)
+        if w.shape != (self.problem.num_observations,):
+            raise ValueError("set_observation_weights: %d values expected" % self.problem.num_observations)
+        _chk(load().rsba_solver_set_observation_weights(self.h, _vp(w)), "rsba_solver_set_observation_weights")
 
     def final_costs(self):
         c, ss = C.c_double(), C.c_double()

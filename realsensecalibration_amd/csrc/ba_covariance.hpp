@@ -511,12 +511,13 @@ __device__ __forceinline__ bool CovSym6Inverse(const double U[21], double rcond,
 // Normal matrix of the marker-chain problem into S (n x n, zeroed by the caller, upper blocks): one wavefront per time block,
 // one lane per row (chunks of 64).  pos[block] = 6 x compact index or -1 (constant / unreferenced / eliminated).  elim[t] != 0:
 // time block t is eliminated — S -= W_x V_t^-1 W_y' over the pairs of its rows' camera / marker blocks, W_x = sum J_x'J_t.
-// kLoss: J of a row scaled by sqrt(rho'(s)) (loss: LossAndScale's signed parameter), s taken over its four corners first.
+// kLoss: J of a row scaled by sqrt(rho'(s)) (loss: LossAndScale's signed parameter), s taken over its four corners first; wts
+// (nullptr: none): the rows' weights a_q (ceres::ScaledLoss) in the rows' order, the factor sqrt(a_q) sqrt(rho').
 template <bool kLoss>
 __global__ void __launch_bounds__(64)
 k_cov_mc_lin(int T, const int* __restrict__ tptr, const CovMcRow* __restrict__ rows, const double* __restrict__ obs8, const double* __restrict__ intr,
              const double* __restrict__ pc, const int* __restrict__ pos, const unsigned char* __restrict__ elim, double half_side, double rcond,
-             int n, double* __restrict__ S, int* __restrict__ flags, double loss = 0.0) {
+             int n, double* __restrict__ S, int* __restrict__ flags, double loss = 0.0, const double* __restrict__ wts = nullptr) {
   __shared__ double Wl[64 * RSBA_COV_MC_LDS];
   __shared__ int Pl[64][2];
   const int lane = threadIdx.x;
@@ -537,6 +538,7 @@ k_cov_mc_lin(int T, const int* __restrict__ tptr, const CovMcRow* __restrict__ r
         ss += r[0] * r[0] + r[1] * r[1];
       }
       (void)LossAndScale(loss, ss, &sq);
+      if (wts != nullptr) sq *= sqrt(wts[q]);
     }
     for (int k = 0; k < 4; ++k) {
       double r[2], J[36];

@@ -146,13 +146,14 @@ k_eval_cam_sum(int C, const double* __restrict__ parts, const unsigned char* __r
 // one after the other (the loop is kept rolled): one corner's 2 x 18 rows are live at a time and J'r is added up corner by corner;
 // the 8 x 18 block is never stored.  A corner's raw residuals are written as they are formed and — s is known only after the
 // fourth corner — scaled in place by the same thread when a loss applies.  kGrad = false calls the same function and never reads
-// its J: the rows are not computed because the compiler drops the dead stores after inlining (80 registers against 208; the code
-// object is the check, tools/kernel_resources.py).
+// its J: the rows are not computed because the compiler drops the dead stores after inlining (82 registers against 208; the code
+// object is the check, tools/kernel_resources.py).  wts (nullptr: none): the observations' weights a_i (ceres::ScaledLoss), passed
+// when the loss applies: the cost a_i rho(s), residuals scaled by sqrt(a_i) sqrt(rho'), J'r by its square.
 template <bool kGrad>
 __global__ void __launch_bounds__(64)
 k_eval_marker(int N, const EvalMarkerRow* __restrict__ rows, const double* __restrict__ obs8, const double* __restrict__ intr,
               const double* __restrict__ pc, double half_side, double loss, double* __restrict__ residuals,
-              double* __restrict__ obs_grad, double* __restrict__ cost_parts) {
+              double* __restrict__ obs_grad, double* __restrict__ cost_parts, const double* __restrict__ wts = nullptr) {
   const int i = blockIdx.x * 64 + threadIdx.x;
   double rho = 0.0;
   if (i < N) {
@@ -179,6 +180,7 @@ k_eval_marker(int N, const EvalMarkerRow* __restrict__ rows, const double* __res
     }
     double sq;
     rho = LossAndScale(loss, ss, &sq);
+    if (wts != nullptr) { const double a = wts[i]; rho *= a; sq *= sqrt(a); }
     if (residuals != nullptr && sq != 1.0) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) residuals[8 * (size_t)i + e] *= sq;

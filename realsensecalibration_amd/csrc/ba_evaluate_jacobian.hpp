@@ -67,10 +67,11 @@ k_eval_jacobian_points(int N, const EvalJacobianPointRow* __restrict__ rows, con
 // kept rolled, as in k_eval_marker — one corner's 2 x 18 rows are live at a time.  A corner's two rows are stored as they are formed,
 // the columns of absent blocks (base, constant) skipped; s is known only after the fourth corner, so with a loss the thread then
 // scales its own 8 x width values in place, as the residual output does: every value is the single rounding of sq * J.
+// wts (nullptr: none): the observations' weights, passed when the loss applies: sq = sqrt(a_i) sqrt(rho').
 __global__ void __launch_bounds__(64)
 k_eval_jacobian_marker(int N, const EvalMarkerRow* __restrict__ rows, const double* __restrict__ obs8, const double* __restrict__ intr,
                        const double* __restrict__ pc, const int64_t* __restrict__ off, const unsigned char* __restrict__ live,
-                       double half_side, double loss, double* __restrict__ values) {
+                       double half_side, double loss, double* __restrict__ values, const double* __restrict__ wts = nullptr) {
   const int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= N) return;
   const int64_t o = off[i];
@@ -102,6 +103,7 @@ k_eval_jacobian_marker(int N, const EvalMarkerRow* __restrict__ rows, const doub
   }
   double sq;
   (void)LossAndScale(loss, ss, &sq);
+  if (wts != nullptr) sq *= sqrt(wts[i]);
   if (sq != 1.0) {
     for (int e = 0; e < 8 * w; ++e) v[e] *= sq;
   }

@@ -86,12 +86,15 @@ struct MarkerObs {
 // Evaluate residual blocks.  with_jacobian: J (8 x 18, columns camera|time|marker) and r (8) are stored.
 // kLoss: the residual block (one observation, 8 residuals) is robustified as Ceres' corrector does it for rho'' <= 0 (Huber,
 // Cauchy): s = |r|^2 over the 8 residuals, J and r stored scaled by sqrt(rho'(s)), rho(s) (the cost) into rho_per_obs;
-// sumsq_per_obs keeps the raw s (the RMS metric).  loss: the signed parameter of LossAndScale.
+// sumsq_per_obs keeps the raw s (the RMS metric).  loss: the signed parameter of LossAndScale (0: rho(s) = s).  wts: the blocks'
+// weights a_i (ceres::ScaledLoss), the problem's order: the cost a_i rho(s), the rows scaled by sqrt(a_i rho'(s)) — formed as
+// sqrt(a_i) sqrt(rho'), so a weight of one changes no bit and a weight of zero leaves exact zeros.
 template <bool kLoss>
 __global__ void __launch_bounds__(64) k_marker_eval(int N, const MarkerObs* __restrict__ mo, const double* __restrict__ obs8,
                               const double* __restrict__ params, const double* __restrict__ intr, double half_side,
                               int with_jacobian, double* __restrict__ Jbuf, double* __restrict__ rbuf,
-                              double* __restrict__ sumsq_per_obs, double loss = 0.0, double* __restrict__ rho_per_obs = nullptr) {
+                              double* __restrict__ sumsq_per_obs, double loss = 0.0, double* __restrict__ rho_per_obs = nullptr,
+                              const double* __restrict__ wts = nullptr) {
   // Jacobian rows leave through LDS: a thread's 36 doubles per corner would otherwise be 64 scattered 288-byte pieces per
   // store instruction (1152 B between neighbouring lanes); staged, consecutive lanes write consecutive words
   __shared__ double stage[64 * 37];
@@ -145,7 +148,9 @@ __global__ void __launch_bounds__(64) k_marker_eval(int N, const MarkerObs* __re
       // Scaling before the store would need s first, i.e. a value pass over the corners ahead of the dual-number one; the
       // re-read of the block's 1152 bytes is the cheaper of the two on this one-workgroup-system path.
       double sq;
-      const double rho = LossAndScale(loss, ss, &sq);
+      const double a = wts[ii];
+      const double rho = a * LossAndScale(loss, ss, &sq);
+      sq *= sqrt(a);
       if (live) {
         rho_per_obs[i] = rho;
         for (int e = 0; e < 8; ++e) rbuf[8 * (size_t)i + e] *= sq;
@@ -158,7 +163,7 @@ __global__ void __launch_bounds__(64) k_marker_eval(int N, const MarkerObs* __re
     }
   }
   if constexpr (kLoss) {
-    if (!with_jacobian && live) { double sq; rho_per_obs[i] = LossAndScale(loss, ss, &sq); }
+    if (!with_jacobian && live) { double sq; rho_per_obs[i] = wts[i] * LossAndScale(loss, ss, &sq); }
   }
   if (live) sumsq_per_obs[i] = ss;
 }
@@ -296,15 +301,18 @@ struct MarkerDevice {
   double *Jbuf = nullptr, *rbuf = nullptr, *ss_x = nullptr, *ss_c = nullptr, *A = nullptr, *scale = nullptr, *grad = nullptr,
          *delta = nullptr, *res = nullptr;
   double *rho_x = nullptr, *rho_c = nullptr;   // rho(s) per residual block at x / at the candidate (a robust loss only)
+  bool with_loss = false;   // the kLoss instances (Upload): a robust loss, or the problem carried observation weights
+  double* wts = nullptr;    // [N] the blocks' weights, the problem's order (with_loss only; all ones when the problem had none)
   int* act_to_full = nullptr;
   int cur = 0;
 
   void Free() {
-    void* ptrs[] = {mo, obs8, intr, params[0], params[1], params0, Jbuf, rbuf, ss_x, ss_c, A, scale, grad, delta, res, act_to_full, rho_x, rho_c};
+    void* ptrs[] = {mo, obs8, intr, params[0], params[1], params0, Jbuf, rbuf, ss_x, ss_c, A, scale, grad, delta, res, act_to_full, rho_x, rho_c, wts};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     mo = nullptr;
   }
-  int Upload(const rsba_problem& p) {
+  int Upload(const rsba_problem& p, bool loss = false) {
+    with_loss = loss;
     N = (int)p.num_observations; nfull = (int)p.parameters.size(); half_side = p.marker_side / 2;
     const int nblocks = p.num_cameras + p.num_times + p.num_markers;
     std::vector<char> used(nblocks, 0);
@@ -337,7 +345,16 @@ struct MarkerDevice {
     if (hipMemcpy(intr, p.intrinsics.data(), p.intrinsics.size() * 8, hipMemcpyHostToDevice) != hipSuccess) return RSBA_ERR_HIP;
     if (hipMemcpy(params0, p.parameters.data(), nfull * 8, hipMemcpyHostToDevice) != hipSuccess) return RSBA_ERR_HIP;
     if (hipMemcpy(act_to_full, a2f.data(), n * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return RSBA_ERR_HIP;
+    if (with_loss) {
+      if (!al((void**)&wts, (size_t)N * 8)) return RSBA_ERR_HIP;
+      const std::vector<double> ones(p.observation_weights.empty() ? (size_t)N : 0, 1.0);
+      return SetWeights(p.observation_weights.empty() ? ones.data() : p.observation_weights.data());
+    }
     return RSBA_OK;
+  }
+  // the blocks' weights, the problem's order (a solver that runs the kLoss instances)
+  int SetWeights(const double* w) {
+    return N == 0 || hipMemcpy(wts, w, (size_t)N * 8, hipMemcpyHostToDevice) == hipSuccess ? RSBA_OK : RSBA_ERR_HIP;
   }
   int Reset(hipStream_t st) {
     if (hipMemcpyAsync(params[0], params0, nfull * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return RSBA_ERR_HIP;
@@ -352,6 +369,7 @@ struct MarkerDevice {
     ip.radius = radius; ip.min_lm_diagonal = o.min_lm_diagonal; ip.max_lm_diagonal = o.max_lm_diagonal; ip.huber_delta = 0.0;
     ip.first = first ? 1 : 0; ip.jacobi_scaling = o.jacobi_scaling;
     // the robust loss, read as the point model reads it (signed: see LossAndScale); the instances without one are untouched
+    // (Upload was told whether the kLoss instances run: a loss, or weights alone with loss = 0, rho(s) = s)
     const double loss = o.huber_delta > 0.0 ? (o.loss_type == RSBA_LOSS_CAUCHY ? -o.huber_delta : o.huber_delta) : 0.0;
     const int x = cur, c = 1 - cur;
     // the candidate array must carry the untouched blocks too
@@ -363,13 +381,13 @@ struct MarkerDevice {
     };
     if (!chk("(before marker step)")) return RSBA_ERR_HIP;
     T.Begin("k_marker_eval", st);
-    if (loss != 0.0) k_marker_eval<true><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[x], intr, half_side, 1, Jbuf, rbuf, ss_x, loss, rho_x);
+    if (with_loss) k_marker_eval<true><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[x], intr, half_side, 1, Jbuf, rbuf, ss_x, loss, rho_x, wts);
     else k_marker_eval<false><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[x], intr, half_side, 1, Jbuf, rbuf, ss_x);
     T.End(st);
     if (!chk("k_marker_eval")) return RSBA_ERR_HIP;
     size_t lds = (size_t)std::max(2 * RSBA_TB * (RSBA_NB + 1) + RSBA_NB * (RSBA_NB + 1), 5 * 1024) * sizeof(double);
     if (n <= RSBA_CHOL_MAXN) lds = std::max(lds, CholeskyLdsDoubles(n) * sizeof(double));
-    const double* cost_x = loss != 0.0 ? rho_x : ss_x;   // what k_marker_system sums into the cost at x
+    const double* cost_x = with_loss ? rho_x : ss_x;   // what k_marker_system sums into the cost at x
     T.Begin("k_marker_system", st);
     if (n <= RSBA_CHOL_MAXN) {
       if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k_marker_system<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -380,11 +398,11 @@ struct MarkerDevice {
     T.End(st);
     if (!chk("k_marker_system")) return RSBA_ERR_HIP;
     T.Begin("k_marker_eval", st);
-    if (loss != 0.0) k_marker_eval<true><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[c], intr, half_side, 0, nullptr, nullptr, ss_c, loss, rho_c);
+    if (with_loss) k_marker_eval<true><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[c], intr, half_side, 0, nullptr, nullptr, ss_c, loss, rho_c, wts);
     else k_marker_eval<false><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[c], intr, half_side, 0, nullptr, nullptr, ss_c);
     T.End(st);
     T.Begin("k_marker_candidate", st);
-    if (loss != 0.0) k_marker_candidate<true><<<1, 256, 0, st>>>(N, mo, Jbuf, rbuf, delta, ss_c, res, rho_c);
+    if (with_loss) k_marker_candidate<true><<<1, 256, 0, st>>>(N, mo, Jbuf, rbuf, delta, ss_c, res, rho_c);
     else k_marker_candidate<false><<<1, 256, 0, st>>>(N, mo, Jbuf, rbuf, delta, ss_c, res);
     T.End(st);
     if (!chk("k_marker_candidate")) return RSBA_ERR_HIP;

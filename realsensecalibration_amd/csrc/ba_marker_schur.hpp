@@ -813,7 +813,7 @@ k_marker_chol_finish(int nr, const double* __restrict__ red, double* __restrict_
 //           -(J d).(r + J d / 2) and the squared residuals of the candidate (four corners through the three candidate poses).
 // Per workgroup (four times): |delta_t|^2, |x_t + delta_t|^2, model cost change, candidate sum of squares.
 // kLoss: the rows scaled by sqrt(rho') at x (wsq, k_mc_block_weight); the candidate's raw sum as without a loss, the workgroup's
-// rho(s_c) - s_c to drho_c[blockIdx.x] (k_marker_schur_finish<true>).
+// a rho(s_c) - s_c (wts: the blocks' weights, the device's time order) to drho_c[blockIdx.x] (k_marker_schur_finish<true>).
 // kConst: a constant time (tconst[t]) takes a zero step (E = 0) and its |x_t|^2 stays out of the candidate's norm.
 template <bool kLoss, bool kConst = false>
 __global__ void __launch_bounds__(256)
@@ -822,7 +822,8 @@ k_time_backsub_terms(int T, const int* __restrict__ time_ptr, const int* __restr
                      const double* __restrict__ posec /* pose constants at x */, const double* __restrict__ tdata,
                      const double* __restrict__ delta_r, const double* __restrict__ params_x, double* __restrict__ params_c,
                      double* __restrict__ delta_t, double* __restrict__ bpart /* gridDim.x x 4 */, double loss = 0.0,
-                     const double* __restrict__ wsq = nullptr, double* __restrict__ drho_c = nullptr, const int* __restrict__ tconst = nullptr) {
+                     const double* __restrict__ wsq = nullptr, double* __restrict__ drho_c = nullptr, const int* __restrict__ tconst = nullptr,
+                     const double* __restrict__ wts = nullptr) {
   __shared__ double s_part[4][4];
   __shared__ double s_dcc[kLoss ? 4 : 1];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -934,7 +935,7 @@ k_time_backsub_terms(int T, const int* __restrict__ time_ptr, const int* __restr
         cc += r0 * r0 + r1 * r1;
         if constexpr (kLoss) sb += r0 * r0 + r1 * r1;
       }
-      if constexpr (kLoss) { double sq; dcc += LossAndScale(loss, sb, &sq) - sb; }
+      if constexpr (kLoss) { double sq; dcc += wts[i] * LossAndScale(loss, sb, &sq) - sb; }
     }
   }
   // the lanes' sums in a fixed tree, then the four times of the workgroup in wave order
@@ -1237,9 +1238,11 @@ struct MarkerSchurDevice {
   hipEvent_t fork_ev[3] = {nullptr, nullptr, nullptr};
   bool backsub_wg = false;   // k_time_backsub_wg instead of k_time_backsub_terms
   double* posec_c = nullptr; // pose constants of the candidate's cameras and markers
-  bool with_loss = false;    // a robust loss (Upload): the kLoss instances, the split elimination and the wavefront-per-time or split back-substitution
+  bool with_loss = false;    // a robust loss or observation weights (Upload): the kLoss instances, the split elimination and the wavefront-per-time or split back-substitution
   double *wsq = nullptr, *drho = nullptr, *drho_c = nullptr;   // [N] each: sqrt(rho'), rho(s) - s at x (k_mc_block_weight); per candidate
                                                                  // workgroup (at most N): its blocks' rho(s_c) - s_c
+  double* wts = nullptr;         // [N] the blocks' weights in the device's time order (with_loss only; all ones when the problem had none)
+  std::vector<int> blk_order;    // device block -> the problem's observation (with_loss only: SetWeights)
   double half_side = 0;
   MarkerObs* mo = nullptr;
   TimeSlots* ts = nullptr;
@@ -1265,7 +1268,7 @@ struct MarkerSchurDevice {
   void Free() {
     void* ptrs[] = {mo, ts, chunk_ptr, time_ptr, slot_ptr, slot_col, time_full, col_full, ok_flag, obs8, intr, params[0], params[1],
                     params0, posec, posec_c, ss_x, scale_t, scale_r, tdata, part, red, A, Wm, delta_r, delta_t, bp_time, solve_out, res, tc_flags, tc_hand, tc_map,
-                    slot_order, slot_time, sb_ptr, sb_blk, xi_ptr, xi_blk, xi_cc, xi_cm, xc_ptr, sp, xout, tscal, blk_time, x_order, wsq, drho, drho_c,
+                    slot_order, slot_time, sb_ptr, sb_blk, xi_ptr, xi_blk, xi_cc, xi_cm, xc_ptr, sp, xout, tscal, blk_time, x_order, wsq, drho, drho_c, wts,
                     cs_ptr, cs_full, tconst, cpose_full};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     mo = nullptr; ts = nullptr;
@@ -1286,7 +1289,7 @@ struct MarkerSchurDevice {
   // its distinct camera and marker blocks, free or constant — holds at most RSBA_MT_MAXD / 6 = 170 entries; the split accumulation's
   // LDS bound counts the free ones (columns) only.  A constant time is eliminated with E = 0.  No free camera or marker at all (n_r = 0):
   // every time is eliminated on its own and the reduced solve is skipped.
-  // loss: a robust loss is set.  Its rows are formed by the split kernels only (round 4's k_time_eliminate and k_time_backsub_wg spread a
+  // loss: a robust loss is set, or the problem carries observation weights (then possibly with huber_delta = 0: rho(s) = s).  Its rows are formed by the split kernels only (round 4's k_time_eliminate and k_time_backsub_wg spread a
   // residual block's corners over lanes and have no block-wide s): RSBA_MT_SPLIT=0 and RSBA_MT_BACKSUB_WG are not taken then, and a problem
   // whose times are too wide for the split accumulation returns RSBA_ERR_UNSUPPORTED (the solver takes the dense path).
   int Upload(const rsba_problem& p, bool loss = false) {
@@ -1518,8 +1521,13 @@ struct MarkerSchurDevice {
         !al((void**)&red, RL.size() * 8) || !al((void**)&A, nA * 8) || (nr > RSBA_CHOL_MAXN && !al((void**)&Wm, nA * 8)) ||
         !al((void**)&delta_r, nr * 8) || !al((void**)&delta_t, 6 * (size_t)T * 8) || !al((void**)&bp_time, 4 * (size_t)nb_time * 8) ||
         !al((void**)&solve_out, 8 * 8) || !al((void**)&res, RES_SIZE * 8) ||
-        (with_loss && (!al((void**)&wsq, N * 8) || !al((void**)&drho, N * 8) || !al((void**)&drho_c, N * 8))))
+        (with_loss && (!al((void**)&wsq, N * 8) || !al((void**)&drho, N * 8) || !al((void**)&drho_c, N * 8) || !al((void**)&wts, N * 8))))
       return RSBA_ERR_HIP;
+    if (with_loss) {
+      blk_order = order;
+      const std::vector<double> ones(p.observation_weights.empty() ? (size_t)N : 0, 1.0);
+      if (SetWeights(p.observation_weights.empty() ? ones.data() : p.observation_weights.data()) != RSBA_OK) return RSBA_ERR_HIP;
+    }
     auto up = [](void* d, const void* h, size_t bytes) { return bytes == 0 || hipMemcpy(d, h, bytes, hipMemcpyHostToDevice) == hipSuccess; };
     if (!up(mo, hmo.data(), N * sizeof(MarkerObs)) || !up(ts, hts.data(), N * sizeof(TimeSlots)) || !up(chunk_ptr, cptr.data(), (G + 1) * 4) ||
         !up(time_ptr, tptr.data(), (T + 1) * 4) || !up(slot_ptr, sptr.data(), (T + 1) * 4) || !up(slot_col, scol.data(), scol.size() * 4) ||
@@ -1609,6 +1617,12 @@ struct MarkerSchurDevice {
     }
     return RSBA_OK;
   }
+  // the blocks' weights, given in the problem's order, into the device's time order (a solver that runs the kLoss instances)
+  int SetWeights(const double* w) {
+    std::vector<double> h((size_t)N);
+    for (int k = 0; k < N; ++k) h[k] = w[blk_order[k]];
+    return hipMemcpy(wts, h.data(), (size_t)N * 8, hipMemcpyHostToDevice) == hipSuccess ? RSBA_OK : RSBA_ERR_HIP;
+  }
   int Reset(hipStream_t st) {
     if (hipMemcpyAsync(params[0], params0, nfull * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return RSBA_ERR_HIP;
     if (hipMemcpyAsync(params[1], params0, nfull * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return RSBA_ERR_HIP;
@@ -1628,7 +1642,8 @@ struct MarkerSchurDevice {
     ip.radius = radius; ip.min_lm_diagonal = o.min_lm_diagonal; ip.max_lm_diagonal = o.max_lm_diagonal; ip.huber_delta = 0.0;
     ip.first = first ? 1 : 0; ip.jacobi_scaling = o.jacobi_scaling;
     // the robust loss, read as the point model reads it (signed: see LossAndScale); Upload was told whether there is one
-    const double loss = with_loss ? (o.loss_type == RSBA_LOSS_CAUCHY ? -o.huber_delta : o.huber_delta) : 0.0;
+    // (with_loss and huber_delta = 0: observation weights alone, rho(s) = s)
+    const double loss = with_loss && o.huber_delta > 0.0 ? (o.loss_type == RSBA_LOSS_CAUCHY ? -o.huber_delta : o.huber_delta) : 0.0;
     const int x = cur, c = 1 - cur;
     if (hipMemcpyAsync(params[c], params[x], nfull * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return RSBA_ERR_HIP;
     auto chk = [&](const char* what) {
@@ -1649,7 +1664,7 @@ struct MarkerSchurDevice {
       if (with_loss) {
         // the corrector's weights at x, wanted by all three product kernels
         Tm.Begin("k_mc_block_weight", st);
-        k_mc_block_weight<<<(N + 255) / 256, 256, 0, st>>>(N, ts, mo, obs8, intr, half_side, posec, loss, wsq, drho);
+        k_mc_block_weight<<<(N + 255) / 256, 256, 0, st>>>(N, ts, mo, obs8, intr, half_side, posec, loss, wts, wsq, drho);
         Tm.End(st);
       }
       // the three product kernels are independent and none fills the chip: side by side on three streams (one after the other
@@ -1752,7 +1767,7 @@ struct MarkerSchurDevice {
       if (fork2 && (hipEventRecord(fork_ev[0], st) != hipSuccess || hipStreamWaitEvent(s_cost, fork_ev[0], 0) != hipSuccess)) return RSBA_ERR_HIP;
       if (with_loss) {
         k_mc_candidate<0, true><<<ncand_wg, 256, 0, st>>>(N, T, ts, mo, obs8, intr, half_side, posec, posec_c, delta_r, delta_t, blk_time, bp_time, loss, wsq, drho_c);
-        k_mc_candidate<1, true><<<ncand_wg, 256, 0, s_cost>>>(N, T, ts, mo, obs8, intr, half_side, posec, posec_c, delta_r, delta_t, blk_time, bp_time, loss, wsq, drho_c);
+        k_mc_candidate<1, true><<<ncand_wg, 256, 0, s_cost>>>(N, T, ts, mo, obs8, intr, half_side, posec, posec_c, delta_r, delta_t, blk_time, bp_time, loss, wsq, drho_c, wts);
       } else {
         k_mc_candidate<0, false><<<ncand_wg, 256, 0, st>>>(N, T, ts, mo, obs8, intr, half_side, posec, posec_c, delta_r, delta_t, blk_time, bp_time);
         k_mc_candidate<1, false><<<ncand_wg, 256, 0, s_cost>>>(N, T, ts, mo, obs8, intr, half_side, posec, posec_c, delta_r, delta_t, blk_time, bp_time);
@@ -1770,10 +1785,10 @@ struct MarkerSchurDevice {
     } else {
       if (with_loss && has_const)
         k_time_backsub_terms<true, true><<<nb_time, 256, 0, st>>>(T, time_ptr, time_full, ts, mo, obs8, intr, half_side, posec, tdata, delta_r, params[x],
-                                                                  params[c], delta_t, bp_time, loss, wsq, drho_c, tconst);
+                                                                  params[c], delta_t, bp_time, loss, wsq, drho_c, tconst, wts);
       else if (with_loss)
         k_time_backsub_terms<true><<<nb_time, 256, 0, st>>>(T, time_ptr, time_full, ts, mo, obs8, intr, half_side, posec, tdata, delta_r, params[x],
-                                                            params[c], delta_t, bp_time, loss, wsq, drho_c);
+                                                            params[c], delta_t, bp_time, loss, wsq, drho_c, nullptr, wts);
       else if (has_const)
         k_time_backsub_terms<false, true><<<nb_time, 256, 0, st>>>(T, time_ptr, time_full, ts, mo, obs8, intr, half_side, posec, tdata, delta_r, params[x],
                                                                    params[c], delta_t, bp_time, 0.0, nullptr, nullptr, tconst);

@@ -143,9 +143,12 @@ struct SplitArgs {
 // rho(s) - s.  The costs keep the loss-free sum of r^2 corner by corner and add the blocks' rho(s) - s beside it: a block inside
 // Huber's threshold adds an exact zero, so a loss no block reaches gives the loss-free bits.  The corners through the rotation matrices
 // and translations of k_pose_constants, as CornerRows forms them.
+// wts: the blocks' weights a_k (ceres::ScaledLoss) in the same order: wsq = sqrt(a_k rho') — formed as sqrt(a_k) sqrt(rho'), a weight of
+// one changes no bit — and drho = a_k rho - s, so every kernel that reads the two is as it was.  A weight of zero: the block's rows
+// are exact zeros and its s leaves the cost again through drho = -s.
 __global__ void __launch_bounds__(256) k_mc_block_weight(int N, const TimeSlots* __restrict__ ts, const MarkerObs* __restrict__ mo, const double* __restrict__ obs8,
                                                          const double* __restrict__ intr, double half_side, const double* __restrict__ posec, double loss,
-                                                         double* __restrict__ wsq, double* __restrict__ drho) {
+                                                         const double* __restrict__ wts, double* __restrict__ wsq, double* __restrict__ drho) {
   const int k = blockIdx.x * 256 + threadIdx.x;
   if (k >= N) return;
   const MarkerObs o = mo[k];
@@ -164,8 +167,9 @@ __global__ void __launch_bounds__(256) k_mc_block_weight(int N, const TimeSlots*
     ss = fma(r[1], r[1], ss);
   }
   double sq;
-  drho[k] = LossAndScale(loss, ss, &sq) - ss;
-  wsq[k] = sq;
+  const double a = wts[k];
+  drho[k] = a * LossAndScale(loss, ss, &sq) - ss;
+  wsq[k] = sq * sqrt(a);
 }
 
 // the corrector on one corner's residuals and the 2 x 6 blocks formed of its rows (nullptr: not formed)
@@ -826,13 +830,14 @@ __global__ void __launch_bounds__(256) k_mc_time_step(int T, const int* __restri
 // kPart 0: the model cost change (the block's rows at x: 340 registers, one wavefront a SIMD); 1: the candidate's residuals (rotation
 // matrices and translations only: four wavefronts a SIMD) — two launches side by side instead of one kernel with the registers of both.
 // kLoss: part 0 from the corrected rows (wsq: sqrt(rho') at x); part 1 sums the raw r_c^2 as without a loss and the workgroup's
-// rho(s_c) - s_c into drho_c[blockIdx.x] (k_marker_schur_finish<true> adds them to the cost).
+// a rho(s_c) - s_c (wts: the blocks' weights) into drho_c[blockIdx.x] (k_marker_schur_finish<true> adds them to the cost).
 template <int kPart, bool kLoss>
 __global__ void __launch_bounds__(256) k_mc_candidate(int N, int T, const TimeSlots* __restrict__ ts, const MarkerObs* __restrict__ mo, const double* __restrict__ obs8,
                                                       const double* __restrict__ intr, double half_side, const double* __restrict__ posec,
                                                       const double* __restrict__ posec_c, const double* __restrict__ delta_r, const double* __restrict__ delta_t,
                                                       const int* __restrict__ blk_time, double* __restrict__ bp_time, double loss = 0.0,
-                                                      const double* __restrict__ wsq = nullptr, double* __restrict__ drho_c = nullptr) {
+                                                      const double* __restrict__ wsq = nullptr, double* __restrict__ drho_c = nullptr,
+                                                      const double* __restrict__ wts = nullptr) {
   __shared__ double s_w[kLoss && kPart == 1 ? 8 : 4];
   const int k = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   double sum = 0.0, dsum = 0.0;
@@ -905,7 +910,7 @@ __global__ void __launch_bounds__(256) k_mc_candidate(int N, int T, const TimeSl
         sum += r0 * r0 + r1 * r1;
         if constexpr (kLoss) sb += r0 * r0 + r1 * r1;
       }
-      if constexpr (kLoss) { double sq; dsum = LossAndScale(loss, sb, &sq) - sb; }
+      if constexpr (kLoss) { double sq; dsum = wts[k] * LossAndScale(loss, sb, &sq) - sb; }
     }
   }
   for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);

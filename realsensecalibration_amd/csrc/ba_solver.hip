@@ -269,6 +269,13 @@ struct rsba_solver {
   MarkerDevice marker;
   MarkerSchurDevice marker_schur;   // time blocks eliminated: the marker-chain model at scale
   bool eliminate_times = false;
+  // observation weights (ceres::ScaledLoss; rsba_solver_set_observation_weights): a solver runs the loss instances — and takes weights —
+  // when it was created with a robust loss or from a problem that carried weights; decided at create, like the path
+  bool weighted = false;
+  bool weights_given = false;  // the problem carried weights at create, or the setter was called: only then do evaluate, the Jacobian and
+                               // the covariance read them (all ones, a loss solver's start, change no bit and are not passed)
+  std::vector<double> obs_w;   // [N] the problem's order (all ones when the problem had none); weighted only
+  double* obs_w_dev = nullptr; // the same on the device: evaluate and the Jacobian index observations in the problem's order
 
   // ---- covariance (rsba_solver_covariance_compute, ba_covariance.hpp): buffers of its own, the LM state is not touched
   bool cov_valid = false;
@@ -385,7 +392,7 @@ static void FreeSolver(rsba_solver* s) {
   s->timer.Reset();
   void* ptrs[] = {s->obs_u, s->obs_v, s->intr, s->obs_cam, s->pt_ptr, s->sl_row_ptr, s->sl_cam, s->sl_uv, s->cam[0], s->cam[1], s->pts[0], s->pts[1], s->camc[0], s->camc[1],
                   s->cam0, s->pts0, s->scale_c, s->scale_p, s->red, s->A, s->W, s->chol_ok, s->S_copy, s->rhs_copy, s->dcam, s->block_scal,
-                  s->block_part, s->small_red, s->gmax, s->res, s->dec, s->red_tri, s->cam_free, s->pt_const, s->mc_flags, s->mc_dg, s->tc_flags, s->tc_map, s->tc_hand, s->tc_xs, s->tc_ys, s->cov_sinv, s->cov_pts, s->cov_arena, s->query_buf};
+                  s->block_part, s->small_red, s->gmax, s->res, s->dec, s->red_tri, s->cam_free, s->pt_const, s->mc_flags, s->mc_dg, s->tc_flags, s->tc_map, s->tc_hand, s->tc_xs, s->tc_ys, s->cov_sinv, s->cov_pts, s->cov_arena, s->query_buf, s->obs_w_dev};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   s->tiled.Free();
   s->marker.Free();
@@ -1967,7 +1974,17 @@ static int CovarianceMarker(rsba_solver* s, const rsba_covariance_options& co) {
   int *pos = nullptr, *tptr_d = nullptr;
   CovMcRow* rows_d = nullptr;
   unsigned char* elim_d = nullptr;
+  // the rows' weights ride on the loss corrector: ignored with it (apply_loss_function = 0), as Ceres ignores the whole LossFunction
+  const bool use_w = s->weights_given && co.apply_loss_function;
+  std::vector<double> wrow;
+  if (use_w) {
+    wrow.resize(rows.size(), 1.0);
+    std::vector<int> fw(tptr.begin(), tptr.end() - 1);
+    for (int64_t i = 0; i < N; ++i) wrow[fw[p.time_index[i]]++] = s->obs_w[i];
+  }
+  double* wrow_d = nullptr;
   auto extra = [&](CovCarve& cv) {
+    if (use_w) wrow_d = cv.take<double>(wrow.size());
     pc = cv.take<double>((size_t)CC_STRIDE * nb); obs_d = cv.take<double>(obs.size()); intr = cv.take<double>(p.intrinsics.size());
     pos = cv.take<int>(nb); tptr_d = cv.take<int>(T + 1); rows_d = cv.take<CovMcRow>(rows.size()); elim_d = cv.take<unsigned char>(elim.size());
   };
@@ -1983,9 +2000,10 @@ static int CovarianceMarker(rsba_solver* s, const rsba_covariance_options& co) {
     hip(hipMemcpyAsync(tptr_d, tptr.data(), (T + 1) * sizeof(int), hipMemcpyHostToDevice, st));
     hip(hipMemcpyAsync(rows_d, rows.data(), rows.size() * sizeof(CovMcRow), hipMemcpyHostToDevice, st));
     hip(hipMemcpyAsync(elim_d, elim.data(), elim.size(), hipMemcpyHostToDevice, st));
+    if (use_w) hip(hipMemcpyAsync(wrow_d, wrow.data(), wrow.size() * sizeof(double), hipMemcpyHostToDevice, st));
     k_cov_pose_constants<<<(nb + 255) / 256, 256, 0, st>>>(nb, params, pc);
-    if (loss != 0.0)
-      k_cov_mc_lin<true><<<std::max(1, std::min(T, 4096)), 64, 0, st>>>(T, tptr_d, rows_d, obs_d, intr, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags, loss);
+    if (loss != 0.0 || use_w)
+      k_cov_mc_lin<true><<<std::max(1, std::min(T, 4096)), 64, 0, st>>>(T, tptr_d, rows_d, obs_d, intr, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags, loss, wrow_d);
     else
       k_cov_mc_lin<false><<<std::max(1, std::min(T, 4096)), 64, 0, st>>>(T, tptr_d, rows_d, obs_d, intr, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags);
     // (the host vectors outlive CovRun, which synchronises the stream before it returns)
@@ -2099,11 +2117,12 @@ static int EvaluateOnDevice(rsba_solver* s, bool apply_loss, double* cost, doubl
     const double* params = s->eliminate_times ? (s->has_run ? s->marker_schur.params[s->marker_schur.cur] : s->marker_schur.params0)
                                               : (s->has_run ? s->marker.params[s->marker.cur] : s->marker.params0);
     k_cov_pose_constants<<<(nb + 255) / 256, 256, 0, st>>>(nb, params, posec);
+    const double* wts = apply_loss && s->weights_given ? s->obs_w_dev : nullptr;   // (the weights go with the loss, as in Ceres)
     if (gradient) {
-      k_eval_marker<true><<<grid, 64, 0, st>>>((int)N, e.rows, e.obs8, e.intr, posec, p.marker_side / 2, loss, res_d, work, cost_parts);
+      k_eval_marker<true><<<grid, 64, 0, st>>>((int)N, e.rows, e.obs8, e.intr, posec, p.marker_side / 2, loss, res_d, work, cost_parts, wts);
       k_eval_marker_block_sum<<<nb, 256, 0, st>>>(e.list_ptr, e.list_obs, e.list_slot, work, e.live, grad_d);
     } else {
-      k_eval_marker<false><<<grid, 64, 0, st>>>((int)N, e.rows, e.obs8, e.intr, posec, p.marker_side / 2, loss, res_d, nullptr, cost_parts);
+      k_eval_marker<false><<<grid, 64, 0, st>>>((int)N, e.rows, e.obs8, e.intr, posec, p.marker_side / 2, loss, res_d, nullptr, cost_parts, wts);
     }
   }
   k_eval_cost<<<1, 256, 0, st>>>(grid, cost_parts, cost_d);
@@ -2228,7 +2247,8 @@ static int JacobianOnDevice(rsba_solver* s, bool apply_loss, double* values) {
     const double* params = s->eliminate_times ? (s->has_run ? s->marker_schur.params[s->marker_schur.cur] : s->marker_schur.params0)
                                               : (s->has_run ? s->marker.params[s->marker.cur] : s->marker.params0);
     k_cov_pose_constants<<<(nb + 255) / 256, 256, 0, st>>>(nb, params, posec);
-    k_eval_jacobian_marker<<<(N + 63) / 64, 64, 0, st>>>(N, e.rows, e.obs8, e.intr, posec, j.off, e.live, p.marker_side / 2, loss, values_d);
+    k_eval_jacobian_marker<<<(N + 63) / 64, 64, 0, st>>>(N, e.rows, e.obs8, e.intr, posec, j.off, e.live, p.marker_side / 2, loss, values_d,
+                                                         apply_loss && s->weights_given ? s->obs_w_dev : nullptr);
   }
   rc = RSBA_OK;
   auto hip = [&](hipError_t err) { if (err != hipSuccess && rc == RSBA_OK) rc = RSBA_ERR_HIP; };
@@ -2370,12 +2390,23 @@ int rsba_solver_create(rsba_problem* p, const rsba_options* o, rsba_solver** out
     if (rc == RSBA_OK && s->tiled.tree_error) s->tiled.error_flag = reinterpret_cast<int*>(s->res_host + RES_SIZE + 4);   // (zeroed above)
   } else {
     s->eliminate_times = rsba::MarkerSchurDevice::Wanted(*p, opt.schur_impl);
-    rc = s->eliminate_times ? s->marker_schur.Upload(*p, opt.huber_delta > 0.0) : s->marker.Upload(*p);
+    // the loss instances: a robust loss, or a problem that carries observation weights (all ones included: how a caller asks for
+    // rsba_solver_set_observation_weights); once, here
+    s->weighted = opt.huber_delta > 0.0 || !p->observation_weights.empty();
+    s->weights_given = !p->observation_weights.empty();
+    if (!p->observation_weights.empty() && (int64_t)p->observation_weights.size() != p->num_observations) { rsba::FreeSolver(s); return RSBA_ERR_ARG; }
+    rc = s->eliminate_times ? s->marker_schur.Upload(*p, s->weighted) : s->marker.Upload(*p, s->weighted);
     if (s->eliminate_times && rc == RSBA_ERR_UNSUPPORTED) {
       // duplicate detections, or a time wider than the kernels' LDS: the dense path is general
       s->marker_schur.Free();
       s->eliminate_times = false;
-      rc = s->marker.Upload(*p);
+      rc = s->marker.Upload(*p, s->weighted);
+    }
+    if (rc == RSBA_OK && s->weighted) {
+      s->obs_w = p->observation_weights;
+      if (s->obs_w.empty()) s->obs_w.assign((size_t)p->num_observations, 1.0);
+      rc = rsba::DevAlloc(&s->obs_w_dev, s->obs_w.size());
+      if (rc == RSBA_OK && !s->obs_w.empty() && hipMemcpy(s->obs_w_dev, s->obs_w.data(), s->obs_w.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = RSBA_ERR_HIP;
     }
   }
   s->eval_const_cam = p->camera_constant; s->eval_const_pt = p->point_constant; s->eval_const_block = p->block_constant;
@@ -2782,6 +2813,29 @@ int rsba_solver_evaluate_jacobian(rsba_solver* s, const rsba_evaluate_options* o
   rsba::CommScope device_turn(s->comm.get());   // (local, no collective; a loopback rank launches on its turn only)
   if (hipSetDevice(s->device) != hipSuccess) return RSBA_ERR_HIP;
   return rsba::JacobianOnDevice(s, eo.apply_loss_function != 0, values);
+}
+
+int rsba_solver_set_observation_weights(rsba_solver* s, const double* weights) {
+  if (!s) return RSBA_ERR_ARG;
+  if (s->prob->model == RSBA_MODEL_POINTS || !s->weighted) return RSBA_ERR_UNSUPPORTED;   // (the instances were chosen at create)
+  if (!weights) return RSBA_ERR_ARG;
+  const size_t n = (size_t)s->prob->num_observations;
+  for (size_t i = 0; i < n; ++i) if (!std::isfinite(weights[i]) || weights[i] < 0.0) return RSBA_ERR_ARG;
+  if (hipSetDevice(s->device) != hipSuccess) return RSBA_ERR_HIP;
+  if (hipStreamSynchronize(s->stream) != hipSuccess) return RSBA_ERR_HIP;
+  // copies into arrays that exist since create: the solve's (its path's block order) and evaluate's (the problem's order); the
+  // covariance permutes the host copy per call.  The host state changes last: a copy that fails puts the old weights back.
+  auto upload = [&](const double* w) {
+    int rc = s->eliminate_times ? s->marker_schur.SetWeights(w) : s->marker.SetWeights(w);
+    if (rc == RSBA_OK && n > 0 && hipMemcpy(s->obs_w_dev, w, n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = RSBA_ERR_HIP;
+    return rc;
+  };
+  const int rc = upload(weights);
+  if (rc != RSBA_OK) { (void)upload(s->obs_w.data()); return rc; }
+  s->obs_w.assign(weights, weights + n);
+  s->weights_given = true;
+  s->cov_valid = false;   // the covariance was that of the old weights
+  return RSBA_OK;
 }
 
 int rsba_solver_set_parameters(rsba_solver* s, const double* parameters) {

@@ -1,5 +1,6 @@
 // C ABI: problem container, options, file formats (no device code here).  Declared in include/rsba.h.
 #include <climits>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 
@@ -95,6 +96,17 @@ int rsba_problem_set_parameter_block_constant(rsba_problem* p, int64_t parameter
   if (p->block_constant.empty()) p->block_constant.assign(nblocks, 0);
   p->block_constant[(size_t)(parameter_offset / 6)] = constant ? 1 : 0;
   return RSBA_OK;
+}
+int rsba_problem_set_observation_weights(rsba_problem* p, const double* weights) {
+  if (!p) return RSBA_ERR_ARG;
+  if (!p->is_marker_chain()) return RSBA_ERR_UNSUPPORTED;   // the point model's loss sites take no per-observation factor
+  if (!weights) { p->observation_weights.clear(); return RSBA_OK; }
+  for (int64_t i = 0; i < p->num_observations; ++i) if (!std::isfinite(weights[i]) || weights[i] < 0.0) return RSBA_ERR_ARG;
+  p->observation_weights.assign(weights, weights + p->num_observations);
+  return RSBA_OK;
+}
+const double* rsba_problem_observation_weights(const rsba_problem* p) {
+  return (p && !p->observation_weights.empty()) ? p->observation_weights.data() : nullptr;
 }
 void rsba_problem_free(rsba_problem* p) { delete p; }
 

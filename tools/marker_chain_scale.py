@@ -1,9 +1,10 @@
 """Marker-chain model at scale on the GPU: per-kernel times of the time-elimination path.
 
-    python tools/marker_chain_scale.py [C T M [huber|cauchy a]] [const=SET] [schur_impl=K] [dump=PATH]
+    python tools/marker_chain_scale.py [C T M [huber|cauchy a]] [const=SET] [schur_impl=K] [dump=PATH] [weights=FRAC]
         default 8 5000 16, no loss; SET: markers | cameras:K (cameras 1..K) | times:K (every T/K-th time) | rig (every camera
         and marker: only the times are free), joined by '+' (e.g. cameras:2+times:100); dump=PATH writes the final parameters
-        and the iteration log (.npz) of the last unprofiled run
+        and the iteration log (.npz) of the last unprofiled run; weights=FRAC: observation weights on the problem (ceres::ScaledLoss),
+        that fraction of the residual blocks (seeded) at weight 0 and the rest at 1 — 0 asks for all ones
 """
 import json
 import os
@@ -46,6 +47,9 @@ gen = time.time() - t0
 p = capi.Problem.marker_chain(prob)
 for b in CONST:
     p.set_parameter_block_constant(6 * b)
+WEIGHTS = float(KW["weights"]) if "weights" in KW else None
+if WEIGHTS is not None:
+    p.set_observation_weights(np.where(np.random.default_rng(12).random(prob["N"]) < WEIGHTS, 0.0, 1.0))
 out = {}
 for mode in (0, 1):
     s = capi.Solver(p, capi.default_options(profile_kernels=mode, schur_impl=int(KW.get("schur_impl", 1)), **LOSS_KW))
@@ -55,6 +59,7 @@ for mode in (0, 1):
     sm = s.run()
     if mode == 0:
         out["constant_blocks"] = len(CONST)
+        out["zero_weight_fraction"] = WEIGHTS
         out["eliminates_times"] = s.eliminates_times()
         if "dump" in KW:
             s.download()
