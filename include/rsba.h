@@ -294,10 +294,21 @@ void rsba_solver_destroy(rsba_solver* s);
  * (the convention of rsba_problem_set_parameter_block_constant).  A constant block has a zero covariance; a block no residual
  * references is RSBA_ERR_ARG.  The solver's trust radius, scales, iteration log, parameters and schedule are left untouched.
  *
- * Point model: every camera x camera block (6 x 6) and the 3 x 3 marginal of every point; camera x point and cross-point blocks
- * are RSBA_ERR_UNSUPPORTED.  Marker-chain models (dense and time-eliminating paths alike): every camera / marker x camera / marker
- * block (6 x 6); time blocks are RSBA_ERR_UNSUPPORTED.  apply_loss_function applies the solve's corrector in both models (the
- * marker chain: sqrt(rho') of each observation's 8 residuals).
+ * Two queries.  rsba_solver_covariance_blocks is the GENERAL one, Covariance::GetCovarianceBlock for any pair: on the point model
+ * any two of the camera and point blocks (camera x point is 6 x 3, point x point' 3 x 3), on the marker-chain models any two of the
+ * camera, time and marker blocks, on the dense and the time-eliminating path alike (the eliminated time blocks and the points are
+ * back-substituted into S^-1 on the GPU); rsba_solver_time_covariances is the bulk form of the time marginals, the twin of
+ * rsba_solver_point_covariances.  rsba_solver_covariance_block is the older single-pair call and keeps its narrower contract: on
+ * the point model every camera x camera block (6 x 6) and the 3 x 3 marginal of every point, camera x point and cross-point blocks
+ * are RSBA_ERR_UNSUPPORTED; on the marker-chain models every camera / marker x camera / marker block (6 x 6), time blocks are
+ * RSBA_ERR_UNSUPPORTED.  apply_loss_function applies the solve's corrector in both models (the marker chain: sqrt(rho') of each
+ * observation's 8 residuals).
+ *
+ * The state a result belongs to: the parameters at rsba_solver_covariance_compute.  A result survives rsba_solver_run, and every
+ * query after compute -> run still describes the state at compute — the general queries re-linearise from a snapshot that the
+ * compute keeps on the device (the marker chain's pose constants, rows, observations and weights; the point model's camera
+ * constants and a copy of its points), never from the live parameters.  rsba_solver_set_parameters and
+ * rsba_solver_set_observation_weights drop the result.
  *
  * A solver with a communicator (point model; world_size > 1, or the one-rank communicator of RSBA_FORCE_COMM):
  * rsba_solver_covariance_compute is COLLECTIVE (the collective contract below).  Every rank linearises its shard into its part of
@@ -319,10 +330,28 @@ void rsba_covariance_options_default(rsba_covariance_options* o);
 /* Linearise at the current parameters, invert the reduced camera system and form the point marginals on the GPU (o: NULL =
  * defaults).  RSBA_ERR_RANK_DEFICIENT leaves no result: the block queries then return RSBA_ERR_ARG. */
 int rsba_solver_covariance_compute(rsba_solver* s, const rsba_covariance_options* o);
-/* Covariance block of the blocks at parameter offsets a and b: na x nb, row-major.  block(b, a) is block(a, b)' exactly. */
+/* Covariance block of the blocks at parameter offsets a and b: na x nb, row-major.  block(b, a) is block(a, b)' exactly.  Time
+ * blocks, camera x point and cross-point pairs are RSBA_ERR_UNSUPPORTED here: rsba_solver_covariance_blocks is the general call. */
 int rsba_solver_covariance_block(const rsba_solver* s, int64_t offset_a, int64_t offset_b, double* out);
 /* Point model: P x 3 x 3 marginals in the problem's point order (zeros for constant and unreferenced points); RSBA_ERR_UNSUPPORTED otherwise. */
 int rsba_solver_point_covariances(const rsba_solver* s, double* out);
+/* Covariance::GetCovarianceBlock for ANY pairs, in one call.  Pair i = blocks at parameter offsets a[i], b[i] (the convention of
+ * rsba_solver_covariance_block); its na x nb block, row-major, in out[36 i .. 36 i + na nb), the rest of the 36 set to 0.0.
+ * Marker-chain models: any two of camera, time and marker blocks; point model: any two of camera and point blocks.  A pair that
+ * names a constant block gives zeros.  An offset that starts no block or names a block no residual references (the fixed base
+ * blocks included) is RSBA_ERR_ARG for the whole call, and nothing is written; so are NULL arguments, num_pairs < 0 and a solver
+ * without a valid result (no compute yet, a failed one, or a result dropped by set_parameters / set_observation_weights).
+ * num_pairs == 0 is RSBA_OK and launches nothing.  A pair that rsba_solver_covariance_block answers gives the same bits here;
+ * blocks(b, a) is blocks(a, b)' exactly for every kind of pair (one orientation is computed, the other transposed on output), and
+ * two calls after one compute return identical bits.  Nothing the solve, evaluate or the Jacobian reads is written.  RSBA_ERR_UNSUPPORTED:
+ * a time of a marker-chain problem touches more than 170 camera / marker blocks.  On a sharded solver the call is LOCAL (no
+ * collective): camera offsets are valid on every rank, point offsets are this rank's own. */
+int rsba_solver_covariance_blocks(rsba_solver* s, int64_t num_pairs, const int64_t* offsets_a, const int64_t* offsets_b, double* out);
+/* Marker-chain models: T x 6 x 6 marginals of the time blocks in the problem's time order (zeros for constant and unreferenced
+ * times); RSBA_ERR_UNSUPPORTED on the point model — the twin of rsba_solver_point_covariances.  Formed by the first call after a
+ * compute and kept until the result is dropped; the (t, t) blocks of rsba_solver_covariance_blocks bit for bit.  RSBA_ERR_ARG
+ * without a valid result. */
+int rsba_solver_time_covariances(rsba_solver* s, double* out);
 
 /* ------------------------------------------------------------------ evaluate and re-solve (ceres::Problem::Evaluate; values changed in place)
  * Not used by the reference, which looks at its residuals by eye (ReprojectionCheck::Reproject draws every reprojected corner beside its

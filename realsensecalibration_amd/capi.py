@@ -30,12 +30,13 @@ EXPORTS = [
     "rsba_problem_initial_camera_poses", "rsba_problem_set_camera_constant", "rsba_problem_set_point_constant", "rsba_problem_set_parameter_block_constant", "rsba_solver_full_report", "rsba_solver_configure_run",
     "rsba_solver_comm_nranks", "rsba_solver_schedule_info", "rsba_comm_shm_id", "rsba_comm_finalize",
     "rsba_covariance_options_default", "rsba_solver_covariance_compute", "rsba_solver_covariance_block", "rsba_solver_point_covariances",
-    "rsba_solver_time_elimination",
+    "rsba_solver_time_elimination", "rsba_solver_covariance_blocks", "rsba_solver_time_covariances",
     "rsba_evaluate_options_default", "rsba_solver_num_residuals", "rsba_solver_evaluate", "rsba_solver_set_parameters",
     "rsba_solver_jacobian_structure", "rsba_solver_evaluate_jacobian",
     "rsba_solver_comm_abort",
     "rsba_problem_set_observation_weights", "rsba_problem_observation_weights", "rsba_solver_set_observation_weights",
 ]
+_SYMBOLS = EXPORTS   # (every symbol of include/rsba.h that load() checks)
 
 
 class Options(C.Structure):
@@ -160,6 +161,8 @@ def load():
     lib.rsba_solver_covariance_compute.argtypes = [C.c_void_p, C.c_void_p]
     lib.rsba_solver_covariance_block.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
     lib.rsba_solver_point_covariances.argtypes = [C.c_void_p, C.c_void_p]
+    lib.rsba_solver_covariance_blocks.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rsba_solver_time_covariances.argtypes = [C.c_void_p, C.c_void_p]
     lib.rsba_evaluate_options_default.argtypes = [C.c_void_p]
     lib.rsba_solver_num_residuals.argtypes = [C.c_void_p]
     lib.rsba_solver_num_residuals.restype = C.c_int64
@@ -382,7 +385,7 @@ class Solver:
         load().rsba_solver_full_report(self.h, buf, n + 1)
         return buf.value.decode()
 
-    # ---- covariance of the solution (ceres::Covariance; point model)
+    # ---- covariance of the solution (ceres::Covariance)
     def covariance_compute(self, **opts):
         """(J'J)^-1 at the solver's current parameters.  opts: min_reciprocal_condition_number, apply_loss_function.
         Raises RsbaError with code ERR_RANK_DEFICIENT when J'J is singular."""
@@ -403,6 +406,30 @@ class Solver:
         """P x 3 x 3 marginals of the points, in the problem's point order."""
         out = np.zeros((self.problem.num_points, 3, 3))
         _chk(load().rsba_solver_point_covariances(self.h, _vp(out)), "rsba_solver_point_covariances")
+        return out
+
+    def covariance_blocks(self, pairs):
+        """Covariance blocks of ANY pairs of parameter blocks, in one call: pairs = [(offset_a, offset_b), ...] (camera_offset,
+        point_offset, time_offset, marker_offset) -> a list of (na, nb) arrays.  The general query: time blocks, camera x point
+        and point x point' pairs included; a constant block gives zeros."""
+        pairs = [(int(a), int(b)) for a, b in pairs]
+        n = len(pairs)
+        oa = np.array([a for a, _ in pairs], np.int64).reshape(n)
+        ob = np.array([b for _, b in pairs], np.int64).reshape(n)
+        out = np.zeros((max(n, 1), 36))
+        _chk(load().rsba_solver_covariance_blocks(self.h, n, _vp(oa) if n else _vp(np.zeros(1, np.int64)), _vp(ob) if n else _vp(np.zeros(1, np.int64)),
+                                                  _vp(out)), "rsba_solver_covariance_blocks")
+        res = []
+        for i, (a, b) in enumerate(pairs):
+            na, nb = self._block_size(a), self._block_size(b)
+            res.append(out[i, :na * nb].reshape(na, nb).copy())
+        return res
+
+    def time_covariances(self):
+        """Marker-chain models: T x 6 x 6 marginals of the time blocks, in the problem's time order (zeros for constant and
+        unreferenced times)."""
+        out = np.zeros((self.problem.num_times, 6, 6))
+        _chk(load().rsba_solver_time_covariances(self.h, _vp(out)), "rsba_solver_time_covariances")
         return out
 
     def camera_offset(self, camera_idx):

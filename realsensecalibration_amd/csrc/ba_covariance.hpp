@@ -653,4 +653,401 @@ k_cov_mc_lin(int T, const int* __restrict__ tptr, const CovMcRow* __restrict__ r
   }
 }
 
+// ---- any pair of blocks (rsba_solver_covariance_blocks, rsba_solver_time_covariances) ----------------------------------------
+// With e the eliminated blocks (time blocks on the time-eliminating marker-chain path, points on the point model), V_e the
+// undamped corrected diagonal block, W_e the blocks J_x'J_e, Y_e = W_e V_e^-1 and Sigma = S^-1 (cov_sinv):
+//   cov(e, e)  = V_e^-1 + sum_{a,b} Y_a' Sigma_ab Y_b        cov(e, e') = sum_{a in e, b in e'} Y_a' Sigma_ab Y'_b
+//   cov(x, e)  = -sum_a Sigma_xa Y_a
+// Every kernel takes a list of requests, one wavefront per request, and re-linearises from the snapshot that the compute left in
+// its arena (never from the live parameters).  Sums run in a fixed order (lanes' rows in chunks of 64 in order, WaveSum): no
+// floating-point atomics, two calls give the same bits.  One orientation of a pair is computed; the host transposes.
+//   k_cov_gather    blocks that exist already: a 6 x 6 block of S^-1 (camera / marker pairs, and time blocks on the dense path),
+//                   or a point's 3 x 3 marginal out of cov_pts
+//   k_cov_mc_cross  (t, t') and (t, x) on the time-eliminating path.  The rows of one time are first summed into ONE W per distinct
+//                   camera / marker block the time touches (at most RSBA_COV_MC_MAXBLK, in LDS; slots from the host's table), so
+//                   the contraction with S^-1 runs over blocks, not rows: Y_d = W_d V_t^-1 in place.  (t, x) is then a sum over
+//                   the blocks; (t, t') walks the rows of t with G = sum_d Sigma_{p, p_d} Y'_d per row block, M += W' G, and
+//                   cov = V_t^-1 M (+ V_t^-1 for t = t')
+//   k_cov_pt_cross  (camera, point j) and (point j, point k), on the pattern of k_cov_points
+struct CovReq { int a, b, kind, out; };   // out: the request's 36 doubles in the staging buffer
+enum { COV_REQ_SINV = 0, COV_REQ_POINT = 1, COV_REQ_TIME_TIME = 2, COV_REQ_TIME_X = 3, COV_REQ_CAM_POINT = 4, COV_REQ_POINT_POINT = 5 };
+
+// a, b: row and column of the block in S^-1 (COV_REQ_SINV); a: the point, the problem's order (COV_REQ_POINT)
+__global__ void __launch_bounds__(64)
+k_cov_gather(int nreq, const CovReq* __restrict__ req, int n, const double* __restrict__ Sinv, const double* __restrict__ cov_pts, double* __restrict__ out) {
+  const int lane = threadIdx.x;
+  for (int i = blockIdx.x; i < nreq; i += gridDim.x) {
+    const CovReq rq = req[i];
+    if (lane >= 36) continue;
+    double v = 0.0;
+    if (rq.kind == COV_REQ_SINV) v = Sinv[(size_t)(rq.a + lane / 6) * n + rq.b + lane % 6];
+    else if (lane < 9) v = cov_pts[9 * (size_t)rq.a + lane];
+    out[36 * (size_t)rq.out + lane] = v;
+  }
+}
+
+#define RSBA_COV_MC_MAXBLK 170   // distinct camera / marker blocks with columns that one time touches: 170 x 36 doubles of LDS
+#define RSBA_COV_MC_STAGE 37     // doubles per staged row (+1: bank padding)
+
+// The marker chain's snapshot (the compute's arena) and the host's slot tables: the distinct blocks of time t are
+// dpos[dptr[t] .. dptr[t + 1]) (their positions in S^-1), rslot[2 q + x] is the slot of row q's camera (x = 0) / marker (x = 1)
+// block among them, -1: no columns.
+struct CovMcSnap {
+  const int* tptr; const CovMcRow* rows; const double* obs8; const double* intr; const double* pc; const double* wts;
+  const int* dptr; const int* dpos; const int* rslot;
+  double half_side, rcond, loss;
+  int lossy, n;
+};
+
+template <int kX> struct CovSide { static constexpr int value = kX; };
+
+// COV_REQ_TIME_TIME: a = t, b = t' (a <= b; out = cov(t, t'), mirrored from its upper triangle for t = t');
+// COV_REQ_TIME_X: a = t, b = x's position in S^-1 (out = cov(t, x)).
+__global__ void __launch_bounds__(64)
+k_cov_mc_cross(int nreq, const CovReq* __restrict__ req, CovMcSnap sn, const double* __restrict__ Sinv, double* __restrict__ out) {
+  __shared__ double Yd[RSBA_COV_MC_MAXBLK * 36];
+  __shared__ double stage[32 * RSBA_COV_MC_STAGE];
+  __shared__ int sl[64];
+  const int lane = threadIdx.x, n = sn.n;
+  const double cx[4] = {-sn.half_side, sn.half_side, sn.half_side, -sn.half_side};
+  const double cy[4] = {sn.half_side, sn.half_side, -sn.half_side, -sn.half_side};
+  // one row's four corners: J (2 x 18 each) through f(J), with k_cov_mc_lin<true>'s corrector and weights when sn.lossy
+  auto corners = [&](int q, auto&& f) {
+    const CovMcRow rw = sn.rows[q];
+    const double* o8 = sn.obs8 + 8 * (size_t)q;
+    const double* pcc = rw.cam_block >= 0 ? sn.pc + (size_t)rw.cam_block * CC_STRIDE : nullptr;
+    const double* pcm = rw.marker_block >= 0 ? sn.pc + (size_t)rw.marker_block * CC_STRIDE : nullptr;
+    double sq = 1.0;
+    if (sn.lossy) {
+      double ss = 0.0;
+      for (int k = 0; k < 4; ++k) {
+        double r[2], J[36];
+        MarkerCornerResidualJacobian(pcc, sn.pc + (size_t)rw.time_block * CC_STRIDE, pcm, sn.intr + 4 * rw.camera, cx[k], cy[k], o8[2 * k], o8[2 * k + 1], r, J);
+        ss += r[0] * r[0] + r[1] * r[1];
+      }
+      (void)LossAndScale(sn.loss, ss, &sq);
+      if (sn.wts != nullptr) sq *= sqrt(sn.wts[q]);
+    }
+    for (int k = 0; k < 4; ++k) {
+      double r[2], J[36];
+      MarkerCornerResidualJacobian(pcc, sn.pc + (size_t)rw.time_block * CC_STRIDE, pcm, sn.intr + 4 * rw.camera, cx[k], cy[k], o8[2 * k], o8[2 * k + 1], r, J);
+      if (sn.lossy) {
+#pragma unroll
+        for (int e = 0; e < 36; ++e) J[e] *= sq;
+      }
+      f(J);
+    }
+  };
+  // V_t^-1 (every lane), V_t summed over the rows as k_cov_mc_lin sums it
+  auto time_inverse = [&](int t, double Vi[36]) {
+    const int b = sn.tptr[t], k = sn.tptr[t + 1] - b;
+    double V[21];
+#pragma unroll
+    for (int e = 0; e < 21; ++e) V[e] = 0.0;
+    for (int q = lane; q < k; q += 64)
+      corners(b + q, [&](const double* J) {
+        int e = 0;
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+          for (int c = a; c < 6; ++c) { V[e] += J[6 + a] * J[6 + c] + J[24 + a] * J[24 + c]; ++e; }
+      });
+#pragma unroll
+    for (int e = 0; e < 21; ++e) V[e] = WaveSum(V[e]);
+    (void)CovSym6Inverse(V, sn.rcond, Vi);   // (k_cov_mc_lin has already raised the flag for a singular block)
+  };
+  for (int i = blockIdx.x; i < nreq; i += gridDim.x) {
+    const CovReq rq = req[i];
+    double* o = out + 36 * (size_t)rq.out;
+    const int tb = rq.kind == COV_REQ_TIME_TIME ? rq.b : rq.a;
+    const int b = sn.tptr[tb], k = sn.tptr[tb + 1] - b, d0 = sn.dptr[tb], nd = sn.dptr[tb + 1] - d0;
+    // ---- W_d = sum over the rows of tb that touch block d of J_d'J_t, rows in order
+    __syncthreads();
+    for (int idx = lane; idx < nd * 36; idx += 64) Yd[idx] = 0.0;
+    for (int q0 = 0; q0 < k; q0 += 64) {
+      const int q = q0 + lane;
+      auto side = [&](auto xc) {
+        constexpr int x = decltype(xc)::value, xo = x == 0 ? 0 : 12;
+        const int slot = q < k ? sn.rslot[2 * (size_t)(b + q) + x] : -1;
+        double w[36];
+#pragma unroll
+        for (int e = 0; e < 36; ++e) w[e] = 0.0;
+        if (slot >= 0)
+          corners(b + q, [&](const double* J) {
+#pragma unroll
+            for (int a = 0; a < 6; ++a)
+#pragma unroll
+              for (int l = 0; l < 6; ++l) w[6 * a + l] += J[xo + a] * J[6 + l] + J[18 + xo + a] * J[24 + l];
+          });
+        __syncthreads();
+        sl[lane] = slot;
+        for (int h = 0; h < 2; ++h) {   // half a chunk at a time through the staging rows
+          if ((lane >> 5) == h) {
+            double* st = stage + (lane & 31) * RSBA_COV_MC_STAGE;
+#pragma unroll
+            for (int e = 0; e < 36; ++e) st[e] = w[e];
+          }
+          __syncthreads();
+          const int nr = min(32, k - q0 - 32 * h);
+          for (int idx = lane; idx < nd * 36; idx += 64) {
+            const int d = idx / 36, e = idx - 36 * d;
+            double v = Yd[idx];
+            for (int bb = 0; bb < nr; ++bb)
+              if (sl[32 * h + bb] == d) v += stage[bb * RSBA_COV_MC_STAGE + e];
+            Yd[idx] = v;
+          }
+          __syncthreads();
+        }
+      };
+      side(CovSide<0>{});
+      side(CovSide<1>{});
+    }
+    // ---- Y_d = W_d V_tb^-1 in place (a lane per row of six)
+    {
+      double Vi[36];
+      time_inverse(tb, Vi);
+      for (int r = lane; r < nd * 6; r += 64) {
+        double w6[6], y6[6];
+#pragma unroll
+        for (int m = 0; m < 6; ++m) w6[m] = Yd[6 * r + m];
+#pragma unroll
+        for (int l = 0; l < 6; ++l) {
+          double v = 0.0;
+#pragma unroll
+          for (int m = 0; m < 6; ++m) v += w6[m] * Vi[6 * m + l];
+          y6[l] = v;
+        }
+#pragma unroll
+        for (int l = 0; l < 6; ++l) Yd[6 * r + l] = y6[l];
+      }
+    }
+    __syncthreads();
+    double acc[36];
+#pragma unroll
+    for (int e = 0; e < 36; ++e) acc[e] = 0.0;
+    if (rq.kind == COV_REQ_TIME_X) {
+      // cov(t, x) = -sum_d Y_d' Sigma_{p_d, x}
+      for (int d = lane; d < nd; d += 64) {
+        const double* Sb = Sinv + (size_t)sn.dpos[d0 + d] * n + rq.b;
+        const double* y = Yd + 36 * d;
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+          double s6[6];
+#pragma unroll
+          for (int c = 0; c < 6; ++c) s6[c] = Sb[(size_t)r * n + c];
+#pragma unroll
+          for (int a = 0; a < 6; ++a) {
+            const double ya = y[6 * r + a];
+#pragma unroll
+            for (int c = 0; c < 6; ++c) acc[6 * a + c] -= ya * s6[c];
+          }
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < 36; ++e) acc[e] = WaveSum(acc[e]);
+      if (lane == 0) {
+#pragma unroll
+        for (int e = 0; e < 36; ++e) o[e] = acc[e];
+      }
+      continue;
+    }
+    // ---- (t, t'): M = sum over the rows of t and their blocks of W' G, G = sum_d Sigma_{p, p_d} Y'_d
+    const int ta = rq.a, ba = sn.tptr[ta], ka = sn.tptr[ta + 1] - ba, da = sn.dptr[ta];
+    for (int q = lane; q < ka; q += 64) {
+      auto side = [&](auto xc) {
+        constexpr int x = decltype(xc)::value, xo = x == 0 ? 0 : 12;
+        const int slot = sn.rslot[2 * (size_t)(ba + q) + x];
+        if (slot < 0) return;
+        const int p = sn.dpos[da + slot];
+        double G[36];
+#pragma unroll
+        for (int e = 0; e < 36; ++e) G[e] = 0.0;
+        for (int d = 0; d < nd; ++d) {
+          const double* Sb = Sinv + (size_t)p * n + sn.dpos[d0 + d];
+          const double* y = Yd + 36 * d;
+#pragma unroll
+          for (int r = 0; r < 6; ++r) {
+            double s6[6];
+#pragma unroll
+            for (int c = 0; c < 6; ++c) s6[c] = Sb[(size_t)r * n + c];
+#pragma unroll
+            for (int l = 0; l < 6; ++l) {
+              double v = 0.0;
+#pragma unroll
+              for (int c = 0; c < 6; ++c) v += s6[c] * y[6 * c + l];
+              G[6 * r + l] += v;
+            }
+          }
+        }
+        corners(ba + q, [&](const double* J) {
+#pragma unroll
+          for (int rho = 0; rho < 2; ++rho) {
+            double h6[6];
+#pragma unroll
+            for (int l = 0; l < 6; ++l) {
+              double v = 0.0;
+#pragma unroll
+              for (int a = 0; a < 6; ++a) v += J[18 * rho + xo + a] * G[6 * a + l];
+              h6[l] = v;
+            }
+#pragma unroll
+            for (int m = 0; m < 6; ++m)
+#pragma unroll
+              for (int l = 0; l < 6; ++l) acc[6 * m + l] += J[18 * rho + 6 + m] * h6[l];
+          }
+        });
+      };
+      side(CovSide<0>{});
+      side(CovSide<1>{});
+    }
+#pragma unroll
+    for (int e = 0; e < 36; ++e) acc[e] = WaveSum(acc[e]);
+    double Via[36];
+    time_inverse(ta, Via);
+    if (lane == 0) {
+      double R[36];
+#pragma unroll
+      for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int l = 0; l < 6; ++l) {
+          double v = ta == tb ? Via[6 * a + l] : 0.0;
+#pragma unroll
+          for (int m = 0; m < 6; ++m) v += Via[6 * a + m] * acc[6 * m + l];
+          R[6 * a + l] = v;
+        }
+#pragma unroll
+      for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int l = 0; l < 6; ++l) o[6 * a + l] = ta == tb && l < a ? R[6 * l + a] : R[6 * a + l];
+    }
+  }
+}
+
+// The point model's snapshot: camc, the column map and the COPY of the points that the compute took (the solver's point order).
+struct CovPtSnap {
+  const double* obs_u; const double* obs_v; const int* obs_cam; const int* pt_ptr;
+  const double* camc; const double* pts; const int* cam_pos;
+  double loss, rcond;
+  int n;
+};
+
+// COV_REQ_CAM_POINT: a = the camera's position in S^-1, b = point j (the solver's order): out = cov(camera, j), 6 x 3 row-major.
+// COV_REQ_POINT_POINT: a = point j, b = point k, j != k: out = cov(j, k), 3 x 3.  Lane a takes view a of each chunk of j; the
+// Y of k's views are broadcast with __shfl.
+__global__ void __launch_bounds__(256)
+k_cov_pt_cross(int nreq, const CovReq* __restrict__ req, CovPtSnap sn, const double* __restrict__ Sinv, double* __restrict__ out) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6, n = sn.n;
+  for (int i = blockIdx.x * nwave + wave; i < nreq; i += gridDim.x * nwave) {
+    const CovReq rq = req[i];
+    double* o = out + 36 * (size_t)rq.out;
+    const int pk = rq.b, bk = sn.pt_ptr[pk], kk = sn.pt_ptr[pk + 1] - bk;
+    const double Xk[3] = {sn.pts[3 * (size_t)pk], sn.pts[3 * (size_t)pk + 1], sn.pts[3 * (size_t)pk + 2]};
+    double V[6], Vik[6];
+    CovPointBlock(sn.camc, sn.obs_u, sn.obs_v, sn.obs_cam, bk, kk, Xk, sn.loss, lane, V);
+    (void)CovPointInverse(V, sn.rcond, Vik);
+    if (rq.kind == COV_REQ_CAM_POINT) {
+      // -sum over the views of Sigma_{camera, c_q} Y_q
+      double acc[18];
+#pragma unroll
+      for (int e = 0; e < 18; ++e) acc[e] = 0.0;
+      for (int q = lane; q < kk; q += 64) {
+        const int cam = sn.obs_cam[bk + q], pq = sn.cam_pos[cam];
+        if (pq < 0) continue;
+        double jc[12], jp[6], W[18], Y[18];
+        CovObsJacobian(sn.camc, cam, Xk, sn.obs_u[bk + q], sn.obs_v[bk + q], sn.loss, jc, jp);
+        CovWY(jc, jp, Vik, W, Y);
+        const double* Sb = Sinv + (size_t)rq.a * n + pq;
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+          double s6[6];
+#pragma unroll
+          for (int c = 0; c < 6; ++c) s6[c] = Sb[(size_t)r * n + c];
+#pragma unroll
+          for (int c3 = 0; c3 < 3; ++c3) {
+            double v = 0.0;
+#pragma unroll
+            for (int c = 0; c < 6; ++c) v += s6[c] * Y[3 * c + c3];
+            acc[3 * r + c3] -= v;
+          }
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < 18; ++e) acc[e] = WaveSum(acc[e]);
+      if (lane == 0) {
+#pragma unroll
+        for (int e = 0; e < 18; ++e) o[e] = acc[e];
+      }
+      continue;
+    }
+    const int pj = rq.a, bj = sn.pt_ptr[pj], kj = sn.pt_ptr[pj + 1] - bj;
+    const double Xj[3] = {sn.pts[3 * (size_t)pj], sn.pts[3 * (size_t)pj + 1], sn.pts[3 * (size_t)pj + 2]};
+    double Vij[6];
+    CovPointBlock(sn.camc, sn.obs_u, sn.obs_v, sn.obs_cam, bj, kj, Xj, sn.loss, lane, V);
+    (void)CovPointInverse(V, sn.rcond, Vij);
+    double acc[9];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) acc[e] = 0.0;
+    for (int qa0 = 0; qa0 < kj; qa0 += 64) {
+      const int qa = qa0 + lane;
+      int pa = -1;
+      double Ya[18];
+#pragma unroll
+      for (int e = 0; e < 18; ++e) Ya[e] = 0.0;
+      if (qa < kj) {
+        const int cam = sn.obs_cam[bj + qa];
+        pa = sn.cam_pos[cam];
+        double jc[12], jp[6], W[18];
+        CovObsJacobian(sn.camc, cam, Xj, sn.obs_u[bj + qa], sn.obs_v[bj + qa], sn.loss, jc, jp);
+        CovWY(jc, jp, Vij, W, Ya);
+      }
+      for (int qb0 = 0; qb0 < kk; qb0 += 64) {
+        const int qb = qb0 + lane;
+        int pb = -1;
+        double Yb[18];
+#pragma unroll
+        for (int e = 0; e < 18; ++e) Yb[e] = 0.0;
+        if (qb < kk) {
+          const int cam = sn.obs_cam[bk + qb];
+          pb = sn.cam_pos[cam];
+          double jc[12], jp[6], W[18];
+          CovObsJacobian(sn.camc, cam, Xk, sn.obs_u[bk + qb], sn.obs_v[bk + qb], sn.loss, jc, jp);
+          CovWY(jc, jp, Vik, W, Yb);
+        }
+        const int nb = min(64, kk - qb0);
+        for (int bb = 0; bb < nb; ++bb) {
+          const int pbb = __shfl(pb, bb, 64);
+          double y[18];
+#pragma unroll
+          for (int e = 0; e < 18; ++e) y[e] = __shfl(Yb[e], bb, 64);
+          if (pa < 0 || pbb < 0) continue;
+          const double* Sb = Sinv + (size_t)pa * n + pbb;
+#pragma unroll
+          for (int r = 0; r < 6; ++r) {
+            double s6[6], z[3];
+#pragma unroll
+            for (int c = 0; c < 6; ++c) s6[c] = Sb[(size_t)r * n + c];
+#pragma unroll
+            for (int c3 = 0; c3 < 3; ++c3) {
+              double v = 0.0;
+#pragma unroll
+              for (int c = 0; c < 6; ++c) v += s6[c] * y[3 * c + c3];
+              z[c3] = v;
+            }
+#pragma unroll
+            for (int a3 = 0; a3 < 3; ++a3)
+#pragma unroll
+              for (int c3 = 0; c3 < 3; ++c3) acc[3 * a3 + c3] += Ya[3 * r + a3] * z[c3];
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 9; ++e) acc[e] = WaveSum(acc[e]);
+    if (lane == 0) {
+#pragma unroll
+      for (int e = 0; e < 9; ++e) o[e] = acc[e];
+    }
+  }
+}
+
 }  // namespace rsba

@@ -288,6 +288,33 @@ struct rsba_solver {
   double* cov_pts = nullptr;                   // P x 9, the problem's point order
   char* cov_arena = nullptr;                   // scratch of the computation, kept between calls (grows only)
   size_t cov_arena_cap = 0;
+  // The SNAPSHOT a result belongs to: what rsba_solver_covariance_blocks / rsba_solver_time_covariances re-linearise from, so that
+  // a query after compute -> run still describes the state at compute.  Pointers into cov_arena (carved by the compute, valid
+  // while cov_valid), never the live parameters.
+  struct CovMarkerSnapshot {
+    double *pc = nullptr, *obs = nullptr, *intr = nullptr, *wrow = nullptr;
+    int* tptr = nullptr;
+    CovMcRow* rows = nullptr;
+    double loss = 0.0, rcond = 0.0, half_side = 0.0;
+    bool use_w = false;
+    std::vector<unsigned char> elim;           // per time: eliminated by this compute (free, referenced, time-eliminating path)
+  } cov_mc;
+  struct CovPointSnapshot {
+    double *camc = nullptr, *pts = nullptr;    // pts: the compute's own copy of the points (the solver's point order)
+    int* pos = nullptr;
+    double loss = 0.0, rcond = 0.0;
+  } cov_pt;
+  uint64_t cov_epoch = 0;                      // counts computes: what is cached below belongs to one of them
+  char* cov_query = nullptr;                   // pair list and output staging of a query (grows only)
+  size_t cov_query_cap = 0;
+  char* cov_tables = nullptr;                  // marker chain, time-eliminating path: the distinct blocks of every time and the rows'
+  size_t cov_tables_cap = 0;                   // slots among them (k_cov_mc_cross), built by the first query after a compute
+  uint64_t cov_tables_epoch = 0;
+  int *cov_dptr = nullptr, *cov_dpos = nullptr, *cov_rslot = nullptr;   // (carved out of cov_tables)
+  double* cov_times = nullptr;                 // T x 36 time marginals, formed by the first rsba_solver_time_covariances after a compute
+  size_t cov_times_cap = 0;
+  uint64_t cov_times_epoch = 0;
+  std::vector<int> cov_pt_dev;                 // point model: a point's index in the problem -> its position on the device
 
   // ---- evaluate (rsba_solver_evaluate, ba_evaluate.hpp): tables and arena of its own, the LM state is not touched
   EvalDevice eval;
@@ -392,7 +419,7 @@ static void FreeSolver(rsba_solver* s) {
   s->timer.Reset();
   void* ptrs[] = {s->obs_u, s->obs_v, s->intr, s->obs_cam, s->pt_ptr, s->sl_row_ptr, s->sl_cam, s->sl_uv, s->cam[0], s->cam[1], s->pts[0], s->pts[1], s->camc[0], s->camc[1],
                   s->cam0, s->pts0, s->scale_c, s->scale_p, s->red, s->A, s->W, s->chol_ok, s->S_copy, s->rhs_copy, s->dcam, s->block_scal,
-                  s->block_part, s->small_red, s->gmax, s->res, s->dec, s->red_tri, s->cam_free, s->pt_const, s->mc_flags, s->mc_dg, s->tc_flags, s->tc_map, s->tc_hand, s->tc_xs, s->tc_ys, s->cov_sinv, s->cov_pts, s->cov_arena, s->query_buf, s->obs_w_dev};
+                  s->block_part, s->small_red, s->gmax, s->res, s->dec, s->red_tri, s->cam_free, s->pt_const, s->mc_flags, s->mc_dg, s->tc_flags, s->tc_map, s->tc_hand, s->tc_xs, s->tc_ys, s->cov_sinv, s->cov_pts, s->cov_arena, s->cov_query, s->cov_tables, s->cov_times, s->query_buf, s->obs_w_dev};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   s->tiled.Free();
   s->marker.Free();
@@ -1895,12 +1922,13 @@ static int CovariancePoints(rsba_solver* s, const rsba_covariance_options& co, C
     if (s->cov_ref_cam[c] && !constant) { s->cov_pos[c] = n; n += 6; }
   }
   if (!s->cov_pts) { int rc = DevAlloc(&s->cov_pts, 9 * (size_t)P); if (rc) return rc; }
-  double *camc = nullptr, *tri = nullptr;
+  double *camc = nullptr, *tri = nullptr, *pts_snap = nullptr;
   int *pos = nullptr, *perm = nullptr;
   const size_t ntri = (size_t)n * (n + 1) / 2 + 1;   // the upper triangle of S and the point flag (k_cov_tri_pack)
   auto extra = [&](CovCarve& cv) {
     camc = cv.take<double>((size_t)CC_STRIDE * C); pos = cv.take<int>(C); perm = s->pt_perm.empty() ? nullptr : cv.take<int>(P);
     if (comm) tri = cv.take<double>(ntri);
+    pts_snap = cv.take<double>(3 * (size_t)P);   // the snapshot's points: the pair queries read this copy, not the live points
   };
   // the current device state: the last run's accepted point, or the uploaded start before the first run
   const double* cam = s->has_run ? s->cam[s->cur] : s->cam0;
@@ -1912,6 +1940,7 @@ static int CovariancePoints(rsba_solver* s, const rsba_covariance_options& co, C
   int rc = CovRun(s, n, rcond, extra, [&](CovSystem& y, auto& hip) {
     hip(hipMemcpyAsync(pos, s->cov_pos.data(), C * sizeof(int), hipMemcpyHostToDevice, st));
     if (perm) hip(hipMemcpyAsync(perm, s->pt_perm.data(), P * sizeof(int), hipMemcpyHostToDevice, st));
+    if (P > 0) hip(hipMemcpyAsync(pts_snap, pts, 3 * (size_t)P * sizeof(double), hipMemcpyDeviceToDevice, st));
     k_camera_constants<<<(C + 63) / 64, 64, 0, st>>>(C, cam, s->intr, camc);
     k_cov_lin<<<grid_pts, 256, 0, st>>>(P, s->obs_u, s->obs_v, s->obs_cam, s->pt_ptr, camc, pts, pos, s->pt_const, loss, rcond, y.n, y.S, y.flags);
   }, [&](CovSystem& y, auto& hip) -> int {
@@ -1930,6 +1959,7 @@ static int CovariancePoints(rsba_solver* s, const rsba_covariance_options& co, C
   k_cov_points<<<grid_pts, 256, 0, st>>>(P, s->obs_u, s->obs_v, s->obs_cam, s->pt_ptr, camc, pts, pos, s->pt_const, perm, loss, rcond, n,
                                          s->cov_sinv, s->cov_pts);
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return RSBA_ERR_HIP;
+  s->cov_pt.camc = camc; s->cov_pt.pts = pts_snap; s->cov_pt.pos = pos; s->cov_pt.loss = loss; s->cov_pt.rcond = rcond;
   s->cov_valid = true;
   return RSBA_OK;
 }
@@ -1993,7 +2023,7 @@ static int CovarianceMarker(rsba_solver* s, const rsba_covariance_options& co) {
   const double rcond = co.min_reciprocal_condition_number;
   const double loss = !co.apply_loss_function || !(s->opt.huber_delta > 0.0) ? 0.0 : (s->opt.loss_type == RSBA_LOSS_CAUCHY ? -s->opt.huber_delta : s->opt.huber_delta);
   hipStream_t st = s->stream;
-  return CovRun(s, n, rcond, extra, [&](CovSystem& y, auto& hip) {
+  const int rc = CovRun(s, n, rcond, extra, [&](CovSystem& y, auto& hip) {
     hip(hipMemcpyAsync(obs_d, obs.data(), obs.size() * sizeof(double), hipMemcpyHostToDevice, st));
     hip(hipMemcpyAsync(intr, p.intrinsics.data(), p.intrinsics.size() * sizeof(double), hipMemcpyHostToDevice, st));
     hip(hipMemcpyAsync(pos, s->cov_pos.data(), nb * sizeof(int), hipMemcpyHostToDevice, st));
@@ -2008,6 +2038,239 @@ static int CovarianceMarker(rsba_solver* s, const rsba_covariance_options& co) {
       k_cov_mc_lin<false><<<std::max(1, std::min(T, 4096)), 64, 0, st>>>(T, tptr_d, rows_d, obs_d, intr, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags);
     // (the host vectors outlive CovRun, which synchronises the stream before it returns)
   }, [](CovSystem&, auto&) { return RSBA_OK; });
+  // the snapshot of the pair queries: the carved pointers and what the linearisation was told
+  s->cov_mc.pc = pc; s->cov_mc.obs = obs_d; s->cov_mc.intr = intr; s->cov_mc.wrow = wrow_d; s->cov_mc.tptr = tptr_d; s->cov_mc.rows = rows_d;
+  s->cov_mc.loss = loss; s->cov_mc.rcond = rcond; s->cov_mc.half_side = p.marker_side / 2; s->cov_mc.use_w = use_w;
+  s->cov_mc.elim = elim;
+  return rc;
+}
+
+
+// ------------------------------------------------------------------------------------------------
+// Any pair of blocks of a covariance result (rsba_solver_covariance_blocks, rsba_solver_time_covariances; kernels and maths:
+// ba_covariance.hpp).  Local on a sharded solver: no collective.  Everything is read from the compute's snapshot.
+// ------------------------------------------------------------------------------------------------
+// One block of a pair: what it is in the result.
+struct CovBlockRef {
+  enum Kind { CONSTANT, REDUCED, TIME, POINT } kind = CONSTANT;
+  int idx = 0;    // REDUCED: position in S^-1; TIME: the time; POINT: the point (the problem's index)
+  int size = 6;
+};
+
+// RSBA_ERR_ARG: the offset starts no block, or names a block no residual references (the fixed base blocks included)
+static int CovResolve(const rsba_solver* s, int64_t off, CovBlockRef* r) {
+  const rsba_problem& p = *s->prob;
+  if (p.model != RSBA_MODEL_POINTS) {
+    const int C = p.num_cameras, T = p.num_times, nb = C + T + p.num_markers;
+    if (off < 0 || off >= 6LL * nb || off % 6) return RSBA_ERR_ARG;
+    const int blk = (int)(off / 6);
+    if (!s->cov_ref_cam[blk]) return RSBA_ERR_ARG;
+    r->size = 6;
+    if (s->cov_pos[blk] >= 0) { r->kind = CovBlockRef::REDUCED; r->idx = s->cov_pos[blk]; }
+    else if (blk >= C && blk < C + T && s->cov_mc.elim[blk - C]) { r->kind = CovBlockRef::TIME; r->idx = blk - C; }
+    else r->kind = CovBlockRef::CONSTANT;
+    return RSBA_OK;
+  }
+  const int64_t cam_end = 6LL * s->C, end = cam_end + 3LL * s->P;
+  if (off < 0 || off >= end) return RSBA_ERR_ARG;
+  if (off < cam_end) {
+    if (off % 6) return RSBA_ERR_ARG;
+    const int c = (int)(off / 6);
+    if (!s->cov_ref_cam[c]) return RSBA_ERR_ARG;
+    r->size = 6;
+    if (s->cov_pos[c] >= 0) { r->kind = CovBlockRef::REDUCED; r->idx = s->cov_pos[c]; } else r->kind = CovBlockRef::CONSTANT;
+    return RSBA_OK;
+  }
+  if ((off - cam_end) % 3) return RSBA_ERR_ARG;
+  const int j = (int)((off - cam_end) / 3);
+  if (!s->cov_ref_pt[j]) return RSBA_ERR_ARG;
+  r->size = 3;
+  const bool constant = j < (int)s->eval_const_pt.size() && s->eval_const_pt[j];
+  r->kind = constant ? CovBlockRef::CONSTANT : CovBlockRef::POINT;
+  r->idx = j;
+  return RSBA_OK;
+}
+
+// Marker chain, time-eliminating path: per time the distinct camera / marker blocks with columns that its rows touch, and every
+// row's two slots among them — the rows in the compute's order (time order, the problem's order within a time).  Built by the first
+// query after a compute, from the compute's column map.
+static int CovMarkerTables(rsba_solver* s) {
+  if (s->cov_tables && s->cov_tables_epoch == s->cov_epoch) return RSBA_OK;
+  const rsba_problem& p = *s->prob;
+  const int T = p.num_times;
+  const int64_t N = p.num_observations;
+  std::vector<int> tptr(T + 1, 0);
+  for (int64_t i = 0; i < N; ++i) tptr[p.time_index[i] + 1]++;
+  for (int t = 0; t < T; ++t) tptr[t + 1] += tptr[t];
+  std::vector<int> fill(tptr.begin(), tptr.end() - 1);
+  std::vector<int> rpos(2 * (size_t)std::max<int64_t>(N, 1), -1);
+  for (int64_t i = 0; i < N; ++i) {
+    const size_t q = (size_t)fill[p.time_index[i]]++;
+    rpos[2 * q] = p.uses_camera(i) ? s->cov_pos[p.camera_block(i)] : -1;
+    rpos[2 * q + 1] = p.uses_marker(i) ? s->cov_pos[p.marker_block(i)] : -1;
+  }
+  std::vector<int> dptr(T + 1, 0), dpos, rslot(rpos.size(), -1);
+  for (int t = 0; t < T; ++t) {
+    const size_t d0 = dpos.size();
+    for (size_t e = 2 * (size_t)tptr[t]; e < 2 * (size_t)tptr[t + 1]; ++e) {
+      if (rpos[e] < 0) continue;
+      size_t d = d0;
+      while (d < dpos.size() && dpos[d] != rpos[e]) ++d;
+      if (d == dpos.size()) dpos.push_back(rpos[e]);
+      rslot[e] = (int)(d - d0);
+    }
+    if (dpos.size() - d0 > RSBA_COV_MC_MAXBLK) return RSBA_ERR_UNSUPPORTED;
+    dptr[t + 1] = (int)dpos.size();
+  }
+  if (dpos.empty()) dpos.push_back(0);
+  int *dptr_d = nullptr, *dpos_d = nullptr, *rslot_d = nullptr;
+  auto carve = [&](CovCarve& cv) { dptr_d = cv.take<int>(dptr.size()); dpos_d = cv.take<int>(dpos.size()); rslot_d = cv.take<int>(rslot.size()); };
+  CovCarve sizing;
+  carve(sizing);
+  int rc;
+  if ((rc = CovGrow(&s->cov_tables, &s->cov_tables_cap, sizing.off))) return rc;
+  CovCarve cv;
+  cv.base = s->cov_tables;
+  carve(cv);
+  hipStream_t st = s->stream;
+  HIPCHK(hipMemcpyAsync(dptr_d, dptr.data(), dptr.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dpos_d, dpos.data(), dpos.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(rslot_d, rslot.data(), rslot.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
+  s->cov_dptr = dptr_d; s->cov_dpos = dpos_d; s->cov_rslot = rslot_d;
+  s->cov_tables_epoch = s->cov_epoch;
+  return RSBA_OK;
+}
+
+// The requests of one query, by kernel.  Queues them on the solver's stream: the list into cov_query, the blocks into `dst` (36
+// doubles per request slot; nullptr: a staging area behind the list, returned through *staging).  The caller synchronises.
+struct CovRequests { std::vector<CovReq> gather, marker, point; };
+
+static int CovQueue(rsba_solver* s, const CovRequests& rq, size_t slots, double* dst, double** staging) {
+  const size_t ng = rq.gather.size(), nm = rq.marker.size(), np = rq.point.size(), nreq = ng + nm + np;
+  if (nm > 0) { int rc = CovMarkerTables(s); if (rc != RSBA_OK) return rc; }
+  CovReq* req_d = nullptr;
+  double* stage_d = nullptr;
+  auto carve = [&](CovCarve& cv) { req_d = cv.take<CovReq>(nreq); stage_d = dst ? dst : cv.take<double>(36 * slots); };
+  CovCarve sizing;
+  carve(sizing);
+  int rc;
+  if ((rc = CovGrow(&s->cov_query, &s->cov_query_cap, sizing.off))) return rc;
+  CovCarve cv;
+  cv.base = s->cov_query;
+  carve(cv);
+  if (staging) *staging = stage_d;
+  if (nreq == 0) return RSBA_OK;
+  std::vector<CovReq> all;
+  all.reserve(nreq);
+  all.insert(all.end(), rq.gather.begin(), rq.gather.end());
+  all.insert(all.end(), rq.marker.begin(), rq.marker.end());
+  all.insert(all.end(), rq.point.begin(), rq.point.end());
+  hipStream_t st = s->stream;
+  HIPCHK(hipMemcpyAsync(req_d, all.data(), nreq * sizeof(CovReq), hipMemcpyHostToDevice, st));
+  if (ng > 0) k_cov_gather<<<(int)std::min<size_t>(ng, 8192), 64, 0, st>>>((int)ng, req_d, s->cov_n, s->cov_sinv, s->cov_pts, stage_d);
+  if (nm > 0) {
+    const auto& m = s->cov_mc;
+    CovMcSnap sn{m.tptr, m.rows, m.obs, m.intr, m.pc, m.use_w ? m.wrow : nullptr, s->cov_dptr, s->cov_dpos, s->cov_rslot,
+                 m.half_side, m.rcond, m.loss, m.loss != 0.0 || m.use_w ? 1 : 0, s->cov_n};
+    k_cov_mc_cross<<<(int)std::min<size_t>(nm, 4096), 64, 0, st>>>((int)nm, req_d + ng, sn, s->cov_sinv, stage_d);
+  }
+  if (np > 0) {
+    const auto& m = s->cov_pt;
+    CovPtSnap sn{s->obs_u, s->obs_v, s->obs_cam, s->pt_ptr, m.camc, m.pts, m.pos, m.loss, m.rcond, s->cov_n};
+    k_cov_pt_cross<<<(int)std::min<size_t>((np + 3) / 4, 8192), 256, 0, st>>>((int)np, req_d + ng + nm, sn, s->cov_sinv, stage_d);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));   // (the host list is read by the copy until here)
+  return RSBA_OK;
+}
+
+static int CovarianceBlocks(rsba_solver* s, int64_t num_pairs, const int64_t* offsets_a, const int64_t* offsets_b, double* out) {
+  // every pair is resolved before anything is written or launched: one bad offset refuses the whole call
+  struct Pair { CovBlockRef a, b; };
+  std::vector<Pair> pairs((size_t)num_pairs);
+  for (int64_t i = 0; i < num_pairs; ++i) {
+    int rc;
+    if ((rc = CovResolve(s, offsets_a[i], &pairs[i].a)) != RSBA_OK || (rc = CovResolve(s, offsets_b[i], &pairs[i].b)) != RSBA_OK) return rc;
+  }
+  if (s->prob->model == RSBA_MODEL_POINTS && s->cov_pt_dev.empty() && !s->pt_perm.empty()) {
+    s->cov_pt_dev.resize(s->pt_perm.size());
+    for (size_t jn = 0; jn < s->pt_perm.size(); ++jn) s->cov_pt_dev[s->pt_perm[jn]] = (int)jn;
+  }
+  auto dev = [&](int j) { return s->cov_pt_dev.empty() ? j : s->cov_pt_dev[j]; };
+  // ONE orientation of every pair is computed (rows x cols below); the other is its transpose on output
+  struct Plan { bool zero, transposed; int rows, cols; };
+  std::vector<Plan> plan((size_t)num_pairs);
+  CovRequests rq;
+  for (int64_t i = 0; i < num_pairs; ++i) {
+    const CovBlockRef &a = pairs[i].a, &b = pairs[i].b;
+    Plan& pl = plan[i];
+    pl = Plan{false, false, a.size, b.size};
+    const int slot = (int)i;
+    if (a.kind == CovBlockRef::CONSTANT || b.kind == CovBlockRef::CONSTANT) { pl.zero = true; continue; }
+    if (a.kind == CovBlockRef::REDUCED && b.kind == CovBlockRef::REDUCED) { rq.gather.push_back(CovReq{a.idx, b.idx, COV_REQ_SINV, slot}); continue; }
+    if (a.kind == CovBlockRef::POINT && b.kind == CovBlockRef::POINT) {
+      if (a.idx == b.idx) { rq.gather.push_back(CovReq{a.idx, a.idx, COV_REQ_POINT, slot}); continue; }
+      pl.transposed = a.idx > b.idx;
+      rq.point.push_back(CovReq{dev(std::min(a.idx, b.idx)), dev(std::max(a.idx, b.idx)), COV_REQ_POINT_POINT, slot});
+      continue;
+    }
+    if (a.kind == CovBlockRef::TIME && b.kind == CovBlockRef::TIME) {
+      pl.transposed = a.idx > b.idx;
+      rq.marker.push_back(CovReq{std::min(a.idx, b.idx), std::max(a.idx, b.idx), COV_REQ_TIME_TIME, slot});
+      continue;
+    }
+    // a reduced block with an eliminated one: computed as (time, x) / (camera, point)
+    const bool a_reduced = a.kind == CovBlockRef::REDUCED;
+    const CovBlockRef &x = a_reduced ? a : b, &e = a_reduced ? b : a;
+    if (e.kind == CovBlockRef::TIME) {
+      pl.transposed = a_reduced; pl.rows = 6; pl.cols = 6;
+      rq.marker.push_back(CovReq{e.idx, x.idx, COV_REQ_TIME_X, slot});
+    } else {
+      pl.transposed = !a_reduced; pl.rows = 6; pl.cols = 3;
+      rq.point.push_back(CovReq{x.idx, dev(e.idx), COV_REQ_CAM_POINT, slot});
+    }
+  }
+  double* stage_d = nullptr;
+  int rc = CovQueue(s, rq, (size_t)num_pairs, nullptr, &stage_d);
+  if (rc != RSBA_OK) return rc;
+  std::vector<double> h(36 * (size_t)num_pairs, 0.0);
+  if (!rq.gather.empty() || !rq.marker.empty() || !rq.point.empty())
+    HIPCHK(hipMemcpy(h.data(), stage_d, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+  for (int64_t i = 0; i < num_pairs; ++i) {
+    const Plan& pl = plan[i];
+    double* o = out + 36 * (size_t)i;
+    const double* g = h.data() + 36 * (size_t)i;
+    const int na = pairs[i].a.size, nb = pairs[i].b.size;
+    for (int e = 0; e < 36; ++e) o[e] = 0.0;
+    if (pl.zero) continue;
+    for (int r = 0; r < na; ++r)
+      for (int c = 0; c < nb; ++c) o[r * nb + c] = pl.transposed ? g[c * pl.cols + r] : g[r * pl.cols + c];
+  }
+  return RSBA_OK;
+}
+
+// T x 36 marginals of the time blocks, formed once per compute into cov_times (zeros for constant and unreferenced times): the
+// request list {(t, t)} — on the dense path the diagonal blocks of S^-1.
+static int CovarianceTimes(rsba_solver* s, double* out) {
+  const rsba_problem& p = *s->prob;
+  const int C = p.num_cameras, T = p.num_times;
+  if (!(s->cov_times && s->cov_times_epoch == s->cov_epoch)) {
+    int rc;
+    if ((rc = CovGrow(&s->cov_times, &s->cov_times_cap, 36 * (size_t)std::max(T, 1)))) return rc;
+    HIPCHK(hipMemsetAsync(s->cov_times, 0, 36 * (size_t)std::max(T, 1) * sizeof(double), s->stream));
+    CovRequests rq;
+    for (int t = 0; t < T; ++t) {
+      if (!s->cov_ref_cam[C + t]) continue;
+      if (s->cov_pos[C + t] >= 0) rq.gather.push_back(CovReq{s->cov_pos[C + t], s->cov_pos[C + t], COV_REQ_SINV, t});
+      else if (s->cov_mc.elim[t]) rq.marker.push_back(CovReq{t, t, COV_REQ_TIME_TIME, t});
+    }
+    if ((rc = CovQueue(s, rq, 0, s->cov_times, nullptr)) != RSBA_OK) return rc;
+    HIPCHK(hipStreamSynchronize(s->stream));
+    s->cov_times_epoch = s->cov_epoch;
+  }
+  if (T > 0) HIPCHK(hipMemcpy(out, s->cov_times, 36 * (size_t)T * sizeof(double), hipMemcpyDeviceToHost));
+  return RSBA_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2699,6 +2962,7 @@ int rsba_solver_covariance_compute(rsba_solver* s, const rsba_covariance_options
     // collective (rsba.h): an argument error of this rank alone travels in the request word, the group refuses together
     if (s->prob->model != RSBA_MODEL_POINTS) return RSBA_ERR_UNSUPPORTED;   // (a marker-chain solver has one rank: nobody waits)
     s->cov_valid = false;
+    ++s->cov_epoch;
     rsba::CommScope device_turn(s->comm.get());
     int rc = hipSetDevice(s->device) == hipSuccess && hipStreamSynchronize(s->stream) == hipSuccess ? RSBA_OK : RSBA_ERR_HIP;
     if (rc == RSBA_OK) {
@@ -2710,6 +2974,7 @@ int rsba_solver_covariance_compute(rsba_solver* s, const rsba_covariance_options
   }
   if (bad) return RSBA_ERR_ARG;
   s->cov_valid = false;
+  ++s->cov_epoch;
   if (hipSetDevice(s->device) != hipSuccess) return RSBA_ERR_HIP;
   if (hipStreamSynchronize(s->stream) != hipSuccess) return RSBA_ERR_HIP;
   return s->prob->model == RSBA_MODEL_POINTS ? rsba::CovariancePoints(s, co, nullptr) : rsba::CovarianceMarker(s, co);
@@ -2771,6 +3036,23 @@ int rsba_solver_point_covariances(const rsba_solver* s, double* out) {
   rsba::CommScope device_turn(s->comm.get());   // (local, no collective; a loopback rank copies on its turn only)
   if (hipSetDevice(s->device) != hipSuccess) return RSBA_ERR_HIP;
   return hipMemcpy(out, s->cov_pts, 9 * (size_t)s->P * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess ? RSBA_OK : RSBA_ERR_HIP;
+}
+
+int rsba_solver_covariance_blocks(rsba_solver* s, int64_t num_pairs, const int64_t* offsets_a, const int64_t* offsets_b, double* out) {
+  if (!s || num_pairs < 0 || !offsets_a || !offsets_b || !out) return RSBA_ERR_ARG;
+  if (!s->cov_valid) return RSBA_ERR_ARG;
+  if (num_pairs == 0) return RSBA_OK;
+  rsba::CommScope device_turn(s->comm.get());   // (local, no collective; a loopback rank launches on its turn only)
+  if (hipSetDevice(s->device) != hipSuccess) return RSBA_ERR_HIP;
+  return rsba::CovarianceBlocks(s, num_pairs, offsets_a, offsets_b, out);
+}
+
+int rsba_solver_time_covariances(rsba_solver* s, double* out) {
+  if (!s || !out) return RSBA_ERR_ARG;
+  if (s->prob->model == RSBA_MODEL_POINTS) return RSBA_ERR_UNSUPPORTED;
+  if (!s->cov_valid) return RSBA_ERR_ARG;
+  if (hipSetDevice(s->device) != hipSuccess) return RSBA_ERR_HIP;
+  return rsba::CovarianceTimes(s, out);
 }
 
 int64_t rsba_solver_num_residuals(const rsba_solver* s) {
