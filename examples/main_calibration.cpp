@@ -17,9 +17,11 @@ int main(int argc, char** argv) {
   const std::string in = argv[1], out = argv[2];
   const char* serials[4] = {"821312061029", "816612062327", "821212062536", "821212061326"};  // my_const.h:15
   std::vector<Intrinsics> K(4);
+  std::vector<DistCoeffs> D(4);   // <distCoeffs> of the same files (my_io.cpp reads both); all zeros on the D400 files
   for (int i = 0; i < 4; ++i) {
     const std::string f = in + "/intrinsics/" + serials[i] + ".xml";
-    if (rsba_read_intrinsics_xml(f.c_str(), K[i].data()) != RSBA_OK) { fprintf(stderr, "File can not be opened: %s\n", f.c_str()); return 1; }
+    const int rc = rsba_read_intrinsics_xml_dist(f.c_str(), K[i].data(), D[i].data());
+    if (rc != RSBA_OK) { fprintf(stderr, "%s: %s\n", rc == RSBA_ERR_IO ? "File can not be opened" : rsba_error_string(rc), f.c_str()); return 1; }
   }
   BAPaths paths;
   paths.correspondence = in + "/hongo/correspondence.txt";
@@ -27,7 +29,7 @@ int main(int argc, char** argv) {
   paths.extrinsics_dir = out;
   paths.point3d = out + "/point3d.txt";
   try {
-    BAManager ba_manager(K, 0.0148, paths);
+    BAManager ba_manager(K, 0.0148, paths, RSBA_MODEL_MARKER_CHAIN, D);
     if (ba_manager.StartBA() != RSBA_OK) return 1;
     ba_manager.Write();
     double err = 0;

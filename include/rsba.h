@@ -209,6 +209,25 @@ int rsba_problem_set_observation_weights(rsba_problem* p, const double* weights 
 /* the problem's copy of the weights; NULL when it has none */
 const double* rsba_problem_observation_weights(const rsba_problem* p);
 
+/* Lens distortion on the marker-chain models: OpenCV's five coefficients k1 k2 p1 p2 k3, as cv::projectPoints applies a 5 x 1 distCoeffs,
+ * on the corner (X, Y, Z) in the detecting camera's frame:
+ *   x = X / Z, y = Y / Z, r2 = x^2 + y^2,  rad = 1 + k1 r2 + k2 r2^2 + k3 r2^3
+ *   xd = x rad + 2 p1 x y + p2 (r2 + 2 x^2),  yd = y rad + p1 (r2 + 2 y^2) + 2 p2 x y,  u = fx xd + ppx, v = fy yd + ppy
+ * dist: 5 doubles per camera index in that order, indexed as the intrinsics are (the detecting camera, whether or not its pose is
+ * a parameter).  Like the intrinsics they are constants of the problem (the reference hands dist_coeffs to every functor and then
+ * projects without them, bundle_adjustment.h:117-118); refining them is not offered.
+ * Host only; the array is copied; NULL removes the coefficients.  A non-finite value: RSBA_ERR_ARG, nothing changes.  The point model:
+ * RSBA_ERR_UNSUPPORTED (its projection sits in the headline kernels).  rsba_solve, rsba_solver_create and rsba_reprojection_error honour
+ * the problem's coefficients, and so does every call on a solver created from it (run, evaluate, evaluate_jacobian,
+ * covariance_compute and the block queries, set_parameters); there is no solver-level setter: fixed at create, like the intrinsics.
+ * Which kernels run is decided at create: no coefficients, or all exactly zero — the instances and the bits of a problem without
+ * them; any non-zero coefficient — the distortion instances for the whole solver (a camera whose five are zero then agrees with
+ * the pinhole form to rounding, not bit for bit).  The path (rsba_solver_time_elimination) does not depend on the coefficients.
+ * OpenCV's 8 / 12 / 14-coefficient models, the fisheye model and RealSense's inverse Brown-Conrady are not offered. */
+int rsba_problem_set_distortion(rsba_problem* p, const double* dist /* 5 per camera, or NULL */);
+/* the problem's copy of the coefficients; NULL when it has none */
+const double* rsba_problem_distortion(const rsba_problem* p);
+
 /* Test1 file "two_cam_data.txt": `C P`, P rows `cam pt u v` (one observation per point,
  * bundle_adjustmenter.cpp:62-64), C x (rvec row, tvec row), P rows xyz.  Also accepts the extended
  * first line `C P N` with N observation rows.  One intrinsics 4-vector is used for every
@@ -223,7 +242,8 @@ int rsba_problem_load_correspondence(const char* path, int32_t model, double mar
 
 /* ------------------------------------------------------------------ initial guesses (the reference's front end)
  * What Correspondencer computes between the ArUco detections and correspondence.txt, without OpenCV.  Poses are
- * 6 doubles (rvec, tvec), p_out = R(rvec) p_in + tvec.  Host code; zero lens distortion (the committed intrinsics). */
+ * 6 doubles (rvec, tvec), p_out = R(rvec) p_in + tvec.  Host code.  The routines see pinhole pixels: detections of a lens with
+ * distortion coefficients go through rsba_undistort_points first (include/rsba/correspondencer.h does). */
 /* correspondencer.cpp:119-127: the base marker's pose in the main camera from the detection of another marker and
  * that marker's pose in the base marker's frame (my_io GetMarkerGeometry). */
 int rsba_base_pose_from_marker_detection(const double* marker_from_camera, const double* marker_from_base,
@@ -232,12 +252,20 @@ int rsba_base_pose_from_marker_detection(const double* marker_from_camera, const
 int rsba_marker_pose_in_camera(const double* base_from_camera, const double* marker_from_base, double* marker_from_camera);
 /* Correspondencer::GetCornersInCameraWorld (correspondencer.cpp:5-39): top-left, top-right, bottom-right, bottom-left. */
 int rsba_marker_corners_in_camera(const double* pose, double marker_side, double* out12);
+/* cv::undistortPoints(src, dst, K, dist, noArray(), K) for the five-coefficient model (k1 k2 p1 p2 k3): pixel coordinates of distorted
+ * detections -> pixel coordinates of the ideal pinhole camera with the same intrinsics.  Fixed-point iteration on the normalised
+ * point until the update is below 1e-14, 50 iterations at most; a point that does not converge (coefficients too strong at its
+ * radius): RSBA_ERR_UNSUPPORTED.  out may be image_points.  All-zero coefficients return the input's bits.  No digit-for-digit claim
+ * against OpenCV. */
+int rsba_undistort_points(int32_t n, const double* image_points /* 2n */, const double* intrinsics4, const double* dist5,
+                          double* out /* 2n */);
 /* cv::solvePnP(object, image, K, dist = 0, rvec, tvec, false, SOLVEPNP_EPNP) as correspondencer.cpp:192-195 calls it.
  * n >= 4 points (the reference exits below 4, :185-190); RSBA_ERR_UNSUPPORTED for a coplanar point set. */
 int rsba_solve_pnp_epnp(int32_t n, const double* object_points /* 3n */, const double* image_points /* 2n */,
                         const double* intrinsics4, double* pose);
 /* Correspondencer::CalculateTransforms (correspondencer.cpp:178-205) on a marker-chain problem whose time and marker
- * blocks are filled: camera 0 := identity, every other camera := EPnP over the corners of all markers it detected. */
+ * blocks are filled: camera 0 := identity, every other camera := EPnP over the corners of all markers it detected (undistorted
+ * first when the problem carries distortion coefficients). */
 int rsba_problem_initial_camera_poses(rsba_problem* p);
 
 void rsba_problem_free(rsba_problem* p);
@@ -533,6 +561,10 @@ int rsba_solver_time_elimination(const rsba_solver* s, int32_t* eliminates_times
 /* IO::GetIntrinsics (my_io.cpp:5-31) without OpenCV: reads <intrinsics> 3x3 from an OpenCV
  * FileStorage XML and returns fx, fy, ppx, ppy. */
 int rsba_read_intrinsics_xml(const char* path, double* out4);
+/* The same, and <distCoeffs> (my_io.cpp reads it beside <intrinsics>): out5 = k1 k2 p1 p2 k3.  A 4 x 1 or 1 x 4 vector sets k3 = 0, a
+ * 5 x 1 or 1 x 5 one is read as it is, a missing node gives zeros.  8, 12 or 14 entries (OpenCV's rational, thin-prism and tilted
+ * models): RSBA_ERR_UNSUPPORTED; any other shape: RSBA_ERR_FORMAT. */
+int rsba_read_intrinsics_xml_dist(const char* path, double* out4, double* out5);
 
 /* BAManager::Write (bundle_adjustment_manager.cpp:98-175).  Any path may be NULL to skip that file.
  *   camera_transform_xml : R{i} 3x3 (Main) or rvec 3x1 (Test2 variant, main.cpp:128) + t{i}
@@ -548,7 +580,9 @@ int rsba_reprojection_error(rsba_problem* p, const rsba_options* o, double* erro
 /* ReprojectionCheck::Reproject end to end from the files it reads (reprojection_check.cpp:5-101): the 6-digit 3D
  * corners of point3d.txt, R{i} (3x3, or the 3x1 rvec of the Test2 variant) and t{i} of Camera_Transform.xml, and the
  * detected corners — taken from correspondence.txt and rounded to float32 as the reference holds them (Point2f,
- * :78) — projected on the GPU with zero distortion (:69).  intrinsics: fx, fy, ppx, ppy per camera.  On the
+ * :78) — projected on the GPU with zero distortion (:69): this call stays pinhole, its signature has no place for coefficients
+ * (rsba_reprojection_error on a problem with rsba_problem_set_distortion is the one that honours them).  intrinsics: fx, fy, ppx,
+ * ppy per camera.  On the
  * committed hongo files this prints the reference's 143.64 / 0.726696 (vs 0.726670 from the unrounded parameters). */
 int rsba_reprojection_check_files(const char* correspondence_txt, const char* point3d_txt, const char* camera_transform_xml,
                                   const double* intrinsics, double* error, double* rms);

@@ -19,6 +19,7 @@ namespace RSCalibration {
 
 struct Point3d { double x, y, z; };
 using Intrinsics = std::array<double, 4>;  // fx, fy, ppx, ppy  (K(0,0), K(1,1), K(0,2), K(1,2))
+using DistCoeffs = std::array<double, 5>;  // k1, k2, p1, p2, k3  (the 5 x 1 distCoeffs of Intrinsics/{serial}.xml)
 
 class BALProblem {
  public:
@@ -30,13 +31,23 @@ class BALProblem {
   // bundle_adjustment.cpp:132-187.  The reference reads MARKER_SIDE and the intrinsics elsewhere; here they are
   // handed in because the functors that used to hold them are gone.  Returns false when the file cannot be
   // opened (as the reference does) or is malformed.
+  // dist_coeffs: the reference's create(observations, marker_side, intrinsics, dist_coeffs) takes them per camera and drops them
+  // (bundle_adjustment.h:117-118); here they are honoured (rsba_problem_set_distortion).  Empty: a pinhole camera, as before; else
+  // one per camera.
   bool loadFile(const char* filename, double marker_side, const std::vector<Intrinsics>& intrinsics,
-                int model = RSBA_MODEL_MARKER_CHAIN) {
+                int model = RSBA_MODEL_MARKER_CHAIN, const std::vector<DistCoeffs>& dist_coeffs = {}) {
     rsba_problem_free(p_);
     p_ = nullptr;
     std::vector<double> k;
     for (const auto& i : intrinsics) k.insert(k.end(), i.begin(), i.end());
-    return rsba_problem_load_correspondence(filename, model, marker_side, k.data(), &p_) == RSBA_OK;
+    if (rsba_problem_load_correspondence(filename, model, marker_side, k.data(), &p_) != RSBA_OK) return false;
+    if (dist_coeffs.empty()) return true;
+    std::vector<double> d;
+    for (const auto& i : dist_coeffs) d.insert(d.end(), i.begin(), i.end());
+    if ((int)dist_coeffs.size() == num_cameras() && rsba_problem_set_distortion(p_, d.data()) == RSBA_OK) return true;
+    rsba_problem_free(p_);
+    p_ = nullptr;
+    return false;
   }
   // Test1 BALProblem::LoadFile (Test1_BundleAdjustment/bundle_adjustmenter.cpp:55-85)
   bool LoadFile(const char* filename, const Intrinsics& intrinsics) {
@@ -63,6 +74,9 @@ class BALProblem {
   // a_i >= 0 per observation, nullptr removes them / none set
   bool set_observation_weights(const double* weights) { return rsba_problem_set_observation_weights(p_, weights) == RSBA_OK; }
   const double* observation_weights() const { return rsba_problem_observation_weights(p_); }
+  // lens distortion (rsba_problem_set_distortion): 5 per camera, nullptr removes them / none set
+  bool set_distortion(const double* dist) { return rsba_problem_set_distortion(p_, dist) == RSBA_OK; }
+  const double* distortion() const { return rsba_problem_distortion(p_); }
   // Test1 accessors
   double* mutable_cameras() { return rsba_problem_parameters(p_); }
   double* mutable_points() { return rsba_problem_parameters(p_) + 6 * num_cameras(); }

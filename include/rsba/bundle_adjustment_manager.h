@@ -23,11 +23,21 @@ class BAManager {
  public:
   // camera_intrinsics: one {fx, fy, ppx, ppy} per camera index, in SERIAL_NUMBERS order (my_const.h:15);
   // the reference takes map<string, Mat> keyed by serial and indexes it with SERIAL_NUMBERS[camera_idx].
+  // camera_dist_coeffs: one {k1, k2, p1, p2, k3} per camera index (the reference's map<string, Mat> dist_coeffs, which it passes on
+  // and never applies); empty = pinhole cameras.
   BAManager(const std::vector<Intrinsics>& camera_intrinsics, double marker_side = 0.0148, const BAPaths& paths = BAPaths(),
-            int model = RSBA_MODEL_MARKER_CHAIN)
+            int model = RSBA_MODEL_MARKER_CHAIN, const std::vector<DistCoeffs>& camera_dist_coeffs = {})
       : paths_(paths) {
     if (!bal_problem.loadFile(paths_.correspondence.c_str(), marker_side, camera_intrinsics, model))
       throw std::runtime_error("unable to open correspondence file " + paths_.correspondence);
+    if (!camera_dist_coeffs.empty()) {
+      if ((int)camera_dist_coeffs.size() != bal_problem.num_cameras())
+        throw std::invalid_argument("BAManager: one distortion vector per camera (" + std::to_string(bal_problem.num_cameras()) + ") expected");
+      std::vector<double> d;
+      for (const DistCoeffs& i : camera_dist_coeffs) d.insert(d.end(), i.begin(), i.end());
+      const int rc = rsba_problem_set_distortion(bal_problem.handle(), d.data());
+      if (rc != RSBA_OK) throw std::runtime_error(std::string("BAManager: distortion coefficients: ") + rsba_error_string(rc));
+    }
     rsba_options_default(&options);
     options.minimizer_progress_to_stdout = 1;  // bundle_adjustment_manager.cpp:92
   }
@@ -65,7 +75,8 @@ class BAManager {
   }
 
   // ReprojectionCheck::Reproject as main.cpp:41-43 runs it after Write(): from the files just written
-  // (reprojection_check.cpp:5-101: 6-digit point3d.txt, Camera_Transform.xml, float32 corners)
+  // (reprojection_check.cpp:5-101: 6-digit point3d.txt, Camera_Transform.xml, float32 corners).  Pinhole, as the reference's check:
+  // with distortion coefficients ReprojectionRms above is the figure that honours them.
   double ReprojectionRmsFromFiles(const std::vector<Intrinsics>& camera_intrinsics, double* error = nullptr) {
     std::vector<double> k;
     for (const Intrinsics& i : camera_intrinsics) k.insert(k.end(), i.begin(), i.end());

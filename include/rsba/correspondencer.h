@@ -25,9 +25,14 @@ struct Point2d { double x, y; };
 
 class Correspondencer {
  public:
-  // intrinsics: {fx, fy, ppx, ppy} per camera in SERIAL_NUMBERS order (my_const.h:15); zero distortion
-  Correspondencer(const std::vector<std::array<double, 4>>& camera_intrinsics, double marker_side)
-      : intrinsics_(camera_intrinsics), marker_side_(marker_side) {}
+  // intrinsics: {fx, fy, ppx, ppy} per camera in SERIAL_NUMBERS order (my_const.h:15); dist_coeffs: {k1, k2, p1, p2, k3} per camera
+  // (empty: pinhole cameras) — the detections are undistorted (rsba_undistort_points) before EPnP sees them, what cv::solvePnP
+  // does with its distCoeffs argument
+  Correspondencer(const std::vector<std::array<double, 4>>& camera_intrinsics, double marker_side,
+                  const std::vector<std::array<double, 5>>& camera_dist_coeffs = {})
+      : intrinsics_(camera_intrinsics), dist_(camera_dist_coeffs), marker_side_(marker_side) {
+    if (!dist_.empty() && dist_.size() != intrinsics_.size()) throw std::invalid_argument("Correspondencer: one distortion vector per camera");
+  }
 
   std::vector<Point3d> GetCornersInCameraWorld(const Transform& t) const {
     double pose[6], out[12];
@@ -58,7 +63,10 @@ class Correspondencer {
       if (image_points[c].size() < 4) throw std::runtime_error("The correspondence points are too few.");   // :185-190
       double pose[6];
       static_assert(sizeof(Point3d) == 3 * sizeof(double) && sizeof(Point2d) == 2 * sizeof(double), "packed points");
-      Check(rsba_solve_pnp_epnp((int32_t)image_points[c].size(), &object_points[c][0].x, &image_points[c][0].x, intrinsics_[c].data(), pose),
+      std::vector<Point2d> ideal(image_points[c]);
+      if (!dist_.empty())
+        Check(rsba_undistort_points((int32_t)ideal.size(), &image_points[c][0].x, intrinsics_[c].data(), dist_[c].data(), &ideal[0].x), "undistort");
+      Check(rsba_solve_pnp_epnp((int32_t)ideal.size(), &object_points[c][0].x, &ideal[0].x, intrinsics_[c].data(), pose),
             "CalculateTransforms");
       cameras[c] = Unpack(pose);
     }
@@ -69,6 +77,7 @@ class Correspondencer {
   static Transform Unpack(const double* p) { Transform t; for (int k = 0; k < 3; ++k) { t.rvec[k] = p[k]; t.tvec[k] = p[3 + k]; } return t; }
   static void Check(int rc, const char* what) { if (rc != RSBA_OK) throw std::runtime_error(std::string(what) + ": " + rsba_error_string(rc)); }
   std::vector<std::array<double, 4>> intrinsics_;
+  std::vector<std::array<double, 5>> dist_;
   double marker_side_;
 };
 

@@ -35,6 +35,7 @@ EXPORTS = [
     "rsba_solver_jacobian_structure", "rsba_solver_evaluate_jacobian",
     "rsba_solver_comm_abort",
     "rsba_problem_set_observation_weights", "rsba_problem_observation_weights", "rsba_solver_set_observation_weights",
+    "rsba_problem_set_distortion", "rsba_problem_distortion", "rsba_read_intrinsics_xml_dist", "rsba_undistort_points",
 ]
 _SYMBOLS = EXPORTS   # (every symbol of include/rsba.h that load() checks)
 
@@ -175,6 +176,11 @@ def load():
     lib.rsba_problem_observation_weights.argtypes = [C.c_void_p]
     lib.rsba_problem_observation_weights.restype = C.POINTER(C.c_double)
     lib.rsba_solver_set_observation_weights.argtypes = [C.c_void_p, C.c_void_p]
+    lib.rsba_problem_set_distortion.argtypes = [C.c_void_p, C.c_void_p]
+    lib.rsba_problem_distortion.argtypes = [C.c_void_p]
+    lib.rsba_problem_distortion.restype = C.POINTER(C.c_double)
+    lib.rsba_read_intrinsics_xml_dist.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p]
+    lib.rsba_undistort_points.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _LIB = lib
     return lib
 
@@ -223,7 +229,8 @@ class Problem:
 
     @classmethod
     def marker_chain(cls, prob, model=MODEL_MARKER_CHAIN):
-        """prob: dict with T, C, M, N, t, c, m (int32 per row), obs (N x 8), params (6 (C + T + M)), intr (C x 4), marker_side."""
+        """prob: dict with T, C, M, N, t, c, m (int32 per row), obs (N x 8), params (6 (C + T + M)), intr (C x 4), marker_side, and
+        optionally dist (C x 5: k1 k2 p1 p2 k3 per camera, set_distortion)."""
         h = C.c_void_p()
         t, c, m = (np.ascontiguousarray(prob[k], np.int32) for k in ("t", "c", "m"))
         obs = np.ascontiguousarray(prob["obs"], np.float64)
@@ -232,7 +239,14 @@ class Problem:
         _chk(load().rsba_problem_create_marker_chain(model, prob["C"], prob["T"], prob["M"], prob["N"], _vp(t), _vp(c), _vp(m), _vp(obs),
                                                      _vp(par), _vp(intr), C.c_double(prob["marker_side"]), C.byref(h)),
              "rsba_problem_create_marker_chain")
-        return cls(h)
+        p = cls(h)
+        if prob.get("dist") is not None:
+            try:
+                p.set_distortion(prob["dist"])
+            except Exception:
+                p.close()
+                raise
+        return p
 
     @classmethod
     def points_file(cls, path, intrinsics4):
@@ -300,6 +314,23 @@ class Problem:
         """A copy of the problem's weights, or None when it has none."""
         q = load().rsba_problem_observation_weights(self.h)
         return np.ctypeslib.as_array(q, shape=(self.num_observations,)).copy() if q else None
+
+    def set_distortion(self, dist):
+        """Marker-chain models: OpenCV's k1 k2 p1 p2 k3 per camera index (C x 5), constants of the problem like the intrinsics; None
+        removes them.  Solvers created afterwards honour them (all zeros: the kernels and bits of a problem without)."""
+        if dist is None:
+            _chk(load().rsba_problem_set_distortion(self.h, None), "rsba_problem_set_distortion")
+            return
+        d = np.ascontiguousarray(dist, np.float64)
+        if d.size != 5 * self.num_cameras:
+            raise ValueError("set_distortion: %d x 5 values expected" % self.num_cameras)
+        _chk(load().rsba_problem_set_distortion(self.h, _vp(d)), "rsba_problem_set_distortion")
+
+    @property
+    def distortion(self):
+        """A copy of the problem's distortion coefficients (C x 5), or None when it has none."""
+        q = load().rsba_problem_distortion(self.h)
+        return np.ctypeslib.as_array(q, shape=(self.num_cameras, 5)).copy() if q else None
 
     def initial_camera_poses(self):
         _chk(load().rsba_problem_initial_camera_poses(self.h), "rsba_problem_initial_camera_poses")
@@ -737,6 +768,24 @@ class ShardedLoopbackGroup:
 def read_intrinsics_xml(path):
     out = np.zeros(4)
     _chk(load().rsba_read_intrinsics_xml(path.encode(), _vp(out)), "rsba_read_intrinsics_xml")
+    return out
+
+
+def read_intrinsics_xml_dist(path):
+    """(fx, fy, ppx, ppy), (k1, k2, p1, p2, k3) of an OpenCV FileStorage XML with <intrinsics> and, optionally, <distCoeffs>."""
+    k, d = np.zeros(4), np.zeros(5)
+    _chk(load().rsba_read_intrinsics_xml_dist(str(path).encode(), _vp(k), _vp(d)), "rsba_read_intrinsics_xml_dist")
+    return k, d
+
+
+def undistort_points(image_points, intrinsics4, dist5):
+    """Pixel coordinates of distorted detections (n x 2) -> pixel coordinates of the ideal pinhole camera with the same intrinsics."""
+    img = np.ascontiguousarray(image_points, np.float64).reshape(-1, 2)
+    k, d = np.ascontiguousarray(intrinsics4, np.float64), np.ascontiguousarray(dist5, np.float64)
+    if k.size != 4 or d.size != 5:
+        raise ValueError("undistort_points: 4 intrinsics and 5 coefficients expected")
+    out = np.zeros_like(img)
+    _chk(load().rsba_undistort_points(len(img), _vp(img), _vp(k), _vp(d), _vp(out)), "rsba_undistort_points")
     return out
 
 

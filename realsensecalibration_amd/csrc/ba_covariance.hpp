@@ -513,9 +513,10 @@ __device__ __forceinline__ bool CovSym6Inverse(const double U[21], double rcond,
 // time block t is eliminated — S -= W_x V_t^-1 W_y' over the pairs of its rows' camera / marker blocks, W_x = sum J_x'J_t.
 // kLoss: J of a row scaled by sqrt(rho'(s)) (loss: LossAndScale's signed parameter), s taken over its four corners first; wts
 // (nullptr: none): the rows' weights a_q (ceres::ScaledLoss) in the rows' order, the factor sqrt(a_q) sqrt(rho').
-template <bool kLoss>
+// kDist: dist = the cameras' five distortion coefficients [C][5], indexed as intr.
+template <bool kLoss, bool kDist = false>
 __global__ void __launch_bounds__(64)
-k_cov_mc_lin(int T, const int* __restrict__ tptr, const CovMcRow* __restrict__ rows, const double* __restrict__ obs8, const double* __restrict__ intr,
+k_cov_mc_lin(int T, const int* __restrict__ tptr, const CovMcRow* __restrict__ rows, const double* __restrict__ obs8, typename IntrArg<kDist>::type intr,
              const double* __restrict__ pc, const int* __restrict__ pos, const unsigned char* __restrict__ elim, double half_side, double rcond,
              int n, double* __restrict__ S, int* __restrict__ flags, double loss = 0.0, const double* __restrict__ wts = nullptr) {
   __shared__ double Wl[64 * RSBA_COV_MC_LDS];
@@ -534,7 +535,7 @@ k_cov_mc_lin(int T, const int* __restrict__ tptr, const CovMcRow* __restrict__ r
       double ss = 0.0;
       for (int k = 0; k < 4; ++k) {
         double r[2], J[36];
-        MarkerCornerResidualJacobian(pcc, pc + (size_t)rw.time_block * CC_STRIDE, pcm, intr + 4 * rw.camera, cx[k], cy[k], o8[2 * k], o8[2 * k + 1], r, J);
+        MarkerCornerResidualJacobian<kDist>(pcc, pc + (size_t)rw.time_block * CC_STRIDE, pcm, IntrOf(intr) + 4 * rw.camera, cx[k], cy[k], o8[2 * k], o8[2 * k + 1], r, J, DistOf(intr, rw.camera));
         ss += r[0] * r[0] + r[1] * r[1];
       }
       (void)LossAndScale(loss, ss, &sq);
@@ -542,7 +543,7 @@ k_cov_mc_lin(int T, const int* __restrict__ tptr, const CovMcRow* __restrict__ r
     }
     for (int k = 0; k < 4; ++k) {
       double r[2], J[36];
-      MarkerCornerResidualJacobian(pcc, pc + (size_t)rw.time_block * CC_STRIDE, pcm, intr + 4 * rw.camera, cx[k], cy[k], o8[2 * k], o8[2 * k + 1], r, J);
+      MarkerCornerResidualJacobian<kDist>(pcc, pc + (size_t)rw.time_block * CC_STRIDE, pcm, IntrOf(intr) + 4 * rw.camera, cx[k], cy[k], o8[2 * k], o8[2 * k + 1], r, J, DistOf(intr, rw.camera));
       if constexpr (kLoss) {
         for (int e = 0; e < 36; ++e) J[e] *= sq;
       }
@@ -698,13 +699,20 @@ struct CovMcSnap {
   double half_side, rcond, loss;
   int lossy, n;
 };
+// k_cov_mc_cross<true>'s argument: the same and the cameras' distortion coefficients [C][5], indexed as intr
+struct CovMcSnapDist : CovMcSnap { const double* dist; };
+template <bool kDist> struct CovMcSnapT { typedef CovMcSnap type; };
+template <> struct CovMcSnapT<true> { typedef CovMcSnapDist type; };
+__device__ __forceinline__ const double* DistOf(const CovMcSnap&, int) { return nullptr; }
+__device__ __forceinline__ const double* DistOf(const CovMcSnapDist& a, int camera) { return a.dist + 5 * camera; }
 
 template <int kX> struct CovSide { static constexpr int value = kX; };
 
 // COV_REQ_TIME_TIME: a = t, b = t' (a <= b; out = cov(t, t'), mirrored from its upper triangle for t = t');
 // COV_REQ_TIME_X: a = t, b = x's position in S^-1 (out = cov(t, x)).
+template <bool kDist = false>
 __global__ void __launch_bounds__(64)
-k_cov_mc_cross(int nreq, const CovReq* __restrict__ req, CovMcSnap sn, const double* __restrict__ Sinv, double* __restrict__ out) {
+k_cov_mc_cross(int nreq, const CovReq* __restrict__ req, typename CovMcSnapT<kDist>::type sn, const double* __restrict__ Sinv, double* __restrict__ out) {
   __shared__ double Yd[RSBA_COV_MC_MAXBLK * 36];
   __shared__ double stage[32 * RSBA_COV_MC_STAGE];
   __shared__ int sl[64];
@@ -722,7 +730,7 @@ k_cov_mc_cross(int nreq, const CovReq* __restrict__ req, CovMcSnap sn, const dou
       double ss = 0.0;
       for (int k = 0; k < 4; ++k) {
         double r[2], J[36];
-        MarkerCornerResidualJacobian(pcc, sn.pc + (size_t)rw.time_block * CC_STRIDE, pcm, sn.intr + 4 * rw.camera, cx[k], cy[k], o8[2 * k], o8[2 * k + 1], r, J);
+        MarkerCornerResidualJacobian<kDist>(pcc, sn.pc + (size_t)rw.time_block * CC_STRIDE, pcm, sn.intr + 4 * rw.camera, cx[k], cy[k], o8[2 * k], o8[2 * k + 1], r, J, DistOf(sn, rw.camera));
         ss += r[0] * r[0] + r[1] * r[1];
       }
       (void)LossAndScale(sn.loss, ss, &sq);
@@ -730,7 +738,7 @@ k_cov_mc_cross(int nreq, const CovReq* __restrict__ req, CovMcSnap sn, const dou
     }
     for (int k = 0; k < 4; ++k) {
       double r[2], J[36];
-      MarkerCornerResidualJacobian(pcc, sn.pc + (size_t)rw.time_block * CC_STRIDE, pcm, sn.intr + 4 * rw.camera, cx[k], cy[k], o8[2 * k], o8[2 * k + 1], r, J);
+      MarkerCornerResidualJacobian<kDist>(pcc, sn.pc + (size_t)rw.time_block * CC_STRIDE, pcm, sn.intr + 4 * rw.camera, cx[k], cy[k], o8[2 * k], o8[2 * k + 1], r, J, DistOf(sn, rw.camera));
       if (sn.lossy) {
 #pragma unroll
         for (int e = 0; e < 36; ++e) J[e] *= sq;

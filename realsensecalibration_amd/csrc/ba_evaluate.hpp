@@ -149,9 +149,10 @@ k_eval_cam_sum(int C, const double* __restrict__ parts, const unsigned char* __r
 // its J: the rows are not computed because the compiler drops the dead stores after inlining (82 registers against 208; the code
 // object is the check, tools/kernel_resources.py).  wts (nullptr: none): the observations' weights a_i (ceres::ScaledLoss), passed
 // when the loss applies: the cost a_i rho(s), residuals scaled by sqrt(a_i) sqrt(rho'), J'r by its square.
-template <bool kGrad>
+// kDist: dist = the cameras' five distortion coefficients [C][5], indexed as intr (ProjectCorner, ba_math.hpp).
+template <bool kGrad, bool kDist = false>
 __global__ void __launch_bounds__(64)
-k_eval_marker(int N, const EvalMarkerRow* __restrict__ rows, const double* __restrict__ obs8, const double* __restrict__ intr,
+k_eval_marker(int N, const EvalMarkerRow* __restrict__ rows, const double* __restrict__ obs8, typename IntrArg<kDist>::type intr,
               const double* __restrict__ pc, double half_side, double loss, double* __restrict__ residuals,
               double* __restrict__ obs_grad, double* __restrict__ cost_parts, const double* __restrict__ wts = nullptr) {
   const int i = blockIdx.x * 64 + threadIdx.x;
@@ -170,7 +171,7 @@ k_eval_marker(int N, const EvalMarkerRow* __restrict__ rows, const double* __res
       // top-left, top-right, bottom-right, bottom-left (bundle_adjustment.h:92-101)
       const double cx = (k == 0 || k == 3) ? -half_side : half_side, cy = k < 2 ? half_side : -half_side;
       double rk[2], J[36];
-      MarkerCornerResidualJacobian(pcc, pct, pcm, intr + 4 * rw.camera, cx, cy, o8[2 * k], o8[2 * k + 1], rk, J);
+      MarkerCornerResidualJacobian<kDist>(pcc, pct, pcm, IntrOf(intr) + 4 * rw.camera, cx, cy, o8[2 * k], o8[2 * k + 1], rk, J, DistOf(intr, rw.camera));
       ss += rk[0] * rk[0] + rk[1] * rk[1];
       if (residuals != nullptr) { residuals[8 * (size_t)i + 2 * k] = rk[0]; residuals[8 * (size_t)i + 2 * k + 1] = rk[1]; }
       if constexpr (kGrad) {

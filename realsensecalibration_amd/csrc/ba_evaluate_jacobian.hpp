@@ -68,8 +68,10 @@ k_eval_jacobian_points(int N, const EvalJacobianPointRow* __restrict__ rows, con
 // the columns of absent blocks (base, constant) skipped; s is known only after the fourth corner, so with a loss the thread then
 // scales its own 8 x width values in place, as the residual output does: every value is the single rounding of sq * J.
 // wts (nullptr: none): the observations' weights, passed when the loss applies: sq = sqrt(a_i) sqrt(rho').
+// kDist: dist = the cameras' five distortion coefficients [C][5], indexed as intr.
+template <bool kDist = false>
 __global__ void __launch_bounds__(64)
-k_eval_jacobian_marker(int N, const EvalMarkerRow* __restrict__ rows, const double* __restrict__ obs8, const double* __restrict__ intr,
+k_eval_jacobian_marker(int N, const EvalMarkerRow* __restrict__ rows, const double* __restrict__ obs8, typename IntrArg<kDist>::type intr,
                        const double* __restrict__ pc, const int64_t* __restrict__ off, const unsigned char* __restrict__ live,
                        double half_side, double loss, double* __restrict__ values, const double* __restrict__ wts = nullptr) {
   const int i = blockIdx.x * 64 + threadIdx.x;
@@ -90,7 +92,7 @@ k_eval_jacobian_marker(int N, const EvalMarkerRow* __restrict__ rows, const doub
     // top-left, top-right, bottom-right, bottom-left (bundle_adjustment.h:92-101)
     const double cx = (k == 0 || k == 3) ? -half_side : half_side, cy = k < 2 ? half_side : -half_side;
     double rk[2], J[36];
-    MarkerCornerResidualJacobian(pcc, pct, pcm, intr + 4 * rw.camera, cx, cy, o8[2 * k], o8[2 * k + 1], rk, J);
+    MarkerCornerResidualJacobian<kDist>(pcc, pct, pcm, IntrOf(intr) + 4 * rw.camera, cx, cy, o8[2 * k], o8[2 * k + 1], rk, J, DistOf(intr, rw.camera));
     ss += rk[0] * rk[0] + rk[1] * rk[1];
     double* d = v + 2 * k * w;
 #pragma unroll

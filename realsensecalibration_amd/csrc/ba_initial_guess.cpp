@@ -12,8 +12,12 @@
 //                                        the repository; 3.x/4.x epnp.cpp are the same algorithm): the restatement is
 //                                        anchored on the reference's own output, the camera rows of the committed
 //                                        Common/Correspondence/hongo/correspondence.txt (tests/test_initial_guess.py).
-//                                        Zero lens distortion only (the committed intrinsics carry zeros; undistortPoints
-//                                        followed by epnp's re-projection with K is then the identity on the pixels).
+//                                        It sees pinhole pixels: detections of a lens with distortion coefficients go
+//                                        through UndistortPoints first (correspondencer.h does so); with zero coefficients
+//                                        that is the identity on the pixels, bit for bit.
+//   UndistortPoints                      cv::undistortPoints(src, dst, K, dist, noArray(), K) for the five-coefficient model:
+//                                        distorted pixels -> pixels of the ideal pinhole camera with the same K, by fixed-point
+//                                        iteration on the normalised point.  No digit-for-digit claim against OpenCV.
 //
 // Host code, double precision, no device work: the problem sizes are a few hundred points per camera.
 #include <algorithm>
@@ -412,8 +416,64 @@ int InitialCameraPoses(rsba_problem* p) {
   for (int c = 1; c < C; ++c) {
     const int n = (int)(img[c].size() / 2);
     if (n < 4) return RSBA_ERR_FORMAT;   // "The correspondence points are too few." (:185-190)
+    if (p->has_distortion()) {   // cv::solvePnP's distCoeffs: EPnP sees the pixels of the ideal pinhole camera
+      const int ru = UndistortPoints(n, img[c].data(), &p->intrinsics[4 * (size_t)c], &p->distortion[5 * (size_t)c], img[c].data());
+      if (ru != RSBA_OK) return ru;
+    }
     const int rc = SolvePnPEPnP(n, obj[c].data(), img[c].data(), &p->intrinsics[4 * (size_t)c], &p->parameters[6 * (size_t)c]);
     if (rc != RSBA_OK) return rc;
+  }
+  return RSBA_OK;
+}
+
+// Distorted pixel coordinates (u, v) -> pixel coordinates of the ideal pinhole camera with the same intrinsics, n points, 2 doubles
+// each; out may be image_points.  dist5 = k1 k2 p1 p2 k3 (OpenCV).  The normalised point solves
+//   x = (xd - 2 p1 x y - p2 (r2 + 2 x^2)) / rad(r2),   y = (yd - p1 (r2 + 2 y^2) - 2 p2 x y) / rad(r2)
+// by fixed-point iteration from (xd, yd): until the update of both coordinates is below 1e-14, at most 50 iterations.  The error
+// behind an update u is up to u c / (1 - c) with the map's contraction c (0.4 .. 0.5 at the image corners of a k1 = -0.3 lens): 1e-14 on
+// the normalised point is still 6e-12 px at fx = 600, so up to four more steps are taken after the test is met (until nothing
+// moves) and leave rounding only (2e-13 px).  A point that does not get there (coefficients too strong for the point's radius: the map is no contraction,
+// or rad <= 0) returns RSBA_ERR_UNSUPPORTED and leaves out as it was for that and the later points.  All-zero coefficients
+// copy the input's bits.
+int UndistortPoints(int32_t n, const double* image_points, const double* intrinsics4, const double* dist5, double* out) {
+  if (n < 0 || (n > 0 && (!image_points || !out)) || !intrinsics4 || !dist5) return RSBA_ERR_ARG;
+  const double fx = intrinsics4[0], fy = intrinsics4[1], ppx = intrinsics4[2], ppy = intrinsics4[3];
+  if (!(fx != 0.0) || !(fy != 0.0) || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(ppx) || !std::isfinite(ppy)) return RSBA_ERR_ARG;
+  bool any = false;
+  for (int i = 0; i < 5; ++i) { if (!std::isfinite(dist5[i])) return RSBA_ERR_ARG; any = any || dist5[i] != 0.0; }
+  if (!any) {
+    if (out != image_points) for (int64_t i = 0; i < 2 * (int64_t)n; ++i) out[i] = image_points[i];
+    return RSBA_OK;
+  }
+  const double k1 = dist5[0], k2 = dist5[1], p1 = dist5[2], p2 = dist5[3], k3 = dist5[4];
+  for (int32_t i = 0; i < n; ++i) {
+    const double xd = (image_points[2 * i] - ppx) / fx, yd = (image_points[2 * i + 1] - ppy) / fy;
+    double x = xd, y = yd;
+    auto step = [&](double* xn, double* yn) {
+      const double r2 = x * x + y * y;
+      const double rad = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3));
+      if (!(rad > 0.0)) return false;
+      *xn = (xd - (2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x))) / rad;
+      *yn = (yd - (p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y)) / rad;
+      return std::isfinite(*xn) && std::isfinite(*yn);
+    };
+    bool done = false;
+    for (int it = 0; it < 50 && !done; ++it) {
+      double xn, yn;
+      if (!step(&xn, &yn)) return RSBA_ERR_UNSUPPORTED;
+      done = std::fabs(xn - x) < 1e-14 && std::fabs(yn - y) < 1e-14;
+      x = xn; y = yn;
+    }
+    if (!done) return RSBA_ERR_UNSUPPORTED;
+    for (int polish = 0; polish < 4; ++polish) {
+      double xn, yn;
+      if (!step(&xn, &yn)) return RSBA_ERR_UNSUPPORTED;
+      const bool same = xn == x && yn == y;
+      x = xn; y = yn;
+      if (same) break;
+    }
+    out[2 * i] = fx * x + ppx;
+    out[2 * i + 1] = fy * y + ppy;
   }
   return RSBA_OK;
 }

@@ -89,9 +89,11 @@ struct MarkerObs {
 // sumsq_per_obs keeps the raw s (the RMS metric).  loss: the signed parameter of LossAndScale (0: rho(s) = s).  wts: the blocks'
 // weights a_i (ceres::ScaledLoss), the problem's order: the cost a_i rho(s), the rows scaled by sqrt(a_i rho'(s)) — formed as
 // sqrt(a_i) sqrt(rho'), so a weight of one changes no bit and a weight of zero leaves exact zeros.
-template <bool kLoss>
+// kDist: dist = the cameras' five distortion coefficients [C][5], indexed as intr; the dual-number pass runs DistortNormalised
+// (ba_math.hpp) on the normalised point, the value pass ProjectCorner's residuals.
+template <bool kLoss, bool kDist = false>
 __global__ void __launch_bounds__(64) k_marker_eval(int N, const MarkerObs* __restrict__ mo, const double* __restrict__ obs8,
-                              const double* __restrict__ params, const double* __restrict__ intr, double half_side,
+                              const double* __restrict__ params, typename IntrArg<kDist>::type intr, double half_side,
                               int with_jacobian, double* __restrict__ Jbuf, double* __restrict__ rbuf,
                               double* __restrict__ sumsq_per_obs, double loss = 0.0, double* __restrict__ rho_per_obs = nullptr,
                               const double* __restrict__ wts = nullptr) {
@@ -102,7 +104,7 @@ __global__ void __launch_bounds__(64) k_marker_eval(int N, const MarkerObs* __re
   const bool live = i < N;
   const int ii = live ? i : N - 1;   // lanes past the end keep going for the barriers, on the last block's data
   const MarkerObs o = mo[ii];
-  const double fx = intr[4 * o.camera], fy = intr[4 * o.camera + 1], ppx = intr[4 * o.camera + 2], ppy = intr[4 * o.camera + 3];
+  const double fx = IntrOf(intr)[4 * o.camera], fy = IntrOf(intr)[4 * o.camera + 1], ppx = IntrOf(intr)[4 * o.camera + 2], ppy = IntrOf(intr)[4 * o.camera + 3];
   const double cx[4] = {-half_side, half_side, half_side, -half_side};
   const double cy[4] = {half_side, half_side, -half_side, -half_side};
   double ss = 0.0;
@@ -112,8 +114,9 @@ __global__ void __launch_bounds__(64) k_marker_eval(int N, const MarkerObs* __re
       if (o.full_marker >= 0) { const double* m = params + o.full_marker; RotateD(m, p); p[0] += m[3]; p[1] += m[4]; p[2] += m[5]; }
       { const double* t = params + o.full_time; RotateD(t, p); p[0] += t[3]; p[1] += t[4]; p[2] += t[5]; }
       if (o.full_cam >= 0) { const double* c = params + o.full_cam; RotateD(c, p); p[0] += c[3]; p[1] += c[4]; p[2] += c[5]; }
-      const double r0 = fx * p[0] / p[2] + ppx - obs8[8 * (size_t)ii + 2 * k];
-      const double r1 = fy * p[1] / p[2] + ppy - obs8[8 * (size_t)ii + 2 * k + 1];
+      double r0, r1;
+      ProjectCornerResidual<kDist>(p[0], p[1], p[2], fx, fy, ppx, ppy, DistOf(intr, o.camera),
+                                   obs8[8 * (size_t)ii + 2 * k], obs8[8 * (size_t)ii + 2 * k + 1], &r0, &r1);
       ss += r0 * r0 + r1 * r1;
     }
   } else {
@@ -129,8 +132,17 @@ __global__ void __launch_bounds__(64) k_marker_eval(int N, const MarkerObs* __re
       if (o.full_marker >= 0) { RotateJet<18>(mar, p); p[0] = p[0] + mar[3]; p[1] = p[1] + mar[4]; p[2] = p[2] + mar[5]; }
       RotateJet<18>(tim, p); p[0] = p[0] + tim[3]; p[1] = p[1] + tim[4]; p[2] = p[2] + tim[5];
       if (o.full_cam >= 0) { RotateJet<18>(cam, p); p[0] = p[0] + cam[3]; p[1] = p[1] + cam[4]; p[2] = p[2] + cam[5]; }
-      const J xp = JConst<18>(fx) * p[0] / p[2] + JConst<18>(ppx);
-      const J yp = JConst<18>(fy) * p[1] / p[2] + JConst<18>(ppy);
+      J xp, yp;
+      if constexpr (kDist) {
+        J kd[5], xd, yd;
+        for (int q = 0; q < 5; ++q) kd[q] = JConst<18>(DistOf(intr, o.camera)[q]);
+        DistortNormalised(p[0] / p[2], p[1] / p[2], kd, JConst<18>(1.0), JConst<18>(2.0), &xd, &yd);
+        xp = JConst<18>(fx) * xd + JConst<18>(ppx);
+        yp = JConst<18>(fy) * yd + JConst<18>(ppy);
+      } else {
+        xp = JConst<18>(fx) * p[0] / p[2] + JConst<18>(ppx);
+        yp = JConst<18>(fy) * p[1] / p[2] + JConst<18>(ppy);
+      }
       const double r0 = xp.a - obs8[8 * (size_t)ii + 2 * k], r1 = yp.a - obs8[8 * (size_t)ii + 2 * k + 1];
       if (live) { rbuf[8 * (size_t)i + 2 * k] = r0; rbuf[8 * (size_t)i + 2 * k + 1] = r1; }
       for (int q = 0; q < 18; ++q) { stage[threadIdx.x * 37 + q] = xp.v[q]; stage[threadIdx.x * 37 + 18 + q] = yp.v[q]; }
@@ -305,9 +317,11 @@ struct MarkerDevice {
   double* wts = nullptr;    // [N] the blocks' weights, the problem's order (with_loss only; all ones when the problem had none)
   int* act_to_full = nullptr;
   int cur = 0;
+  bool with_dist = false;   // the kDist instances (Upload): some distortion coefficient of the problem is not zero
+  double* dist = nullptr;   // [C][5], indexed as intr
 
   void Free() {
-    void* ptrs[] = {mo, obs8, intr, params[0], params[1], params0, Jbuf, rbuf, ss_x, ss_c, A, scale, grad, delta, res, act_to_full, rho_x, rho_c, wts};
+    void* ptrs[] = {mo, obs8, intr, params[0], params[1], params0, Jbuf, rbuf, ss_x, ss_c, A, scale, grad, delta, res, act_to_full, rho_x, rho_c, wts, dist};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     mo = nullptr;
   }
@@ -345,6 +359,9 @@ struct MarkerDevice {
     if (hipMemcpy(intr, p.intrinsics.data(), p.intrinsics.size() * 8, hipMemcpyHostToDevice) != hipSuccess) return RSBA_ERR_HIP;
     if (hipMemcpy(params0, p.parameters.data(), nfull * 8, hipMemcpyHostToDevice) != hipSuccess) return RSBA_ERR_HIP;
     if (hipMemcpy(act_to_full, a2f.data(), n * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return RSBA_ERR_HIP;
+    with_dist = p.has_distortion();
+    if (with_dist && (!al((void**)&dist, p.distortion.size() * 8) ||
+                      hipMemcpy(dist, p.distortion.data(), p.distortion.size() * 8, hipMemcpyHostToDevice) != hipSuccess)) return RSBA_ERR_HIP;
     if (with_loss) {
       if (!al((void**)&wts, (size_t)N * 8)) return RSBA_ERR_HIP;
       const std::vector<double> ones(p.observation_weights.empty() ? (size_t)N : 0, 1.0);
@@ -381,7 +398,10 @@ struct MarkerDevice {
     };
     if (!chk("(before marker step)")) return RSBA_ERR_HIP;
     T.Begin("k_marker_eval", st);
-    if (with_loss) k_marker_eval<true><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[x], intr, half_side, 1, Jbuf, rbuf, ss_x, loss, rho_x, wts);
+    if (with_dist) {
+      if (with_loss) k_marker_eval<true, true><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[x], IntrDist{intr, dist}, half_side, 1, Jbuf, rbuf, ss_x, loss, rho_x, wts);
+      else k_marker_eval<false, true><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[x], IntrDist{intr, dist}, half_side, 1, Jbuf, rbuf, ss_x);
+    } else if (with_loss) k_marker_eval<true><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[x], intr, half_side, 1, Jbuf, rbuf, ss_x, loss, rho_x, wts);
     else k_marker_eval<false><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[x], intr, half_side, 1, Jbuf, rbuf, ss_x);
     T.End(st);
     if (!chk("k_marker_eval")) return RSBA_ERR_HIP;
@@ -398,7 +418,10 @@ struct MarkerDevice {
     T.End(st);
     if (!chk("k_marker_system")) return RSBA_ERR_HIP;
     T.Begin("k_marker_eval", st);
-    if (with_loss) k_marker_eval<true><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[c], intr, half_side, 0, nullptr, nullptr, ss_c, loss, rho_c, wts);
+    if (with_dist) {
+      if (with_loss) k_marker_eval<true, true><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[c], IntrDist{intr, dist}, half_side, 0, nullptr, nullptr, ss_c, loss, rho_c, wts);
+      else k_marker_eval<false, true><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[c], IntrDist{intr, dist}, half_side, 0, nullptr, nullptr, ss_c);
+    } else if (with_loss) k_marker_eval<true><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[c], intr, half_side, 0, nullptr, nullptr, ss_c, loss, rho_c, wts);
     else k_marker_eval<false><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[c], intr, half_side, 0, nullptr, nullptr, ss_c);
     T.End(st);
     T.Begin("k_marker_candidate", st);
@@ -412,7 +435,8 @@ struct MarkerDevice {
   }
   int SumSquares(hipStream_t st, double* out) {
     if (Reset(st) != RSBA_OK) return RSBA_ERR_HIP;
-    k_marker_eval<false><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[0], intr, half_side, 0, nullptr, nullptr, ss_x);
+    if (with_dist) k_marker_eval<false, true><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[0], IntrDist{intr, dist}, half_side, 0, nullptr, nullptr, ss_x);
+    else k_marker_eval<false><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[0], intr, half_side, 0, nullptr, nullptr, ss_x);
     std::vector<double> h(N);
     if (hipMemcpyAsync(h.data(), ss_x, N * 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return RSBA_ERR_HIP;
     double s = 0; for (double v : h) s += v;

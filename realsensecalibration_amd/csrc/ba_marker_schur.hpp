@@ -164,6 +164,15 @@ struct ElimArgs {
   const int* __restrict__ tconst;      // [T]
   int pmax;                            // the widest pose cache (free + pose-only slots); dmax stays the widest free part
 };
+// the kDist instances' argument: the same and the cameras' distortion coefficients [C][5], indexed as intr
+struct ElimArgsDist : ElimArgs { const double* __restrict__ dist; };
+template <bool kDist> struct ElimArgT { typedef ElimArgs type; };
+template <> struct ElimArgT<true> { typedef ElimArgsDist type; };
+__device__ __forceinline__ const double* DistOf(const ElimArgs&, int) { return nullptr; }
+__device__ __forceinline__ const double* DistOf(const ElimArgsDist& a, int camera) { return a.dist + 5 * camera; }
+
+// the kernel instances with (D = true) or without lens distortion, by the device's with_dist
+#define RSBA_DIST_SWITCH(...) do { if (with_dist) { constexpr bool D = true; __VA_ARGS__; } else { constexpr bool D = false; __VA_ARGS__; } } while (0)
 
 #ifdef RSBA_PROFILE_PHASES
 __device__ long long g_mt_cycles[16];
@@ -182,9 +191,9 @@ __device__ __forceinline__ int LocalColumn(int slot, int q, int sc, int sm) { re
 // eliminates it with E = 0 (infinitely stiff): no step, no W'EW, its rows still add U and g_r.
 __device__ __forceinline__ int ConstSlotPose(int slot, int nslot) { return nslot - 2 - slot; }
 
-template <bool kLdsS, bool kConst = false>
+template <bool kLdsS, bool kConst = false, bool kDist = false>
 __global__ void __launch_bounds__(RSBA_MT_THREADS)
-k_time_eliminate(ElimArgs a) {
+k_time_eliminate(typename ElimArgT<kDist>::type a) {
   extern __shared__ double lds[];
   const int tid = threadIdx.x, nr = a.nr, dmax = a.dmax;
   const PartLayout RL{nr};
@@ -263,6 +272,7 @@ k_time_eliminate(ElimArgs a) {
         const int slot_cam = nsc, slot_marker = nsm;
         const double* in = a.intr + 4 * ncam;   // a handful of cameras per chunk: from the L1
         const double u = nu, v = nv, fx = in[0], fy = in[1], ppx = in[2], ppy = in[3];
+        const double* ds = DistOf(a, ncam);
         fetch(b0 + nb);
         if (sb_i < RSBA_ABL_STAGE * nb) {
           const double hs = a.half_side;
@@ -272,8 +282,8 @@ k_time_eliminate(ElimArgs a) {
             if (kConst && slot <= -2) return pcl + (size_t)(1 + ConstSlotPose(slot, nslot)) * CC_STRIDE;
             return nullptr;
           };
-          MarkerCornerJacobianPart(sp, pose_of(slot_cam), pcl, pose_of(slot_marker),
-                                   fx, fy, ppx, ppy, cx, cy, u, v, rt + sb_i * 8 + 2 * sk, Jt + sb_i * RSBA_MT_JLD + 36 * sk);
+          MarkerCornerJacobianPart<kDist>(sp, pose_of(slot_cam), pcl, pose_of(slot_marker),
+                                          fx, fy, ppx, ppy, cx, cy, u, v, rt + sb_i * 8 + 2 * sk, Jt + sb_i * RSBA_MT_JLD + 36 * sk, ds);
           if (sp == 0 && sk == 0) { sl[2 * sb_i] = slot_cam; sl[2 * sb_i + 1] = slot_marker; }
         }
       }
@@ -815,10 +825,10 @@ k_marker_chol_finish(int nr, const double* __restrict__ red, double* __restrict_
 // kLoss: the rows scaled by sqrt(rho') at x (wsq, k_mc_block_weight); the candidate's raw sum as without a loss, the workgroup's
 // a rho(s_c) - s_c (wts: the blocks' weights, the device's time order) to drho_c[blockIdx.x] (k_marker_schur_finish<true>).
 // kConst: a constant time (tconst[t]) takes a zero step (E = 0) and its |x_t|^2 stays out of the candidate's norm.
-template <bool kLoss, bool kConst = false>
+template <bool kLoss, bool kConst = false, bool kDist = false>
 __global__ void __launch_bounds__(256)
 k_time_backsub_terms(int T, const int* __restrict__ time_ptr, const int* __restrict__ time_full, const TimeSlots* __restrict__ ts,
-                     const MarkerObs* __restrict__ mo, const double* __restrict__ obs8, const double* __restrict__ intr, double half_side,
+                     const MarkerObs* __restrict__ mo, const double* __restrict__ obs8, typename IntrArg<kDist>::type intr, double half_side,
                      const double* __restrict__ posec /* pose constants at x */, const double* __restrict__ tdata,
                      const double* __restrict__ delta_r, const double* __restrict__ params_x, double* __restrict__ params_c,
                      double* __restrict__ delta_t, double* __restrict__ bpart /* gridDim.x x 4 */, double loss = 0.0,
@@ -845,8 +855,8 @@ k_time_backsub_terms(int T, const int* __restrict__ time_ptr, const int* __restr
 #pragma unroll 1
       for (int k = 0; k < 4; ++k) {
         double rr[2], Jc[36];
-        MarkerCornerResidualJacobian(pcc, pct, pcm, intr + 4 * o.camera, (k == 0 || k == 3) ? -half_side : half_side, k < 2 ? half_side : -half_side,
-                                     obs8[8 * (size_t)i + 2 * k], obs8[8 * (size_t)i + 2 * k + 1], rr, Jc);
+        MarkerCornerResidualJacobian<kDist>(pcc, pct, pcm, IntrOf(intr) + 4 * o.camera, (k == 0 || k == 3) ? -half_side : half_side, k < 2 ? half_side : -half_side,
+                                            obs8[8 * (size_t)i + 2 * k], obs8[8 * (size_t)i + 2 * k + 1], rr, Jc, DistOf(intr, o.camera));
         if constexpr (kLoss) {
           const double w = wsq[i];
 #pragma unroll
@@ -905,8 +915,8 @@ k_time_backsub_terms(int T, const int* __restrict__ time_ptr, const int* __restr
 #pragma unroll 1
         for (int k = 0; k < 4; ++k) {
           double rr[2], Jc[36];
-          MarkerCornerResidualJacobian(pcc, pct, pcm, intr + 4 * o.camera, (k == 0 || k == 3) ? -half_side : half_side, k < 2 ? half_side : -half_side,
-                                       obs8[8 * (size_t)i + 2 * k], obs8[8 * (size_t)i + 2 * k + 1], rr, Jc);
+          MarkerCornerResidualJacobian<kDist>(pcc, pct, pcm, IntrOf(intr) + 4 * o.camera, (k == 0 || k == 3) ? -half_side : half_side, k < 2 ? half_side : -half_side,
+                                              obs8[8 * (size_t)i + 2 * k], obs8[8 * (size_t)i + 2 * k + 1], rr, Jc, DistOf(intr, o.camera));
           if constexpr (kLoss) {
             const double w = wsq[i];
             rr[0] *= w; rr[1] *= w;
@@ -923,15 +933,16 @@ k_time_backsub_terms(int T, const int* __restrict__ time_ptr, const int* __restr
         }
       }
       // candidate residuals: cameras and markers of the candidate are in params_c already (reduced solve), the time here
-      const double fx = intr[4 * o.camera], fy = intr[4 * o.camera + 1], ppx = intr[4 * o.camera + 2], ppy = intr[4 * o.camera + 3];
+      const double fx = IntrOf(intr)[4 * o.camera], fy = IntrOf(intr)[4 * o.camera + 1], ppx = IntrOf(intr)[4 * o.camera + 2], ppy = IntrOf(intr)[4 * o.camera + 3];
       double sb = 0.0;   // (kLoss: the block's s_c)
       for (int k = 0; k < 4; ++k) {
         double pt[3] = {cx[k], cy[k], 0.0};
         if (o.full_marker >= 0) { const double* m = params_c + o.full_marker; RotateD(m, pt); pt[0] += m[3]; pt[1] += m[4]; pt[2] += m[5]; }
         RotateD(tc, pt); pt[0] += tc[3]; pt[1] += tc[4]; pt[2] += tc[5];
         if (o.full_cam >= 0) { const double* c = params_c + o.full_cam; RotateD(c, pt); pt[0] += c[3]; pt[1] += c[4]; pt[2] += c[5]; }
-        const double r0 = fx * pt[0] / pt[2] + ppx - obs8[8 * (size_t)i + 2 * k];
-        const double r1 = fy * pt[1] / pt[2] + ppy - obs8[8 * (size_t)i + 2 * k + 1];
+        double r0, r1;
+        ProjectCornerResidual<kDist>(pt[0], pt[1], pt[2], fx, fy, ppx, ppy, DistOf(intr, o.camera),
+                                     obs8[8 * (size_t)i + 2 * k], obs8[8 * (size_t)i + 2 * k + 1], &r0, &r1);
         cc += r0 * r0 + r1 * r1;
         if constexpr (kLoss) sb += r0 * r0 + r1 * r1;
       }
@@ -979,10 +990,11 @@ __global__ void __launch_bounds__(64) k_pose_constants_reduced(int nred_poses, c
 // Sums in a fixed order: lanes by butterfly, the four wavefronts in order.  bpart: one entry (4 doubles) per time.
 // kConst: the time's constant camera / marker blocks as pose-only slots behind the free ones (cs_ptr / cs_full: ElimArgs); their
 // candidate is their pose at x.
-template <int kPer, int kThreads, bool kConst = false>
-__global__ void __launch_bounds__(kThreads)
+// kDist: held to its sibling's two wavefronts a SIMD (256 registers; it would take 258) by the launch bounds' second argument (0: not set).
+template <int kPer, int kThreads, bool kConst = false, bool kDist = false>
+__global__ void __launch_bounds__(kThreads, kDist ? 2 : 0)
 k_time_backsub_wg(int T, const int* __restrict__ time_ptr, const int* __restrict__ time_full, const TimeSlots* __restrict__ ts,
-                  const MarkerObs* __restrict__ mo, const double* __restrict__ obs8, const double* __restrict__ intr, double half_side,
+                  const MarkerObs* __restrict__ mo, const double* __restrict__ obs8, typename IntrArg<kDist>::type intr, double half_side,
                   const double* __restrict__ posec /* pose constants at x */, const double* __restrict__ posec_c /* candidate: cameras, markers */,
                   const double* __restrict__ tdata, const double* __restrict__ delta_r, const double* __restrict__ params_x,
                   double* __restrict__ params_c, double* __restrict__ delta_t, double* __restrict__ bpart /* T x 4 */,
@@ -1058,8 +1070,8 @@ k_time_backsub_wg(int T, const int* __restrict__ time_ptr, const int* __restrict
       const double* pcm = sl.slot_marker >= 0 ? s_pc + (size_t)(1 + sl.slot_marker) * CC_STRIDE
                           : (kConst && sl.slot_marker <= -2 ? s_pc + (size_t)(1 + ConstSlotPose(sl.slot_marker, nslot)) * CC_STRIDE : nullptr);
       double rr[2], Jc[36];
-      MarkerCornerResidualJacobian(pcc, pct, pcm, intr + 4 * sl.camera, (k == 0 || k == 3) ? -half_side : half_side, k < 2 ? half_side : -half_side,
-                                   obs8[8 * (size_t)i + 2 * k], obs8[8 * (size_t)i + 2 * k + 1], rr, Jc);
+      MarkerCornerResidualJacobian<kDist>(pcc, pct, pcm, IntrOf(intr) + 4 * sl.camera, (k == 0 || k == 3) ? -half_side : half_side, k < 2 ? half_side : -half_side,
+                                          obs8[8 * (size_t)i + 2 * k], obs8[8 * (size_t)i + 2 * k + 1], rr, Jc, DistOf(intr, sl.camera));
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
         double m = 0.0;
@@ -1139,7 +1151,7 @@ k_time_backsub_wg(int T, const int* __restrict__ time_ptr, const int* __restrict
     if (e < ncorner) {
       const int i = o0 + (e >> 2), k = e & 3;
       const TimeSlots sl = ts[i];
-      const double fx = intr[4 * sl.camera], fy = intr[4 * sl.camera + 1], ppx = intr[4 * sl.camera + 2], ppy = intr[4 * sl.camera + 3];
+      const double fx = IntrOf(intr)[4 * sl.camera], fy = IntrOf(intr)[4 * sl.camera + 1], ppx = IntrOf(intr)[4 * sl.camera + 2], ppy = IntrOf(intr)[4 * sl.camera + 3];
       double pt[3] = {(k == 0 || k == 3) ? -half_side : half_side, k < 2 ? half_side : -half_side, 0.0};
       auto apply = [&](const double* R, const double* tr) {
         const double a0 = R[0] * pt[0] + R[1] * pt[1] + R[2] * pt[2], a1 = R[3] * pt[0] + R[4] * pt[1] + R[5] * pt[2], a2 = R[6] * pt[0] + R[7] * pt[1] + R[8] * pt[2];
@@ -1150,8 +1162,9 @@ k_time_backsub_wg(int T, const int* __restrict__ time_ptr, const int* __restrict
       apply(Rt, tc + 3);
       if (sl.slot_cam >= 0) { const double* pc = s_cd + 12 * sl.slot_cam; apply(pc, pc + 9); }
       else if (kConst && sl.slot_cam <= -2) { const double* pc = s_cd + 12 * ConstSlotPose(sl.slot_cam, nslot); apply(pc, pc + 9); }
-      const double r0 = fx * pt[0] / pt[2] + ppx - obs8[8 * (size_t)i + 2 * k];
-      const double r1 = fy * pt[1] / pt[2] + ppy - obs8[8 * (size_t)i + 2 * k + 1];
+      double r0, r1;
+      ProjectCornerResidual<kDist>(pt[0], pt[1], pt[2], fx, fy, ppx, ppy, DistOf(intr, sl.camera),
+                                   obs8[8 * (size_t)i + 2 * k], obs8[8 * (size_t)i + 2 * k + 1], &r0, &r1);
       cc += r0 * r0 + r1 * r1;
     }
   }
@@ -1264,12 +1277,15 @@ struct MarkerSchurDevice {
   int pmax = 0;         // widest pose cache of a time: its free slots and its pose-only (constant) slots
   int ncpose = 0;       // constant camera / marker poses some residual applies
   int *cs_ptr = nullptr, *cs_full = nullptr, *tconst = nullptr, *cpose_full = nullptr;
+  // lens distortion (Upload): the kDist instances run when some coefficient of the problem is not zero; no path rule reads it
+  bool with_dist = false;
+  double* dist = nullptr;   // [C][5], indexed as intr
 
   void Free() {
     void* ptrs[] = {mo, ts, chunk_ptr, time_ptr, slot_ptr, slot_col, time_full, col_full, ok_flag, obs8, intr, params[0], params[1],
                     params0, posec, posec_c, ss_x, scale_t, scale_r, tdata, part, red, A, Wm, delta_r, delta_t, bp_time, solve_out, res, tc_flags, tc_hand, tc_map,
                     slot_order, slot_time, sb_ptr, sb_blk, xi_ptr, xi_blk, xi_cc, xi_cm, xc_ptr, sp, xout, tscal, blk_time, x_order, wsq, drho, drho_c, wts,
-                    cs_ptr, cs_full, tconst, cpose_full};
+                    cs_ptr, cs_full, tconst, cpose_full, dist};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     mo = nullptr; ts = nullptr;
     for (auto& q : fork_s) if (q) { (void)hipStreamDestroy(q); q = nullptr; }
@@ -1536,6 +1552,8 @@ struct MarkerSchurDevice {
         !up(params0, p.parameters.data(), nfull * 8))
       return RSBA_ERR_HIP;
     if (hipMemset(res, 0, RES_SIZE * 8) != hipSuccess) return RSBA_ERR_HIP;
+    with_dist = p.has_distortion();
+    if (with_dist && (!al((void**)&dist, p.distortion.size() * 8) || !up(dist, p.distortion.data(), p.distortion.size() * 8))) return RSBA_ERR_HIP;
     if (has_const) {
       std::vector<int> cpf(6 * (size_t)ncpose, 0);   // (k_pose_constants_reduced's layout: a pose's offset at every sixth entry)
       for (int k = 0; k < ncpose; ++k) cpf[6 * (size_t)k] = hcpose[k];
@@ -1577,13 +1595,16 @@ struct MarkerSchurDevice {
     }
     if (backsub_wg) {
       const size_t lds_bw = (size_t)(pmax + 1) * (CC_STRIDE + 12 + 6) * sizeof(double);
-      if (lds_bw > 48 * 1024 && hipFuncSetAttribute(has_const ? (const void*)k_time_backsub_wg<2, 256, true> : (const void*)k_time_backsub_wg<2, 256>,
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bw) != hipSuccess) return RSBA_ERR_HIP;
+      const void* kbw = nullptr;
+      RSBA_DIST_SWITCH(kbw = has_const ? (const void*)k_time_backsub_wg<2, 256, true, D> : (const void*)k_time_backsub_wg<2, 256, false, D>);
+      if (lds_bw > 48 * 1024 && hipFuncSetAttribute(kbw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bw) != hipSuccess) return RSBA_ERR_HIP;
     }
-    if (!split && lds_elim > 48 * 1024 &&
-        hipFuncSetAttribute(has_const ? (lds_s ? (const void*)k_time_eliminate<true, true> : (const void*)k_time_eliminate<false, true>)
-                                      : (lds_s ? (const void*)k_time_eliminate<true> : (const void*)k_time_eliminate<false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_elim) != hipSuccess) return RSBA_ERR_HIP;
+    if (!split && lds_elim > 48 * 1024) {
+      const void* kel = nullptr;
+      RSBA_DIST_SWITCH(kel = has_const ? (lds_s ? (const void*)k_time_eliminate<true, true, D> : (const void*)k_time_eliminate<false, true, D>)
+                                       : (lds_s ? (const void*)k_time_eliminate<true, false, D> : (const void*)k_time_eliminate<false, false, D>));
+      if (hipFuncSetAttribute(kel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_elim) != hipSuccess) return RSBA_ERR_HIP;
+    }
     if (nr == 0) {
       // (no reduced solve)
     } else if (nr <= RSBA_CHOL_MAXN) {
@@ -1658,13 +1679,17 @@ struct MarkerSchurDevice {
     Tm.End(st);
     ElimArgs ea{nr, dmax, (int)N, chunk_ptr, time_ptr, slot_ptr, slot_col, time_full, col_full, ts, mo, obs8, intr, posec, half_side, params[x], scale_t, tdata, part, ip,
                 cs_ptr, cs_full, tconst, pmax};
+    ElimArgsDist ead; static_cast<ElimArgs&>(ead) = ea; ead.dist = dist;
+    auto elim_args = [&](auto d) -> const typename ElimArgT<decltype(d)::value>::type& { if constexpr (decltype(d)::value) return ead; else return ea; };
     if (split) {
       SplitArgs sa{nslots, T, nx, ncam_cols, nx_threads, slot_order, x_order, slot_time, slot_col, sb_ptr, sb_blk, time_ptr, time_full, col_full, ts, mo, obs8, intr, posec, half_side,
                    xi_ptr, xi_blk, xi_cc, xi_cm, sp, xout, wsq, drho};
+      SplitArgsDist sad; static_cast<SplitArgs&>(sad) = sa; sad.dist = dist;
+      auto split_args = [&](auto d) -> const typename SplitArgT<decltype(d)::value>::type& { if constexpr (decltype(d)::value) return sad; else return sa; };
       if (with_loss) {
         // the corrector's weights at x, wanted by all three product kernels
         Tm.Begin("k_mc_block_weight", st);
-        k_mc_block_weight<<<(N + 255) / 256, 256, 0, st>>>(N, ts, mo, obs8, intr, half_side, posec, loss, wts, wsq, drho);
+        RSBA_DIST_SWITCH(k_mc_block_weight<D><<<(N + 255) / 256, 256, 0, st>>>(N, ts, mo, obs8, IntrPass<D>(intr, dist), half_side, posec, loss, wts, wsq, drho));
         Tm.End(st);
       }
       // the three product kernels are independent and none fills the chip: side by side on three streams (one after the other
@@ -1677,23 +1702,23 @@ struct MarkerSchurDevice {
       }
       if (nslots > 0) {   // (none: n_r = 0)
         Tm.Begin("k_mc_slot_products", st);
-        if (with_loss) k_mc_slot_products<true><<<(nslots + 255) / 256, 256, 0, st>>>(sa);
-        else k_mc_slot_products<false><<<(nslots + 255) / 256, 256, 0, st>>>(sa);
+        if (with_loss) RSBA_DIST_SWITCH(k_mc_slot_products<true, D><<<(nslots + 255) / 256, 256, 0, st>>>(split_args(std::integral_constant<bool, D>())));
+        else RSBA_DIST_SWITCH(k_mc_slot_products<false, D><<<(nslots + 255) / 256, 256, 0, st>>>(split_args(std::integral_constant<bool, D>())));
         Tm.End(st);
       }
       Tm.Begin("k_mc_time_products", st);
       if (has_const) {
-        if (with_loss) k_mc_time_products<true, true><<<(T + 3) / 4, 256, 0, s_time>>>(sa, ip, params[x], scale_t, tdata, tscal, tconst);
-        else k_mc_time_products<false, true><<<(T + 3) / 4, 256, 0, s_time>>>(sa, ip, params[x], scale_t, tdata, tscal, tconst);
+        if (with_loss) RSBA_DIST_SWITCH(k_mc_time_products<true, true, D><<<(T + 3) / 4, 256, 0, s_time>>>(split_args(std::integral_constant<bool, D>()), ip, params[x], scale_t, tdata, tscal, tconst));
+        else RSBA_DIST_SWITCH(k_mc_time_products<false, true, D><<<(T + 3) / 4, 256, 0, s_time>>>(split_args(std::integral_constant<bool, D>()), ip, params[x], scale_t, tdata, tscal, tconst));
       } else {
-        if (with_loss) k_mc_time_products<true><<<(T + 3) / 4, 256, 0, s_time>>>(sa, ip, params[x], scale_t, tdata, tscal);
-        else k_mc_time_products<false><<<(T + 3) / 4, 256, 0, s_time>>>(sa, ip, params[x], scale_t, tdata, tscal);
+        if (with_loss) RSBA_DIST_SWITCH(k_mc_time_products<true, false, D><<<(T + 3) / 4, 256, 0, s_time>>>(split_args(std::integral_constant<bool, D>()), ip, params[x], scale_t, tdata, tscal));
+        else RSBA_DIST_SWITCH(k_mc_time_products<false, false, D><<<(T + 3) / 4, 256, 0, s_time>>>(split_args(std::integral_constant<bool, D>()), ip, params[x], scale_t, tdata, tscal));
       }
       Tm.End(st);
       if (nx > 0) {
         Tm.Begin("k_mc_cross", st);
-        if (with_loss) k_mc_cross<true><<<(nx_threads + 255) / 256, 256, 0, s_cross>>>(sa);
-        else k_mc_cross<false><<<(nx_threads + 255) / 256, 256, 0, s_cross>>>(sa);
+        if (with_loss) RSBA_DIST_SWITCH(k_mc_cross<true, D><<<(nx_threads + 255) / 256, 256, 0, s_cross>>>(split_args(std::integral_constant<bool, D>())));
+        else RSBA_DIST_SWITCH(k_mc_cross<false, D><<<(nx_threads + 255) / 256, 256, 0, s_cross>>>(split_args(std::integral_constant<bool, D>())));
         Tm.End(st);
       }
       if (fork) {
@@ -1712,10 +1737,10 @@ struct MarkerSchurDevice {
     } else {
       Tm.Begin("k_time_eliminate", st);
       if (has_const) {
-        if (lds_s) k_time_eliminate<true, true><<<G, RSBA_MT_THREADS, lds_elim, st>>>(ea);
-        else k_time_eliminate<false, true><<<G, RSBA_MT_THREADS, lds_elim, st>>>(ea);
-      } else if (lds_s) k_time_eliminate<true><<<G, RSBA_MT_THREADS, lds_elim, st>>>(ea);
-      else k_time_eliminate<false><<<G, RSBA_MT_THREADS, lds_elim, st>>>(ea);
+        if (lds_s) RSBA_DIST_SWITCH(k_time_eliminate<true, true, D><<<G, RSBA_MT_THREADS, lds_elim, st>>>(elim_args(std::integral_constant<bool, D>())));
+        else RSBA_DIST_SWITCH(k_time_eliminate<false, true, D><<<G, RSBA_MT_THREADS, lds_elim, st>>>(elim_args(std::integral_constant<bool, D>())));
+      } else if (lds_s) RSBA_DIST_SWITCH(k_time_eliminate<true, false, D><<<G, RSBA_MT_THREADS, lds_elim, st>>>(elim_args(std::integral_constant<bool, D>())));
+      else RSBA_DIST_SWITCH(k_time_eliminate<false, false, D><<<G, RSBA_MT_THREADS, lds_elim, st>>>(elim_args(std::integral_constant<bool, D>())));
       Tm.End(st);
       if (!chk("k_time_eliminate")) return RSBA_ERR_HIP;
     }
@@ -1766,35 +1791,35 @@ struct MarkerSchurDevice {
       hipStream_t s_cost = fork2 ? fork_s[0] : st;
       if (fork2 && (hipEventRecord(fork_ev[0], st) != hipSuccess || hipStreamWaitEvent(s_cost, fork_ev[0], 0) != hipSuccess)) return RSBA_ERR_HIP;
       if (with_loss) {
-        k_mc_candidate<0, true><<<ncand_wg, 256, 0, st>>>(N, T, ts, mo, obs8, intr, half_side, posec, posec_c, delta_r, delta_t, blk_time, bp_time, loss, wsq, drho_c);
-        k_mc_candidate<1, true><<<ncand_wg, 256, 0, s_cost>>>(N, T, ts, mo, obs8, intr, half_side, posec, posec_c, delta_r, delta_t, blk_time, bp_time, loss, wsq, drho_c, wts);
+        RSBA_DIST_SWITCH(k_mc_candidate<0, true, D><<<ncand_wg, 256, 0, st>>>(N, T, ts, mo, obs8, IntrPass<D>(intr, dist), half_side, posec, posec_c, delta_r, delta_t, blk_time, bp_time, loss, wsq, drho_c));
+        RSBA_DIST_SWITCH(k_mc_candidate<1, true, D><<<ncand_wg, 256, 0, s_cost>>>(N, T, ts, mo, obs8, IntrPass<D>(intr, dist), half_side, posec, posec_c, delta_r, delta_t, blk_time, bp_time, loss, wsq, drho_c, wts));
       } else {
-        k_mc_candidate<0, false><<<ncand_wg, 256, 0, st>>>(N, T, ts, mo, obs8, intr, half_side, posec, posec_c, delta_r, delta_t, blk_time, bp_time);
-        k_mc_candidate<1, false><<<ncand_wg, 256, 0, s_cost>>>(N, T, ts, mo, obs8, intr, half_side, posec, posec_c, delta_r, delta_t, blk_time, bp_time);
+        RSBA_DIST_SWITCH(k_mc_candidate<0, false, D><<<ncand_wg, 256, 0, st>>>(N, T, ts, mo, obs8, IntrPass<D>(intr, dist), half_side, posec, posec_c, delta_r, delta_t, blk_time, bp_time));
+        RSBA_DIST_SWITCH(k_mc_candidate<1, false, D><<<ncand_wg, 256, 0, s_cost>>>(N, T, ts, mo, obs8, IntrPass<D>(intr, dist), half_side, posec, posec_c, delta_r, delta_t, blk_time, bp_time));
       }
       if (fork2 && (hipEventRecord(fork_ev[1], s_cost) != hipSuccess || hipStreamWaitEvent(st, fork_ev[1], 0) != hipSuccess)) return RSBA_ERR_HIP;
     } else if (backsub_wg) {
       if (nr > 0) k_pose_constants_reduced<<<(nr / 6 + 63) / 64, 64, 0, st>>>(nr / 6, col_full, params[c], posec_c);
       const size_t lds_bw = (size_t)(pmax + 1) * (CC_STRIDE + 12 + 6) * sizeof(double);   // the shot's tables (k_time_backsub_wg)
       if (has_const)
-        k_time_backsub_wg<2, 256, true><<<T, 256, lds_bw, st>>>(T, time_ptr, time_full, ts, mo, obs8, intr, half_side, posec, posec_c, tdata, delta_r, params[x],
-                                                           params[c], delta_t, bp_time, slot_ptr, slot_col, col_full, cs_ptr, cs_full, tconst);
+        RSBA_DIST_SWITCH(k_time_backsub_wg<2, 256, true, D><<<T, 256, lds_bw, st>>>(T, time_ptr, time_full, ts, mo, obs8, IntrPass<D>(intr, dist), half_side, posec, posec_c, tdata, delta_r, params[x],
+                                                           params[c], delta_t, bp_time, slot_ptr, slot_col, col_full, cs_ptr, cs_full, tconst));
       else
-        k_time_backsub_wg<2, 256><<<T, 256, lds_bw, st>>>(T, time_ptr, time_full, ts, mo, obs8, intr, half_side, posec, posec_c, tdata, delta_r, params[x],
-                                                     params[c], delta_t, bp_time, slot_ptr, slot_col, col_full);
+        RSBA_DIST_SWITCH(k_time_backsub_wg<2, 256, false, D><<<T, 256, lds_bw, st>>>(T, time_ptr, time_full, ts, mo, obs8, IntrPass<D>(intr, dist), half_side, posec, posec_c, tdata, delta_r, params[x],
+                                                     params[c], delta_t, bp_time, slot_ptr, slot_col, col_full));
     } else {
       if (with_loss && has_const)
-        k_time_backsub_terms<true, true><<<nb_time, 256, 0, st>>>(T, time_ptr, time_full, ts, mo, obs8, intr, half_side, posec, tdata, delta_r, params[x],
-                                                                  params[c], delta_t, bp_time, loss, wsq, drho_c, tconst, wts);
+        RSBA_DIST_SWITCH(k_time_backsub_terms<true, true, D><<<nb_time, 256, 0, st>>>(T, time_ptr, time_full, ts, mo, obs8, IntrPass<D>(intr, dist), half_side, posec, tdata, delta_r, params[x],
+                                                                  params[c], delta_t, bp_time, loss, wsq, drho_c, tconst, wts));
       else if (with_loss)
-        k_time_backsub_terms<true><<<nb_time, 256, 0, st>>>(T, time_ptr, time_full, ts, mo, obs8, intr, half_side, posec, tdata, delta_r, params[x],
-                                                            params[c], delta_t, bp_time, loss, wsq, drho_c, nullptr, wts);
+        RSBA_DIST_SWITCH(k_time_backsub_terms<true, false, D><<<nb_time, 256, 0, st>>>(T, time_ptr, time_full, ts, mo, obs8, IntrPass<D>(intr, dist), half_side, posec, tdata, delta_r, params[x],
+                                                            params[c], delta_t, bp_time, loss, wsq, drho_c, nullptr, wts));
       else if (has_const)
-        k_time_backsub_terms<false, true><<<nb_time, 256, 0, st>>>(T, time_ptr, time_full, ts, mo, obs8, intr, half_side, posec, tdata, delta_r, params[x],
-                                                                   params[c], delta_t, bp_time, 0.0, nullptr, nullptr, tconst);
+        RSBA_DIST_SWITCH(k_time_backsub_terms<false, true, D><<<nb_time, 256, 0, st>>>(T, time_ptr, time_full, ts, mo, obs8, IntrPass<D>(intr, dist), half_side, posec, tdata, delta_r, params[x],
+                                                                   params[c], delta_t, bp_time, 0.0, nullptr, nullptr, tconst));
       else
-        k_time_backsub_terms<false><<<nb_time, 256, 0, st>>>(T, time_ptr, time_full, ts, mo, obs8, intr, half_side, posec, tdata, delta_r, params[x],
-                                                             params[c], delta_t, bp_time);
+        RSBA_DIST_SWITCH(k_time_backsub_terms<false, false, D><<<nb_time, 256, 0, st>>>(T, time_ptr, time_full, ts, mo, obs8, IntrPass<D>(intr, dist), half_side, posec, tdata, delta_r, params[x],
+                                                             params[c], delta_t, bp_time));
     }
     Tm.End(st);
     Tm.Begin("k_marker_schur_finish", st);
@@ -1815,7 +1840,7 @@ struct MarkerSchurDevice {
   }
   int SumSquares(hipStream_t st, double* out) {
     if (Reset(st) != RSBA_OK) return RSBA_ERR_HIP;
-    k_marker_eval<false><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[0], intr, half_side, 0, nullptr, nullptr, ss_x);
+    RSBA_DIST_SWITCH(k_marker_eval<false, D><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[0], IntrPass<D>(intr, dist), half_side, 0, nullptr, nullptr, ss_x));
     std::vector<double> h(N);
     if (hipMemcpyAsync(h.data(), ss_x, N * 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return RSBA_ERR_HIP;
     double s = 0; for (double v : h) s += v;

@@ -55,9 +55,11 @@ __device__ __forceinline__ PoseC LoadPose(const double* __restrict__ posec, int 
 
 // One corner's residuals and the wanted 2 x 6 blocks of its rows: the arithmetic of MarkerCornerResidualJacobian (ba_math.hpp), operation
 // for operation, on pose constants held in registers.  A wanted block's pose is present (the caller owns it).
-template <bool kC, bool kT, bool kM>
+// kDist: ds = the detecting camera's five distortion coefficients (ProjectCorner, ba_math.hpp); Q loses its two structural zeros.
+template <bool kC, bool kT, bool kM, bool kDist = false>
 __device__ __forceinline__ void CornerRows(const PoseC& cam, const PoseC& tim, const PoseC& mar, double fx, double fy, double ppx, double ppy,
-                                           double cx, double cy, double u, double v, double r[2], double Jc[2][6], double Jt[2][6], double Jm[2][6]) {
+                                           double cx, double cy, double u, double v, double r[2], double Jc[2][6], double Jt[2][6], double Jm[2][6],
+                                           const double* ds = nullptr) {
   auto rot = [](const PoseC& p, const double in[3], double q[3], double out[3]) {
     q[0] = p.R[0] * in[0] + p.R[1] * in[1] + p.R[2] * in[2];
     q[1] = p.R[3] * in[0] + p.R[4] * in[1] + p.R[5] * in[2];
@@ -83,18 +85,31 @@ __device__ __forceinline__ void CornerRows(const PoseC& cam, const PoseC& tim, c
   rot(tim, pm, qt, pt);
   double qc[3] = {0, 0, 0}, pcm[3] = {pt[0], pt[1], pt[2]};
   if (cam.on) rot(cam, pt, qc, pcm);
-  const double iz = 1.0 / pcm[2];
-  r[0] = fx * pcm[0] * iz + ppx - u;
-  r[1] = fy * pcm[1] * iz + ppy - v;
-  const double al = fx * iz, be = fy * iz;
-  const double ga = -al * pcm[0] * iz, de = -be * pcm[1] * iz;
   double Qt[6];
-  if (cam.on) {
-    if (kC) { const double Qc[6] = {al, 0.0, ga, 0.0, be, de}; block(cam, Qc, pt, qc, Jc); }
+  if constexpr (kDist) {
+    double Qc[6];
+    ProjectCorner<true>(pcm[0], pcm[1], pcm[2], fx, fy, ppx, ppy, ds, u, v, r, Qc);
+    if (cam.on) {
+      if (kC) block(cam, Qc, pt, qc, Jc);
+      CarryQ(Qc, cam.R, Qt);
+    } else {
 #pragma unroll
-    for (int j = 0; j < 3; ++j) { Qt[j] = al * cam.R[j] + ga * cam.R[6 + j]; Qt[3 + j] = be * cam.R[3 + j] + de * cam.R[6 + j]; }
+      for (int j = 0; j < 6; ++j) Qt[j] = Qc[j];
+    }
   } else {
-    Qt[0] = al; Qt[1] = 0.0; Qt[2] = ga; Qt[3] = 0.0; Qt[4] = be; Qt[5] = de;
+    // (ProjectCorner<false> and the pinhole carry, written out: this instance is the code it was, instruction for instruction)
+    const double iz = 1.0 / pcm[2];
+    r[0] = fx * pcm[0] * iz + ppx - u;
+    r[1] = fy * pcm[1] * iz + ppy - v;
+    const double al = fx * iz, be = fy * iz;
+    const double ga = -al * pcm[0] * iz, de = -be * pcm[1] * iz;
+    if (cam.on) {
+      if (kC) { const double Qc[6] = {al, 0.0, ga, 0.0, be, de}; block(cam, Qc, pt, qc, Jc); }
+#pragma unroll
+      for (int j = 0; j < 3; ++j) { Qt[j] = al * cam.R[j] + ga * cam.R[6 + j]; Qt[3 + j] = be * cam.R[3 + j] + de * cam.R[6 + j]; }
+    } else {
+      Qt[0] = al; Qt[1] = 0.0; Qt[2] = ga; Qt[3] = 0.0; Qt[4] = be; Qt[5] = de;
+    }
   }
   if (kT) block(tim, Qt, pm, qt, Jt);
   if (kM) {
@@ -137,6 +152,13 @@ struct SplitArgs {
   const double* __restrict__ wsq;       // [N] with a robust loss (kLoss instances): sqrt(rho'(s)) of each residual block at x ...
   const double* __restrict__ drho;      // [N] ... and rho(s) - s (k_mc_block_weight)
 };
+// the kDist instances' argument: the same and the cameras' distortion coefficients [C][5], indexed as intr (the distortion-free
+// instances keep the argument they had)
+struct SplitArgsDist : SplitArgs { const double* __restrict__ dist; };
+template <bool kDist> struct SplitArgT { typedef SplitArgs type; };
+template <> struct SplitArgT<true> { typedef SplitArgsDist type; };
+__device__ __forceinline__ const double* DistOf(const SplitArgs&, int) { return nullptr; }
+__device__ __forceinline__ const double* DistOf(const SplitArgsDist& a, int camera) { return a.dist + 5 * camera; }
 
 // With a robust loss: per residual block (thread per block, the device's time order) s = |r|^2 over its 8 residuals at x, the corrector's
 // sqrt(rho'(s)), which every kLoss kernel below applies to the rows it forms (r and J scaled, Ceres' corrector for rho'' <= 0), and
@@ -146,13 +168,16 @@ struct SplitArgs {
 // wts: the blocks' weights a_k (ceres::ScaledLoss) in the same order: wsq = sqrt(a_k rho') — formed as sqrt(a_k) sqrt(rho'), a weight of
 // one changes no bit — and drho = a_k rho - s, so every kernel that reads the two is as it was.  A weight of zero: the block's rows
 // are exact zeros and its s leaves the cost again through drho = -s.
+// (kDist: 132 registers where the pinhole instance has 122 — three wavefronts a SIMD instead of four.  Held to 128 by the launch bounds
+//  it spills four registers to scratch, which its sibling does not use: not taken.  DESIGN §4 has the measured cost.)
+template <bool kDist = false>
 __global__ void __launch_bounds__(256) k_mc_block_weight(int N, const TimeSlots* __restrict__ ts, const MarkerObs* __restrict__ mo, const double* __restrict__ obs8,
-                                                         const double* __restrict__ intr, double half_side, const double* __restrict__ posec, double loss,
+                                                         typename IntrArg<kDist>::type intr, double half_side, const double* __restrict__ posec, double loss,
                                                          const double* __restrict__ wts, double* __restrict__ wsq, double* __restrict__ drho) {
   const int k = blockIdx.x * 256 + threadIdx.x;
   if (k >= N) return;
   const MarkerObs o = mo[k];
-  const double* in = intr + 4 * ts[k].camera;
+  const double* in = IntrOf(intr) + 4 * ts[k].camera;
   const double fx = in[0], fy = in[1], ppx = in[2], ppy = in[3];
   const PoseC cam = LoadPose<false>(posec, o.full_cam >= 0 ? o.full_cam / 6 : -1);
   const PoseC tim = LoadPose<false>(posec, o.full_time / 6);
@@ -162,7 +187,8 @@ __global__ void __launch_bounds__(256) k_mc_block_weight(int N, const TimeSlots*
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     double r[2];
-    CornerRows<false, false, false>(cam, tim, mar, fx, fy, ppx, ppy, CornerX(c, half_side), CornerY(c, half_side), ob[2 * c], ob[2 * c + 1], r, nullptr, nullptr, nullptr);
+    CornerRows<false, false, false, kDist>(cam, tim, mar, fx, fy, ppx, ppy, CornerX(c, half_side), CornerY(c, half_side), ob[2 * c], ob[2 * c + 1], r, nullptr, nullptr, nullptr,
+                                           DistOf(intr, ts[k].camera));
     ss = fma(r[0], r[0], ss);
     ss = fma(r[1], r[1], ss);
   }
@@ -182,8 +208,8 @@ __device__ __forceinline__ void ScaleCorner(double w, double r[2], double (*Ja)[
   }
 }
 
-template <bool kCam, bool kLoss>
-__device__ __forceinline__ void SlotProducts(const SplitArgs& a, int S, const PoseC& own, const PoseC& tim) {
+template <bool kCam, bool kLoss, bool kDist>
+__device__ __forceinline__ void SlotProducts(const typename SplitArgT<kDist>::type& a, int S, const PoseC& own, const PoseC& tim) {
   double W[36], gs[6], U[21];
 #pragma unroll
   for (int i = 0; i < 36; ++i) W[i] = 0.0;
@@ -195,7 +221,7 @@ __device__ __forceinline__ void SlotProducts(const SplitArgs& a, int S, const Po
   // What a residual block's rows need from memory — the other block's pose, the observed corners, the intrinsics — is asked for ONE ENTRY AHEAD,
   // and the entry's own record two ahead: as block -> slots -> column -> pose -> constants it was four dependent trips to memory per entry, on one
   // wavefront a SIMD with nothing to run meanwhile (5 us an entry; the arithmetic is 1.2).
-  struct Fetched { PoseC oth; double ob[8], in[4], w; };
+  struct Fetched { PoseC oth; double ob[8], in[4], w, ds[5]; };
   auto fetch = [&](const int4 r, Fetched& f) {
     f.oth = LoadPose<false>(a.posec, r.y);
     f.w = kLoss ? a.wsq[r.x] : 1.0;
@@ -205,6 +231,10 @@ __device__ __forceinline__ void SlotProducts(const SplitArgs& a, int S, const Po
     const double* in = a.intr + 4 * r.z;
 #pragma unroll
     for (int i = 0; i < 4; ++i) f.in[i] = in[i];
+    if constexpr (kDist) {
+#pragma unroll
+      for (int i = 0; i < 5; ++i) f.ds[i] = a.dist[5 * r.z + i];
+    }
   };
   int e = a.sb_ptr[S];
   const int e1 = a.sb_ptr[S + 1];
@@ -225,8 +255,8 @@ __device__ __forceinline__ void SlotProducts(const SplitArgs& a, int S, const Po
       const double ou = c == 0 ? cur.ob[0] : (c == 1 ? cur.ob[2] : (c == 2 ? cur.ob[4] : cur.ob[6]));
       const double ov = c == 0 ? cur.ob[1] : (c == 1 ? cur.ob[3] : (c == 2 ? cur.ob[5] : cur.ob[7]));
       double r[2], Jo[2][6], Jt[2][6];
-      if (kCam) CornerRows<true, true, false>(own, tim, oth, fx, fy, ppx, ppy, CornerX(c, hs), CornerY(c, hs), ou, ov, r, Jo, Jt, nullptr);
-      else CornerRows<false, true, true>(oth, tim, own, fx, fy, ppx, ppy, CornerX(c, hs), CornerY(c, hs), ou, ov, r, nullptr, Jt, Jo);
+      if (kCam) CornerRows<true, true, false, kDist>(own, tim, oth, fx, fy, ppx, ppy, CornerX(c, hs), CornerY(c, hs), ou, ov, r, Jo, Jt, nullptr, cur.ds);
+      else CornerRows<false, true, true, kDist>(oth, tim, own, fx, fy, ppx, ppy, CornerX(c, hs), CornerY(c, hs), ou, ov, r, nullptr, Jt, Jo, cur.ds);
       if constexpr (kLoss) ScaleCorner(cur.w, r, Jo, Jt);
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
@@ -255,23 +285,23 @@ __device__ __forceinline__ void SlotProducts(const SplitArgs& a, int S, const Po
   out[63] = 0.0;
 }
 
-template <bool kLoss>
-__global__ void __launch_bounds__(256) k_mc_slot_products(SplitArgs a) {
+template <bool kLoss, bool kDist = false>
+__global__ void __launch_bounds__(256) k_mc_slot_products(typename SplitArgT<kDist>::type a) {
   const int g = blockIdx.x * 256 + threadIdx.x;
   if (g >= a.nslots) return;
   const int S = a.slot_order[g], col = a.slot_col[S];
   const PoseC own = LoadPose<true>(a.posec, a.col_full[col] / 6);
   const PoseC tim = LoadPose<true>(a.posec, a.time_full[a.slot_time[S]] / 6);
-  if (col < a.ncam_cols) SlotProducts<true, kLoss>(a, S, own, tim);
-  else SlotProducts<false, kLoss>(a, S, own, tim);
+  if (col < a.ncam_cols) SlotProducts<true, kLoss, kDist>(a, S, own, tim);
+  else SlotProducts<false, kLoss, kDist>(a, S, own, tim);
 }
 
 // Wavefront per time.  tdata[t]: E (36) | g_t (6) | E g_t (6); tscal[t]: sum r^2 (kLoss: + sum (rho(s) - s)), |x_t|^2, 1.0 if V + D is not
 // positive definite, max |g_t|.  kLoss: V, g_t and so the time's Jacobi scale from the corrected rows.  kConst: the camera and marker
 // poses through the residual blocks' full offsets (a constant block has no column); a constant time (tconst[t] = 1) gets E = 0 and only
 // its cost.
-template <bool kLoss, bool kConst = false>
-__global__ void __launch_bounds__(256) k_mc_time_products(SplitArgs a, IterParams ip, const double* __restrict__ params_x, double* __restrict__ scale_t,
+template <bool kLoss, bool kConst = false, bool kDist = false>
+__global__ void __launch_bounds__(256) k_mc_time_products(typename SplitArgT<kDist>::type a, IterParams ip, const double* __restrict__ params_x, double* __restrict__ scale_t,
                                                           double* __restrict__ tdata, double* __restrict__ tscal, const int* __restrict__ tconst = nullptr) {
   __shared__ double s_v[4][3 * 36 + 8];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -296,7 +326,8 @@ __global__ void __launch_bounds__(256) k_mc_time_products(SplitArgs a, IterParam
 #pragma unroll 1
     for (int c = 0; c < 4; ++c) {
       double r[2], Jt[2][6];
-      CornerRows<false, true, false>(cam, tim, mar, fx, fy, ppx, ppy, CornerX(c, hs), CornerY(c, hs), ob[2 * c], ob[2 * c + 1], r, nullptr, Jt, nullptr);
+      CornerRows<false, true, false, kDist>(cam, tim, mar, fx, fy, ppx, ppy, CornerX(c, hs), CornerY(c, hs), ob[2 * c], ob[2 * c + 1], r, nullptr, Jt, nullptr,
+                                            DistOf(a, s.camera));
 #pragma unroll
       for (int i = 0; i < 2; ++i) ss = fma(r[i], r[i], ss);   // (the raw residuals)
       if constexpr (kLoss) ScaleCorner(w, r, Jt, nullptr);
@@ -376,8 +407,8 @@ __global__ void __launch_bounds__(256) k_mc_time_products(SplitArgs a, IterParam
   if (lane == 0) { tscal[4 * (size_t)t] = ss; tscal[4 * (size_t)t + 1] = xn2; tscal[4 * (size_t)t + 2] = ok ? 0.0 : 1.0; tscal[4 * (size_t)t + 3] = gmax; }
 }
 
-template <bool kLoss>
-__global__ void __launch_bounds__(256) k_mc_cross(SplitArgs a) {
+template <bool kLoss, bool kDist = false>
+__global__ void __launch_bounds__(256) k_mc_cross(typename SplitArgT<kDist>::type a) {
   const int g = blockIdx.x * 256 + threadIdx.x;
   if (g >= a.nx_threads) return;
   // a long item on TWO neighbouring lanes — even and odd entries, the sums meet by one lane exchange (even + odd: a fixed order): the items are
@@ -391,7 +422,7 @@ __global__ void __launch_bounds__(256) k_mc_cross(SplitArgs a) {
   for (int i = 0; i < 36; ++i) X[i] = 0.0;
   const double hs = a.half_side;
   // (the time's pose, the corners and the intrinsics one entry ahead, the entry's record two: see SlotProducts)
-  struct Fetched { PoseC tim; double ob[8], in[4], w; };
+  struct Fetched { PoseC tim; double ob[8], in[4], w, ds[5]; };
   auto fetch = [&](const int4 r, Fetched& f) {
     f.tim = LoadPose<false>(a.posec, r.y);
     f.w = kLoss ? a.wsq[r.x] : 1.0;
@@ -401,6 +432,10 @@ __global__ void __launch_bounds__(256) k_mc_cross(SplitArgs a) {
     const double* in = a.intr + 4 * r.z;
 #pragma unroll
     for (int i = 0; i < 4; ++i) f.in[i] = in[i];
+    if constexpr (kDist) {
+#pragma unroll
+      for (int i = 0; i < 5; ++i) f.ds[i] = a.dist[5 * r.z + i];
+    }
   };
   const int step = 1 + two, e1 = a.xi_ptr[it + 1];
   int e = a.xi_ptr[it] + part;
@@ -420,7 +455,7 @@ __global__ void __launch_bounds__(256) k_mc_cross(SplitArgs a) {
       const double ou = c == 0 ? cur.ob[0] : (c == 1 ? cur.ob[2] : (c == 2 ? cur.ob[4] : cur.ob[6]));
       const double ov = c == 0 ? cur.ob[1] : (c == 1 ? cur.ob[3] : (c == 2 ? cur.ob[5] : cur.ob[7]));
       double r[2], Jc[2][6], Jm[2][6];
-      CornerRows<true, false, true>(cam, tim, mar, fx, fy, ppx, ppy, CornerX(c, hs), CornerY(c, hs), ou, ov, r, Jc, nullptr, Jm);
+      CornerRows<true, false, true, kDist>(cam, tim, mar, fx, fy, ppx, ppy, CornerX(c, hs), CornerY(c, hs), ou, ov, r, Jc, nullptr, Jm, cur.ds);
       if constexpr (kLoss) ScaleCorner(cur.w, r, Jc, Jm);
 #pragma unroll
       for (int i = 0; i < 2; ++i)
@@ -828,12 +863,15 @@ __global__ void __launch_bounds__(256) k_mc_time_step(int T, const int* __restri
 }
 
 // kPart 0: the model cost change (the block's rows at x: 340 registers, one wavefront a SIMD); 1: the candidate's residuals (rotation
-// matrices and translations only: four wavefronts a SIMD) — two launches side by side instead of one kernel with the registers of both.
+// matrices and translations only: four wavefronts a SIMD, three with distortion) — two launches side by side instead of one kernel with the registers of both.
 // kLoss: part 0 from the corrected rows (wsq: sqrt(rho') at x); part 1 sums the raw r_c^2 as without a loss and the workgroup's
 // a rho(s_c) - s_c (wts: the blocks' weights) into drho_c[blockIdx.x] (k_marker_schur_finish<true> adds them to the cost).
-template <int kPart, bool kLoss>
+// kDist: part 0 takes 292 registers where the pinhole instance sits at 256 (one wavefront a SIMD instead of two), part 1 132 / 134 where
+// it has 122 / 124 (three instead of four; held to 128 by the launch bounds it spills to scratch, which its sibling does not use: not
+// taken).  DESIGN §4 has both measured.
+template <int kPart, bool kLoss, bool kDist = false>
 __global__ void __launch_bounds__(256) k_mc_candidate(int N, int T, const TimeSlots* __restrict__ ts, const MarkerObs* __restrict__ mo, const double* __restrict__ obs8,
-                                                      const double* __restrict__ intr, double half_side, const double* __restrict__ posec,
+                                                      typename IntrArg<kDist>::type intr, double half_side, const double* __restrict__ posec,
                                                       const double* __restrict__ posec_c, const double* __restrict__ delta_r, const double* __restrict__ delta_t,
                                                       const int* __restrict__ blk_time, double* __restrict__ bp_time, double loss = 0.0,
                                                       const double* __restrict__ wsq = nullptr, double* __restrict__ drho_c = nullptr,
@@ -844,9 +882,10 @@ __global__ void __launch_bounds__(256) k_mc_candidate(int N, int T, const TimeSl
   if (k < N) {
     const TimeSlots s = ts[k];
     const MarkerObs o = mo[k];
-    const double* in = intr + 4 * s.camera;
+    const double* in = IntrOf(intr) + 4 * s.camera;
     const double fx = in[0], fy = in[1], ppx = in[2], ppy = in[3];
     const double* ob = obs8 + 8 * (size_t)k;
+    const double* ds = DistOf(intr, s.camera);
     if (kPart == 0) {
       const PoseC cam = LoadPose<true>(posec, o.full_cam >= 0 ? o.full_cam / 6 : -1);
       const PoseC tim = LoadPose<true>(posec, o.full_time / 6);
@@ -868,7 +907,7 @@ __global__ void __launch_bounds__(256) k_mc_candidate(int N, int T, const TimeSl
         for (int i = 0; i < 2; ++i)
 #pragma unroll
           for (int q = 0; q < 6; ++q) Jc[i][q] = 0.0;   // (an absent camera transform: CornerRows leaves the block alone)
-        CornerRows<true, true, true>(cam, tim, mar, fx, fy, ppx, ppy, cx, cy, u, v, r, Jc, Jt, Jm);
+        CornerRows<true, true, true, kDist>(cam, tim, mar, fx, fy, ppx, ppy, cx, cy, u, v, r, Jc, Jt, Jm, ds);
         if constexpr (kLoss) {
           ScaleCorner(w, r, Jc, Jt);
 #pragma unroll
@@ -906,7 +945,8 @@ __global__ void __launch_bounds__(256) k_mc_candidate(int N, int T, const TimeSl
         if (cmar.on) apply(cmar);
         apply(ctim);
         if (ccam.on) apply(ccam);
-        const double r0 = fx * pt[0] / pt[2] + ppx - u, r1 = fy * pt[1] / pt[2] + ppy - v;
+        double r0, r1;
+        ProjectCornerResidual<kDist>(pt[0], pt[1], pt[2], fx, fy, ppx, ppy, ds, u, v, &r0, &r1);
         sum += r0 * r0 + r1 * r1;
         if constexpr (kLoss) sb += r0 * r0 + r1 * r1;
       }

@@ -171,6 +171,104 @@ RSBA_HD void ResidualJacobian(const double* cc, const double X[3], double u, dou
 }
 
 // ------------------------------------------------------------------------------------------------
+// Lens distortion, OpenCV's five coefficients (k1 k2 p1 p2 k3) as cv::projectPoints applies a 5 x 1 distCoeffs, on the
+// normalised point (x, y) = (X / Z, Y / Z) of the detecting camera's frame:
+//   r2 = x^2 + y^2,  rad = 1 + k1 r2 + k2 r2^2 + k3 r2^3
+//   xd = x rad + 2 p1 x y + p2 (r2 + 2 x^2),   yd = y rad + p1 (r2 + 2 y^2) + 2 p2 x y
+// Any scalar type with + and *: doubles, the device's dual numbers (k_marker_eval), a test's.  The coefficients and the
+// constants one and two come in that type.
+// ------------------------------------------------------------------------------------------------
+template <typename T>
+RSBA_HD void DistortNormalised(const T& x, const T& y, const T k[5], const T& one, const T& two, T* xd, T* yd) {
+  const T xx = x * x, yy = y * y, xy = x * y;
+  const T r2 = xx + yy;
+  const T rad = one + r2 * (k[0] + r2 * (k[1] + r2 * k[4]));
+  *xd = x * rad + (two * k[2] * xy + k[3] * (r2 + two * xx));
+  *yd = y * rad + (k[2] * (r2 + two * yy) + two * k[3] * xy);
+}
+
+// The projection of the marker chain: the point (X, Y, Z) in the detecting camera's frame to the residual pair and
+// Q = d r / d (X, Y, Z), 2 x 3 row-major.  The distortion instance of every kernel that forms rows calls ProjectCorner<true> (through
+// CornerRows, MarkerCornerResidualJacobian or its per-part twin).  ProjectCorner<false> states the pinhole form those three functions
+// keep WRITTEN OUT in their kDist = false branch, in the place and order it had: calling it there changed the registers and spills of
+// k_mc_candidate<0, true> and k_time_eliminate, and the distortion-free instances are to be the code they were.  The product does not
+// run ProjectCorner<false>; tests/distortion_math_driver.cpp holds the written-out branches (through MarkerCornerResidualJacobian<false>
+// and MarkerCornerJacobianPart<false>) and this function to the same bits.
+//   kDist = false: the pinhole camera, Q = [[fx/Z, 0, -fx X/Z^2], [0, fy/Z, -fy Y/Z^2]] (two structural zeros), the
+//                  expressions of the functors without coefficients, operation for operation;
+//   kDist = true:  u = fx xd + ppx, v = fy yd + ppy with dist5 = (k1 k2 p1 p2 k3) of the detecting camera, and
+//                  Q = diag(fx, fy) D [1/Z 0 -x/Z; 0 1/Z -y/Z],  D = d (xd, yd) / d (x, y)  (symmetric: D01 = D10).
+template <bool kDist>
+RSBA_HD void ProjectCorner(double X, double Y, double Z, double fx, double fy, double ppx, double ppy, const double* dist5,
+                           double u, double v, double r[2], double Q[6]) {
+  const double iz = 1.0 / Z;
+  if constexpr (!kDist) {
+    r[0] = fx * X * iz + ppx - u;
+    r[1] = fy * Y * iz + ppy - v;
+    const double al = fx * iz, be = fy * iz;
+    const double ga = -al * X * iz, de = -be * Y * iz;
+    Q[0] = al; Q[1] = 0.0; Q[2] = ga; Q[3] = 0.0; Q[4] = be; Q[5] = de;
+  } else {
+    const double k1 = dist5[0], k2 = dist5[1], p1 = dist5[2], p2 = dist5[3], k3 = dist5[4];
+    const double x = X * iz, y = Y * iz;
+    const double xx = x * x, yy = y * y, xy = x * y;
+    const double r2 = xx + yy;
+    const double rad = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3));
+    const double drad = k1 + r2 * (2.0 * k2 + 3.0 * k3 * r2);   // d rad / d r2
+    const double xd = x * rad + (2.0 * p1 * xy + p2 * (r2 + 2.0 * xx));
+    const double yd = y * rad + (p1 * (r2 + 2.0 * yy) + 2.0 * p2 * xy);
+    r[0] = fx * xd + ppx - u;
+    r[1] = fy * yd + ppy - v;
+    const double d00 = rad + 2.0 * xx * drad + (2.0 * p1 * y + 6.0 * p2 * x);
+    const double d01 = 2.0 * xy * drad + (2.0 * p1 * x + 2.0 * p2 * y);
+    const double d11 = rad + 2.0 * yy * drad + (6.0 * p1 * y + 2.0 * p2 * x);
+    const double al = fx * iz, be = fy * iz;
+    Q[0] = al * d00; Q[1] = al * d01; Q[2] = -al * (d00 * x + d01 * y);
+    Q[3] = be * d01; Q[4] = be * d11; Q[5] = -be * (d01 * x + d11 * y);
+  }
+}
+
+// The residual pair alone where no row is wanted (a candidate's cost).  kDist = false: the pinhole form of those sites, a
+// division per coordinate, as it was.
+template <bool kDist>
+RSBA_HD void ProjectCornerResidual(double X, double Y, double Z, double fx, double fy, double ppx, double ppy, const double* dist5,
+                                   double u, double v, double* r0, double* r1) {
+  if constexpr (kDist) {
+    double r[2], Q[6];
+    ProjectCorner<true>(X, Y, Z, fx, fy, ppx, ppy, dist5, u, v, r, Q);
+    *r0 = r[0]; *r1 = r[1];
+  } else {
+    *r0 = fx * X / Z + ppx - u;
+    *r1 = fy * Y / Z + ppy - v;
+  }
+}
+
+// A kernel's intrinsics argument: the [C][4] array alone, or — its distortion instance — that array and the [C][5] coefficients
+// beside it.  The type of the argument depends on kDist, so the distortion-free instance keeps exactly the argument list it had.
+struct IntrDist { const double* intr; const double* dist; };
+template <bool kDist> struct IntrArg { typedef const double* __restrict__ type; };
+template <> struct IntrArg<true> { typedef IntrDist type; };
+RSBA_HD const double* IntrOf(const double* a) { return a; }
+RSBA_HD const double* IntrOf(const IntrDist& a) { return a.intr; }
+RSBA_HD const double* DistOf(const double*, int) { return nullptr; }
+RSBA_HD const double* DistOf(const IntrDist& a, int camera) { return a.dist + 5 * camera; }
+template <bool kDist> RSBA_HD typename IntrArg<kDist>::type IntrPass(const double* intr, const double* dist) {
+  if constexpr (kDist) return IntrDist{intr, dist}; else return intr;
+}
+
+// A full Q (2 x 3) carried through a rotation: Q R, the sensitivity to the point entering the transform.  (The pinhole rows skip the
+// middle-row terms, which meet Q's structural zeros there: Q_t = al R_0 + ga R_2, be R_1 + de R_2, written out where they are formed.)
+RSBA_HD void CarryQ(const double Q[6], const double* R, double Qt[6]) {
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+  for (int j = 0; j < 3; ++j) {
+    Qt[j] = Q[0] * R[j] + Q[1] * R[3 + j] + Q[2] * R[6 + j];
+    Qt[3 + j] = Q[3] * R[j] + Q[4] * R[3 + j] + Q[5] * R[6 + j];
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Marker-chain functors (Main_Calibration/bundle_adjustment.h:56-343), ONE CORNER, analytically.
 //
 //   X = (cx, cy, 0)  --marker-->  p_m = R_m X + t_m  --time-->  p_t = R_t p_m + t_t  --camera-->  p_c = R_c p_t + t_c
@@ -186,8 +284,10 @@ RSBA_HD void ResidualJacobian(const double* cc, const double X[3], double u, dou
 // Replaces the DJet<18> evaluation of k_marker_eval where the marker-chain model runs at scale: ~1.2k FMAs per residual
 // block instead of ~20k, cheap enough to be recomputed wherever a Jacobian row is needed instead of being stored.
 // ------------------------------------------------------------------------------------------------
+// kDist: dist5 = the detecting camera's five coefficients (ProjectCorner); Q is then full and Qt gets its middle-row term.
+template <bool kDist = false>
 RSBA_HD void MarkerCornerResidualJacobian(const double* pc_cam, const double* pc_time, const double* pc_marker, const double* intr4,
-                                          double cx, double cy, double u, double v, double r[2], double J[36]) {
+                                          double cx, double cy, double u, double v, double r[2], double J[36], const double* dist5 = nullptr) {
   auto rot = [](const double* pc, const double in[3], double q[3], double out[3]) {
     const double* R = pc + CC_R;
     q[0] = R[0] * in[0] + R[1] * in[1] + R[2] * in[2];
@@ -217,21 +317,34 @@ RSBA_HD void MarkerCornerResidualJacobian(const double* pc_cam, const double* pc
   double qc[3] = {0, 0, 0}, pcm[3] = {pt[0], pt[1], pt[2]};
   if (pc_cam) rot(pc_cam, pt, qc, pcm);
   const double fx = intr4[0], fy = intr4[1], ppx = intr4[2], ppy = intr4[3];
-  const double iz = 1.0 / pcm[2];
-  r[0] = fx * pcm[0] * iz + ppx - u;
-  r[1] = fy * pcm[1] * iz + ppy - v;
-  const double al = fx * iz, be = fy * iz;
-  const double ga = -al * pcm[0] * iz, de = -be * pcm[1] * iz;
-  for (int i = 0; i < 36; ++i) J[i] = 0.0;
-  // camera transform
   double Qt[6];   // sensitivity to p_t
-  if (pc_cam) {
-    const double Qc[6] = {al, 0.0, ga, 0.0, be, de};
-    block(pc_cam, Qc, pt, qc, J + 0);
-    const double* R = pc_cam + CC_R;
-    for (int j = 0; j < 3; ++j) { Qt[j] = al * R[j] + ga * R[6 + j]; Qt[3 + j] = be * R[3 + j] + de * R[6 + j]; }
+  if constexpr (kDist) {
+    double Qc[6];
+    ProjectCorner<true>(pcm[0], pcm[1], pcm[2], fx, fy, ppx, ppy, dist5, u, v, r, Qc);
+    for (int i = 0; i < 36; ++i) J[i] = 0.0;
+    if (pc_cam) {
+      block(pc_cam, Qc, pt, qc, J + 0);
+      CarryQ(Qc, pc_cam + CC_R, Qt);
+    } else {
+      for (int j = 0; j < 6; ++j) Qt[j] = Qc[j];
+    }
   } else {
-    Qt[0] = al; Qt[1] = 0.0; Qt[2] = ga; Qt[3] = 0.0; Qt[4] = be; Qt[5] = de;
+    // (ProjectCorner<false> and the pinhole carry, written out: this instance is the code it was, instruction for instruction)
+    const double iz = 1.0 / pcm[2];
+    r[0] = fx * pcm[0] * iz + ppx - u;
+    r[1] = fy * pcm[1] * iz + ppy - v;
+    const double al = fx * iz, be = fy * iz;
+    const double ga = -al * pcm[0] * iz, de = -be * pcm[1] * iz;
+    for (int i = 0; i < 36; ++i) J[i] = 0.0;
+    // camera transform
+    if (pc_cam) {
+      const double Qc[6] = {al, 0.0, ga, 0.0, be, de};
+      block(pc_cam, Qc, pt, qc, J + 0);
+      const double* R = pc_cam + CC_R;
+      for (int j = 0; j < 3; ++j) { Qt[j] = al * R[j] + ga * R[6 + j]; Qt[3 + j] = be * R[3 + j] + de * R[6 + j]; }
+    } else {
+      Qt[0] = al; Qt[1] = 0.0; Qt[2] = ga; Qt[3] = 0.0; Qt[4] = be; Qt[5] = de;
+    }
   }
   // time transform
   block(pc_time, Qt, pm, qt, J + 6);
@@ -249,9 +362,10 @@ RSBA_HD void MarkerCornerResidualJacobian(const double* pc_cam, const double* pc
 // block, 2: marker block), the same arithmetic: k_time_eliminate stages a corner on three lanes.  The intrinsics come by
 // value (the caller fetched them a tile ahead).  J has the row stride 18 of the full rows; a block whose pose is not a
 // parameter is written as zeros.
+template <bool kDist = false>
 RSBA_HD void MarkerCornerJacobianPart(int part, const double* pc_cam, const double* pc_time, const double* pc_marker,
                                                 double fx, double fy, double ppx, double ppy, double cx, double cy, double u, double v,
-                                                double* r, double* J) {
+                                                double* r, double* J, const double* dist5 = nullptr) {
   auto rot = [](const double* pc, const double in[3], double q[3], double out[3]) {
     const double* R = pc + CC_R;
     q[0] = R[0] * in[0] + R[1] * in[1] + R[2] * in[2];
@@ -286,6 +400,39 @@ RSBA_HD void MarkerCornerJacobianPart(int part, const double* pc_cam, const doub
   rot(pc_time, pm, qt, pt);
   double qc[3] = {0, 0, 0}, pcm[3] = {pt[0], pt[1], pt[2]};
   if (pc_cam) rot(pc_cam, pt, qc, pcm);
+  if constexpr (kDist) {
+    double rr[2], Qc[6];
+    ProjectCorner<true>(pcm[0], pcm[1], pcm[2], fx, fy, ppx, ppy, dist5, u, v, rr, Qc);
+    if (part == 0) {
+      r[0] = rr[0];
+      r[1] = rr[1];
+      if (pc_cam) block(pc_cam, Qc, pt, qc, J + 0);
+      else zeros(J + 0);
+      return;
+    }
+    double Qt[6];
+    if (pc_cam) {
+      CarryQ(Qc, pc_cam + CC_R, Qt);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 6; ++j) Qt[j] = Qc[j];
+    }
+    if (part == 1) { block(pc_time, Qt, pm, qt, J + 6); return; }
+    if (pc_marker) {
+      const double* R = pc_time + CC_R;
+      double Qm[6];
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) Qm[3 * i + j] = Qt[3 * i] * R[j] + Qt[3 * i + 1] * R[3 + j] + Qt[3 * i + 2] * R[6 + j];
+      block(pc_marker, Qm, X, qm, J + 12);
+    } else {
+      zeros(J + 12);
+    }
+    return;
+  }
+  // kDist = false from here on: ProjectCorner<false> and the pinhole carry written out — this instance is the code it was, instruction for
+  // instruction (tools/kernel_resources.py: k_time_eliminate's registers and spills move with the shape of this function)
   const double iz = 1.0 / pcm[2];
   const double al = fx * iz, be = fy * iz;
   const double ga = -al * pcm[0] * iz, de = -be * pcm[1] * iz;

@@ -154,6 +154,32 @@ static int ReadXmlMatrix(const std::string& text, const std::string& name, int* 
   return RSBA_OK;
 }
 
+// <intrinsics> as ReadIntrinsicsXml, plus <distCoeffs>: 4 entries (k1 k2 p1 p2; k3 = 0) or 5 (k1 k2 p1 p2 k3) as a row or a column;
+// no node: zeros.  OpenCV's longer models (8 rational, 12 thin-prism, 14 tilted) are not this library's.
+int ReadIntrinsicsXmlDist(const char* path, double* out4, double* out5) {
+  if (!path || !out4 || !out5) return RSBA_ERR_ARG;
+  double k4[4];
+  const int rc = ReadIntrinsicsXml(path, k4);
+  if (rc != RSBA_OK) return rc;
+  std::string text;
+  if (!ReadAll(path, &text)) return RSBA_ERR_IO;
+  double d5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  if (text.find("<distCoeffs") != std::string::npos) {
+    int rows = 0, cols = 0;
+    std::vector<double> d;
+    const int rd = ReadXmlMatrix(text, "distCoeffs", &rows, &cols, &d);
+    if (rd != RSBA_OK) return rd;
+    if (rows != 1 && cols != 1) return RSBA_ERR_FORMAT;
+    const int n = rows * cols;
+    if (n == 8 || n == 12 || n == 14) return RSBA_ERR_UNSUPPORTED;
+    if (n != 4 && n != 5) return RSBA_ERR_FORMAT;
+    for (int i = 0; i < n; ++i) { if (!std::isfinite(d[i])) return RSBA_ERR_FORMAT; d5[i] = d[i]; }
+  }
+  for (int i = 0; i < 4; ++i) out4[i] = k4[i];
+  for (int i = 0; i < 5; ++i) out5[i] = d5[i];
+  return RSBA_OK;
+}
+
 // Rotation matrix (row-major) -> angle-axis, the inverse of Rodrigues above (what cv::projectPoints does with the 3x3
 // "rvec" reprojection_check.cpp:65-69 hands it).
 void RotationToAngleAxis(const double R[9], double aa[3]) {

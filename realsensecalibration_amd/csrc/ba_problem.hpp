@@ -29,10 +29,13 @@ struct rsba_problem {
   std::vector<uint8_t> point_constant;   // point model: the same for point blocks (round 6)
   std::vector<uint8_t> block_constant;   // marker-chain models: per block of [C cameras | T times | M markers] (round 6); empty = none
   std::vector<double> observation_weights;   // marker-chain models: a_i >= 0 per residual block (ceres::ScaledLoss); empty = none
+  std::vector<double> distortion;     // marker-chain models: 5 per camera (k1 k2 p1 p2 k3, OpenCV), indexed as intrinsics; empty = none
 
   int64_t num_parameters() const { return (int64_t)parameters.size(); }
   int obs_dim() const { return model == RSBA_MODEL_POINTS ? 2 : 8; }
   bool is_marker_chain() const { return model != RSBA_MODEL_POINTS; }
+  // some coefficient is not exactly zero: a solver then runs the distortion instances of its kernels (none, or all zeros: today's)
+  bool has_distortion() const { for (double v : distortion) if (v != 0.0) return true; return false; }
   // wiring rules of bundle_adjustment_manager.cpp:26-87 / Test2 main.cpp:64-96
   bool uses_camera(int64_t i) const { return camera_index[i] != 0; }
   bool uses_marker(int64_t i) const { return model == RSBA_MODEL_MARKER_CHAIN_TEST2 ? true : marker_index[i] != 0; }
@@ -47,6 +50,8 @@ int LoadPointsFile(const char* path, const double* intrinsics4, rsba_problem** o
 int LoadCorrespondence(const char* path, int32_t model, double marker_side, const double* intrinsics,
                        rsba_problem** out);
 int ReadIntrinsicsXml(const char* path, double* out4);
+int ReadIntrinsicsXmlDist(const char* path, double* out4, double* out5);
+int UndistortPoints(int32_t n, const double* image_points, const double* intrinsics4, const double* dist5, double* out);
 void Rodrigues(const double rvec[3], double R[9]);
 void RotationToAngleAxis(const double R[9], double aa[3]);
 int LoadReprojectionCheck(const char* correspondence_txt, const char* point3d_txt, const char* camera_transform_xml,

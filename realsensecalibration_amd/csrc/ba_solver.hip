@@ -276,6 +276,10 @@ struct rsba_solver {
                                // the covariance read them (all ones, a loss solver's start, change no bit and are not passed)
   std::vector<double> obs_w;   // [N] the problem's order (all ones when the problem had none); weighted only
   double* obs_w_dev = nullptr; // the same on the device: evaluate and the Jacobian index observations in the problem's order
+  // lens distortion (rsba_problem_set_distortion): fixed at create, like the intrinsics.  Not null: some coefficient of the problem was not
+  // zero and every kernel of this solver that forms rows or residuals runs its distortion instance.
+  double* dist_dev = nullptr;  // [C][5], indexed as the intrinsics: the path's own upload (marker.dist / marker_schur.dist, which owns it), for
+                               // evaluate, the Jacobian and the covariance
 
   // ---- covariance (rsba_solver_covariance_compute, ba_covariance.hpp): buffers of its own, the LM state is not touched
   bool cov_valid = false;
@@ -2032,10 +2036,14 @@ static int CovarianceMarker(rsba_solver* s, const rsba_covariance_options& co) {
     hip(hipMemcpyAsync(elim_d, elim.data(), elim.size(), hipMemcpyHostToDevice, st));
     if (use_w) hip(hipMemcpyAsync(wrow_d, wrow.data(), wrow.size() * sizeof(double), hipMemcpyHostToDevice, st));
     k_cov_pose_constants<<<(nb + 255) / 256, 256, 0, st>>>(nb, params, pc);
-    if (loss != 0.0 || use_w)
-      k_cov_mc_lin<true><<<std::max(1, std::min(T, 4096)), 64, 0, st>>>(T, tptr_d, rows_d, obs_d, intr, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags, loss, wrow_d);
-    else
+    if (loss != 0.0 || use_w) {
+      if (s->dist_dev) k_cov_mc_lin<true, true><<<std::max(1, std::min(T, 4096)), 64, 0, st>>>(T, tptr_d, rows_d, obs_d, IntrDist{intr, s->dist_dev}, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags, loss, wrow_d);
+      else k_cov_mc_lin<true><<<std::max(1, std::min(T, 4096)), 64, 0, st>>>(T, tptr_d, rows_d, obs_d, intr, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags, loss, wrow_d);
+    } else if (s->dist_dev) {
+      k_cov_mc_lin<false, true><<<std::max(1, std::min(T, 4096)), 64, 0, st>>>(T, tptr_d, rows_d, obs_d, IntrDist{intr, s->dist_dev}, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags);
+    } else {
       k_cov_mc_lin<false><<<std::max(1, std::min(T, 4096)), 64, 0, st>>>(T, tptr_d, rows_d, obs_d, intr, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags);
+    }
     // (the host vectors outlive CovRun, which synchronises the stream before it returns)
   }, [](CovSystem&, auto&) { return RSBA_OK; });
   // the snapshot of the pair queries: the carved pointers and what the linearisation was told
@@ -2173,7 +2181,9 @@ static int CovQueue(rsba_solver* s, const CovRequests& rq, size_t slots, double*
     const auto& m = s->cov_mc;
     CovMcSnap sn{m.tptr, m.rows, m.obs, m.intr, m.pc, m.use_w ? m.wrow : nullptr, s->cov_dptr, s->cov_dpos, s->cov_rslot,
                  m.half_side, m.rcond, m.loss, m.loss != 0.0 || m.use_w ? 1 : 0, s->cov_n};
-    k_cov_mc_cross<<<(int)std::min<size_t>(nm, 4096), 64, 0, st>>>((int)nm, req_d + ng, sn, s->cov_sinv, stage_d);
+    CovMcSnapDist snd; static_cast<CovMcSnap&>(snd) = sn; snd.dist = s->dist_dev;
+    if (s->dist_dev) k_cov_mc_cross<true><<<(int)std::min<size_t>(nm, 4096), 64, 0, st>>>((int)nm, req_d + ng, snd, s->cov_sinv, stage_d);
+    else k_cov_mc_cross<false><<<(int)std::min<size_t>(nm, 4096), 64, 0, st>>>((int)nm, req_d + ng, sn, s->cov_sinv, stage_d);
   }
   if (np > 0) {
     const auto& m = s->cov_pt;
@@ -2382,10 +2392,12 @@ static int EvaluateOnDevice(rsba_solver* s, bool apply_loss, double* cost, doubl
     k_cov_pose_constants<<<(nb + 255) / 256, 256, 0, st>>>(nb, params, posec);
     const double* wts = apply_loss && s->weights_given ? s->obs_w_dev : nullptr;   // (the weights go with the loss, as in Ceres)
     if (gradient) {
-      k_eval_marker<true><<<grid, 64, 0, st>>>((int)N, e.rows, e.obs8, e.intr, posec, p.marker_side / 2, loss, res_d, work, cost_parts, wts);
+      if (s->dist_dev) k_eval_marker<true, true><<<grid, 64, 0, st>>>((int)N, e.rows, e.obs8, IntrDist{e.intr, s->dist_dev}, posec, p.marker_side / 2, loss, res_d, work, cost_parts, wts);
+      else k_eval_marker<true><<<grid, 64, 0, st>>>((int)N, e.rows, e.obs8, e.intr, posec, p.marker_side / 2, loss, res_d, work, cost_parts, wts);
       k_eval_marker_block_sum<<<nb, 256, 0, st>>>(e.list_ptr, e.list_obs, e.list_slot, work, e.live, grad_d);
     } else {
-      k_eval_marker<false><<<grid, 64, 0, st>>>((int)N, e.rows, e.obs8, e.intr, posec, p.marker_side / 2, loss, res_d, nullptr, cost_parts, wts);
+      if (s->dist_dev) k_eval_marker<false, true><<<grid, 64, 0, st>>>((int)N, e.rows, e.obs8, IntrDist{e.intr, s->dist_dev}, posec, p.marker_side / 2, loss, res_d, nullptr, cost_parts, wts);
+      else k_eval_marker<false><<<grid, 64, 0, st>>>((int)N, e.rows, e.obs8, e.intr, posec, p.marker_side / 2, loss, res_d, nullptr, cost_parts, wts);
     }
   }
   k_eval_cost<<<1, 256, 0, st>>>(grid, cost_parts, cost_d);
@@ -2510,8 +2522,10 @@ static int JacobianOnDevice(rsba_solver* s, bool apply_loss, double* values) {
     const double* params = s->eliminate_times ? (s->has_run ? s->marker_schur.params[s->marker_schur.cur] : s->marker_schur.params0)
                                               : (s->has_run ? s->marker.params[s->marker.cur] : s->marker.params0);
     k_cov_pose_constants<<<(nb + 255) / 256, 256, 0, st>>>(nb, params, posec);
-    k_eval_jacobian_marker<<<(N + 63) / 64, 64, 0, st>>>(N, e.rows, e.obs8, e.intr, posec, j.off, e.live, p.marker_side / 2, loss, values_d,
-                                                         apply_loss && s->weights_given ? s->obs_w_dev : nullptr);
+    if (s->dist_dev) k_eval_jacobian_marker<true><<<(N + 63) / 64, 64, 0, st>>>(N, e.rows, e.obs8, IntrDist{e.intr, s->dist_dev}, posec, j.off, e.live, p.marker_side / 2, loss, values_d,
+                                                                                 apply_loss && s->weights_given ? s->obs_w_dev : nullptr);
+    else k_eval_jacobian_marker<false><<<(N + 63) / 64, 64, 0, st>>>(N, e.rows, e.obs8, e.intr, posec, j.off, e.live, p.marker_side / 2, loss, values_d,
+                                                                      apply_loss && s->weights_given ? s->obs_w_dev : nullptr);
   }
   rc = RSBA_OK;
   auto hip = [&](hipError_t err) { if (err != hipSuccess && rc == RSBA_OK) rc = RSBA_ERR_HIP; };
@@ -2658,6 +2672,7 @@ int rsba_solver_create(rsba_problem* p, const rsba_options* o, rsba_solver** out
     s->weighted = opt.huber_delta > 0.0 || !p->observation_weights.empty();
     s->weights_given = !p->observation_weights.empty();
     if (!p->observation_weights.empty() && (int64_t)p->observation_weights.size() != p->num_observations) { rsba::FreeSolver(s); return RSBA_ERR_ARG; }
+    if (!p->distortion.empty() && p->distortion.size() != 5 * (size_t)p->num_cameras) { rsba::FreeSolver(s); return RSBA_ERR_ARG; }
     rc = s->eliminate_times ? s->marker_schur.Upload(*p, s->weighted) : s->marker.Upload(*p, s->weighted);
     if (s->eliminate_times && rc == RSBA_ERR_UNSUPPORTED) {
       // duplicate detections, or a time wider than the kernels' LDS: the dense path is general
@@ -2665,6 +2680,7 @@ int rsba_solver_create(rsba_problem* p, const rsba_options* o, rsba_solver** out
       s->eliminate_times = false;
       rc = s->marker.Upload(*p, s->weighted);
     }
+    if (rc == RSBA_OK) s->dist_dev = s->eliminate_times ? s->marker_schur.dist : s->marker.dist;   // (null without coefficients)
     if (rc == RSBA_OK && s->weighted) {
       s->obs_w = p->observation_weights;
       if (s->obs_w.empty()) s->obs_w.assign((size_t)p->num_observations, 1.0);

@@ -108,6 +108,18 @@ int rsba_problem_set_observation_weights(rsba_problem* p, const double* weights)
 const double* rsba_problem_observation_weights(const rsba_problem* p) {
   return (p && !p->observation_weights.empty()) ? p->observation_weights.data() : nullptr;
 }
+int rsba_problem_set_distortion(rsba_problem* p, const double* dist) {
+  if (!p) return RSBA_ERR_ARG;
+  if (!p->is_marker_chain()) return RSBA_ERR_UNSUPPORTED;   // the point model's projection sits in the headline kernels
+  if (!dist) { p->distortion.clear(); return RSBA_OK; }
+  const size_t n = 5 * (size_t)p->num_cameras;
+  for (size_t i = 0; i < n; ++i) if (!std::isfinite(dist[i])) return RSBA_ERR_ARG;
+  p->distortion.assign(dist, dist + n);
+  return RSBA_OK;
+}
+const double* rsba_problem_distortion(const rsba_problem* p) {
+  return (p && !p->distortion.empty()) ? p->distortion.data() : nullptr;
+}
 void rsba_problem_free(rsba_problem* p) { delete p; }
 
 int rsba_base_pose_from_marker_detection(const double* marker_from_camera, const double* marker_from_base, double* base_from_camera) {
@@ -175,6 +187,10 @@ void rsba_evaluate_options_default(rsba_evaluate_options* o) {
 }
 
 int rsba_read_intrinsics_xml(const char* path, double* out4) { return rsba::ReadIntrinsicsXml(path, out4); }
+int rsba_read_intrinsics_xml_dist(const char* path, double* out4, double* out5) { return rsba::ReadIntrinsicsXmlDist(path, out4, out5); }
+int rsba_undistort_points(int32_t n, const double* image_points, const double* intrinsics4, const double* dist5, double* out) {
+  return rsba::UndistortPoints(n, image_points, intrinsics4, dist5, out);
+}
 int rsba_write_outputs(rsba_problem* p, const char* xml, const char* dir, const char* p3d) {
   if (!p) return RSBA_ERR_ARG;
   return rsba::WriteOutputs(*p, xml, dir, p3d);

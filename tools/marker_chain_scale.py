@@ -1,10 +1,11 @@
 """Marker-chain model at scale on the GPU: per-kernel times of the time-elimination path.
 
-    python tools/marker_chain_scale.py [C T M [huber|cauchy a]] [const=SET] [schur_impl=K] [dump=PATH] [weights=FRAC]
+    python tools/marker_chain_scale.py [C T M [huber|cauchy a]] [const=SET] [schur_impl=K] [dump=PATH] [weights=FRAC] [dist=SEED]
         default 8 5000 16, no loss; SET: markers | cameras:K (cameras 1..K) | times:K (every T/K-th time) | rig (every camera
         and marker: only the times are free), joined by '+' (e.g. cameras:2+times:100); dump=PATH writes the final parameters
         and the iteration log (.npz) of the last unprofiled run; weights=FRAC: observation weights on the problem (ceres::ScaledLoss),
-        that fraction of the residual blocks (seeded) at weight 0 and the rest at 1 — 0 asks for all ones
+        that fraction of the residual blocks (seeded) at weight 0 and the rest at 1 — 0 asks for all ones; dist=SEED: lens distortion,
+        tests/marker_distortion_ref.py's coefficients(C, SEED) on the problem and its detections redetected through them
 """
 import json
 import os
@@ -44,6 +45,11 @@ LOSS_KW = {} if LOSS == "none" else {"huber_delta": LOSS_A, "loss_type": 1 if LO
 t0 = time.time()
 prob = synthetic.make_marker_chain(C_, T_, M_, seed=11)
 gen = time.time() - t0
+DIST = int(KW["dist"]) if "dist" in KW else None
+if DIST is not None:
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import marker_distortion_ref as dref  # noqa: E402
+    prob = dref.redetect(prob, dref.coefficients(C_, DIST), 0.3, DIST)
 p = capi.Problem.marker_chain(prob)
 for b in CONST:
     p.set_parameter_block_constant(6 * b)
@@ -60,6 +66,7 @@ for mode in (0, 1):
     if mode == 0:
         out["constant_blocks"] = len(CONST)
         out["zero_weight_fraction"] = WEIGHTS
+        out["distortion_seed"] = DIST
         out["eliminates_times"] = s.eliminates_times()
         if "dump" in KW:
             s.download()
