@@ -189,6 +189,37 @@ int rsba_problem_set_point_constant(rsba_problem* p, int32_t point_idx, int32_t 
  * constant only the time blocks are solved, each on its own (rsba_solver_time_elimination tells which path a solver runs). */
 int rsba_problem_set_parameter_block_constant(rsba_problem* p, int64_t parameter_offset, int32_t constant);
 
+/* ceres::SubsetParameterization(6, constant_parameters) on a pose block of the marker-chain models: single components of a block
+ * held constant.  `parameter_offset` names the block as above (a multiple of 6 inside [C | T | M]); bit q of `constant_mask` set
+ * means component q of (rvec[0..2], tvec[0..2]) is constant.  Ceres 1.14's semantics:
+ *   - a constant component never moves: it keeps its bits through every step, accepted or rejected, in the download and in
+ *     rsba_problem_parameters; cost and residuals use its value;
+ *   - it has no column in the linear system: the free components' step, their Jacobi scales, the damping, the model cost change,
+ *     the gradient and gradient_max_norm are those of the program without it, for any option values (min_lm_diagonal = 0 included);
+ *   - the norms of the convergence tests are ambient, as TrustRegionMinimizer's x_.norm() is: |x| counts the constant components
+ *     of a partly constant block, the step norm gets 0 from them; a wholly constant block stays out as before;
+ *   - a block that is also constant as a whole (rsba_problem_set_parameter_block_constant), a fixed base block (camera 0 / marker 0
+ *     of the wiring) or a block no residual names: the mask is ignored.
+ * A mask of 0 removes the subset.  A mask of all six bits (63; Ceres CHECK-fails: use the block call), bits above 5, a negative
+ * mask, an offset that is no multiple of 6 or outside [C | T | M]: RSBA_ERR_ARG, nothing changes.  The point model:
+ * RSBA_ERR_UNSUPPORTED (its camera rows sit in the headline kernels).  Host only.
+ * rsba_solve and rsba_solver_create honour the masks; they are fixed at create, like constant blocks.  No mask, or only zero masks:
+ * the kernels and the bits of a problem without them.  Any non-zero mask: both paths take it, together with a robust loss, weights,
+ * distortion and constant blocks; the path rule (rsba_solver_time_elimination) does not read the masks.  On the time-eliminating
+ * path a masked solver always runs the split elimination and the split back-substitution (the masks are applied to their small
+ * products), whatever RSBA_MT_SPLIT, RSBA_MT_SPLIT_BACKSUB and RSBA_MT_BACKSUB_WG say.
+ * Queries on such a solver: rsba_solver_evaluate writes 0.0 in the masked slots of the gradient.  rsba_solver_jacobian_structure
+ * is unchanged — the block keeps its six columns — and rsba_solver_evaluate_jacobian writes exact 0.0 in the masked columns, so
+ * J'r equals the gradient slot for slot.  THIS DEPARTS FROM CERES, whose CRS matrix has the block's local size (6 - k) columns.
+ * rsba_solver_set_parameters takes new values for masked components too; they are held at the new values.
+ * rsba_solver_covariance_compute inverts the system of the free components only (a constant component is decoupled, with a unit
+ * diagonal, where the system is formed) and reports no rank deficiency because of a constant component; rsba_solver_covariance_block,
+ * rsba_solver_covariance_blocks and rsba_solver_time_covariances return exact zeros in the rows and columns of constant components —
+ * Ceres' lift of the local covariance through the parameterisation's Jacobian. */
+int rsba_problem_set_parameter_subset_constant(rsba_problem* p, int64_t parameter_offset, int32_t constant_mask);
+/* the block's mask; 0 when it has none (or the arguments name no block) */
+int32_t rsba_problem_parameter_subset_constant(const rsba_problem* p, int64_t parameter_offset);
+
 /* Per-observation weights on the marker-chain models: what `new ceres::ScaledLoss(loss_or_NULL, a_i, TAKE_OWNERSHIP)` around each
  * residual block's loss does (Ceres 1.14 loss_function.h, corrector.cc).  One weight a_i >= 0 per residual block (one detected
  * marker, 8 residuals), in the problem's observation order.  With s_i = |r_i|^2 over the block's 8 residuals and rho the

@@ -77,6 +77,14 @@ class BALProblem {
   // lens distortion (rsba_problem_set_distortion): 5 per camera, nullptr removes them / none set
   bool set_distortion(const double* dist) { return rsba_problem_set_distortion(p_, dist) == RSBA_OK; }
   const double* distortion() const { return rsba_problem_distortion(p_); }
+  // problem.SetParameterization(block, new ceres::SubsetParameterization(6, constant_parameters)) on a pose block handed out by the
+  // mutable_* accessors above: the listed components of (rvec, tvec) are held (rsba_problem_set_parameter_subset_constant); an empty
+  // list removes the subset.  False for a pointer that starts no pose block, an index outside 0..5 or all six components.
+  bool SetSubsetConstant(double* block, const std::vector<int>& constant_parameters) {
+    int mask = 0;
+    for (int q : constant_parameters) { if (q < 0 || q > 5) return false; mask |= 1 << q; }
+    return rsba_problem_set_parameter_subset_constant(p_, block - rsba_problem_parameters(p_), mask) == RSBA_OK;
+  }
   // Test1 accessors
   double* mutable_cameras() { return rsba_problem_parameters(p_); }
   double* mutable_points() { return rsba_problem_parameters(p_) + 6 * num_cameras(); }

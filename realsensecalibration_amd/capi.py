@@ -35,7 +35,7 @@ EXPORTS = [
     "rsba_solver_jacobian_structure", "rsba_solver_evaluate_jacobian",
     "rsba_solver_comm_abort",
     "rsba_problem_set_observation_weights", "rsba_problem_observation_weights", "rsba_solver_set_observation_weights",
-    "rsba_problem_set_distortion", "rsba_problem_distortion", "rsba_read_intrinsics_xml_dist", "rsba_undistort_points",
+    "rsba_problem_set_parameter_subset_constant", "rsba_problem_parameter_subset_constant", "rsba_problem_set_distortion", "rsba_problem_distortion", "rsba_read_intrinsics_xml_dist", "rsba_undistort_points",
 ]
 _SYMBOLS = EXPORTS   # (every symbol of include/rsba.h that load() checks)
 
@@ -176,6 +176,9 @@ def load():
     lib.rsba_problem_observation_weights.argtypes = [C.c_void_p]
     lib.rsba_problem_observation_weights.restype = C.POINTER(C.c_double)
     lib.rsba_solver_set_observation_weights.argtypes = [C.c_void_p, C.c_void_p]
+    lib.rsba_problem_set_parameter_subset_constant.argtypes = [C.c_void_p, C.c_int64, C.c_int32]
+    lib.rsba_problem_parameter_subset_constant.argtypes = [C.c_void_p, C.c_int64]
+    lib.rsba_problem_parameter_subset_constant.restype = C.c_int32
     lib.rsba_problem_set_distortion.argtypes = [C.c_void_p, C.c_void_p]
     lib.rsba_problem_distortion.argtypes = [C.c_void_p]
     lib.rsba_problem_distortion.restype = C.POINTER(C.c_double)
@@ -297,6 +300,24 @@ class Problem:
 
     def set_parameter_block_constant(self, parameter_offset, constant=True):
         _chk(load().rsba_problem_set_parameter_block_constant(self.h, parameter_offset, 1 if constant else 0), "rsba_problem_set_parameter_block_constant")
+
+    def set_parameter_subset_constant(self, parameter_offset, components):
+        """Marker-chain models: hold single components of the pose block at parameter_offset (ceres::SubsetParameterization).
+        components: a 6-bit mask (bit q = component q of rvec, tvec) or an iterable of component indices; 0 / empty removes it."""
+        if isinstance(components, (int, np.integer)):
+            mask = int(components)
+        else:
+            mask = 0
+            for q in components:
+                q = int(q)
+                if q < 0 or q > 5:
+                    raise ValueError("set_parameter_subset_constant: component %d is not in 0..5" % q)
+                mask |= 1 << q
+        _chk(load().rsba_problem_set_parameter_subset_constant(self.h, parameter_offset, mask), "rsba_problem_set_parameter_subset_constant")
+
+    def parameter_subset_constant(self, parameter_offset):
+        """The block's mask of constant components; 0 when it has none."""
+        return int(load().rsba_problem_parameter_subset_constant(self.h, parameter_offset))
 
     def set_observation_weights(self, w):
         """Marker-chain models: one weight a_i >= 0 per residual block (ceres::ScaledLoss), the problem's observation order; None

@@ -508,15 +508,59 @@ __device__ __forceinline__ bool CovSym6Inverse(const double U[21], double rcond,
 
 #define RSBA_COV_MC_LDS 73   // doubles per row of the staged W blocks: cam 6x6 | marker 6x6 (+1: bank padding)
 
+// Constant components of partly constant blocks (ceres::SubsetParameterization; the kSub instances below).  sub18[q]: the constant
+// components among row q's 18 local columns camera | time | marker (rows in the compute's order; 0 for a block without columns).
+// Ceres evaluates such a block through its 6 x (6 - k) local Jacobian, inverts the system of the free components and lifts the result
+// back with zeros.  Here: the rows' constant columns are set to exact zeros where the rows are formed, every constant component gets
+// a unit diagonal (in V_t and, by k_cov_subset_diag, in S) — decoupled from the free ones, so the inverse of the rest is that of the
+// system without it and no rank deficiency is reported because of it — and its rows and columns of the result are written as exact
+// zeros (k_cov_subset_sinv for S^-1; k_cov_mc_cross for the blocks it forms).
+// The masks travel in the argument that carries the intrinsics, so the instances without them keep the signature they had.
+struct IntrDistSub : IntrDist { const int* sub18; };
+template <bool kDist, bool kSub> struct CovIntrArg { typedef typename IntrArg<kDist>::type type; };
+template <bool kDist> struct CovIntrArg<kDist, true> { typedef IntrDistSub type; };
+__device__ __forceinline__ int SubOf(const double*, int) { return 0; }
+__device__ __forceinline__ int SubOf(const IntrDist&, int) { return 0; }
+__device__ __forceinline__ int SubOf(const IntrDistSub& a, int q) { return a.sub18[q]; }
+// the constant columns of one corner's 2 x 18 rows
+__device__ __forceinline__ void SubsetZeroColumns(int sub, double J[36]) {
+#pragma unroll
+  for (int e = 0; e < 36; ++e) if ((sub >> (e % 18)) & 1) J[e] = 0.0;
+}
+// the unit diagonal of a time's constant components in the upper triangle V (rows a, columns c >= a, row by row)
+__device__ __forceinline__ void SubsetUnitDiagonal(int sub6, double V[21]) {
+#pragma unroll
+  for (int a = 0; a < 6; ++a) if ((sub6 >> a) & 1) V[6 * a - a * (a - 1) / 2] = 1.0;
+}
+// S (n x n, upper blocks, before the inverse): a one on the diagonal of every constant component.  bsub[b]: block b's mask.
+__global__ void __launch_bounds__(256) k_cov_subset_diag(int nb, const int* __restrict__ pos, const unsigned char* __restrict__ bsub, int n, double* __restrict__ S) {
+  const int g = blockIdx.x * 256 + threadIdx.x, b = g / 6, q = g - 6 * b;
+  if (b >= nb || pos[b] < 0 || !((bsub[b] >> q) & 1)) return;
+  const size_t i = (size_t)pos[b] + q;
+  S[i * n + i] = 1.0;
+}
+// S^-1: the rows and columns of the constant components as exact zeros (workgroup per block)
+__global__ void __launch_bounds__(256) k_cov_subset_sinv(const int* __restrict__ pos, const unsigned char* __restrict__ bsub, int n, double* __restrict__ Sinv) {
+  const int b = blockIdx.x, sub = bsub[b];
+  if (pos[b] < 0 || sub == 0) return;
+  for (int q = 0; q < 6; ++q) {
+    if (!((sub >> q) & 1)) continue;
+    const size_t i = (size_t)pos[b] + q;
+    for (int j = threadIdx.x; j < n; j += 256) { Sinv[i * n + j] = 0.0; Sinv[(size_t)j * n + i] = 0.0; }
+  }
+}
+
 // Normal matrix of the marker-chain problem into S (n x n, zeroed by the caller, upper blocks): one wavefront per time block,
 // one lane per row (chunks of 64).  pos[block] = 6 x compact index or -1 (constant / unreferenced / eliminated).  elim[t] != 0:
 // time block t is eliminated — S -= W_x V_t^-1 W_y' over the pairs of its rows' camera / marker blocks, W_x = sum J_x'J_t.
 // kLoss: J of a row scaled by sqrt(rho'(s)) (loss: LossAndScale's signed parameter), s taken over its four corners first; wts
 // (nullptr: none): the rows' weights a_q (ceres::ScaledLoss) in the rows' order, the factor sqrt(a_q) sqrt(rho').
 // kDist: dist = the cameras' five distortion coefficients [C][5], indexed as intr.
-template <bool kLoss, bool kDist = false>
+// kSub: the rows' constant columns are zeros and V_t has a unit diagonal there (see IntrDistSub above; S gets its own from
+// k_cov_subset_diag).
+template <bool kLoss, bool kDist = false, bool kSub = false>
 __global__ void __launch_bounds__(64)
-k_cov_mc_lin(int T, const int* __restrict__ tptr, const CovMcRow* __restrict__ rows, const double* __restrict__ obs8, typename IntrArg<kDist>::type intr,
+k_cov_mc_lin(int T, const int* __restrict__ tptr, const CovMcRow* __restrict__ rows, const double* __restrict__ obs8, typename CovIntrArg<kDist, kSub>::type intr,
              const double* __restrict__ pc, const int* __restrict__ pos, const unsigned char* __restrict__ elim, double half_side, double rcond,
              int n, double* __restrict__ S, int* __restrict__ flags, double loss = 0.0, const double* __restrict__ wts = nullptr) {
   __shared__ double Wl[64 * RSBA_COV_MC_LDS];
@@ -547,6 +591,7 @@ k_cov_mc_lin(int T, const int* __restrict__ tptr, const CovMcRow* __restrict__ r
       if constexpr (kLoss) {
         for (int e = 0; e < 36; ++e) J[e] *= sq;
       }
+      if constexpr (kSub) SubsetZeroColumns(SubOf(intr, q), J);
       f(J);
     }
   };
@@ -599,6 +644,7 @@ k_cov_mc_lin(int T, const int* __restrict__ tptr, const CovMcRow* __restrict__ r
     if (!el) continue;
 #pragma unroll
     for (int e = 0; e < 21; ++e) V[e] = WaveSum(V[e]);
+    if constexpr (kSub) SubsetUnitDiagonal((SubOf(intr, b) >> 6) & 63, V);
     double Vi[36];
     if (!CovSym6Inverse(V, rcond, Vi)) {
       if (lane == 0) atomicOr(&flags[COV_FLAG_POINT], 1);
@@ -701,8 +747,11 @@ struct CovMcSnap {
 };
 // k_cov_mc_cross<true>'s argument: the same and the cameras' distortion coefficients [C][5], indexed as intr
 struct CovMcSnapDist : CovMcSnap { const double* dist; };
-template <bool kDist> struct CovMcSnapT { typedef CovMcSnap type; };
-template <> struct CovMcSnapT<true> { typedef CovMcSnapDist type; };
+// the kSub instances': the same and the rows' constant columns (sub18, see IntrDistSub; dist unused without kDist)
+struct CovMcSnapSub : CovMcSnapDist { const int* sub18; };
+template <bool kDist, bool kSub = false> struct CovMcSnapT { typedef CovMcSnap type; };
+template <> struct CovMcSnapT<true, false> { typedef CovMcSnapDist type; };
+template <bool kDist> struct CovMcSnapT<kDist, true> { typedef CovMcSnapSub type; };
 __device__ __forceinline__ const double* DistOf(const CovMcSnap&, int) { return nullptr; }
 __device__ __forceinline__ const double* DistOf(const CovMcSnapDist& a, int camera) { return a.dist + 5 * camera; }
 
@@ -710,9 +759,12 @@ template <int kX> struct CovSide { static constexpr int value = kX; };
 
 // COV_REQ_TIME_TIME: a = t, b = t' (a <= b; out = cov(t, t'), mirrored from its upper triangle for t = t');
 // COV_REQ_TIME_X: a = t, b = x's position in S^-1 (out = cov(t, x)).
-template <bool kDist = false>
+// kSub: constant components (see IntrDistSub above) — the rows' constant columns are zeros, V_t has a unit diagonal there as in
+// k_cov_mc_lin<., ., true>, S^-1 arrives with their rows and columns zeroed (k_cov_subset_sinv), and the rows / columns of a time's
+// constant components leave as exact zeros.
+template <bool kDist = false, bool kSub = false>
 __global__ void __launch_bounds__(64)
-k_cov_mc_cross(int nreq, const CovReq* __restrict__ req, typename CovMcSnapT<kDist>::type sn, const double* __restrict__ Sinv, double* __restrict__ out) {
+k_cov_mc_cross(int nreq, const CovReq* __restrict__ req, typename CovMcSnapT<kDist, kSub>::type sn, const double* __restrict__ Sinv, double* __restrict__ out) {
   __shared__ double Yd[RSBA_COV_MC_MAXBLK * 36];
   __shared__ double stage[32 * RSBA_COV_MC_STAGE];
   __shared__ int sl[64];
@@ -743,9 +795,12 @@ k_cov_mc_cross(int nreq, const CovReq* __restrict__ req, typename CovMcSnapT<kDi
 #pragma unroll
         for (int e = 0; e < 36; ++e) J[e] *= sq;
       }
+      if constexpr (kSub) SubsetZeroColumns(sn.sub18[q], J);
       f(J);
     }
   };
+  // a time's constant components (its rows carry them; a time in a request has rows)
+  auto time_sub = [&](int t) { if constexpr (kSub) return (sn.sub18[sn.tptr[t]] >> 6) & 63; else return 0; };
   // V_t^-1 (every lane), V_t summed over the rows as k_cov_mc_lin sums it
   auto time_inverse = [&](int t, double Vi[36]) {
     const int b = sn.tptr[t], k = sn.tptr[t + 1] - b;
@@ -762,6 +817,7 @@ k_cov_mc_cross(int nreq, const CovReq* __restrict__ req, typename CovMcSnapT<kDi
       });
 #pragma unroll
     for (int e = 0; e < 21; ++e) V[e] = WaveSum(V[e]);
+    if constexpr (kSub) SubsetUnitDiagonal(time_sub(t), V);
     (void)CovSym6Inverse(V, sn.rcond, Vi);   // (k_cov_mc_lin has already raised the flag for a singular block)
   };
   for (int i = blockIdx.x; i < nreq; i += gridDim.x) {
@@ -854,8 +910,9 @@ k_cov_mc_cross(int nreq, const CovReq* __restrict__ req, typename CovMcSnapT<kDi
 #pragma unroll
       for (int e = 0; e < 36; ++e) acc[e] = WaveSum(acc[e]);
       if (lane == 0) {
+        const int sa = time_sub(tb);
 #pragma unroll
-        for (int e = 0; e < 36; ++e) o[e] = acc[e];
+        for (int e = 0; e < 36; ++e) o[e] = kSub && ((sa >> (e / 6)) & 1) ? 0.0 : acc[e];
       }
       continue;
     }
@@ -927,6 +984,11 @@ k_cov_mc_cross(int nreq, const CovReq* __restrict__ req, typename CovMcSnapT<kDi
       for (int a = 0; a < 6; ++a)
 #pragma unroll
         for (int l = 0; l < 6; ++l) o[6 * a + l] = ta == tb && l < a ? R[6 * l + a] : R[6 * a + l];
+      if constexpr (kSub) {
+        const int sa = time_sub(ta), sb = time_sub(tb);
+#pragma unroll
+        for (int e = 0; e < 36; ++e) if (((sa >> (e / 6)) | (sb >> (e % 6))) & 1) o[e] = 0.0;
+      }
     }
   }
 }

@@ -220,6 +220,15 @@ k_eval_marker_block_sum(const int* __restrict__ list_ptr, const int* __restrict_
   }
 }
 
+// Constant components of partly constant blocks (rsba_problem_set_parameter_subset_constant): 0.0 in their gradient slots, after
+// k_eval_marker_block_sum wrote the blocks' sums (Ceres' gradient has the block's local size; here the slots stay and hold zeros).
+// bsub[b]: block b's mask.
+__global__ void __launch_bounds__(256) k_eval_subset_gradient(int nb, const unsigned char* __restrict__ bsub, double* __restrict__ gradient) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= 6 * nb) return;
+  if ((bsub[i / 6] >> (i % 6)) & 1) gradient[i] = 0.0;
+}
+
 // cost = 1/2 x the n partials, summed in index order by one workgroup
 __global__ void __launch_bounds__(256) k_eval_cost(int n, const double* __restrict__ parts, double* __restrict__ cost) {
   __shared__ double lds[4];
@@ -269,11 +278,12 @@ struct EvalDevice {
   unsigned char* list_slot = nullptr;
   unsigned char* live = nullptr;   // per block of the gradient: != 0 computed, 0 written as 0.0 (EvalPointLive / EvalMarkerLive)
   unsigned char* cam_const = nullptr;   // point model with a communicator: per camera, != 0 constant (k_eval_shard_unpack)
+  unsigned char* bsub = nullptr;        // marker chain, a solver with constant components: per block its mask (nullptr: none)
   char* arena = nullptr;
   size_t arena_cap = 0;
 
   void Free() {
-    void* ptrs[] = {cam_ptr, cam_slot, cam_point, order, pt_perm, rows, obs8, intr, list_ptr, list_obs, list_slot, live, cam_const, arena};
+    void* ptrs[] = {cam_ptr, cam_slot, cam_point, order, pt_perm, rows, obs8, intr, list_ptr, list_obs, list_slot, live, cam_const, bsub, arena};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     *this = EvalDevice();
   }

@@ -111,6 +111,31 @@ k_eval_jacobian_marker(int N, const EvalMarkerRow* __restrict__ rows, const doub
   }
 }
 
+// Constant components of partly constant blocks (rsba_problem_set_parameter_subset_constant): exact 0.0 in their columns of the
+// values k_eval_jacobian_marker wrote — the structure keeps the block's six columns, so J'r equals the gradient slot for slot.
+// One thread per observation, the layout k_eval_jacobian_marker walks.  bsub[b]: block b's mask.
+__global__ void __launch_bounds__(64)
+k_eval_jacobian_subset(int N, const EvalMarkerRow* __restrict__ rows, const int64_t* __restrict__ off, const unsigned char* __restrict__ live,
+                       const unsigned char* __restrict__ bsub, double* __restrict__ values) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= N) return;
+  const int64_t o = off[i];
+  const int w = (int)(off[i + 1] - o) >> 3;
+  if (w == 0) return;
+  const EvalMarkerRow rw = rows[i];
+  const int blk[3] = {rw.cam_block, rw.time_block, rw.marker_block};
+  double* v = values + o;
+  int col = 0;
+  for (int b = 0; b < 3; ++b) {
+    if (blk[b] < 0 || live[blk[b]] == 0) continue;
+    const int sub = bsub[blk[b]];
+    for (int a = 0; a < 6; ++a)
+      if ((sub >> a) & 1)
+        for (int r = 0; r < 8; ++r) v[r * w + col + a] = 0.0;
+    col += 6;
+  }
+}
+
 // What a solver keeps for rsba_solver_evaluate_jacobian beyond EvalDevice: the layout on the host (rsba_solver_jacobian_structure
 // answers from it and launches nothing) and, from the first call that wants values, the observations' offsets and the point
 // model's problem-order tables on the device.  The values are carved from EvalDevice's arena.

@@ -80,8 +80,19 @@ struct MarkerObs {
   int full_cam, full_time, full_marker;  // -1: block not part of this residual
   int act_cam, act_time, act_marker;
   int camera;                            // intrinsics index
-  int pad;
+  int pad;                               // constant components (ceres::SubsetParameterization): bit q of the 18 local columns camera | time | marker
 };
+#define RSBA_SUBSET_BIT (1 << 30)        // act_to_full: the active column is a constant component of a partly constant block
+
+// A partly constant block (rsba_problem_set_parameter_subset_constant): the columns of its constant components leave the stored rows
+// as exact zeros — what seeding the component as a constant in the dual-number pass gives — after k_marker_eval (and its corrector's
+// scaling) wrote them.  Thread per entry of the N x 8 x 18 rows.
+__global__ void __launch_bounds__(256) k_marker_subset_rows(int N, const MarkerObs* __restrict__ mo, double* __restrict__ Jbuf) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (size_t)N * 144) return;
+  const int i = (int)(e / 144), q = (int)(e - (size_t)i * 144) % 18;
+  if ((mo[i].pad >> q) & 1) Jbuf[e] = 0.0;
+}
 
 // Evaluate residual blocks.  with_jacobian: J (8 x 18, columns camera|time|marker) and r (8) are stored.
 // kLoss: the residual block (one observation, 8 residuals) is robustified as Ceres' corrector does it for rho'' <= 0 (Huber,
@@ -182,7 +193,11 @@ __global__ void __launch_bounds__(64) k_marker_eval(int N, const MarkerObs* __re
 
 // One workgroup: normal equations in a fixed order, Jacobi scale, LM damping, Cholesky, step, candidate.
 //   A : (n+1) x n work matrix; H/g accumulated by thread-per-entry loops over the observations in order.
-template <int kThreads>
+// kSub: some active column is a constant component (RSBA_SUBSET_BIT in act_to_full; its rows' entries are exact zeros,
+// k_marker_subset_rows): it gets a unit diagonal before the Jacobi scale is taken — row, column and gradient are zero, so it is
+// decoupled from the free columns whatever the damping options are, and its step is an exact zero.  It stays in |x| (Ceres' norms
+// are those of the ambient vector).
+template <int kThreads, bool kSub = false>
 __global__ void __launch_bounds__(kThreads)
 k_marker_system(int N, int n, const MarkerObs* __restrict__ mo, const double* __restrict__ Jbuf, const double* __restrict__ rbuf,
                 const double* __restrict__ sumsq_per_obs, double* __restrict__ A, double* __restrict__ scale,
@@ -218,6 +233,11 @@ k_marker_system(int N, int n, const MarkerObs* __restrict__ mo, const double* __
     __threadfence_block();
     __syncthreads();
   }
+  if constexpr (kSub) {
+    for (int i = tid; i < n; i += nt) if (act_to_full[i] & RSBA_SUBSET_BIT) A[(size_t)i * n + i] = 1.0;
+    __threadfence_block();
+    __syncthreads();
+  }
   // gradient (unscaled), scale (iteration 0), damping
   for (int i = tid; i < n; i += nt) {
     grad[i] = A[(size_t)n * n + i];
@@ -236,7 +256,7 @@ k_marker_system(int N, int n, const MarkerObs* __restrict__ mo, const double* __
   __syncthreads();
   double* ysol = A + (size_t)n * n;
   if (kThreads == 512) CholeskySolvePanelLDS(n, A, ysol, &s_ok, lds, PanelSource{nullptr, nullptr, nullptr, 0.0, 0.0, 0.0, nullptr, nullptr, 0});
-  else CholeskySolveBlocked(n, A, ysol, &s_ok, lds);
+  else CholeskySolveBlocked<kSub ? 1 : 0>(n, A, ysol, &s_ok, lds);
   __syncthreads();
   // step, candidate, norms, cost at x
   double* scr = lds;
@@ -244,8 +264,9 @@ k_marker_system(int N, int n, const MarkerObs* __restrict__ mo, const double* __
   for (int i = tid; i < n; i += nt) {
     const double d = -scale[i] * ysol[i];
     delta_act[i] = d;
-    const double x = params_x[act_to_full[i]], xc = x + d;
-    params_c[act_to_full[i]] = xc;
+    const int fi = kSub ? act_to_full[i] & ~RSBA_SUBSET_BIT : act_to_full[i];
+    const double x = params_x[fi], xc = x + d;
+    params_c[fi] = xc;
     d2 += d * d; x2 += x * x; xc2 += xc * xc; gm = fmax(gm, fabs(grad[i]));
   }
   double cs = 0;
@@ -317,6 +338,7 @@ struct MarkerDevice {
   double* wts = nullptr;    // [N] the blocks' weights, the problem's order (with_loss only; all ones when the problem had none)
   int* act_to_full = nullptr;
   int cur = 0;
+  bool with_subset = false; // some block in the program has constant components (Upload): k_marker_subset_rows and k_marker_system<., true>
   bool with_dist = false;   // the kDist instances (Upload): some distortion coefficient of the problem is not zero
   double* dist = nullptr;   // [C][5], indexed as intr
 
@@ -336,7 +358,14 @@ struct MarkerDevice {
     for (int b = 0; b < nblocks && b < (int)p.block_constant.size(); ++b) if (p.block_constant[b]) used[b] = 0;
     std::vector<int> act(nblocks, -1), a2f;
     int na = 0;
-    for (int b = 0; b < nblocks; ++b) if (used[b]) { act[b] = 6 * na++; for (int q = 0; q < 6; ++q) a2f.push_back(6 * b + q); }
+    // constant components (block_subset) of a block in the program: the column stays, marked; a constant or unused block's mask is ignored
+    with_subset = false;
+    for (int b = 0; b < nblocks; ++b) if (used[b]) {
+      act[b] = 6 * na++;
+      const int mask = p.subset_mask(b);
+      with_subset = with_subset || mask != 0;
+      for (int q = 0; q < 6; ++q) a2f.push_back((6 * b + q) | (((mask >> q) & 1) ? RSBA_SUBSET_BIT : 0));
+    }
     n = 6 * na;
     std::vector<MarkerObs> h(N);
     for (int i = 0; i < N; ++i) {
@@ -346,6 +375,9 @@ struct MarkerDevice {
       o.act_cam = p.uses_camera(i) ? act[p.camera_block(i)] : -1; o.act_time = act[p.time_block(i)];
       o.act_marker = p.uses_marker(i) ? act[p.marker_block(i)] : -1;
       o.camera = p.camera_index[i]; o.pad = 0;
+      if (o.act_cam >= 0) o.pad |= p.subset_mask(p.camera_block(i));
+      if (o.act_time >= 0) o.pad |= p.subset_mask(p.time_block(i)) << 6;
+      if (o.act_marker >= 0) o.pad |= p.subset_mask(p.marker_block(i)) << 12;
     }
     auto al = [](void** q, size_t bytes) { return hipMalloc(q, std::max<size_t>(bytes, 8)) == hipSuccess; };
     if (!al((void**)&mo, N * sizeof(MarkerObs)) || !al((void**)&obs8, 8 * (size_t)N * 8) || !al((void**)&intr, p.intrinsics.size() * 8) ||
@@ -405,11 +437,23 @@ struct MarkerDevice {
     else k_marker_eval<false><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[x], intr, half_side, 1, Jbuf, rbuf, ss_x);
     T.End(st);
     if (!chk("k_marker_eval")) return RSBA_ERR_HIP;
+    if (with_subset) {
+      T.Begin("k_marker_subset_rows", st);
+      k_marker_subset_rows<<<(unsigned)(((size_t)N * 144 + 255) / 256), 256, 0, st>>>(N, mo, Jbuf);
+      T.End(st);
+    }
     size_t lds = (size_t)std::max(2 * RSBA_TB * (RSBA_NB + 1) + RSBA_NB * (RSBA_NB + 1), 5 * 1024) * sizeof(double);
     if (n <= RSBA_CHOL_MAXN) lds = std::max(lds, CholeskyLdsDoubles(n) * sizeof(double));
     const double* cost_x = with_loss ? rho_x : ss_x;   // what k_marker_system sums into the cost at x
     T.Begin("k_marker_system", st);
-    if (n <= RSBA_CHOL_MAXN) {
+    if (with_subset) {
+      if (n <= RSBA_CHOL_MAXN) {
+        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k_marker_system<512, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        k_marker_system<512, true><<<1, 512, lds, st>>>(N, n, mo, Jbuf, rbuf, cost_x, A, scale, grad, act_to_full, params[x], params[c], delta, res, ip);
+      } else {
+        k_marker_system<1024, true><<<1, 1024, lds, st>>>(N, n, mo, Jbuf, rbuf, cost_x, A, scale, grad, act_to_full, params[x], params[c], delta, res, ip);
+      }
+    } else if (n <= RSBA_CHOL_MAXN) {
       if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k_marker_system<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       k_marker_system<512><<<1, 512, lds, st>>>(N, n, mo, Jbuf, rbuf, cost_x, A, scale, grad, act_to_full, params[x], params[c], delta, res, ip);
     } else {

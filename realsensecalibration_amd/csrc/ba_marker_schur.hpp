@@ -1280,12 +1280,17 @@ struct MarkerSchurDevice {
   // lens distortion (Upload): the kDist instances run when some coefficient of the problem is not zero; no path rule reads it
   bool with_dist = false;
   double* dist = nullptr;   // [C][5], indexed as intr
+  // constant components (block_subset, Upload): some block in the program has a non-zero mask.  The split elimination and the split
+  // back-substitution then, whatever the switches say: the masks are applied to their small products (ba_marker_split.hpp)
+  bool with_subset = false;
+  int* tflags = nullptr;            // [T] bit 0: a constant time; bits 8..13: the time's constant components
+  unsigned char* rmask = nullptr;   // [nr / 6] the reduced blocks' constant components
 
   void Free() {
     void* ptrs[] = {mo, ts, chunk_ptr, time_ptr, slot_ptr, slot_col, time_full, col_full, ok_flag, obs8, intr, params[0], params[1],
                     params0, posec, posec_c, ss_x, scale_t, scale_r, tdata, part, red, A, Wm, delta_r, delta_t, bp_time, solve_out, res, tc_flags, tc_hand, tc_map,
                     slot_order, slot_time, sb_ptr, sb_blk, xi_ptr, xi_blk, xi_cc, xi_cm, xc_ptr, sp, xout, tscal, blk_time, x_order, wsq, drho, drho_c, wts,
-                    cs_ptr, cs_full, tconst, cpose_full, dist};
+                    cs_ptr, cs_full, tconst, cpose_full, dist, tflags, rmask};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     mo = nullptr; ts = nullptr;
     for (auto& q : fork_s) if (q) { (void)hipStreamDestroy(q); q = nullptr; }
@@ -1330,9 +1335,19 @@ struct MarkerSchurDevice {
       for (int q = 0; q < 6; ++q) cf.push_back(full + q);
     }
     nr = 6 * K;   // (0: nothing but time blocks are free)
+    // constant components: of the blocks in the program only (a constant, base or unreferenced block's mask is ignored)
+    std::vector<unsigned char> hrmask;
+    for (int b = 0; b < C + M; ++b) if (red_col[b] >= 0) hrmask.push_back((unsigned char)p.subset_mask(b < C ? b : Tn + b));
+    with_subset = std::find_if(hrmask.begin(), hrmask.end(), [](unsigned char v) { return v != 0; }) != hrmask.end();
     std::vector<int> tid_of(Tn, -1), tfull, htc;
     T = 0;
-    for (int t = 0; t < Tn; ++t) if (tused[t]) { tid_of[t] = T++; tfull.push_back(6 * (C + t)); htc.push_back(is_const(C + t) ? 1 : 0); }
+    std::vector<int> htflags;
+    for (int t = 0; t < Tn; ++t) if (tused[t]) {
+      tid_of[t] = T++; tfull.push_back(6 * (C + t)); htc.push_back(is_const(C + t) ? 1 : 0);
+      const int mask = is_const(C + t) ? 0 : p.subset_mask(C + t);
+      with_subset = with_subset || mask != 0;
+      htflags.push_back(htc.back() | (mask << 8));
+    }
     // residual blocks in time order (stable)
     std::vector<int> order(N);
     for (int i = 0; i < N; ++i) order[i] = i;
@@ -1402,7 +1417,8 @@ struct MarkerSchurDevice {
     }
     if (6 * pmax > RSBA_MT_MAXD) return RSBA_ERR_UNSUPPORTED;
     ncpose = (int)hcpose.size();
-    has_const = ncpose > 0 || std::find(htc.begin(), htc.end(), 1) != htc.end();
+    // (constant components ride on the kConst instances of the split kernels: the time's flags arrive where tconst does)
+    has_const = with_subset || ncpose > 0 || std::find(htc.begin(), htc.end(), 1) != htc.end();
     const int npc = has_const ? pmax : dmax / 6;   // k_time_eliminate's pose cache holds the pose-only slots too; its other tables are the free columns'
     // chunks of consecutive times, balanced by work; the partial systems together stay below 2 GB
     const RedLayout RL{nr};
@@ -1411,7 +1427,7 @@ struct MarkerSchurDevice {
     lds_s = lds_elim + (PL.packed() + 3 * (size_t)nr) * sizeof(double) <= 156 * 1024;
     if (lds_s) lds_elim += (PL.packed() + 3 * (size_t)nr) * sizeof(double);
     const bool lds_s_elim = lds_s;   // (k_time_eliminate's own choice, should the split kernels not take the problem)
-    split = with_loss || !(getenv("RSBA_MT_SPLIT") && atoi(getenv("RSBA_MT_SPLIT")) == 0);
+    split = with_loss || with_subset || !(getenv("RSBA_MT_SPLIT") && atoi(getenv("RSBA_MT_SPLIT")) == 0);
     if (split) {
       const int per_wave = (AccMfmaTiles(nr) + 15) / 16;
       acc_tiles = (per_wave <= 8 && !(getenv("RSBA_MT_ACC_MFMA") && atoi(getenv("RSBA_MT_ACC_MFMA")) == 0)) ? (per_wave <= 3 ? 3 : 8) : 0;
@@ -1426,7 +1442,7 @@ struct MarkerSchurDevice {
       if (lds_acc > 156 * 1024) {
         // times that touch more blocks than the accumulation's double-buffered records hold in LDS (~110 of the 170 the model allows):
         // round 4's kernel, which stages 32 residual blocks at a time whatever the width
-        if (with_loss) return RSBA_ERR_UNSUPPORTED;
+        if (with_loss || with_subset) return RSBA_ERR_UNSUPPORTED;
         split = false; acc_tiles = 0; lds_s = lds_s_elim;
       }
     }
@@ -1520,9 +1536,9 @@ struct MarkerSchurDevice {
       }
     }
     // (k_time_backsub_wg: a corner of a residual block per lane, two per lane at most; wider times take the wavefront-per-time kernel)
-    { int widest = 0; for (int t = 0; t < T; ++t) widest = std::max(widest, tptr[t + 1] - tptr[t]); backsub_wg = !with_loss && widest <= 128 /* 4 x 128 corners = 512 lanes */ && !(getenv("RSBA_MT_BACKSUB_WG") && atoi(getenv("RSBA_MT_BACKSUB_WG")) == 0); }
+    { int widest = 0; for (int t = 0; t < T; ++t) widest = std::max(widest, tptr[t + 1] - tptr[t]); backsub_wg = !with_loss && !with_subset && widest <= 128 /* 4 x 128 corners = 512 lanes */ && !(getenv("RSBA_MT_BACKSUB_WG") && atoi(getenv("RSBA_MT_BACKSUB_WG")) == 0); }
     nb_time = backsub_wg ? T : (T + 3) / 4;
-    split_backsub = split && !(getenv("RSBA_MT_SPLIT_BACKSUB") && atoi(getenv("RSBA_MT_SPLIT_BACKSUB")) == 0);
+    split_backsub = split && (with_subset || !(getenv("RSBA_MT_SPLIT_BACKSUB") && atoi(getenv("RSBA_MT_SPLIT_BACKSUB")) == 0));
     if (split_backsub) { ncand_wg = (N + 255) / 256; nb_time = T + ncand_wg; }
     auto al = [](void** q, size_t bytes) { return hipMalloc(q, std::max<size_t>(bytes, 8)) == hipSuccess; };
     const size_t nA = (size_t)(nr + 2) * nr;
@@ -1560,6 +1576,10 @@ struct MarkerSchurDevice {
       if (!al((void**)&cs_ptr, (T + 1) * 4) || !al((void**)&cs_full, csfull.size() * 4) || !al((void**)&tconst, T * 4) || !al((void**)&cpose_full, cpf.size() * 4) ||
           !up(cs_ptr, csptr.data(), (T + 1) * 4) || !up(cs_full, csfull.data(), csfull.size() * 4) || !up(tconst, htc.data(), T * 4) ||
           !up(cpose_full, cpf.data(), cpf.size() * 4))
+        return RSBA_ERR_HIP;
+    }
+    if (with_subset) {
+      if (!al((void**)&tflags, (size_t)T * 4) || !al((void**)&rmask, hrmask.size()) || !up(tflags, htflags.data(), (size_t)T * 4) || !up(rmask, hrmask.data(), hrmask.size()))
         return RSBA_ERR_HIP;
     }
     if (nr == 0) {
@@ -1705,9 +1725,17 @@ struct MarkerSchurDevice {
         if (with_loss) RSBA_DIST_SWITCH(k_mc_slot_products<true, D><<<(nslots + 255) / 256, 256, 0, st>>>(split_args(std::integral_constant<bool, D>())));
         else RSBA_DIST_SWITCH(k_mc_slot_products<false, D><<<(nslots + 255) / 256, 256, 0, st>>>(split_args(std::integral_constant<bool, D>())));
         Tm.End(st);
+        if (with_subset) {
+          Tm.Begin("k_mc_subset_slots", st);
+          k_mc_subset_slots<<<(unsigned)(((size_t)nslots * 64 + 255) / 256), 256, 0, st>>>(nslots, slot_time, slot_col, tflags, rmask, sp);
+          Tm.End(st);
+        }
       }
       Tm.Begin("k_mc_time_products", st);
-      if (has_const) {
+      if (with_subset) {
+        if (with_loss) RSBA_DIST_SWITCH(k_mc_time_products<true, true, D, true><<<(T + 3) / 4, 256, 0, s_time>>>(split_args(std::integral_constant<bool, D>()), ip, params[x], scale_t, tdata, tscal, tflags));
+        else RSBA_DIST_SWITCH(k_mc_time_products<false, true, D, true><<<(T + 3) / 4, 256, 0, s_time>>>(split_args(std::integral_constant<bool, D>()), ip, params[x], scale_t, tdata, tscal, tflags));
+      } else if (has_const) {
         if (with_loss) RSBA_DIST_SWITCH(k_mc_time_products<true, true, D><<<(T + 3) / 4, 256, 0, s_time>>>(split_args(std::integral_constant<bool, D>()), ip, params[x], scale_t, tdata, tscal, tconst));
         else RSBA_DIST_SWITCH(k_mc_time_products<false, true, D><<<(T + 3) / 4, 256, 0, s_time>>>(split_args(std::integral_constant<bool, D>()), ip, params[x], scale_t, tdata, tscal, tconst));
       } else {
@@ -1720,6 +1748,11 @@ struct MarkerSchurDevice {
         if (with_loss) RSBA_DIST_SWITCH(k_mc_cross<true, D><<<(nx_threads + 255) / 256, 256, 0, s_cross>>>(split_args(std::integral_constant<bool, D>())));
         else RSBA_DIST_SWITCH(k_mc_cross<false, D><<<(nx_threads + 255) / 256, 256, 0, s_cross>>>(split_args(std::integral_constant<bool, D>())));
         Tm.End(st);
+        if (with_subset) {
+          Tm.Begin("k_mc_subset_cross", st);
+          k_mc_subset_cross<<<(unsigned)(((size_t)nx * 36 + 255) / 256), 256, 0, s_cross>>>(nx, xi_cc, xi_cm, rmask, xout);
+          Tm.End(st);
+        }
       }
       if (fork) {
         if (hipEventRecord(fork_ev[1], s_time) != hipSuccess || hipEventRecord(fork_ev[2], s_cross) != hipSuccess ||

@@ -300,7 +300,11 @@ __global__ void __launch_bounds__(256) k_mc_slot_products(typename SplitArgT<kDi
 // positive definite, max |g_t|.  kLoss: V, g_t and so the time's Jacobi scale from the corrected rows.  kConst: the camera and marker
 // poses through the residual blocks' full offsets (a constant block has no column); a constant time (tconst[t] = 1) gets E = 0 and only
 // its cost.
-template <bool kLoss, bool kConst = false, bool kDist = false>
+// kSub (with kConst): tconst[t] holds the time's flags — bit 0 the constant time, bits 8..13 its constant components
+// (ceres::SubsetParameterization).  The rows and columns of a constant component leave V and its entry leaves g_t once the lanes' sums
+// are in (what zero columns of J_t give, exactly), and it gets a unit diagonal: decoupled from the free components in V + D and in E
+// whatever the damping options, E g_t = 0 there.  |x_t|^2 stays that of all six (Ceres' norms are ambient).
+template <bool kLoss, bool kConst = false, bool kDist = false, bool kSub = false>
 __global__ void __launch_bounds__(256) k_mc_time_products(typename SplitArgT<kDist>::type a, IterParams ip, const double* __restrict__ params_x, double* __restrict__ scale_t,
                                                           double* __restrict__ tdata, double* __restrict__ tscal, const int* __restrict__ tconst = nullptr) {
   __shared__ double s_v[4][3 * 36 + 8];
@@ -353,8 +357,19 @@ __global__ void __launch_bounds__(256) k_mc_time_products(typename SplitArgT<kDi
     if constexpr (kLoss) corr += __shfl_xor(corr, off, 64);
   }
   if constexpr (kLoss) ss += corr;
+  if constexpr (kSub) {
+    const int sub = tconst[t] >> 8;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {
+      if ((sub >> q) & 1) {
+        g[q] = 0.0;
+#pragma unroll
+        for (int p = 0; p < 6; ++p) { const int hi = p > q ? p : q, lo = p > q ? q : p; V[hi * (hi + 1) / 2 + lo] = p == q ? 1.0 : 0.0; }
+      }
+    }
+  }
   if constexpr (kConst) {
-    if (tconst[t]) {   // (wave-uniform)
+    if (kSub ? (tconst[t] & 1) != 0 : tconst[t] != 0) {   // (wave-uniform)
       double* td = tdata + (size_t)t * 48;
       if (lane < 36) td[lane] = 0.0;
 #pragma unroll
@@ -473,6 +488,43 @@ __global__ void __launch_bounds__(256) k_mc_cross(typename SplitArgT<kDist>::typ
   double* out = a.xout + (size_t)it * 36;
 #pragma unroll
   for (int i = 0; i < 36; ++i) out[i] = X[i];
+}
+
+// Constant components of partly constant blocks (rsba_problem_set_parameter_subset_constant) on the small products, once they are
+// formed — the rows are formed as without them, so every product kernel is the instance it was:
+//   k_mc_subset_slots   thread per entry of a (time, slot) record: W loses the rows of the time's constant components and the columns
+//                       of the slot block's, g_s its entries, U_ss their rows and columns — exact zeros, what zero columns of J give —
+//                       and U_ss gets a one on their diagonal.  The reduced system's diagonal there is the number of the column's
+//                       records (>= 1), its row, column and both right-hand sides zero: decoupled, a positive pivot whatever the
+//                       damping options, a zero step, in all three reduced solves and both accumulations, none of which changes.
+//   k_mc_subset_cross   thread per entry of U_cm: the marker block's rows, the camera block's columns.
+// tflags: [T] bits 8..13 a time's mask (bit 0: a constant time); rmask: the mask of each reduced block (column / 6).
+__global__ void __launch_bounds__(256) k_mc_subset_slots(int nslots, const int* __restrict__ slot_time, const int* __restrict__ slot_col,
+                                                         const int* __restrict__ tflags, const unsigned char* __restrict__ rmask, double* __restrict__ sp) {
+  const int g = blockIdx.x * 256 + threadIdx.x, S = g >> 6, i = g & 63;
+  if (S >= nslots || i == 63) return;
+  const int tm = tflags[slot_time[S]] >> 8, om = rmask[slot_col[S] / 6];
+  if ((tm | om) == 0) return;
+  double* rec = sp + (size_t)S * RSBA_SP_STRIDE;
+  if (i < 36) {
+    const int x = i / 6, q = i - 6 * x;
+    if (((tm >> x) | (om >> q)) & 1) rec[i] = 0.0;
+  } else if (i < 42) {
+    if ((om >> (i - 36)) & 1) rec[i] = 0.0;
+  } else {
+    const int tri = i - 42;
+    int rq = 0;
+    while ((rq + 1) * (rq + 2) / 2 <= tri) ++rq;
+    const int cq = tri - rq * (rq + 1) / 2;
+    if (((om >> rq) | (om >> cq)) & 1) rec[i] = rq == cq ? 1.0 : 0.0;
+  }
+}
+__global__ void __launch_bounds__(256) k_mc_subset_cross(int nx, const int* __restrict__ xi_cc, const int* __restrict__ xi_cm,
+                                                         const unsigned char* __restrict__ rmask, double* __restrict__ xout) {
+  const int g = blockIdx.x * 256 + threadIdx.x, it = g / 36, q = g - 36 * it;
+  if (it >= nx) return;
+  const int qm = q / 6, qc = q - 6 * qm;
+  if (((rmask[xi_cm[it] / 6] >> qm) | (rmask[xi_cc[it] / 6] >> qc)) & 1) xout[(size_t)it * 36 + q] = 0.0;
 }
 
 struct AccArgs {

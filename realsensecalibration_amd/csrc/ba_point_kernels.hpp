@@ -370,6 +370,10 @@ __device__ __forceinline__ void CameraStepEpilogue(int C, const double* __restri
 #define RSBA_NB 32
 #define RSBA_TB 64
 
+// (kCaller: one instantiation per calling kernel instance.  With a single caller the function is inlined into it; a second caller
+//  of the same function made it a call in both — k_marker_system<1024> lost 25 kB of code and gained 200 bytes of scratch when its
+//  constant-components twin appeared.  The twin instantiates its own copy.)
+template <int kCaller = 0>
 __device__ void CholeskySolveBlocked(int n, double* __restrict__ A, double* __restrict__ x_out, int* ok_out,
                                      double* lds /* >= 2*64*33 + 32*33 doubles */) {
   const int tid = threadIdx.x, nt = blockDim.x;

@@ -28,6 +28,8 @@ struct rsba_problem {
   std::vector<uint8_t> camera_constant;  // point model: 1 = problem.SetParameterBlockConstant(camera); empty = none
   std::vector<uint8_t> point_constant;   // point model: the same for point blocks (round 6)
   std::vector<uint8_t> block_constant;   // marker-chain models: per block of [C cameras | T times | M markers] (round 6); empty = none
+  std::vector<uint8_t> block_subset;     // marker-chain models: per block of [C | T | M] a 6-bit mask, bit q set = component q of (rvec, tvec) is
+                                         // constant (ceres::SubsetParameterization); empty = none
   std::vector<double> observation_weights;   // marker-chain models: a_i >= 0 per residual block (ceres::ScaledLoss); empty = none
   std::vector<double> distortion;     // marker-chain models: 5 per camera (k1 k2 p1 p2 k3, OpenCV), indexed as intrinsics; empty = none
 
@@ -36,6 +38,9 @@ struct rsba_problem {
   bool is_marker_chain() const { return model != RSBA_MODEL_POINTS; }
   // some coefficient is not exactly zero: a solver then runs the distortion instances of its kernels (none, or all zeros: today's)
   bool has_distortion() const { for (double v : distortion) if (v != 0.0) return true; return false; }
+  // some block carries a non-zero subset mask: a solver then masks those components' columns (none, or all zero: today's kernels)
+  bool has_subset() const { for (uint8_t v : block_subset) if (v != 0) return true; return false; }
+  int subset_mask(int block) const { return block >= 0 && block < (int)block_subset.size() ? block_subset[block] : 0; }
   // wiring rules of bundle_adjustment_manager.cpp:26-87 / Test2 main.cpp:64-96
   bool uses_camera(int64_t i) const { return camera_index[i] != 0; }
   bool uses_marker(int64_t i) const { return model == RSBA_MODEL_MARKER_CHAIN_TEST2 ? true : marker_index[i] != 0; }

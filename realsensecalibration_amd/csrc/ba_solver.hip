@@ -299,6 +299,7 @@ struct rsba_solver {
     double *pc = nullptr, *obs = nullptr, *intr = nullptr, *wrow = nullptr;
     int* tptr = nullptr;
     CovMcRow* rows = nullptr;
+    int* sub18 = nullptr;                      // the rows' constant columns (a solver with constant components; else nullptr)
     double loss = 0.0, rcond = 0.0, half_side = 0.0;
     bool use_w = false;
     std::vector<unsigned char> elim;           // per time: eliminated by this compute (free, referenced, time-eliminating path)
@@ -324,6 +325,7 @@ struct rsba_solver {
   EvalDevice eval;
   EvalJacobianDevice eval_jac;   // rsba_solver_jacobian_structure / rsba_solver_evaluate_jacobian (ba_evaluate_jacobian.hpp)
   std::vector<uint8_t> eval_const_cam, eval_const_pt, eval_const_block;   // the problem's constant flags as they were at create
+  std::vector<uint8_t> eval_subset;   // marker chain: the blocks' masks of constant components as they were at create (empty: none set)
 
   // ---- the three above on a solver with a communicator (ShardedQuery): the request word and the camera check travel from here
   double* query_buf = nullptr;                 // device scratch, kept between calls (grows only)
@@ -2016,8 +2018,23 @@ static int CovarianceMarker(rsba_solver* s, const rsba_covariance_options& co) {
     std::vector<int> fw(tptr.begin(), tptr.end() - 1);
     for (int64_t i = 0; i < N; ++i) wrow[fw[p.time_index[i]]++] = s->obs_w[i];
   }
+  // constant components (eval_subset) of the blocks with columns or eliminated: the rows' 18-bit column masks, the blocks' masks
+  std::vector<unsigned char> bsub(nb, 0);
+  bool with_sub = false;
+  for (int b = 0; b < nb && b < (int)s->eval_subset.size(); ++b) if (is_free(b)) { bsub[b] = s->eval_subset[b]; with_sub = with_sub || bsub[b] != 0; }
+  std::vector<int> sub18;
+  if (with_sub) {
+    sub18.resize(rows.size(), 0);
+    for (size_t q = 0; q < (size_t)N; ++q) {
+      const CovMcRow& rw = rows[q];
+      sub18[q] = (rw.cam_block >= 0 ? bsub[rw.cam_block] : 0) | (bsub[rw.time_block] << 6) | (rw.marker_block >= 0 ? bsub[rw.marker_block] << 12 : 0);
+    }
+  }
+  int* sub18_d = nullptr;
+  unsigned char* bsub_d = nullptr;
   double* wrow_d = nullptr;
   auto extra = [&](CovCarve& cv) {
+    if (with_sub) { sub18_d = cv.take<int>(sub18.size()); bsub_d = cv.take<unsigned char>(nb); }
     if (use_w) wrow_d = cv.take<double>(wrow.size());
     pc = cv.take<double>((size_t)CC_STRIDE * nb); obs_d = cv.take<double>(obs.size()); intr = cv.take<double>(p.intrinsics.size());
     pos = cv.take<int>(nb); tptr_d = cv.take<int>(T + 1); rows_d = cv.take<CovMcRow>(rows.size()); elim_d = cv.take<unsigned char>(elim.size());
@@ -2036,7 +2053,18 @@ static int CovarianceMarker(rsba_solver* s, const rsba_covariance_options& co) {
     hip(hipMemcpyAsync(elim_d, elim.data(), elim.size(), hipMemcpyHostToDevice, st));
     if (use_w) hip(hipMemcpyAsync(wrow_d, wrow.data(), wrow.size() * sizeof(double), hipMemcpyHostToDevice, st));
     k_cov_pose_constants<<<(nb + 255) / 256, 256, 0, st>>>(nb, params, pc);
-    if (loss != 0.0 || use_w) {
+    if (with_sub) {
+      hip(hipMemcpyAsync(sub18_d, sub18.data(), sub18.size() * sizeof(int), hipMemcpyHostToDevice, st));
+      hip(hipMemcpyAsync(bsub_d, bsub.data(), nb, hipMemcpyHostToDevice, st));
+      IntrDistSub ids; ids.intr = intr; ids.dist = s->dist_dev; ids.sub18 = sub18_d;
+      const int grid = std::max(1, std::min(T, 4096));
+      const bool lossy = loss != 0.0 || use_w;
+      if (lossy && s->dist_dev) k_cov_mc_lin<true, true, true><<<grid, 64, 0, st>>>(T, tptr_d, rows_d, obs_d, ids, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags, loss, wrow_d);
+      else if (lossy) k_cov_mc_lin<true, false, true><<<grid, 64, 0, st>>>(T, tptr_d, rows_d, obs_d, ids, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags, loss, wrow_d);
+      else if (s->dist_dev) k_cov_mc_lin<false, true, true><<<grid, 64, 0, st>>>(T, tptr_d, rows_d, obs_d, ids, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags);
+      else k_cov_mc_lin<false, false, true><<<grid, 64, 0, st>>>(T, tptr_d, rows_d, obs_d, ids, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags);
+      k_cov_subset_diag<<<(6 * nb + 255) / 256, 256, 0, st>>>(nb, pos, bsub_d, y.n, y.S);
+    } else if (loss != 0.0 || use_w) {
       if (s->dist_dev) k_cov_mc_lin<true, true><<<std::max(1, std::min(T, 4096)), 64, 0, st>>>(T, tptr_d, rows_d, obs_d, IntrDist{intr, s->dist_dev}, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags, loss, wrow_d);
       else k_cov_mc_lin<true><<<std::max(1, std::min(T, 4096)), 64, 0, st>>>(T, tptr_d, rows_d, obs_d, intr, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags, loss, wrow_d);
     } else if (s->dist_dev) {
@@ -2046,6 +2074,12 @@ static int CovarianceMarker(rsba_solver* s, const rsba_covariance_options& co) {
     }
     // (the host vectors outlive CovRun, which synchronises the stream before it returns)
   }, [](CovSystem&, auto&) { return RSBA_OK; });
+  if (rc == RSBA_OK && with_sub && n > 0) {
+    // the lift through the parameterisations' Jacobians: zeros in the constant components' rows and columns of S^-1
+    k_cov_subset_sinv<<<nb, 256, 0, st>>>(pos, bsub_d, n, s->cov_sinv);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { s->cov_valid = false; return RSBA_ERR_HIP; }
+  }
+  s->cov_mc.sub18 = with_sub ? sub18_d : nullptr;
   // the snapshot of the pair queries: the carved pointers and what the linearisation was told
   s->cov_mc.pc = pc; s->cov_mc.obs = obs_d; s->cov_mc.intr = intr; s->cov_mc.wrow = wrow_d; s->cov_mc.tptr = tptr_d; s->cov_mc.rows = rows_d;
   s->cov_mc.loss = loss; s->cov_mc.rcond = rcond; s->cov_mc.half_side = p.marker_side / 2; s->cov_mc.use_w = use_w;
@@ -2182,7 +2216,11 @@ static int CovQueue(rsba_solver* s, const CovRequests& rq, size_t slots, double*
     CovMcSnap sn{m.tptr, m.rows, m.obs, m.intr, m.pc, m.use_w ? m.wrow : nullptr, s->cov_dptr, s->cov_dpos, s->cov_rslot,
                  m.half_side, m.rcond, m.loss, m.loss != 0.0 || m.use_w ? 1 : 0, s->cov_n};
     CovMcSnapDist snd; static_cast<CovMcSnap&>(snd) = sn; snd.dist = s->dist_dev;
-    if (s->dist_dev) k_cov_mc_cross<true><<<(int)std::min<size_t>(nm, 4096), 64, 0, st>>>((int)nm, req_d + ng, snd, s->cov_sinv, stage_d);
+    if (m.sub18) {
+      CovMcSnapSub sns; static_cast<CovMcSnapDist&>(sns) = snd; sns.sub18 = m.sub18;
+      if (s->dist_dev) k_cov_mc_cross<true, true><<<(int)std::min<size_t>(nm, 4096), 64, 0, st>>>((int)nm, req_d + ng, sns, s->cov_sinv, stage_d);
+      else k_cov_mc_cross<false, true><<<(int)std::min<size_t>(nm, 4096), 64, 0, st>>>((int)nm, req_d + ng, sns, s->cov_sinv, stage_d);
+    } else if (s->dist_dev) k_cov_mc_cross<true><<<(int)std::min<size_t>(nm, 4096), 64, 0, st>>>((int)nm, req_d + ng, snd, s->cov_sinv, stage_d);
     else k_cov_mc_cross<false><<<(int)std::min<size_t>(nm, 4096), 64, 0, st>>>((int)nm, req_d + ng, sn, s->cov_sinv, stage_d);
   }
   if (np > 0) {
@@ -2331,6 +2369,12 @@ static int EvalBuildTables(rsba_solver* s) {
         (rc = EvalUpload(&e.list_ptr, lists.ptr)) || (rc = EvalUpload(&e.list_obs, lists.obs)) || (rc = EvalUpload(&e.list_slot, lists.slot)) ||
         (rc = EvalUpload(&e.live, live)))
       return rc;
+    if (!s->eval_subset.empty()) {
+      // the masks of the blocks whose gradient is computed (a constant, base or unreferenced block's is ignored)
+      std::vector<unsigned char> bsub(nb, 0);
+      for (int b = 0; b < nb && b < (int)s->eval_subset.size(); ++b) bsub[b] = live[b] ? s->eval_subset[b] : 0;
+      if ((rc = EvalUpload(&e.bsub, bsub))) return rc;
+    }
   }
   return RSBA_OK;
 }
@@ -2395,6 +2439,7 @@ static int EvaluateOnDevice(rsba_solver* s, bool apply_loss, double* cost, doubl
       if (s->dist_dev) k_eval_marker<true, true><<<grid, 64, 0, st>>>((int)N, e.rows, e.obs8, IntrDist{e.intr, s->dist_dev}, posec, p.marker_side / 2, loss, res_d, work, cost_parts, wts);
       else k_eval_marker<true><<<grid, 64, 0, st>>>((int)N, e.rows, e.obs8, e.intr, posec, p.marker_side / 2, loss, res_d, work, cost_parts, wts);
       k_eval_marker_block_sum<<<nb, 256, 0, st>>>(e.list_ptr, e.list_obs, e.list_slot, work, e.live, grad_d);
+      if (e.bsub) k_eval_subset_gradient<<<(6 * nb + 255) / 256, 256, 0, st>>>(nb, e.bsub, grad_d);
     } else {
       if (s->dist_dev) k_eval_marker<false, true><<<grid, 64, 0, st>>>((int)N, e.rows, e.obs8, IntrDist{e.intr, s->dist_dev}, posec, p.marker_side / 2, loss, res_d, nullptr, cost_parts, wts);
       else k_eval_marker<false><<<grid, 64, 0, st>>>((int)N, e.rows, e.obs8, e.intr, posec, p.marker_side / 2, loss, res_d, nullptr, cost_parts, wts);
@@ -2526,6 +2571,7 @@ static int JacobianOnDevice(rsba_solver* s, bool apply_loss, double* values) {
                                                                                  apply_loss && s->weights_given ? s->obs_w_dev : nullptr);
     else k_eval_jacobian_marker<false><<<(N + 63) / 64, 64, 0, st>>>(N, e.rows, e.obs8, e.intr, posec, j.off, e.live, p.marker_side / 2, loss, values_d,
                                                                       apply_loss && s->weights_given ? s->obs_w_dev : nullptr);
+    if (e.bsub) k_eval_jacobian_subset<<<(N + 63) / 64, 64, 0, st>>>(N, e.rows, j.off, e.live, e.bsub, values_d);
   }
   rc = RSBA_OK;
   auto hip = [&](hipError_t err) { if (err != hipSuccess && rc == RSBA_OK) rc = RSBA_ERR_HIP; };
@@ -2689,6 +2735,7 @@ int rsba_solver_create(rsba_problem* p, const rsba_options* o, rsba_solver** out
     }
   }
   s->eval_const_cam = p->camera_constant; s->eval_const_pt = p->point_constant; s->eval_const_block = p->block_constant;
+  if (p->is_marker_chain() && p->has_subset()) s->eval_subset = p->block_subset;   // (fixed here, like the constant flags)
   if (rc == RSBA_OK && hipDeviceSynchronize() != hipSuccess) rc = RSBA_ERR_HIP;
   if (rc != RSBA_OK) { if (comm_keep) comm_keep->Abort(); rsba::FreeSolver(s); return rc; }
   s->setup_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

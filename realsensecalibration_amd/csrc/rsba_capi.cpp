@@ -97,6 +97,20 @@ int rsba_problem_set_parameter_block_constant(rsba_problem* p, int64_t parameter
   p->block_constant[(size_t)(parameter_offset / 6)] = constant ? 1 : 0;
   return RSBA_OK;
 }
+int rsba_problem_set_parameter_subset_constant(rsba_problem* p, int64_t parameter_offset, int32_t constant_mask) {
+  if (!p) return RSBA_ERR_ARG;
+  if (!p->is_marker_chain()) return RSBA_ERR_UNSUPPORTED;   // the point model's camera rows sit in the headline kernels
+  const int64_t nblocks = (int64_t)p->num_cameras + p->num_times + p->num_markers;
+  if (parameter_offset < 0 || parameter_offset >= 6 * nblocks || parameter_offset % 6) return RSBA_ERR_ARG;
+  if (constant_mask < 0 || constant_mask >= 63) return RSBA_ERR_ARG;   // all six: the block call (Ceres 1.14 CHECK-fails)
+  if (p->block_subset.empty()) p->block_subset.assign((size_t)nblocks, 0);
+  p->block_subset[(size_t)(parameter_offset / 6)] = (uint8_t)constant_mask;
+  return RSBA_OK;
+}
+int32_t rsba_problem_parameter_subset_constant(const rsba_problem* p, int64_t parameter_offset) {
+  if (!p || !p->is_marker_chain() || parameter_offset < 0 || parameter_offset % 6) return 0;
+  return parameter_offset / 6 < (int64_t)p->block_subset.size() ? p->block_subset[(size_t)(parameter_offset / 6)] : 0;
+}
 int rsba_problem_set_observation_weights(rsba_problem* p, const double* weights) {
   if (!p) return RSBA_ERR_ARG;
   if (!p->is_marker_chain()) return RSBA_ERR_UNSUPPORTED;   // the point model's loss sites take no per-observation factor

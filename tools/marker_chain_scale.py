@@ -1,11 +1,13 @@
 """Marker-chain model at scale on the GPU: per-kernel times of the time-elimination path.
 
-    python tools/marker_chain_scale.py [C T M [huber|cauchy a]] [const=SET] [schur_impl=K] [dump=PATH] [weights=FRAC] [dist=SEED]
+    python tools/marker_chain_scale.py [C T M [huber|cauchy a]] [const=SET] [schur_impl=K] [dump=PATH] [weights=FRAC] [dist=SEED] [subset=FRAC]
         default 8 5000 16, no loss; SET: markers | cameras:K (cameras 1..K) | times:K (every T/K-th time) | rig (every camera
         and marker: only the times are free), joined by '+' (e.g. cameras:2+times:100); dump=PATH writes the final parameters
         and the iteration log (.npz) of the last unprofiled run; weights=FRAC: observation weights on the problem (ceres::ScaledLoss),
         that fraction of the residual blocks (seeded) at weight 0 and the rest at 1 — 0 asks for all ones; dist=SEED: lens distortion,
-        tests/marker_distortion_ref.py's coefficients(C, SEED) on the problem and its detections redetected through them
+        tests/marker_distortion_ref.py's coefficients(C, SEED) on the problem and its detections redetected through them;
+        subset=FRAC: constant components (ceres::SubsetParameterization) — that fraction of the camera, time and marker blocks
+        (seeded) each get a random mask of one to five components
 """
 import json
 import os
@@ -56,6 +58,13 @@ for b in CONST:
 WEIGHTS = float(KW["weights"]) if "weights" in KW else None
 if WEIGHTS is not None:
     p.set_observation_weights(np.where(np.random.default_rng(12).random(prob["N"]) < WEIGHTS, 0.0, 1.0))
+SUBSET = float(KW["subset"]) if "subset" in KW else None
+NSUB = 0
+if SUBSET:
+    rng = np.random.default_rng(13)
+    for b in np.flatnonzero(rng.random(C_ + T_ + M_) < SUBSET):
+        p.set_parameter_subset_constant(6 * int(b), int(rng.integers(1, 63)))
+        NSUB += 1
 out = {}
 for mode in (0, 1):
     s = capi.Solver(p, capi.default_options(profile_kernels=mode, schur_impl=int(KW.get("schur_impl", 1)), **LOSS_KW))
@@ -67,6 +76,7 @@ for mode in (0, 1):
         out["constant_blocks"] = len(CONST)
         out["zero_weight_fraction"] = WEIGHTS
         out["distortion_seed"] = DIST
+        out["subset_blocks"] = NSUB
         out["eliminates_times"] = s.eliminates_times()
         if "dump" in KW:
             s.download()
