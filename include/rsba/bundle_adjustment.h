@@ -85,6 +85,12 @@ class BALProblem {
     for (int q : constant_parameters) { if (q < 0 || q > 5) return false; mask |= 1 << q; }
     return rsba_problem_set_parameter_subset_constant(p_, block - rsba_problem_parameters(p_), mask) == RSBA_OK;
   }
+  // problem.AddResidualBlock(new ceres::NormalPrior(A, b), NULL, block) on a camera or marker block handed out by the mutable_*
+  // accessors above (rsba_problem_set_block_prior): A 6 x 6 row-major, b 6; A = nullptr removes the prior.  False for a pointer that
+  // starts no such block, a fixed base block, a time block or a non-finite value.
+  bool SetNormalPrior(double* block, const double* A, const double* b) {
+    return rsba_problem_set_block_prior(p_, block - rsba_problem_parameters(p_), A, b) == RSBA_OK;
+  }
   // Test1 accessors
   double* mutable_cameras() { return rsba_problem_parameters(p_); }
   double* mutable_points() { return rsba_problem_parameters(p_) + 6 * num_cameras(); }

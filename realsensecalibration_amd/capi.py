@@ -36,6 +36,7 @@ EXPORTS = [
     "rsba_solver_comm_abort",
     "rsba_problem_set_observation_weights", "rsba_problem_observation_weights", "rsba_solver_set_observation_weights",
     "rsba_problem_set_parameter_subset_constant", "rsba_problem_parameter_subset_constant", "rsba_problem_set_distortion", "rsba_problem_distortion", "rsba_read_intrinsics_xml_dist", "rsba_undistort_points",
+    "rsba_problem_set_block_prior", "rsba_problem_block_prior", "rsba_problem_num_block_priors", "rsba_solver_set_block_prior",
 ]
 _SYMBOLS = EXPORTS   # (every symbol of include/rsba.h that load() checks)
 
@@ -184,6 +185,11 @@ def load():
     lib.rsba_problem_distortion.restype = C.POINTER(C.c_double)
     lib.rsba_read_intrinsics_xml_dist.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p]
     lib.rsba_undistort_points.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rsba_problem_set_block_prior.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.rsba_problem_block_prior.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.rsba_problem_num_block_priors.argtypes = [C.c_void_p]
+    lib.rsba_problem_num_block_priors.restype = C.c_int32
+    lib.rsba_solver_set_block_prior.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     _LIB = lib
     return lib
 
@@ -207,6 +213,16 @@ def default_options(**kw):
 
 def _vp(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def _prior_arrays(A, b):
+    A = np.ascontiguousarray(A, np.float64)
+    b = np.ascontiguousarray(b, np.float64)
+    if A.ndim != 2 or A.shape[1] != 6 or not 1 <= A.shape[0] <= 6 or b.shape != (6,):
+        raise ValueError("a block prior takes A of up to 6 x 6 and b of 6 values")
+    full = np.zeros((6, 6))
+    full[:A.shape[0]] = A
+    return full, b
 
 
 class Problem:
@@ -352,6 +368,24 @@ class Problem:
         """A copy of the problem's distortion coefficients (C x 5), or None when it has none."""
         q = load().rsba_problem_distortion(self.h)
         return np.ctypeslib.as_array(q, shape=(self.num_cameras, 5)).copy() if q else None
+
+    def set_block_prior(self, parameter_offset, A, b=None):
+        """Marker-chain models: a Gaussian prior (ceres::NormalPrior) on the camera or marker block at `parameter_offset`: the
+        residual A (x - b), A 6 x 6 (fewer rows: zero rows), b 6, no loss.  A = None removes it."""
+        if A is None:
+            _chk(load().rsba_problem_set_block_prior(self.h, parameter_offset, None, None), "rsba_problem_set_block_prior")
+            return
+        A, b = _prior_arrays(A, b)
+        _chk(load().rsba_problem_set_block_prior(self.h, parameter_offset, _vp(A), _vp(b)), "rsba_problem_set_block_prior")
+
+    def block_prior(self, parameter_offset):
+        """(A 6 x 6, b 6) of the block's prior, or None when it has none."""
+        A, b = np.zeros((6, 6)), np.zeros(6)
+        return (A, b) if load().rsba_problem_block_prior(self.h, parameter_offset, _vp(A), _vp(b)) else None
+
+    @property
+    def num_block_priors(self):
+        return int(load().rsba_problem_num_block_priors(self.h))
 
     def initial_camera_poses(self):
         _chk(load().rsba_problem_initial_camera_poses(self.h), "rsba_problem_initial_camera_poses")
@@ -555,6 +589,12 @@ class Solver:
         if w.shape != (self.problem.num_observations,):
             raise ValueError("set_observation_weights: %d values expected" % self.problem.num_observations)
         _chk(load().rsba_solver_set_observation_weights(self.h, _vp(w)), "rsba_solver_set_observation_weights")
+
+    def set_block_prior(self, parameter_offset, A, b):
+        """New (A, b) for a block that had a prior when the solver was created, for the next run(), evaluate(), Jacobian or
+        covariance_compute(); parameters, log and summary stay."""
+        A, b = _prior_arrays(A, b)
+        _chk(load().rsba_solver_set_block_prior(self.h, parameter_offset, _vp(A), _vp(b)), "rsba_solver_set_block_prior")
 
     def final_costs(self):
         c, ss = C.c_double(), C.c_double()

@@ -539,6 +539,19 @@ __global__ void __launch_bounds__(256) k_cov_subset_diag(int nb, const int* __re
   const size_t i = (size_t)pos[b] + q;
   S[i * n + i] = 1.0;
 }
+// The priors of a marker-chain solver (PriorDevice): S += A~'A~ on the diagonal 6 x 6 of every prior block with columns in S, behind
+// k_cov_mc_lin and in front of k_cov_subset_diag / the scaling.  A~: A without the columns of the block's constant components.
+// Thread per entry; a block carries at most one prior, so no two threads meet.
+__global__ void __launch_bounds__(256) k_cov_prior(int K, const int* __restrict__ full, const int* __restrict__ mask, const double* __restrict__ ab,
+                                                   const int* __restrict__ pos, int n, double* __restrict__ S) {
+  const int e = blockIdx.x * 256 + threadIdx.x, k = e / 36, a = (e - 36 * k) / 6, c = (e - 36 * k) % 6;
+  if (k >= K) return;
+  const int p0 = pos[full[k] / 6];
+  if (p0 < 0 || ((mask[k] >> a) & 1) || ((mask[k] >> c) & 1)) return;
+  double h = 0.0;
+  for (int i = 0; i < 6; ++i) h += ab[42 * (size_t)k + 6 * i + a] * ab[42 * (size_t)k + 6 * i + c];
+  S[(size_t)(p0 + a) * n + (p0 + c)] += h;
+}
 // S^-1: the rows and columns of the constant components as exact zeros (workgroup per block)
 __global__ void __launch_bounds__(256) k_cov_subset_sinv(const int* __restrict__ pos, const unsigned char* __restrict__ bsub, int n, double* __restrict__ Sinv) {
   const int b = blockIdx.x, sub = bsub[b];

@@ -238,6 +238,35 @@ __global__ void __launch_bounds__(256) k_eval_cost(int n, const double* __restri
   if (threadIdx.x == 0) *cost = 0.5 * v[0];
 }
 
+// The priors of a marker-chain solver (PriorDevice, ba_marker_kernels.hpp) behind the observations' work: residuals A (x - b) (six per
+// prior, ascending parameter offset; res: where the first goes, or nullptr), A~'A (x - b) added to the gradient slots of a block with
+// columns (col >= 0; A~: without the columns of its constant components, whose slots stay 0.0) and sum |A (x - b)|^2 as one more of
+// the cost's partials, summed over the priors in order by thread 0.  No loss applies to a prior.  One workgroup, thread per prior.
+__global__ void __launch_bounds__(256) k_eval_prior(int K, const int* __restrict__ full, const int* __restrict__ col, const int* __restrict__ mask,
+                                                    const double* __restrict__ ab, const double* __restrict__ params, double* __restrict__ res,
+                                                    double* __restrict__ gradient, double* __restrict__ pe, double* __restrict__ cost_part) {
+  for (int k = threadIdx.x; k < K; k += 256) {
+    const double* __restrict__ A = ab + 42 * (size_t)k;
+    const double* __restrict__ x = params + full[k];
+    double d[6], r[6], ss = 0.0;
+    for (int q = 0; q < 6; ++q) d[q] = x[q] - A[36 + q];
+    for (int i = 0; i < 6; ++i) { double t = 0.0; for (int q = 0; q < 6; ++q) t += A[6 * i + q] * d[q]; r[i] = t; ss += t * t; }
+    pe[k] = ss;
+    if (res) for (int i = 0; i < 6; ++i) res[6 * (size_t)k + i] = r[i];
+    if (gradient && col[k] >= 0) {
+      for (int q = 0; q < 6; ++q) {
+        if ((mask[k] >> q) & 1) continue;
+        double g = 0.0;
+        for (int i = 0; i < 6; ++i) g += A[6 * i + q] * r[i];
+        gradient[full[k] + q] += g;
+      }
+    }
+  }
+  __threadfence_block();
+  __syncthreads();
+  if (threadIdx.x == 0) { double t = 0.0; for (int k = 0; k < K; ++k) t += pe[k]; *cost_part = t; }
+}
+
 // Point model on a sharded solver: what the ranks add up, [cost | 6C camera gradient | C "some observation of mine references
 // camera c" flags], from this rank's cost and k_eval_cam_sum's output (the shard's own sums; 0.0 where the shard has nothing).
 // grad false: the cost alone.

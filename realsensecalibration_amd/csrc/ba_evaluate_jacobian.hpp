@@ -153,4 +153,16 @@ struct EvalJacobianDevice {
   }
 };
 
+// The priors' rows of the CRS Jacobian, behind the observations' values (base: their count): six rows of six values A[i][q] per prior
+// whose block has columns (col >= 0), in the priors' order; exact 0.0 in the columns of constant components; none for a prior on a
+// constant block (its rows are empty).  Thread per value.
+__global__ void __launch_bounds__(256) k_eval_jacobian_prior(int K, const int* __restrict__ col, const int* __restrict__ mask, const double* __restrict__ ab,
+                                                             int64_t base, double* __restrict__ values) {
+  const int e = blockIdx.x * 256 + threadIdx.x, k = e / 36, iq = e - 36 * k;
+  if (k >= K || col[k] < 0) return;
+  int before = 0;
+  for (int j = 0; j < k; ++j) before += col[j] >= 0 ? 1 : 0;
+  values[base + 36 * (int64_t)before + iq] = ((mask[k] >> (iq % 6)) & 1) ? 0.0 : ab[42 * (size_t)k + iq];
+}
+
 }  // namespace rsba

@@ -326,6 +326,80 @@ k_marker_candidate(int N, const MarkerObs* __restrict__ mo, const double* __rest
 
 class KernelTimer;
 
+// Gaussian priors on camera and marker blocks (rsba_problem_set_block_prior, ceres::NormalPrior): the residual A (x - b) of a block, no
+// loss.  The tables of a solver created with K priors, in ascending parameter offset; which blocks carry one is fixed at create, the
+// values (ab) can be replaced (Set).
+struct PriorDevice {
+  int K = 0;
+  int *full = nullptr;   // [K] the block's offset in the full parameter array
+  int *col = nullptr;    // [K] its first column in the path's linear system (active / reduced), -1: constant as a whole
+  int *mask = nullptr;   // [K] its constant components (bit q), 0 for a constant block
+  double* ab = nullptr;  // [K][42] A row-major, then b
+  std::vector<int> hfull, hcol;   // (the host's copies: the setter and the Jacobian's structure)
+  void Free() { for (void* q : {(void*)full, (void*)col, (void*)mask, (void*)ab}) if (q) (void)hipFree(q); full = col = mask = nullptr; ab = nullptr; K = 0; }
+  // cols: per prior of the problem (the map's order = ascending offset) its first column
+  int Upload(const rsba_problem& p, const std::vector<int>& cols) {
+    K = (int)p.block_priors.size();
+    hcol = cols;
+    if (K == 0) return RSBA_OK;
+    std::vector<int> hmask; std::vector<double> hab;
+    hfull.clear();
+    int k = 0;
+    for (const auto& kv : p.block_priors) {
+      hfull.push_back(6 * kv.first); hmask.push_back(cols[k] >= 0 ? p.subset_mask(kv.first) : 0);
+      hab.insert(hab.end(), kv.second.begin(), kv.second.end()); ++k;
+    }
+    if (hipMalloc((void**)&full, K * 4) != hipSuccess || hipMalloc((void**)&col, K * 4) != hipSuccess || hipMalloc((void**)&mask, K * 4) != hipSuccess ||
+        hipMalloc((void**)&ab, (size_t)K * 42 * 8) != hipSuccess) return RSBA_ERR_HIP;
+    if (hipMemcpy(full, hfull.data(), K * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(col, cols.data(), K * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(mask, hmask.data(), K * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(ab, hab.data(), (size_t)K * 42 * 8, hipMemcpyHostToDevice) != hipSuccess)
+      return RSBA_ERR_HIP;
+    return RSBA_OK;
+  }
+  // new values for the prior of the block at `offset`: RSBA_ERR_UNSUPPORTED when the block had none at create
+  int Set(int64_t offset, const double* A, const double* b) {
+    if (offset < 0 || offset > INT32_MAX) return RSBA_ERR_UNSUPPORTED;
+    const auto it = std::lower_bound(hfull.begin(), hfull.end(), (int)offset);
+    if (it == hfull.end() || *it != offset) return RSBA_ERR_UNSUPPORTED;
+    double v[42];
+    memcpy(v, A, 36 * 8); memcpy(v + 36, b, 6 * 8);
+    return hipMemcpy(ab + 42 * (size_t)(it - hfull.begin()), v, sizeof(v), hipMemcpyHostToDevice) == hipSuccess ? RSBA_OK : RSBA_ERR_HIP;
+  }
+};
+
+// The priors as K pseudo residual blocks behind the N observations' (dense path): rows 0..5 of block N + k hold A in the column group
+// of its block (camera: 0..5, marker: 12..17; exact zeros in the columns of constant components and everywhere else), rows 6..7 are
+// zero, r = A (x - b).  rho gets |r|^2 (what k_marker_system / k_marker_candidate sum into the cost: a solver with priors runs the
+// loss instances), the raw sum of squares 0.0: the reprojection metric never sees a prior.  with_rows = 0: the candidate, sums only.
+// Thread per prior.
+__global__ void __launch_bounds__(64) k_marker_prior_rows(int K, int N, const MarkerObs* __restrict__ mo, const int* __restrict__ mask,
+                                                          const double* __restrict__ ab, const double* __restrict__ params, int with_rows,
+                                                          double* __restrict__ Jbuf, double* __restrict__ rbuf, double* __restrict__ sumsq,
+                                                          double* __restrict__ rho) {
+  const int k = blockIdx.x * 64 + threadIdx.x;
+  if (k >= K) return;
+  const MarkerObs o = mo[N + k];
+  const int g = o.full_cam >= 0 ? 0 : 12;
+  const double* __restrict__ A = ab + 42 * (size_t)k;
+  const double* __restrict__ x = params + (o.full_cam >= 0 ? o.full_cam : o.full_marker);
+  double d[6], ss = 0.0;
+  for (int q = 0; q < 6; ++q) d[q] = x[q] - A[36 + q];
+  for (int i = 0; i < 8; ++i) {
+    double r = 0.0;
+    if (i < 6) for (int q = 0; q < 6; ++q) r += A[6 * i + q] * d[q];
+    ss += r * r;
+    if (with_rows) {
+      rbuf[8 * (size_t)(N + k) + i] = r;
+      double* __restrict__ row = Jbuf + ((size_t)(N + k) * 8 + i) * 18;
+      for (int q = 0; q < 18; ++q) row[q] = 0.0;
+      if (i < 6) for (int q = 0; q < 6; ++q) row[g + q] = ((mask[k] >> q) & 1) ? 0.0 : A[6 * i + q];
+    }
+  }
+  sumsq[N + k] = 0.0;
+  rho[N + k] = ss;
+}
+
+
 struct MarkerDevice {
   int N = 0, n = 0, nfull = 0;
   double half_side = 0;
@@ -341,8 +415,10 @@ struct MarkerDevice {
   bool with_subset = false; // some block in the program has constant components (Upload): k_marker_subset_rows and k_marker_system<., true>
   bool with_dist = false;   // the kDist instances (Upload): some distortion coefficient of the problem is not zero
   double* dist = nullptr;   // [C][5], indexed as intr
+  PriorDevice prior;        // K priors: K pseudo residual blocks behind the N observations' (k_marker_prior_rows); with_loss then
 
   void Free() {
+    prior.Free();
     void* ptrs[] = {mo, obs8, intr, params[0], params[1], params0, Jbuf, rbuf, ss_x, ss_c, A, scale, grad, delta, res, act_to_full, rho_x, rho_c, wts, dist};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     mo = nullptr;
@@ -367,7 +443,21 @@ struct MarkerDevice {
       for (int q = 0; q < 6; ++q) a2f.push_back((6 * b + q) | (((mask >> q) & 1) ? RSBA_SUBSET_BIT : 0));
     }
     n = 6 * na;
-    std::vector<MarkerObs> h(N);
+    const int K = (int)p.block_priors.size();
+    std::vector<int> pcols;
+    std::vector<MarkerObs> h(N + K);
+    {
+      int k = 0;
+      for (const auto& kv : p.block_priors) {
+        const int b = kv.first;
+        MarkerObs& o = h[N + k++];
+        o.full_cam = b < p.num_cameras ? 6 * b : -1; o.full_time = -1; o.full_marker = b < p.num_cameras ? -1 : 6 * b;
+        o.act_cam = b < p.num_cameras ? act[b] : -1; o.act_time = -1; o.act_marker = b < p.num_cameras ? -1 : act[b];
+        o.camera = 0; o.pad = 0;
+        pcols.push_back(act[b]);
+      }
+    }
+    const int NK = N + K;
     for (int i = 0; i < N; ++i) {
       MarkerObs& o = h[i];
       o.full_cam = p.uses_camera(i) ? 6 * p.camera_block(i) : -1; o.full_time = 6 * p.time_block(i);
@@ -380,13 +470,14 @@ struct MarkerDevice {
       if (o.act_marker >= 0) o.pad |= p.subset_mask(p.marker_block(i)) << 12;
     }
     auto al = [](void** q, size_t bytes) { return hipMalloc(q, std::max<size_t>(bytes, 8)) == hipSuccess; };
-    if (!al((void**)&mo, N * sizeof(MarkerObs)) || !al((void**)&obs8, 8 * (size_t)N * 8) || !al((void**)&intr, p.intrinsics.size() * 8) ||
+    if (!al((void**)&mo, NK * sizeof(MarkerObs)) || !al((void**)&obs8, 8 * (size_t)N * 8) || !al((void**)&intr, p.intrinsics.size() * 8) ||
         !al((void**)&params[0], nfull * 8) || !al((void**)&params[1], nfull * 8) || !al((void**)&params0, nfull * 8) ||
-        !al((void**)&Jbuf, (size_t)N * 8 * 18 * 8) || !al((void**)&rbuf, (size_t)N * 8 * 8) || !al((void**)&ss_x, N * 8) || !al((void**)&ss_c, N * 8) ||
+        !al((void**)&Jbuf, (size_t)NK * 8 * 18 * 8) || !al((void**)&rbuf, (size_t)NK * 8 * 8) || !al((void**)&ss_x, NK * 8) || !al((void**)&ss_c, NK * 8) ||
         !al((void**)&A, (size_t)(n + 2) * n * 8) || !al((void**)&scale, n * 8) || !al((void**)&grad, n * 8) || !al((void**)&delta, n * 8) ||
-        !al((void**)&res, RES_SIZE * 8) || !al((void**)&act_to_full, n * sizeof(int)) || !al((void**)&rho_x, N * 8) || !al((void**)&rho_c, N * 8))
+        !al((void**)&res, RES_SIZE * 8) || !al((void**)&act_to_full, n * sizeof(int)) || !al((void**)&rho_x, NK * 8) || !al((void**)&rho_c, NK * 8))
       return RSBA_ERR_HIP;
-    if (hipMemcpy(mo, h.data(), N * sizeof(MarkerObs), hipMemcpyHostToDevice) != hipSuccess) return RSBA_ERR_HIP;
+    if (hipMemcpy(mo, h.data(), NK * sizeof(MarkerObs), hipMemcpyHostToDevice) != hipSuccess) return RSBA_ERR_HIP;
+    if (prior.Upload(p, pcols) != RSBA_OK) return RSBA_ERR_HIP;
     if (hipMemcpy(obs8, p.observations.data(), 8 * (size_t)N * 8, hipMemcpyHostToDevice) != hipSuccess) return RSBA_ERR_HIP;
     if (hipMemcpy(intr, p.intrinsics.data(), p.intrinsics.size() * 8, hipMemcpyHostToDevice) != hipSuccess) return RSBA_ERR_HIP;
     if (hipMemcpy(params0, p.parameters.data(), nfull * 8, hipMemcpyHostToDevice) != hipSuccess) return RSBA_ERR_HIP;
@@ -442,6 +533,12 @@ struct MarkerDevice {
       k_marker_subset_rows<<<(unsigned)(((size_t)N * 144 + 255) / 256), 256, 0, st>>>(N, mo, Jbuf);
       T.End(st);
     }
+    const int NK = N + prior.K;   // the residual blocks k_marker_system and k_marker_candidate walk
+    if (prior.K > 0) {
+      T.Begin("k_marker_prior_rows", st);
+      k_marker_prior_rows<<<(prior.K + 63) / 64, 64, 0, st>>>(prior.K, N, mo, prior.mask, prior.ab, params[x], 1, Jbuf, rbuf, ss_x, rho_x);
+      T.End(st);
+    }
     size_t lds = (size_t)std::max(2 * RSBA_TB * (RSBA_NB + 1) + RSBA_NB * (RSBA_NB + 1), 5 * 1024) * sizeof(double);
     if (n <= RSBA_CHOL_MAXN) lds = std::max(lds, CholeskyLdsDoubles(n) * sizeof(double));
     const double* cost_x = with_loss ? rho_x : ss_x;   // what k_marker_system sums into the cost at x
@@ -449,15 +546,15 @@ struct MarkerDevice {
     if (with_subset) {
       if (n <= RSBA_CHOL_MAXN) {
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k_marker_system<512, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        k_marker_system<512, true><<<1, 512, lds, st>>>(N, n, mo, Jbuf, rbuf, cost_x, A, scale, grad, act_to_full, params[x], params[c], delta, res, ip);
+        k_marker_system<512, true><<<1, 512, lds, st>>>(NK, n, mo, Jbuf, rbuf, cost_x, A, scale, grad, act_to_full, params[x], params[c], delta, res, ip);
       } else {
-        k_marker_system<1024, true><<<1, 1024, lds, st>>>(N, n, mo, Jbuf, rbuf, cost_x, A, scale, grad, act_to_full, params[x], params[c], delta, res, ip);
+        k_marker_system<1024, true><<<1, 1024, lds, st>>>(NK, n, mo, Jbuf, rbuf, cost_x, A, scale, grad, act_to_full, params[x], params[c], delta, res, ip);
       }
     } else if (n <= RSBA_CHOL_MAXN) {
       if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k_marker_system<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      k_marker_system<512><<<1, 512, lds, st>>>(N, n, mo, Jbuf, rbuf, cost_x, A, scale, grad, act_to_full, params[x], params[c], delta, res, ip);
+      k_marker_system<512><<<1, 512, lds, st>>>(NK, n, mo, Jbuf, rbuf, cost_x, A, scale, grad, act_to_full, params[x], params[c], delta, res, ip);
     } else {
-      k_marker_system<1024><<<1, 1024, lds, st>>>(N, n, mo, Jbuf, rbuf, cost_x, A, scale, grad, act_to_full, params[x], params[c], delta, res, ip);
+      k_marker_system<1024><<<1, 1024, lds, st>>>(NK, n, mo, Jbuf, rbuf, cost_x, A, scale, grad, act_to_full, params[x], params[c], delta, res, ip);
     }
     T.End(st);
     if (!chk("k_marker_system")) return RSBA_ERR_HIP;
@@ -468,9 +565,14 @@ struct MarkerDevice {
     } else if (with_loss) k_marker_eval<true><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[c], intr, half_side, 0, nullptr, nullptr, ss_c, loss, rho_c, wts);
     else k_marker_eval<false><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[c], intr, half_side, 0, nullptr, nullptr, ss_c);
     T.End(st);
+    if (prior.K > 0) {
+      T.Begin("k_marker_prior_rows", st);
+      k_marker_prior_rows<<<(prior.K + 63) / 64, 64, 0, st>>>(prior.K, N, mo, prior.mask, prior.ab, params[c], 0, nullptr, nullptr, ss_c, rho_c);
+      T.End(st);
+    }
     T.Begin("k_marker_candidate", st);
-    if (with_loss) k_marker_candidate<true><<<1, 256, 0, st>>>(N, mo, Jbuf, rbuf, delta, ss_c, res, rho_c);
-    else k_marker_candidate<false><<<1, 256, 0, st>>>(N, mo, Jbuf, rbuf, delta, ss_c, res);
+    if (with_loss) k_marker_candidate<true><<<1, 256, 0, st>>>(NK, mo, Jbuf, rbuf, delta, ss_c, res, rho_c);
+    else k_marker_candidate<false><<<1, 256, 0, st>>>(NK, mo, Jbuf, rbuf, delta, ss_c, res);
     T.End(st);
     if (!chk("k_marker_candidate")) return RSBA_ERR_HIP;
     if (hipMemcpyAsync(res_host, res, RES_SIZE * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess) return RSBA_ERR_HIP;

@@ -1227,6 +1227,81 @@ k_marker_schur_finish(int nb_time, const double* __restrict__ bp_time, const dou
   }
 }
 
+// The priors (PriorDevice) on the time-eliminating path: ONE MORE PARTIAL SYSTEM behind the chunks', summed by k_marker_reduce in its
+// fixed order.  The partial system is zeroed ONCE, at create (MarkerSchurDevice::Upload): which blocks carry a prior is fixed there, so
+// every step writes the same entries and no other — per prior the packed lower triangle of A'A on its block's diagonal, A'A (x - b)
+// into gc, diag(A'A) into diagU and, by thread 0 in the priors' order, sum |A (x - b)|^2 into scal[0] (the chunks' convention: twice
+// the cost).  The columns of a block's constant components are taken out of A first (exact zeros: the unit diagonal
+// is k_mc_subset_slots'), the residual keeps the held values.  A prior on a constant block (col < 0) counts in the cost only.
+// One workgroup, thread per prior.
+__global__ void __launch_bounds__(256) k_mc_prior_system(int nr, int K, const int* __restrict__ full, const int* __restrict__ col,
+                                                         const int* __restrict__ mask, const double* __restrict__ ab,
+                                                         const double* __restrict__ params_x, double* __restrict__ P, double* __restrict__ pe) {
+  const PartLayout PL{nr};
+  const int tid = threadIdx.x;
+  for (int k = tid; k < K; k += 256) {
+    const double* __restrict__ A = ab + 42 * (size_t)k;
+    const double* __restrict__ x = params_x + full[k];
+    double d[6], r[6], ss = 0.0;
+    for (int q = 0; q < 6; ++q) d[q] = x[q] - A[36 + q];
+    for (int i = 0; i < 6; ++i) { double t = 0.0; for (int q = 0; q < 6; ++q) t += A[6 * i + q] * d[q]; r[i] = t; ss += t * t; }
+    pe[k] = ss;
+    const int c = col[k], m = mask[k];
+    if (c < 0) continue;
+    for (int a = 0; a < 6; ++a) {
+      const bool ha = (m >> a) & 1;
+      double g = 0.0;
+      for (int i = 0; i < 6; ++i) g += (ha ? 0.0 : A[6 * i + a]) * r[i];
+      P[PL.gc() + c + a] = g;
+      for (int b = 0; b <= a; ++b) {
+        const bool hb = (m >> b) & 1;
+        double h = 0.0;
+        for (int i = 0; i < 6; ++i) h += (ha ? 0.0 : A[6 * i + a]) * (hb ? 0.0 : A[6 * i + b]);
+        P[PL.S() + (size_t)(c + a) * (c + a + 1) / 2 + (c + b)] = h;
+        if (a == b) P[PL.diagU() + c + a] = h;
+      }
+    }
+  }
+  __threadfence_block();
+  __syncthreads();
+  if (tid == 0) { double t = 0.0; for (int k = 0; k < K; ++k) t += pe[k]; P[PL.scal()] = t; }
+}
+
+// ... and behind the reduced solve: the priors' share of the model cost change -(A d).(r + A d / 2) (d: the block's reduced step) as one
+// more entry (0, 0, mcc, 0) of bp_time, and sum |A (x_c - b)|^2 at the candidate as one more entry of drho_c: it joins the candidate's
+// cost and stays out of its raw sum of squares (k_marker_schur_finish<true>).  One workgroup, thread per prior, the sums by thread 0.
+__global__ void __launch_bounds__(256) k_mc_prior_candidate(int K, const int* __restrict__ full, const int* __restrict__ col,
+                                                            const int* __restrict__ mask, const double* __restrict__ ab,
+                                                            const double* __restrict__ params_x, const double* __restrict__ params_c,
+                                                            const double* __restrict__ delta_r, double* __restrict__ pe,
+                                                            double* __restrict__ bp_entry, double* __restrict__ drho_entry) {
+  const int tid = threadIdx.x;
+  for (int k = tid; k < K; k += 256) {
+    const double* __restrict__ A = ab + 42 * (size_t)k;
+    const double* __restrict__ x = params_x + full[k];
+    const double* __restrict__ xc = params_c + full[k];
+    const int c = col[k], m = mask[k];
+    double d[6], dc[6], dl[6];
+    for (int q = 0; q < 6; ++q) { d[q] = x[q] - A[36 + q]; dc[q] = xc[q] - A[36 + q]; dl[q] = (c < 0 || ((m >> q) & 1)) ? 0.0 : delta_r[c + q]; }
+    double mcc = 0.0, sc = 0.0;
+    for (int i = 0; i < 6; ++i) {
+      double r = 0.0, rc = 0.0, mr = 0.0;
+      for (int q = 0; q < 6; ++q) { r += A[6 * i + q] * d[q]; rc += A[6 * i + q] * dc[q]; mr += A[6 * i + q] * dl[q]; }
+      mcc -= mr * (r + 0.5 * mr);
+      sc += rc * rc;
+    }
+    pe[2 * k] = mcc; pe[2 * k + 1] = sc;
+  }
+  __threadfence_block();
+  __syncthreads();
+  if (tid == 0) {
+    double m = 0.0, c = 0.0;
+    for (int k = 0; k < K; ++k) { m += pe[2 * k]; c += pe[2 * k + 1]; }
+    bp_entry[0] = 0.0; bp_entry[1] = 0.0; bp_entry[2] = m; bp_entry[3] = 0.0;
+    drho_entry[0] = c;
+  }
+}
+
 }  // namespace rsba
 #include "ba_marker_split.hpp"
 namespace rsba {
@@ -1285,8 +1360,13 @@ struct MarkerSchurDevice {
   bool with_subset = false;
   int* tflags = nullptr;            // [T] bit 0: a constant time; bits 8..13: the time's constant components
   unsigned char* rmask = nullptr;   // [nr / 6] the reduced blocks' constant components
+  PriorDevice prior;                // K priors: one more partial system and one more bp_time / drho_c entry (with_loss then)
+  double* prior_pe = nullptr;       // [2 K] the priors' terms, summed in order by thread 0
+  bool prior_part_zero = false;
 
   void Free() {
+    prior.Free();
+    if (prior_pe) { (void)hipFree(prior_pe); prior_pe = nullptr; }
     void* ptrs[] = {mo, ts, chunk_ptr, time_ptr, slot_ptr, slot_col, time_full, col_full, ok_flag, obs8, intr, params[0], params[1],
                     params0, posec, posec_c, ss_x, scale_t, scale_r, tdata, part, red, A, Wm, delta_r, delta_t, bp_time, solve_out, res, tc_flags, tc_hand, tc_map,
                     slot_order, slot_time, sb_ptr, sb_blk, xi_ptr, xi_blk, xi_cc, xi_cm, xc_ptr, sp, xout, tscal, blk_time, x_order, wsq, drho, drho_c, wts,
@@ -1541,6 +1621,13 @@ struct MarkerSchurDevice {
     split_backsub = split && (with_subset || !(getenv("RSBA_MT_SPLIT_BACKSUB") && atoi(getenv("RSBA_MT_SPLIT_BACKSUB")) == 0));
     if (split_backsub) { ncand_wg = (N + 255) / 256; nb_time = T + ncand_wg; }
     auto al = [](void** q, size_t bytes) { return hipMalloc(q, std::max<size_t>(bytes, 8)) == hipSuccess; };
+    const int np = p.block_priors.empty() ? 0 : 1;   // the priors' partial system and their entry behind the times'
+    if (np) {
+      std::vector<int> pcols;
+      for (const auto& kv : p.block_priors) pcols.push_back(red_col[kv.first < C ? kv.first : kv.first - Tn]);
+      if (prior.Upload(p, pcols) != RSBA_OK || !al((void**)&prior_pe, 2 * (size_t)prior.K * 8)) return RSBA_ERR_HIP;
+    }
+    prior_part_zero = np != 0;   // (zeroed below, once part is allocated)
     const size_t nA = (size_t)(nr + 2) * nr;
     if (!al((void**)&mo, N * sizeof(MarkerObs)) || !al((void**)&ts, N * sizeof(TimeSlots)) || !al((void**)&chunk_ptr, (G + 1) * 4) ||
         !al((void**)&time_ptr, (T + 1) * 4) || !al((void**)&slot_ptr, (T + 1) * 4) || !al((void**)&slot_col, scol.size() * 4) ||
@@ -1549,11 +1636,11 @@ struct MarkerSchurDevice {
         !al((void**)&params[1], nfull * 8) || !al((void**)&params0, nfull * 8) || !al((void**)&posec, (size_t)(nfull / 6) * CC_STRIDE * 8) ||
         !al((void**)&posec_c, (size_t)(nfull / 6) * CC_STRIDE * 8) ||
         !al((void**)&ss_x, N * 8) || !al((void**)&scale_t, 6 * (size_t)T * 8) ||
-        !al((void**)&scale_r, nr * 8) || !al((void**)&tdata, 48 * (size_t)T * 8) || !al((void**)&part, (size_t)G * PL.size() * 8) ||
+        !al((void**)&scale_r, nr * 8) || !al((void**)&tdata, 48 * (size_t)T * 8) || !al((void**)&part, (size_t)(G + np) * PL.size() * 8) ||
         !al((void**)&red, RL.size() * 8) || !al((void**)&A, nA * 8) || (nr > RSBA_CHOL_MAXN && !al((void**)&Wm, nA * 8)) ||
-        !al((void**)&delta_r, nr * 8) || !al((void**)&delta_t, 6 * (size_t)T * 8) || !al((void**)&bp_time, 4 * (size_t)nb_time * 8) ||
+        !al((void**)&delta_r, nr * 8) || !al((void**)&delta_t, 6 * (size_t)T * 8) || !al((void**)&bp_time, 4 * (size_t)(nb_time + np) * 8) ||
         !al((void**)&solve_out, 8 * 8) || !al((void**)&res, RES_SIZE * 8) ||
-        (with_loss && (!al((void**)&wsq, N * 8) || !al((void**)&drho, N * 8) || !al((void**)&drho_c, N * 8) || !al((void**)&wts, N * 8))))
+        (with_loss && (!al((void**)&wsq, N * 8) || !al((void**)&drho, N * 8) || !al((void**)&drho_c, (size_t)(N + np) * 8) || !al((void**)&wts, N * 8))))
       return RSBA_ERR_HIP;
     if (with_loss) {
       blk_order = order;
@@ -1568,6 +1655,8 @@ struct MarkerSchurDevice {
         !up(params0, p.parameters.data(), nfull * 8))
       return RSBA_ERR_HIP;
     if (hipMemset(res, 0, RES_SIZE * 8) != hipSuccess) return RSBA_ERR_HIP;
+    // the priors' partial system: zeros for good, k_mc_prior_system writes the prior blocks' entries only
+    if (prior_part_zero && hipMemset(part + (size_t)G * PL.size(), 0, PL.size() * 8) != hipSuccess) return RSBA_ERR_HIP;
     with_dist = p.has_distortion();
     if (with_dist && (!al((void**)&dist, p.distortion.size() * 8) || !up(dist, p.distortion.data(), p.distortion.size() * 8))) return RSBA_ERR_HIP;
     if (has_const) {
@@ -1777,8 +1866,14 @@ struct MarkerSchurDevice {
       Tm.End(st);
       if (!chk("k_time_eliminate")) return RSBA_ERR_HIP;
     }
+    const int np = prior.K > 0 ? 1 : 0;
+    if (np) {
+      Tm.Begin("k_mc_prior_system", st);
+      k_mc_prior_system<<<1, 256, 0, st>>>(nr, prior.K, prior.full, prior.col, prior.mask, prior.ab, params[x], part + (size_t)G * PartLayout{nr}.size(), prior_pe);
+      Tm.End(st);
+    }
     Tm.Begin("k_marker_reduce", st);
-    k_marker_reduce<<<(unsigned)((PartLayout{nr}.size() + 63) / 64), 512, 0, st>>>(nr, G, part, red);
+    k_marker_reduce<<<(unsigned)((PartLayout{nr}.size() + 63) / 64), 512, 0, st>>>(nr, G + np, part, red);
     Tm.End(st);
     if (nr == 0) {
       // nothing but time blocks are free: solve_out holds the empty system's result (Upload)
@@ -1855,8 +1950,14 @@ struct MarkerSchurDevice {
                                                              params[c], delta_t, bp_time));
     }
     Tm.End(st);
+    const int nd = split_backsub ? ncand_wg : nb_time;
+    if (np) {
+      Tm.Begin("k_mc_prior_candidate", st);
+      k_mc_prior_candidate<<<1, 256, 0, st>>>(prior.K, prior.full, prior.col, prior.mask, prior.ab, params[x], params[c], delta_r, prior_pe, bp_time + 4 * (size_t)nb_time, drho_c + nd);
+      Tm.End(st);
+    }
     Tm.Begin("k_marker_schur_finish", st);
-    if (with_loss) k_marker_schur_finish<true><<<1, 1024, 0, st>>>(nb_time, bp_time, red + RL.scal(), solve_out, res, split_backsub ? ncand_wg : nb_time, drho_c);
+    if (with_loss) k_marker_schur_finish<true><<<1, 1024, 0, st>>>(nb_time + np, bp_time, red + RL.scal(), solve_out, res, nd + np, drho_c);
     else k_marker_schur_finish<false><<<1, 1024, 0, st>>>(nb_time, bp_time, red + RL.scal(), solve_out, res);
     Tm.End(st);
     if (!chk("k_marker_schur_finish")) return RSBA_ERR_HIP;

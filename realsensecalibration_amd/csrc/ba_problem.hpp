@@ -3,7 +3,9 @@
 //  /root/reference/Test1_BundleAdjustment/bundle_adjustmenter.cpp:14-104 for the point model).
 // Owns flat arrays in the reference's layouts; the solver writes its result back into `parameters`.
 #pragma once
+#include <array>
 #include <cstdint>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -32,6 +34,8 @@ struct rsba_problem {
                                          // constant (ceres::SubsetParameterization); empty = none
   std::vector<double> observation_weights;   // marker-chain models: a_i >= 0 per residual block (ceres::ScaledLoss); empty = none
   std::vector<double> distortion;     // marker-chain models: 5 per camera (k1 k2 p1 p2 k3, OpenCV), indexed as intrinsics; empty = none
+  std::map<int, std::array<double, 42>> block_priors;   // marker-chain models: block of [C | T | M] -> A (6 x 6 row-major) then b (6): the
+                                                        // residual A (x - b) with no loss (ceres::NormalPrior); camera and marker blocks only
 
   int64_t num_parameters() const { return (int64_t)parameters.size(); }
   int obs_dim() const { return model == RSBA_MODEL_POINTS ? 2 : 8; }

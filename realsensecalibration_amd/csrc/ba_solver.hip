@@ -326,6 +326,7 @@ struct rsba_solver {
   EvalJacobianDevice eval_jac;   // rsba_solver_jacobian_structure / rsba_solver_evaluate_jacobian (ba_evaluate_jacobian.hpp)
   std::vector<uint8_t> eval_const_cam, eval_const_pt, eval_const_block;   // the problem's constant flags as they were at create
   std::vector<uint8_t> eval_subset;   // marker chain: the blocks' masks of constant components as they were at create (empty: none set)
+  int num_priors = 0;                 // marker chain: the priors (rsba_problem_set_block_prior) the solver was created with
 
   // ---- the three above on a solver with a communicator (ShardedQuery): the request word and the camera check travel from here
   double* query_buf = nullptr;                 // device scratch, kept between calls (grows only)
@@ -2063,7 +2064,6 @@ static int CovarianceMarker(rsba_solver* s, const rsba_covariance_options& co) {
       else if (lossy) k_cov_mc_lin<true, false, true><<<grid, 64, 0, st>>>(T, tptr_d, rows_d, obs_d, ids, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags, loss, wrow_d);
       else if (s->dist_dev) k_cov_mc_lin<false, true, true><<<grid, 64, 0, st>>>(T, tptr_d, rows_d, obs_d, ids, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags);
       else k_cov_mc_lin<false, false, true><<<grid, 64, 0, st>>>(T, tptr_d, rows_d, obs_d, ids, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags);
-      k_cov_subset_diag<<<(6 * nb + 255) / 256, 256, 0, st>>>(nb, pos, bsub_d, y.n, y.S);
     } else if (loss != 0.0 || use_w) {
       if (s->dist_dev) k_cov_mc_lin<true, true><<<std::max(1, std::min(T, 4096)), 64, 0, st>>>(T, tptr_d, rows_d, obs_d, IntrDist{intr, s->dist_dev}, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags, loss, wrow_d);
       else k_cov_mc_lin<true><<<std::max(1, std::min(T, 4096)), 64, 0, st>>>(T, tptr_d, rows_d, obs_d, intr, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags, loss, wrow_d);
@@ -2072,6 +2072,12 @@ static int CovarianceMarker(rsba_solver* s, const rsba_covariance_options& co) {
     } else {
       k_cov_mc_lin<false><<<std::max(1, std::min(T, 4096)), 64, 0, st>>>(T, tptr_d, rows_d, obs_d, intr, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags);
     }
+    if (s->num_priors > 0 && y.n > 0) {
+      // the priors: S += A'A on their blocks' diagonals (in front of the constant components' unit diagonal and the scaling)
+      const PriorDevice& pd = elim_path ? s->marker_schur.prior : s->marker.prior;
+      k_cov_prior<<<(36 * pd.K + 255) / 256, 256, 0, st>>>(pd.K, pd.full, pd.mask, pd.ab, pos, y.n, y.S);
+    }
+    if (with_sub) k_cov_subset_diag<<<(6 * nb + 255) / 256, 256, 0, st>>>(nb, pos, bsub_d, y.n, y.S);
     // (the host vectors outlive CovRun, which synchronises the stream before it returns)
   }, [](CovSystem&, auto&) { return RSBA_OK; });
   if (rc == RSBA_OK && with_sub && n > 0) {
@@ -2396,19 +2402,20 @@ static int EvaluateOnDevice(rsba_solver* s, bool apply_loss, double* cost, doubl
   int rc = EvalBuild(s);
   if (rc != RSBA_OK) return rc;
   const bool points = p.model == RSBA_MODEL_POINTS;
-  const size_t N = (size_t)p.num_observations, nres = (size_t)p.obs_dim() * N, npar = p.parameters.size();
+  const size_t N = (size_t)p.num_observations, nres = (size_t)p.obs_dim() * N + 6 * (size_t)s->num_priors, npar = p.parameters.size();
   const int C = p.num_cameras, nb = points ? 0 : C + p.num_times + p.num_markers;
   const int grid = points ? std::max(1, std::min((s->P + 3) / 4, 8192)) : (int)std::max<size_t>(1, (N + 63) / 64);   // = the cost's partials
   const double loss = !apply_loss || !(s->opt.huber_delta > 0.0) ? 0.0 : (s->opt.loss_type == RSBA_LOSS_CAUCHY ? -s->opt.huber_delta : s->opt.huber_delta);
-  double *posec = nullptr, *res_d = nullptr, *grad_d = nullptr, *work = nullptr, *cost_parts = nullptr, *cost_d = nullptr, *pay = nullptr;
+  double *posec = nullptr, *res_d = nullptr, *grad_d = nullptr, *work = nullptr, *cost_parts = nullptr, *cost_d = nullptr, *pay = nullptr, *prior_pe = nullptr;
   auto carve = [&](CovCarve& cv) {
     posec = cv.take<double>((size_t)CC_STRIDE * (points ? C : nb));
     res_d = residuals ? cv.take<double>(nres) : nullptr;
     grad_d = gradient ? cv.take<double>(npar) : nullptr;
     // the camera gradient's segment sums / every observation's J'r
     work = gradient ? cv.take<double>(points ? (size_t)C * RSBA_EVAL_CAM_SEGS * 6 : 18 * N) : nullptr;
-    cost_parts = cv.take<double>(grid);
+    cost_parts = cv.take<double>(grid + (s->num_priors > 0 ? 1 : 0));   // (the priors' share: one more partial)
     cost_d = cv.take<double>(1);
+    if (s->num_priors > 0) prior_pe = cv.take<double>(s->num_priors);
     if (comm) pay = cv.take<double>(7 * (size_t)C + 1);
   };
   CovCarve sizing;
@@ -2445,7 +2452,13 @@ static int EvaluateOnDevice(rsba_solver* s, bool apply_loss, double* cost, doubl
       else k_eval_marker<false><<<grid, 64, 0, st>>>((int)N, e.rows, e.obs8, e.intr, posec, p.marker_side / 2, loss, res_d, nullptr, cost_parts, wts);
     }
   }
-  k_eval_cost<<<1, 256, 0, st>>>(grid, cost_parts, cost_d);
+  if (s->num_priors > 0) {
+    const PriorDevice& pd = s->eliminate_times ? s->marker_schur.prior : s->marker.prior;
+    const double* params = s->eliminate_times ? (s->has_run ? s->marker_schur.params[s->marker_schur.cur] : s->marker_schur.params0)
+                                              : (s->has_run ? s->marker.params[s->marker.cur] : s->marker.params0);
+    k_eval_prior<<<1, 256, 0, st>>>(pd.K, pd.full, pd.col, pd.mask, pd.ab, params, res_d ? res_d + 8 * N : nullptr, grad_d, prior_pe, cost_parts + grid);
+  }
+  k_eval_cost<<<1, 256, 0, st>>>(grid + (s->num_priors > 0 ? 1 : 0), cost_parts, cost_d);
   rc = RSBA_OK;
   auto hip = [&](hipError_t err) { if (err != hipSuccess && rc == RSBA_OK) rc = RSBA_ERR_HIP; };
   hip(hipGetLastError());
@@ -2495,10 +2508,25 @@ static int JacobianStructure(rsba_solver* s, int64_t* num_rows, int64_t* num_col
   if (rc != RSBA_OK) return rc;
   const rsba_problem& p = *s->prob;
   const EvalJacobianLayout& l = s->eval_jac.layout;
-  if (num_rows) *num_rows = (int64_t)p.obs_dim() * p.num_observations;
+  // the priors' rows behind the observations': six per prior, six columns each, empty for a prior on a constant block
+  const std::vector<int>& pcol = s->eliminate_times ? s->marker_schur.prior.hcol : s->marker.prior.hcol;
+  const std::vector<int>& pfull = s->eliminate_times ? s->marker_schur.prior.hfull : s->marker.prior.hfull;
+  const int K = s->num_priors;
+  int klive = 0;
+  for (int k = 0; k < K; ++k) klive += pcol[k] >= 0 ? 1 : 0;
+  const int64_t nrows_obs = (int64_t)p.obs_dim() * p.num_observations;
+  if (num_rows) *num_rows = nrows_obs + 6LL * K;
   if (num_cols) *num_cols = p.num_parameters();
-  if (num_nonzeros) *num_nonzeros = l.off.back();
+  if (num_nonzeros) *num_nonzeros = l.off.back() + 36LL * klive;
   EvalJacobianRowPtr(l, p.obs_dim(), row_ptr);
+  {
+    int64_t at = l.off.back();
+    for (int k = 0; k < K; ++k)
+      for (int i = 0; i < 6; ++i) {
+        if (pcol[k] >= 0) { if (cols) for (int q = 0; q < 6; ++q) cols[at + q] = pfull[k] + q; at += 6; }
+        if (row_ptr) row_ptr[nrows_obs + 6 * k + i + 1] = at;
+      }
+  }
   if (cols) {
     if (p.model == RSBA_MODEL_POINTS)
       EvalPointJacobianCols(l, p.num_cameras, p.camera_index.data(), p.point_index.data(), s->eval_const_cam, s->eval_const_pt, cols);
@@ -2542,7 +2570,10 @@ static int JacobianOnDevice(rsba_solver* s, bool apply_loss, double* values) {
   EvalJacobianDevice& j = s->eval_jac;
   const bool points = p.model == RSBA_MODEL_POINTS;
   const int N = (int)p.num_observations;
-  const size_t nnz = (size_t)j.layout.off.back();
+  const PriorDevice* pd = s->num_priors > 0 ? (s->eliminate_times ? &s->marker_schur.prior : &s->marker.prior) : nullptr;
+  const size_t nnz_obs = (size_t)j.layout.off.back();
+  size_t nnz = nnz_obs;
+  if (pd) for (int c : pd->hcol) nnz += c >= 0 ? 36 : 0;
   if (nnz == 0) return RSBA_OK;
   const int C = p.num_cameras, nb = points ? 0 : C + p.num_times + p.num_markers;
   const double loss = !apply_loss || !(s->opt.huber_delta > 0.0) ? 0.0 : (s->opt.loss_type == RSBA_LOSS_CAUCHY ? -s->opt.huber_delta : s->opt.huber_delta);
@@ -2572,6 +2603,7 @@ static int JacobianOnDevice(rsba_solver* s, bool apply_loss, double* values) {
     else k_eval_jacobian_marker<false><<<(N + 63) / 64, 64, 0, st>>>(N, e.rows, e.obs8, e.intr, posec, j.off, e.live, p.marker_side / 2, loss, values_d,
                                                                       apply_loss && s->weights_given ? s->obs_w_dev : nullptr);
     if (e.bsub) k_eval_jacobian_subset<<<(N + 63) / 64, 64, 0, st>>>(N, e.rows, j.off, e.live, e.bsub, values_d);
+    if (pd) k_eval_jacobian_prior<<<(36 * pd->K + 255) / 256, 256, 0, st>>>(pd->K, pd->col, pd->mask, pd->ab, (int64_t)nnz_obs, values_d);
   }
   rc = RSBA_OK;
   auto hip = [&](hipError_t err) { if (err != hipSuccess && rc == RSBA_OK) rc = RSBA_ERR_HIP; };
@@ -2715,10 +2747,19 @@ int rsba_solver_create(rsba_problem* p, const rsba_options* o, rsba_solver** out
     s->eliminate_times = rsba::MarkerSchurDevice::Wanted(*p, opt.schur_impl);
     // the loss instances: a robust loss, or a problem that carries observation weights (all ones included: how a caller asks for
     // rsba_solver_set_observation_weights); once, here
-    s->weighted = opt.huber_delta > 0.0 || !p->observation_weights.empty();
+    // ... or block priors: their cost travels where rho(s) does and stays out of the raw sum of squares (k_marker_prior_rows,
+    // k_mc_prior_candidate)
+    s->weighted = opt.huber_delta > 0.0 || !p->observation_weights.empty() || !p->block_priors.empty();
     s->weights_given = !p->observation_weights.empty();
     if (!p->observation_weights.empty() && (int64_t)p->observation_weights.size() != p->num_observations) { rsba::FreeSolver(s); return RSBA_ERR_ARG; }
     if (!p->distortion.empty() && p->distortion.size() != 5 * (size_t)p->num_cameras) { rsba::FreeSolver(s); return RSBA_ERR_ARG; }
+    if (!p->block_priors.empty()) {
+      // a prior on a block no observation names: the column maps come from the observations (rsba.h)
+      std::vector<char> named((size_t)p->num_cameras + p->num_times + p->num_markers, 0);
+      for (int64_t i = 0; i < p->num_observations; ++i) { if (p->uses_camera(i)) named[p->camera_block(i)] = 1; if (p->uses_marker(i)) named[p->marker_block(i)] = 1; }
+      for (const auto& kv : p->block_priors) if (!named[kv.first]) { rsba::FreeSolver(s); return RSBA_ERR_UNSUPPORTED; }
+      s->num_priors = (int)p->block_priors.size();
+    }
     rc = s->eliminate_times ? s->marker_schur.Upload(*p, s->weighted) : s->marker.Upload(*p, s->weighted);
     if (s->eliminate_times && rc == RSBA_ERR_UNSUPPORTED) {
       // duplicate detections, or a time wider than the kernels' LDS: the dense path is general
@@ -2888,7 +2929,7 @@ int rsba_solver_full_report(const rsba_solver* s, char* buf, int32_t capacity) {
     for (int b = 0; b < nb && b < (int)p.block_constant.size(); ++b) nconst += (used[b] && p.block_constant[b]) ? 1 : 0;
     // blocks no residual touches never enter the ceres::Problem (camera 0 / marker 0 of the reference's wiring); constant ones leave the reduced program
     blocks0 = nu; params0 = 6LL * nu; blocks1 = nu - nconst; params1 = 6LL * (nu - nconst);
-    rblocks = p.num_observations; residuals = 8 * rblocks;
+    rblocks = p.num_observations + s->num_priors; residuals = 8 * p.num_observations + 6LL * s->num_priors;
   }
   static const char* kTerm[] = {"CONVERGENCE", "NO_CONVERGENCE", "FAILURE"};
   char why[192] = "";
@@ -3120,7 +3161,7 @@ int rsba_solver_time_covariances(rsba_solver* s, double* out) {
 
 int64_t rsba_solver_num_residuals(const rsba_solver* s) {
   if (!s) return -(int64_t)RSBA_ERR_ARG;
-  return (int64_t)s->prob->obs_dim() * s->prob->num_observations;
+  return (int64_t)s->prob->obs_dim() * s->prob->num_observations + 6 * (int64_t)s->num_priors;
 }
 
 int rsba_solver_evaluate(rsba_solver* s, const rsba_evaluate_options* o, double* cost, double* residuals, double* gradient) {
@@ -3181,6 +3222,19 @@ int rsba_solver_set_observation_weights(rsba_solver* s, const double* weights) {
   s->weights_given = true;
   s->cov_valid = false;   // the covariance was that of the old weights
   return RSBA_OK;
+}
+
+int rsba_solver_set_block_prior(rsba_solver* s, int64_t parameter_offset, const double* A, const double* b) {
+  if (!s) return RSBA_ERR_ARG;
+  if (!A || !b) return RSBA_ERR_ARG;
+  for (int i = 0; i < 36; ++i) if (!std::isfinite(A[i])) return RSBA_ERR_ARG;
+  for (int i = 0; i < 6; ++i) if (!std::isfinite(b[i])) return RSBA_ERR_ARG;
+  if (s->prob->model == RSBA_MODEL_POINTS || s->num_priors == 0) return RSBA_ERR_UNSUPPORTED;   // (which blocks carry one was fixed at create)
+  if (hipSetDevice(s->device) != hipSuccess) return RSBA_ERR_HIP;
+  if (hipStreamSynchronize(s->stream) != hipSuccess) return RSBA_ERR_HIP;
+  const int rc = s->eliminate_times ? s->marker_schur.prior.Set(parameter_offset, A, b) : s->marker.prior.Set(parameter_offset, A, b);
+  if (rc == RSBA_OK) s->cov_valid = false;   // the covariance was that of the old prior
+  return rc;
 }
 
 int rsba_solver_set_parameters(rsba_solver* s, const double* parameters) {

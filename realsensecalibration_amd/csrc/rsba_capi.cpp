@@ -134,6 +134,40 @@ int rsba_problem_set_distortion(rsba_problem* p, const double* dist) {
 const double* rsba_problem_distortion(const rsba_problem* p) {
   return (p && !p->distortion.empty()) ? p->distortion.data() : nullptr;
 }
+// the block a prior may sit on: a camera or marker block that is a parameter block of the model's wiring (-1 - code otherwise)
+static int PriorBlock(const rsba_problem* p, int64_t parameter_offset) {
+  if (!p) return -1 - RSBA_ERR_ARG;
+  if (!p->is_marker_chain()) return -1 - RSBA_ERR_UNSUPPORTED;   // like weights, distortion and subsets
+  const int64_t C = p->num_cameras, T = p->num_times, M = p->num_markers;
+  if (parameter_offset < 0 || parameter_offset >= 6 * (C + T + M) || parameter_offset % 6) return -1 - RSBA_ERR_ARG;
+  const int64_t b = parameter_offset / 6;
+  if (b >= C && b < C + T) return -1 - RSBA_ERR_UNSUPPORTED;     // time blocks are the eliminated ones
+  // the wiring's fixed base blocks are no parameter blocks
+  if (b == 0 || (b == C + T && p->model == RSBA_MODEL_MARKER_CHAIN)) return -1 - RSBA_ERR_ARG;
+  return (int)b;
+}
+int rsba_problem_set_block_prior(rsba_problem* p, int64_t parameter_offset, const double* A, const double* b) {
+  const int blk = PriorBlock(p, parameter_offset);
+  if (blk < 0) return -1 - blk;
+  if (!A) { p->block_priors.erase(blk); return RSBA_OK; }
+  if (!b) return RSBA_ERR_ARG;
+  for (int i = 0; i < 36; ++i) if (!std::isfinite(A[i])) return RSBA_ERR_ARG;
+  for (int i = 0; i < 6; ++i) if (!std::isfinite(b[i])) return RSBA_ERR_ARG;
+  std::array<double, 42>& v = p->block_priors[blk];
+  std::copy(A, A + 36, v.begin());
+  std::copy(b, b + 6, v.begin() + 36);
+  return RSBA_OK;
+}
+int rsba_problem_block_prior(const rsba_problem* p, int64_t parameter_offset, double* A, double* b) {
+  if (!p || !p->is_marker_chain() || parameter_offset < 0 || parameter_offset % 6) return 0;
+  if (parameter_offset >= 6 * ((int64_t)p->num_cameras + p->num_times + p->num_markers)) return 0;
+  const auto it = p->block_priors.find((int)(parameter_offset / 6));
+  if (it == p->block_priors.end()) return 0;
+  if (A) std::copy(it->second.begin(), it->second.begin() + 36, A);
+  if (b) std::copy(it->second.begin() + 36, it->second.end(), b);
+  return 1;
+}
+int32_t rsba_problem_num_block_priors(const rsba_problem* p) { return p ? (int32_t)p->block_priors.size() : 0; }
 void rsba_problem_free(rsba_problem* p) { delete p; }
 
 int rsba_base_pose_from_marker_detection(const double* marker_from_camera, const double* marker_from_base, double* base_from_camera) {

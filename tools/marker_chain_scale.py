@@ -1,13 +1,14 @@
 """Marker-chain model at scale on the GPU: per-kernel times of the time-elimination path.
 
-    python tools/marker_chain_scale.py [C T M [huber|cauchy a]] [const=SET] [schur_impl=K] [dump=PATH] [weights=FRAC] [dist=SEED] [subset=FRAC]
+    python tools/marker_chain_scale.py [C T M [huber|cauchy a]] [const=SET] [schur_impl=K] [dump=PATH] [weights=FRAC] [dist=SEED] [subset=FRAC] [priors=SIGMA]
         default 8 5000 16, no loss; SET: markers | cameras:K (cameras 1..K) | times:K (every T/K-th time) | rig (every camera
         and marker: only the times are free), joined by '+' (e.g. cameras:2+times:100); dump=PATH writes the final parameters
         and the iteration log (.npz) of the last unprofiled run; weights=FRAC: observation weights on the problem (ceres::ScaledLoss),
         that fraction of the residual blocks (seeded) at weight 0 and the rest at 1 — 0 asks for all ones; dist=SEED: lens distortion,
         tests/marker_distortion_ref.py's coefficients(C, SEED) on the problem and its detections redetected through them;
         subset=FRAC: constant components (ceres::SubsetParameterization) — that fraction of the camera, time and marker blocks
-        (seeded) each get a random mask of one to five components
+        (seeded) each get a random mask of one to five components; priors=SIGMA: a Gaussian prior (ceres::NormalPrior) with
+        A = diag(1 / SIGMA) around the start values on every free camera and marker block
 """
 import json
 import os
@@ -65,6 +66,13 @@ if SUBSET:
     for b in np.flatnonzero(rng.random(C_ + T_ + M_) < SUBSET):
         p.set_parameter_subset_constant(6 * int(b), int(rng.integers(1, 63)))
         NSUB += 1
+NPRIOR = 0
+if "priors" in KW:
+    start = np.asarray(prob["params"], float).reshape(-1, 6)
+    for b in [c for c in range(1, C_)] + [C_ + T_ + m for m in range(1, M_)]:
+        if b not in CONST:
+            p.set_block_prior(6 * b, np.eye(6) / float(KW["priors"]), start[b])
+            NPRIOR += 1
 out = {}
 for mode in (0, 1):
     s = capi.Solver(p, capi.default_options(profile_kernels=mode, schur_impl=int(KW.get("schur_impl", 1)), **LOSS_KW))
@@ -77,6 +85,7 @@ for mode in (0, 1):
         out["zero_weight_fraction"] = WEIGHTS
         out["distortion_seed"] = DIST
         out["subset_blocks"] = NSUB
+        out["prior_blocks"] = NPRIOR
         out["eliminates_times"] = s.eliminates_times()
         if "dump" in KW:
             s.download()
