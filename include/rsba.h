@@ -207,7 +207,7 @@ int rsba_problem_set_parameter_block_constant(rsba_problem* p, int64_t parameter
  * the kernels and the bits of a problem without them.  Any non-zero mask: both paths take it, together with a robust loss, weights,
  * distortion and constant blocks; the path rule (rsba_solver_time_elimination) does not read the masks.  On the time-eliminating
  * path a masked solver always runs the split elimination and the split back-substitution (the masks are applied to their small
- * products), whatever RSBA_MT_SPLIT, RSBA_MT_SPLIT_BACKSUB and RSBA_MT_BACKSUB_WG say.
+ * products), whatever RSBA_MT_SPLIT, RSBA_MT_SPLIT_BACKSUB and RSBA_MT_BACKSUB_WG say (MarkerSwitches, csrc/ba_marker_plan.hpp).
  * Queries on such a solver: rsba_solver_evaluate writes 0.0 in the masked slots of the gradient.  rsba_solver_jacobian_structure
  * is unchanged — the block keeps its six columns — and rsba_solver_evaluate_jacobian writes exact 0.0 in the masked columns, so
  * J'r equals the gradient slot for slot.  THIS DEPARTS FROM CERES, whose CRS matrix has the block's local size (6 - k) columns.
@@ -630,8 +630,12 @@ int rsba_solver_comm_abort(rsba_solver* s);
 int rsba_solver_schedule_info(const rsba_solver* s, rsba_schedule_info* out);
 /* Marker-chain models: which path the solver runs.  *eliminates_times = 1 when the time blocks are eliminated (rsba_options.schur_impl 2,
  * or 1 above RSBA_CHOL_MAXN unknowns), 0 on the dense one-workgroup path — the choice falls back to it silently for duplicate
- * detections, a time that touches more than 170 camera / marker blocks, or a robust loss with times too wide for the split
- * accumulation.  RSBA_ERR_UNSUPPORTED for the point model, RSBA_ERR_ARG for NULL. */
+ * detections, a time that touches more than 170 camera / marker blocks, or a solver that needs the split elimination (a robust
+ * loss, observation weights, priors or subset masks) with times too wide for the split accumulation (about 120 camera / marker
+ * blocks).  The rules, and the RSBA_MT_* environment switches of the time-eliminating path (RSBA_MT_SPLIT, RSBA_MT_ACC_MFMA,
+ * RSBA_MT_CHUNKS, RSBA_MT_BACKSUB_WG, RSBA_MT_SPLIT_BACKSUB, RSBA_MT_FORK, RSBA_MT_SOLVE_LDS), are in one place:
+ * PlanMarkerChain and MarkerSwitches::FromEnv, the switches' single reader, in csrc/ba_marker_plan.hpp; they are read at every
+ * rsba_solver_create.  RSBA_ERR_UNSUPPORTED for the point model, RSBA_ERR_ARG for NULL. */
 int rsba_solver_time_elimination(const rsba_solver* s, int32_t* eliminates_times);
 
 /* ------------------------------------------------------------------ files either side of the path */

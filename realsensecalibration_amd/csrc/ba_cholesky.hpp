@@ -26,8 +26,7 @@
 
 namespace rsba {
 
-// (RSBA_PB, the panel width: ba_schur_plan.hpp)
-#define RSBA_PLD (RSBA_PB + 1)           // LDS leading dimension (bank-conflict padding)
+// (RSBA_PB, the panel width, RSBA_PLD, its LDS leading dimension, and CholeskyLdsDoubles: ba_schur_plan.hpp)
 
 typedef double d4_t __attribute__((ext_vector_type(4)));
 
@@ -46,14 +45,6 @@ __device__ __forceinline__ double ReadLaneD(double v, int lane) {
   lo = __builtin_amdgcn_readlane(lo, lane);
   hi = __builtin_amdgcn_readlane(hi, lane);
   return __hiloint2double(hi, lo);
-}
-
-// LDS doubles: (n+2) x 33 shared by the panel and the B strip, 32 x 33 tiles for T and the padded L11, 32 inverse
-// pivots, scratch, the column scale, four 32 x 33 tiles for the look-ahead products of the next diagonal block.
-__host__ __device__ inline size_t CholeskyLdsDoubles(int n) {
-  const size_t fact = (size_t)(n + 2) * RSBA_PLD + 2 * RSBA_PB * RSBA_PLD + RSBA_PB + 64 + (size_t)n + 4 * RSBA_PB * RSBA_PLD;
-  const size_t back = (size_t)((n + 63) & ~63) + 3 * RSBA_PB * RSBA_PLD + 64;
-  return fact > back ? fact : back;
 }
 
 // Optional fused source: when src.S != nullptr the panel rows are not read from A but built on the fly from the

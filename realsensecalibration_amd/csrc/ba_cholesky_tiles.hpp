@@ -143,33 +143,7 @@ struct TileSysSource {
   int sym_full = 0;
 };
 
-// Which tile the workgroup with index t works on.  With more tiles than CUs, the workgroups t and t + (number of CUs) end up
-// on the same CU (measured: RSBA_MC_TRACE=1 lists the pairs), and a diagonal tile that shares its CU with a tile busy
-// updating takes ~6 us longer per tile column: row by row, the first eleven diagonal tiles of 256 cameras were paired with
-// tiles of the last three tile rows, busy from the first panel to the last.  So: the first `extra` indices go to tiles that
-// retire early and are off the chain (I >= J + 2 of the first tile columns), their partners at the end of the launch are the
-// tiles of the LAST tile columns (idle until late), everybody else — every early diagonal and sub-diagonal tile — has a CU alone.
-inline std::vector<int> TileOrder(int nrt, int num_cus) {
-  const int ntiles = nrt * (nrt + 1) / 2, extra = std::max(0, std::min(ntiles - num_cus, ntiles / 2));
-  std::vector<int> order;
-  order.reserve(ntiles);
-  if (extra == 0 || nrt > 255) {
-    for (int I = 0; I < nrt; ++I) for (int J = 0; J <= I; ++J) order.push_back(I << 8 | J);
-    return order;
-  }
-  std::vector<char> taken((size_t)nrt * nrt, 0);
-  std::vector<int> first, last;
-  for (int J = 0; J < nrt && (int)first.size() < extra; ++J)
-    for (int I = J + 2; I < nrt && (int)first.size() < extra; ++I) { first.push_back(I << 8 | J); taken[(size_t)I * nrt + J] = 1; }
-  for (int J = nrt - 1; J >= 0 && (int)last.size() < (int)first.size(); --J)
-    for (int I = nrt - 1; I >= J && (int)last.size() < (int)first.size(); --I)
-      if (!taken[(size_t)I * nrt + J]) { last.push_back(I << 8 | J); taken[(size_t)I * nrt + J] = 1; }
-  order = first;
-  for (int I = 0; I < nrt; ++I) for (int J = 0; J <= I; ++J) if (!taken[(size_t)I * nrt + J]) order.push_back(I << 8 | J);
-  order.insert(order.end(), last.begin(), last.end());
-  return order;
-}
-
+// (TileOrder, which tile the workgroup with index t works on: ba_schur_plan.hpp)
 __device__ __forceinline__ void TileStamp(const TileCholFlags& f, int tile, int k) { if (f.trace != nullptr && threadIdx.x == 0) f.trace[tile * 24 + k] = wall_clock64(); }
 // a value of L / y into F (real entries only; the rhs row m lands in row n)
 __device__ __forceinline__ void TileStoreF(double* __restrict__ F, int n, int m, int gi, int gj, double v) {

@@ -20,6 +20,7 @@
 #include <cstring>
 #include <vector>
 
+#include "ba_marker_plan.hpp"
 #include "ba_point_kernels.hpp"
 #include "ba_problem.hpp"
 
@@ -74,14 +75,7 @@ __device__ inline void RotateD(const double w[3], double p[3]) {
   p[0] = r0; p[1] = r1; p[2] = r2;
 }
 
-// Per-observation wiring: offsets (in doubles) of the three blocks inside the FULL parameter array, or -1
-// when the functor variant has no such block; and offsets inside the ACTIVE vector.
-struct MarkerObs {
-  int full_cam, full_time, full_marker;  // -1: block not part of this residual
-  int act_cam, act_time, act_marker;
-  int camera;                            // intrinsics index
-  int pad;                               // constant components (ceres::SubsetParameterization): bit q of the 18 local columns camera | time | marker
-};
+// (MarkerObs, the per-observation wiring: ba_marker_plan.hpp)
 #define RSBA_SUBSET_BIT (1 << 30)        // act_to_full: the active column is a constant component of a partly constant block
 
 // A partly constant block (rsba_problem_set_parameter_subset_constant): the columns of its constant components leave the stored rows

@@ -28,16 +28,16 @@
 // effective damping D_t = clamp(s^2 V_ii) / (radius s^2), the Jacobi scale and the LM diagonal of the reduced blocks
 // are applied by the Cholesky's panel loads (PanelSource).
 #pragma once
+#include <type_traits>
+
 #include "ba_cholesky_large.hpp"
 #include "ba_cholesky_tiles.hpp"
 #include "ba_marker_kernels.hpp"
+#include "ba_marker_plan.hpp"
 
 namespace rsba {
 
-#define RSBA_MT_TILE 32        // residual blocks staged per tile (32 x 152 doubles of LDS)
-#define RSBA_MT_MAXD 1020      // widest local system of one time: 170 camera + marker blocks
-
-#define RSBA_MT_THREADS 1024
+// (RSBA_MT_TILE, RSBA_MT_MAXD, RSBA_MT_THREADS, RSBA_MT_JLD, PartLayout, TimeSlots: ba_marker_plan.hpp)
 // (ablation hooks of the profiling builds: tools/ablate_marker.sh)
 #ifndef RSBA_ABL_Q
 #define RSBA_ABL_Q 8
@@ -48,27 +48,7 @@ namespace rsba {
 #ifndef RSBA_ABL_STAGE
 #define RSBA_ABL_STAGE 1
 #endif
-#define RSBA_MT_JLD 145        // LDS stride of a staged 8 x 18 Jacobian
 #define RSBA_MT_PW (RSBA_MT_JLD + 8)   // doubles of a residual block's products (they take the place of its rows and residuals)
-
-// A workgroup's partial system: S as packed lower triangle (row i, column j <= i at i (i + 1) / 2 + j), then the vectors.
-struct PartLayout {
-  int nr;
-  __host__ __device__ size_t packed() const { return (size_t)nr * (nr + 1) / 2; }
-  __host__ __device__ size_t S() const { return 0; }
-  __host__ __device__ size_t gc() const { return packed(); }
-  __host__ __device__ size_t corr() const { return packed() + nr; }
-  __host__ __device__ size_t diagU() const { return packed() + 2 * (size_t)nr; }
-  __host__ __device__ size_t scal() const { return packed() + 3 * (size_t)nr; }
-  __host__ __device__ size_t size() const { return packed() + 3 * (size_t)nr + 8; }
-};
-
-struct TimeSlots {  // per residual block, in time order: where its camera / marker block sits
-  int slot_cam, slot_marker;   // index in its time's slot list (-1: block not part of the residual; -2 - j: a constant block, the
-                               // time's j-th pose-only slot, ConstSlotPose)
-  int col_cam, col_marker;     // first column in the reduced system (-1)
-  int camera, pad;             // camera index of the detection (its intrinsics), whether or not the camera pose is a parameter
-};
 
 // LDS written by some lanes of a wavefront, read by others of the same wavefront.
 #define RSBA_WAVE_LDS_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
@@ -170,9 +150,6 @@ template <bool kDist> struct ElimArgT { typedef ElimArgs type; };
 template <> struct ElimArgT<true> { typedef ElimArgsDist type; };
 __device__ __forceinline__ const double* DistOf(const ElimArgs&, int) { return nullptr; }
 __device__ __forceinline__ const double* DistOf(const ElimArgsDist& a, int camera) { return a.dist + 5 * camera; }
-
-// the kernel instances with (D = true) or without lens distortion, by the device's with_dist
-#define RSBA_DIST_SWITCH(...) do { if (with_dist) { constexpr bool D = true; __VA_ARGS__; } else { constexpr bool D = false; __VA_ARGS__; } } while (0)
 
 #ifdef RSBA_PROFILE_PHASES
 __device__ long long g_mt_cycles[16];
@@ -608,13 +585,7 @@ k_marker_reduced_solve(int nr, const double* __restrict__ red, double* __restric
 // row; padding columns are identity), loaded once; right-looking: per panel DiagFactorInverse (one wavefront), X = rows T' and the
 // trailing panels' updates on the matrix cores, T kept where L_pp was; then L' x = y from LDS.  Nothing goes to memory but x.
 // Same scaling and damping as PanelSource's (ba_cholesky.hpp); fixed orders: bitwise reproducible.
-#define RSBA_MRS_MAXP 5
-__host__ __device__ inline size_t MarkerSolveLdsDoubles(int nr) {
-  const int np = (nr + RSBA_PB - 1) / RSBA_PB, npad = RSBA_PB * np;
-  size_t rows = 0;
-  for (int p = 0; p < np; ++p) rows += (size_t)(npad + 1 - RSBA_PB * p);
-  return rows * RSBA_PLD + 2 * RSBA_PB * RSBA_PLD + RSBA_PB + 2 * (size_t)npad;   // panels (>= 2048 doubles: the epilogue's scratch, once they are done with) | T | Lt | invd | scl | y, then x
-}
+// (RSBA_MRS_MAXP, its five panels, and MarkerSolveLdsDoubles, its LDS: ba_marker_plan.hpp)
 __global__ void __launch_bounds__(512)
 k_marker_reduced_solve_lds(int nr, const double* __restrict__ red, double* __restrict__ A, double* __restrict__ scale_r,
                            const int* __restrict__ col_full, const double* __restrict__ params_x, double* __restrict__ params_c,
@@ -1306,32 +1277,31 @@ __global__ void __launch_bounds__(256) k_mc_prior_candidate(int K, const int* __
 #include "ba_marker_split.hpp"
 namespace rsba {
 
+// Runtime flags as template arguments: Dispatch(f, a, b) calls f(std::integral_constant<bool, a>(), std::integral_constant<bool, b>()).
+// f's body is instantiated for every combination of the flags: a launch whose kernel exists only for some of them rules the others
+// out with if constexpr.
+template <typename F> void Dispatch(F&& f) { f(); }
+template <typename F, typename... R> void Dispatch(F&& f, bool b, R... rest) {
+  if (b) Dispatch([&](auto... c) { f(std::true_type(), c...); }, rest...);
+  else Dispatch([&](auto... c) { f(std::false_type(), c...); }, rest...);
+}
+
+// The time-eliminating path on the device: what PlanMarkerChain (ba_marker_plan.hpp) planned, allocated and uploaded, and the step
+// that launches from the plan.
 struct MarkerSchurDevice {
-  int N = 0, T = 0, nr = 0, nfull = 0, G = 0, dmax = 0, nb_time = 0;
-  // the split elimination (ba_marker_split.hpp; RSBA_MT_SPLIT=0: k_time_eliminate)
-  bool split = true;
-  int nslots = 0, nx = 0, ncam_cols = 0, nx_threads = 0;
+  MarkerPlan plan;   // Upload; its tables are dropped once they are on the device
+  // the split elimination (ba_marker_split.hpp)
   int* x_order = nullptr;
   int4 *sb_blk = nullptr, *xi_blk = nullptr;
   int *slot_order = nullptr, *slot_time = nullptr, *sb_ptr = nullptr, *xi_ptr = nullptr, *xi_cc = nullptr, *xi_cm = nullptr, *xc_ptr = nullptr;
   double *sp = nullptr, *xout = nullptr, *tscal = nullptr;
-  size_t lds_acc = 0;
-  bool solve_lds = false;       // k_marker_reduced_solve_lds (the whole triangle in LDS: up to 160 reduced columns)
-  bool split_backsub = false;   // k_mc_time_step + k_mc_candidate instead of k_time_backsub_wg / _terms
   int* blk_time = nullptr;
-  int ncand_wg = 0;
-  int acc_tiles = 0;   // > 0: k_mc_accumulate_mfma with that many tiles a wavefront
-  int acc_tb = 2;      // ... and times per step (three tiles a wavefront; eight: one)
   hipStream_t fork_s[2] = {nullptr, nullptr};   // the three product kernels side by side
   hipEvent_t fork_ev[3] = {nullptr, nullptr, nullptr};
-  bool backsub_wg = false;   // k_time_backsub_wg instead of k_time_backsub_terms
   double* posec_c = nullptr; // pose constants of the candidate's cameras and markers
-  bool with_loss = false;    // a robust loss or observation weights (Upload): the kLoss instances, the split elimination and the wavefront-per-time or split back-substitution
   double *wsq = nullptr, *drho = nullptr, *drho_c = nullptr;   // [N] each: sqrt(rho'), rho(s) - s at x (k_mc_block_weight); per candidate
-                                                                 // workgroup (at most N): its blocks' rho(s_c) - s_c
+                                                                 // workgroup (at most N): its blocks' rho(s_c) - s_c (with_loss only)
   double* wts = nullptr;         // [N] the blocks' weights in the device's time order (with_loss only; all ones when the problem had none)
-  std::vector<int> blk_order;    // device block -> the problem's observation (with_loss only: SetWeights)
-  double half_side = 0;
   MarkerObs* mo = nullptr;
   TimeSlots* ts = nullptr;
   int *chunk_ptr = nullptr, *time_ptr = nullptr, *slot_ptr = nullptr, *slot_col = nullptr, *time_full = nullptr, *col_full = nullptr,
@@ -1344,35 +1314,31 @@ struct MarkerSchurDevice {
   int* tc_flags = nullptr;   // persistent tiled factorisation of a large reduced system (ba_cholesky_tiles.hpp)
   double* tc_hand = nullptr; // ... its diagonal chain's hand-over buffers
   int* tc_map = nullptr;     // ... which tile each workgroup takes (TileOrder)
-  int tc_np = 0, tc_nrt = 0, tc_tiles = 0, tc_tag = 0;
-  size_t lds_elim = 0;
-  bool lds_s = false;   // the chunk sums of S live in LDS
-  // constant blocks (Upload): the kConst instances run when a residual names a constant camera, marker or time block
-  bool has_const = false;
-  int pmax = 0;         // widest pose cache of a time: its free slots and its pose-only (constant) slots
-  int ncpose = 0;       // constant camera / marker poses some residual applies
+  int tc_tag = 0;
+  // constant blocks (has_const only): the times' pose-only slots, constant flags, the constant poses some residual applies
   int *cs_ptr = nullptr, *cs_full = nullptr, *tconst = nullptr, *cpose_full = nullptr;
-  // lens distortion (Upload): the kDist instances run when some coefficient of the problem is not zero; no path rule reads it
-  bool with_dist = false;
-  double* dist = nullptr;   // [C][5], indexed as intr
-  // constant components (block_subset, Upload): some block in the program has a non-zero mask.  The split elimination and the split
-  // back-substitution then, whatever the switches say: the masks are applied to their small products (ba_marker_split.hpp)
-  bool with_subset = false;
-  int* tflags = nullptr;            // [T] bit 0: a constant time; bits 8..13: the time's constant components
-  unsigned char* rmask = nullptr;   // [nr / 6] the reduced blocks' constant components
+  double* dist = nullptr;           // [C][5], indexed as intr (with_dist only)
+  int* tflags = nullptr;            // [T] bit 0: a constant time; bits 8..13: the time's constant components (with_subset only)
+  unsigned char* rmask = nullptr;   // [nr / 6] the reduced blocks' constant components (with_subset only)
   PriorDevice prior;                // K priors: one more partial system and one more bp_time / drho_c entry (with_loss then)
   double* prior_pe = nullptr;       // [2 K] the priors' terms, summed in order by thread 0
-  bool prior_part_zero = false;
 
+  // Every device buffer above has one owner: Alloc records the member it fills, Free releases what was recorded.
+  std::vector<void**> owned;
+  // n elements (at least 8 bytes), and h's n elements in them when h is given
+  template <typename Td, typename Th = Td>
+  bool Alloc(Td** q, size_t n, const Th* h = nullptr) {
+    static_assert(sizeof(Td) == sizeof(Th), "uploaded as it lies on the host");
+    if (hipMalloc((void**)q, std::max<size_t>(n * sizeof(Td), 8)) != hipSuccess) return false;
+    owned.push_back((void**)q);
+    return h == nullptr || n == 0 || hipMemcpy(*q, h, n * sizeof(Td), hipMemcpyHostToDevice) == hipSuccess;
+  }
+  template <typename Td, typename Th>
+  bool Alloc(Td** q, const std::vector<Th>& h) { return Alloc(q, h.size(), h.data()); }
   void Free() {
     prior.Free();
-    if (prior_pe) { (void)hipFree(prior_pe); prior_pe = nullptr; }
-    void* ptrs[] = {mo, ts, chunk_ptr, time_ptr, slot_ptr, slot_col, time_full, col_full, ok_flag, obs8, intr, params[0], params[1],
-                    params0, posec, posec_c, ss_x, scale_t, scale_r, tdata, part, red, A, Wm, delta_r, delta_t, bp_time, solve_out, res, tc_flags, tc_hand, tc_map,
-                    slot_order, slot_time, sb_ptr, sb_blk, xi_ptr, xi_blk, xi_cc, xi_cm, xc_ptr, sp, xout, tscal, blk_time, x_order, wsq, drho, drho_c, wts,
-                    cs_ptr, cs_full, tconst, cpose_full, dist, tflags, rmask};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    mo = nullptr; ts = nullptr;
+    for (void** q : owned) { (void)hipFree(*q); *q = nullptr; }
+    owned.clear();
     for (auto& q : fork_s) if (q) { (void)hipStreamDestroy(q); q = nullptr; }
     for (auto& q : fork_ev) if (q) { (void)hipEventDestroy(q); q = nullptr; }
   }
@@ -1385,380 +1351,98 @@ struct MarkerSchurDevice {
     return 6 * nblocks > RSBA_CHOL_MAXN;
   }
 
-  // Constant blocks (block_constant, Ceres' SetParameterBlockConstant): a constant camera or marker has no reduced column; a time's
-  // constant cameras and markers are its pose-only slots, behind its free slots (ConstSlotPose).  The width rule: a time's pose cache —
-  // its distinct camera and marker blocks, free or constant — holds at most RSBA_MT_MAXD / 6 = 170 entries; the split accumulation's
-  // LDS bound counts the free ones (columns) only.  A constant time is eliminated with E = 0.  No free camera or marker at all (n_r = 0):
-  // every time is eliminated on its own and the reduced solve is skipped.
-  // loss: a robust loss is set, or the problem carries observation weights (then possibly with huber_delta = 0: rho(s) = s).  Its rows are formed by the split kernels only (round 4's k_time_eliminate and k_time_backsub_wg spread a
-  // residual block's corners over lanes and have no block-wide s): RSBA_MT_SPLIT=0 and RSBA_MT_BACKSUB_WG are not taken then, and a problem
-  // whose times are too wide for the split accumulation returns RSBA_ERR_UNSUPPORTED (the solver takes the dense path).
+  // The kernels whose dynamic LDS can exceed the default limit, by the plan: Upload raises the limit of, and Step launches, the same one.
+  auto AccKernel() const -> void (*)(AccArgs) {
+    const MarkerPlan& P = plan;
+    return P.acc_tiles == 3 ? (P.acc_tb == 2 ? k_mc_accumulate_mfma<3, 2> : k_mc_accumulate_mfma<3, 1>) : P.acc_tiles == 8 ? k_mc_accumulate_mfma<8, 1>
+           : P.lds_s ? k_mc_accumulate<true> : k_mc_accumulate<false>;
+  }
+  template <typename F> void WithElimKernel(F&& f) const {   // f(kernel, D)
+    Dispatch([&](auto S, auto Cn, auto D) { f(k_time_eliminate<S.value, Cn.value, D.value>, D); }, plan.lds_s, plan.has_const, plan.with_dist);
+  }
+  template <typename F> void WithBacksubWgKernel(F&& f) const {   // f(kernel, D)
+    Dispatch([&](auto Cn, auto D) { f(k_time_backsub_wg<2, 256, Cn.value, D.value>, D); }, plan.has_const, plan.with_dist);
+  }
+  static bool RaiseLds(const void* kernel, size_t bytes) {
+    return bytes <= 48 * 1024 || hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
+  }
+
+  // loss: a robust loss is set, or the problem carries observation weights or priors (PlanMarkerChain).  RSBA_ERR_UNSUPPORTED: the
+  // solver takes the dense path.
   int Upload(const rsba_problem& p, bool loss = false) {
-    with_loss = loss;
-    N = (int)p.num_observations; nfull = (int)p.parameters.size(); half_side = p.marker_side / 2;
-    if (N <= 0) return RSBA_ERR_ARG;
-    const int C = p.num_cameras, Tn = p.num_times, M = p.num_markers;
-    auto is_const = [&](int block) { return block < (int)p.block_constant.size() && p.block_constant[block] != 0; };
-    // reduced blocks: the free cameras and markers some residual uses, cameras first
-    std::vector<int> red_col(C + M, -1);
-    std::vector<char> used(C + M, 0), tused(Tn, 0);
-    for (int i = 0; i < N; ++i) {
-      if (p.uses_camera(i)) used[p.camera_index[i]] = 1;
-      if (p.uses_marker(i)) used[C + p.marker_index[i]] = 1;
-      tused[p.time_index[i]] = 1;
-    }
-    std::vector<int> cf;
-    int K = 0;
-    for (int b = 0; b < C + M; ++b) if (used[b] && !is_const(b < C ? b : Tn + b)) {
-      red_col[b] = 6 * K++;
-      const int full = 6 * (b < C ? b : Tn + b);   // [C | T | M] x 6
-      for (int q = 0; q < 6; ++q) cf.push_back(full + q);
-    }
-    nr = 6 * K;   // (0: nothing but time blocks are free)
-    // constant components: of the blocks in the program only (a constant, base or unreferenced block's mask is ignored)
-    std::vector<unsigned char> hrmask;
-    for (int b = 0; b < C + M; ++b) if (red_col[b] >= 0) hrmask.push_back((unsigned char)p.subset_mask(b < C ? b : Tn + b));
-    with_subset = std::find_if(hrmask.begin(), hrmask.end(), [](unsigned char v) { return v != 0; }) != hrmask.end();
-    std::vector<int> tid_of(Tn, -1), tfull, htc;
-    T = 0;
-    std::vector<int> htflags;
-    for (int t = 0; t < Tn; ++t) if (tused[t]) {
-      tid_of[t] = T++; tfull.push_back(6 * (C + t)); htc.push_back(is_const(C + t) ? 1 : 0);
-      const int mask = is_const(C + t) ? 0 : p.subset_mask(C + t);
-      with_subset = with_subset || mask != 0;
-      htflags.push_back(htc.back() | (mask << 8));
-    }
-    // residual blocks in time order (stable)
-    std::vector<int> order(N);
-    for (int i = 0; i < N; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return p.time_index[x] < p.time_index[y]; });
-    std::vector<int> tptr(T + 1, 0), sptr(T + 1, 0), scol;
-    std::vector<MarkerObs> hmo(N);
-    std::vector<TimeSlots> hts(N);
-    std::vector<double> hobs(8 * (size_t)N);
-    for (int k = 0; k < N; ++k) tptr[tid_of[p.time_index[order[k]]] + 1]++;
-    for (int t = 0; t < T; ++t) tptr[t + 1] += tptr[t];
-    dmax = 0; pmax = 0;
-    std::vector<double> work(T);
-    std::vector<int> csptr(T + 1, 0), csfull;
-    std::vector<char> cpose_seen(C + M, 0);
-    std::vector<int> hcpose;
-    for (int t = 0; t < T; ++t) {
-      std::vector<int> cols, cfl;   // the time's free slots (reduced columns) and pose-only slots (full offsets of constant blocks)
-      for (int k = tptr[t]; k < tptr[t + 1]; ++k) {
-        const int i = order[k];
-        if (p.uses_camera(i)) {
-          const int b = p.camera_index[i];
-          if (red_col[b] >= 0) cols.push_back(red_col[b]);
-          else { cfl.push_back(6 * p.camera_block(i)); if (!cpose_seen[b]) { cpose_seen[b] = 1; hcpose.push_back(6 * p.camera_block(i)); } }
-        }
-        if (p.uses_marker(i)) {
-          const int b = C + p.marker_index[i];
-          if (red_col[b] >= 0) cols.push_back(red_col[b]);
-          else { cfl.push_back(6 * p.marker_block(i)); if (!cpose_seen[b]) { cpose_seen[b] = 1; hcpose.push_back(6 * p.marker_block(i)); } }
-        }
-      }
-      std::sort(cols.begin(), cols.end());
-      cols.erase(std::unique(cols.begin(), cols.end()), cols.end());
-      std::sort(cfl.begin(), cfl.end());
-      cfl.erase(std::unique(cfl.begin(), cfl.end()), cfl.end());
-      {
-        // the kernel relies on one residual block per (time, camera, marker); the same detection listed twice goes to
-        // the dense path
-        std::vector<std::pair<int, int>> cm;
-        for (int k = tptr[t]; k < tptr[t + 1]; ++k) cm.emplace_back(p.camera_index[order[k]], p.marker_index[order[k]]);
-        std::sort(cm.begin(), cm.end());
-        if (std::adjacent_find(cm.begin(), cm.end()) != cm.end()) return RSBA_ERR_UNSUPPORTED;
-      }
-      for (int k = tptr[t]; k < tptr[t + 1]; ++k) {
-        const int i = order[k];
-        MarkerObs& o = hmo[k];
-        o.full_cam = p.uses_camera(i) ? 6 * p.camera_block(i) : -1; o.full_time = 6 * p.time_block(i);
-        o.full_marker = p.uses_marker(i) ? 6 * p.marker_block(i) : -1;
-        o.act_cam = o.act_time = o.act_marker = -1; o.camera = p.camera_index[i]; o.pad = 0;
-        TimeSlots& s = hts[k];
-        s.col_cam = p.uses_camera(i) ? red_col[p.camera_index[i]] : -1;
-        s.col_marker = p.uses_marker(i) ? red_col[C + p.marker_index[i]] : -1;
-        s.camera = p.camera_index[i]; s.pad = 0;
-        auto const_slot = [&](int full) { return -2 - (int)(std::lower_bound(cfl.begin(), cfl.end(), full) - cfl.begin()); };
-        s.slot_cam = s.col_cam >= 0 ? (int)(std::lower_bound(cols.begin(), cols.end(), s.col_cam) - cols.begin()) : (o.full_cam >= 0 ? const_slot(o.full_cam) : -1);
-        s.slot_marker = s.col_marker >= 0 ? (int)(std::lower_bound(cols.begin(), cols.end(), s.col_marker) - cols.begin())
-                                          : (o.full_marker >= 0 ? const_slot(o.full_marker) : -1);
-        memcpy(&hobs[8 * (size_t)k], &p.observations[8 * (size_t)i], 8 * sizeof(double));
-      }
-      sptr[t + 1] = sptr[t] + (int)cols.size();
-      scol.insert(scol.end(), cols.begin(), cols.end());
-      csptr[t + 1] = csptr[t] + (int)cfl.size();
-      csfull.insert(csfull.end(), cfl.begin(), cfl.end());
-      const int d = 6 * (int)cols.size();
-      dmax = std::max(dmax, d);
-      pmax = std::max(pmax, (int)(cols.size() + cfl.size()));
-      work[t] = (double)d * d * (1.0 + 0.25 * (tptr[t + 1] - tptr[t])) + 2000.0;
-    }
-    if (6 * pmax > RSBA_MT_MAXD) return RSBA_ERR_UNSUPPORTED;
-    ncpose = (int)hcpose.size();
-    // (constant components ride on the kConst instances of the split kernels: the time's flags arrive where tconst does)
-    has_const = with_subset || ncpose > 0 || std::find(htc.begin(), htc.end(), 1) != htc.end();
-    const int npc = has_const ? pmax : dmax / 6;   // k_time_eliminate's pose cache holds the pose-only slots too; its other tables are the free columns'
-    // chunks of consecutive times, balanced by work; the partial systems together stay below 2 GB
-    const RedLayout RL{nr};
-    const PartLayout PL{nr};
-    lds_elim = (size_t)(13 * dmax + 96 + RSBA_MT_TILE * (RSBA_MT_JLD + 9) + (npc + 2) * CC_STRIDE) * sizeof(double) + (size_t)(2 * RSBA_MT_TILE + 3 * (dmax / 6 + 1) + 2) * sizeof(int);
-    lds_s = lds_elim + (PL.packed() + 3 * (size_t)nr) * sizeof(double) <= 156 * 1024;
-    if (lds_s) lds_elim += (PL.packed() + 3 * (size_t)nr) * sizeof(double);
-    const bool lds_s_elim = lds_s;   // (k_time_eliminate's own choice, should the split kernels not take the problem)
-    split = with_loss || with_subset || !(getenv("RSBA_MT_SPLIT") && atoi(getenv("RSBA_MT_SPLIT")) == 0);
-    if (split) {
-      const int per_wave = (AccMfmaTiles(nr) + 15) / 16;
-      acc_tiles = (per_wave <= 8 && !(getenv("RSBA_MT_ACC_MFMA") && atoi(getenv("RSBA_MT_ACC_MFMA")) == 0)) ? (per_wave <= 3 ? 3 : 8) : 0;
-      if (acc_tiles > 0) {
-        lds_s = true;   // (the chunk's sums never touch memory before the end: one chunk per CU, as with the sums in LDS)
-        if (acc_tiles == 8) acc_tb = 1;
-        lds_acc = AccMfmaLdsBytes(nr, acc_tb);
-      } else {
-        lds_s = AccLdsBytes(dmax, PL.packed() + 3 * (size_t)nr) <= 156 * 1024;
-        lds_acc = AccLdsBytes(dmax, lds_s ? PL.packed() + 3 * (size_t)nr : 0);
-      }
-      if (lds_acc > 156 * 1024) {
-        // times that touch more blocks than the accumulation's double-buffered records hold in LDS (~110 of the 170 the model allows):
-        // round 4's kernel, which stages 32 residual blocks at a time whatever the width
-        if (with_loss || with_subset) return RSBA_ERR_UNSUPPORTED;
-        split = false; acc_tiles = 0; lds_s = lds_s_elim;
-      }
-    }
-    // Without the LDS accumulators every entry is a read-modify-write in the partial system: few enough workgroups that
-    // their partial systems stay in the L2s (8 x 4 MB) then, as many as there are times otherwise (at most 1024).
-    // With the sums in LDS a workgroup fills a CU: one chunk per CU (more chunks only add partial systems to write, to
-    // zero and to reduce: 1024 chunks cost 11 % of the iteration on 5000 times)
-    size_t cap_lds = 256;
-    { int dev = 0; hipDeviceProp_t prop; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cap_lds = (size_t)prop.multiProcessorCount; }
-    if (getenv("RSBA_MT_CHUNKS")) cap_lds = (size_t)std::max(1, atoi(getenv("RSBA_MT_CHUNKS")));
-    const size_t cap = lds_s ? cap_lds : std::min<size_t>(1024, std::max<size_t>(64, ((size_t)24 << 20) / (PL.size() * sizeof(double))));
-    G = (int)std::min<size_t>((size_t)T, cap);
-    std::vector<int> cptr(G + 1, 0);
-    {
-      double total = 0; for (double w : work) total += w;
-      double acc = 0; int g = 0;
-      for (int t = 0; t < T; ++t) {
-        acc += work[t];
-        // close chunk g when it has its share and enough times remain for the others
-        while (g < G - 1 && acc >= total * (g + 1) / G && T - (t + 1) >= G - 1 - g) cptr[++g] = t + 1;
-      }
-      while (g < G) cptr[++g] = T;
-      // chunks may not be empty in the middle: compact
-      std::vector<int> c2; c2.push_back(0);
-      for (int k = 1; k <= G; ++k) if (cptr[k] > c2.back()) c2.push_back(cptr[k]);
-      G = (int)c2.size() - 1; cptr = c2;
-    }
-    // the split elimination's tables: a (time, slot)'s residual blocks, the thread order, the camera-marker pairs of every chunk
-    std::vector<int> h_slot_time, h_sb_ptr, h_order, h_xi_ptr, h_xi_cc, h_xi_cm, h_xc_ptr, h_xorder;
-    std::vector<int4> h_sb_blk, h_xi_blk;
-    auto pose_of_full = [](int full) { return full >= 0 ? full / 6 : -1; };   // full offset -> pose in the parameter array
-    const int kShareFrom = 10;   // an item of k_mc_cross with this many residual blocks or more runs on two neighbouring lanes
-    if (split) {
-      nslots = (int)scol.size();
-      ncam_cols = 0;
-      for (int b = 0; b < C; ++b) if (red_col[b] >= 0) ncam_cols += 6;   // (the free cameras: the reduced columns below the markers')
-      h_slot_time.resize(nslots);
-      h_sb_ptr.assign(nslots + 1, 0);
-      for (int t = 0; t < T; ++t) {
-        for (int S = sptr[t]; S < sptr[t + 1]; ++S) h_slot_time[S] = t;
-        for (int k = tptr[t]; k < tptr[t + 1]; ++k) {
-          if (hts[k].slot_cam >= 0) h_sb_ptr[sptr[t] + hts[k].slot_cam + 1]++;
-          if (hts[k].slot_marker >= 0) h_sb_ptr[sptr[t] + hts[k].slot_marker + 1]++;
-        }
-      }
-      for (int S = 0; S < nslots; ++S) h_sb_ptr[S + 1] += h_sb_ptr[S];
-      h_sb_blk.resize(h_sb_ptr[nslots]);
-      {
-        std::vector<int> fill(h_sb_ptr.begin(), h_sb_ptr.end() - 1);
-        for (int t = 0; t < T; ++t)
-          for (int k = tptr[t]; k < tptr[t + 1]; ++k) {
-            // (the other block's pose whether it is free or constant)
-            if (hts[k].slot_cam >= 0) h_sb_blk[fill[sptr[t] + hts[k].slot_cam]++] = int4{k, pose_of_full(hmo[k].full_marker), hts[k].camera, 0};
-            if (hts[k].slot_marker >= 0) h_sb_blk[fill[sptr[t] + hts[k].slot_marker]++] = int4{k, pose_of_full(hmo[k].full_cam), hts[k].camera, 0};
-          }
-      }
-      h_order.resize(nslots);
-      for (int S = 0; S < nslots; ++S) h_order[S] = S;
-      std::stable_sort(h_order.begin(), h_order.end(), [&](int x, int y) {
-        const bool cx = scol[x] < ncam_cols, cy = scol[y] < ncam_cols;
-        if (cx != cy) return cx;
-        return h_sb_ptr[x + 1] - h_sb_ptr[x] > h_sb_ptr[y + 1] - h_sb_ptr[y];
-      });
-      h_xc_ptr.assign(G + 1, 0);
-      h_xi_ptr.push_back(0);
-      for (int g = 0; g < G; ++g) {
-        std::vector<std::pair<std::pair<int, int>, int>> items;   // ((camera column, marker column), residual block)
-        for (int t = cptr[g]; t < cptr[g + 1]; ++t)
-          for (int k = tptr[t]; k < tptr[t + 1]; ++k)
-            if (hts[k].col_cam >= 0 && hts[k].col_marker >= 0) items.push_back({{hts[k].col_cam, hts[k].col_marker}, k});
-        std::stable_sort(items.begin(), items.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
-        for (size_t i = 0; i < items.size(); ++i) {
-          if (i == 0 || items[i].first != items[i - 1].first) {
-            if (i != 0) h_xi_ptr.push_back((int)h_xi_blk.size());
-            h_xi_cc.push_back(items[i].first.first); h_xi_cm.push_back(items[i].first.second);
-          }
-          h_xi_blk.push_back(int4{items[i].second, hmo[items[i].second].full_time / 6, hts[items[i].second].camera, 0});
-        }
-        if (!items.empty()) h_xi_ptr.push_back((int)h_xi_blk.size());
-        h_xc_ptr[g + 1] = (int)h_xi_cc.size();
-      }
-      nx = (int)h_xi_cc.size();
-      {
-        std::vector<int> ord(nx);
-        for (int it = 0; it < nx; ++it) ord[it] = it;
-        auto len = [&](int it) { return h_xi_ptr[it + 1] - h_xi_ptr[it]; };
-        std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return len(x) > len(y); });
-        for (int it : ord) if (len(it) >= kShareFrom) { h_xorder.push_back(4 * it + 2); h_xorder.push_back(4 * it + 3); }
-        for (int it : ord) if (len(it) < kShareFrom) h_xorder.push_back(4 * it);
-        nx_threads = (int)h_xorder.size();
-      }
-    }
-    // (k_time_backsub_wg: a corner of a residual block per lane, two per lane at most; wider times take the wavefront-per-time kernel)
-    { int widest = 0; for (int t = 0; t < T; ++t) widest = std::max(widest, tptr[t + 1] - tptr[t]); backsub_wg = !with_loss && !with_subset && widest <= 128 /* 4 x 128 corners = 512 lanes */ && !(getenv("RSBA_MT_BACKSUB_WG") && atoi(getenv("RSBA_MT_BACKSUB_WG")) == 0); }
-    nb_time = backsub_wg ? T : (T + 3) / 4;
-    split_backsub = split && (with_subset || !(getenv("RSBA_MT_SPLIT_BACKSUB") && atoi(getenv("RSBA_MT_SPLIT_BACKSUB")) == 0));
-    if (split_backsub) { ncand_wg = (N + 255) / 256; nb_time = T + ncand_wg; }
-    auto al = [](void** q, size_t bytes) { return hipMalloc(q, std::max<size_t>(bytes, 8)) == hipSuccess; };
-    const int np = p.block_priors.empty() ? 0 : 1;   // the priors' partial system and their entry behind the times'
-    if (np) {
-      std::vector<int> pcols;
-      for (const auto& kv : p.block_priors) pcols.push_back(red_col[kv.first < C ? kv.first : kv.first - Tn]);
-      if (prior.Upload(p, pcols) != RSBA_OK || !al((void**)&prior_pe, 2 * (size_t)prior.K * 8)) return RSBA_ERR_HIP;
-    }
-    prior_part_zero = np != 0;   // (zeroed below, once part is allocated)
-    const size_t nA = (size_t)(nr + 2) * nr;
-    if (!al((void**)&mo, N * sizeof(MarkerObs)) || !al((void**)&ts, N * sizeof(TimeSlots)) || !al((void**)&chunk_ptr, (G + 1) * 4) ||
-        !al((void**)&time_ptr, (T + 1) * 4) || !al((void**)&slot_ptr, (T + 1) * 4) || !al((void**)&slot_col, scol.size() * 4) ||
-        !al((void**)&time_full, T * 4) || !al((void**)&col_full, nr * 4) || !al((void**)&ok_flag, 4) ||
-        !al((void**)&obs8, 8 * (size_t)N * 8) || !al((void**)&intr, p.intrinsics.size() * 8) || !al((void**)&params[0], nfull * 8) ||
-        !al((void**)&params[1], nfull * 8) || !al((void**)&params0, nfull * 8) || !al((void**)&posec, (size_t)(nfull / 6) * CC_STRIDE * 8) ||
-        !al((void**)&posec_c, (size_t)(nfull / 6) * CC_STRIDE * 8) ||
-        !al((void**)&ss_x, N * 8) || !al((void**)&scale_t, 6 * (size_t)T * 8) ||
-        !al((void**)&scale_r, nr * 8) || !al((void**)&tdata, 48 * (size_t)T * 8) || !al((void**)&part, (size_t)(G + np) * PL.size() * 8) ||
-        !al((void**)&red, RL.size() * 8) || !al((void**)&A, nA * 8) || (nr > RSBA_CHOL_MAXN && !al((void**)&Wm, nA * 8)) ||
-        !al((void**)&delta_r, nr * 8) || !al((void**)&delta_t, 6 * (size_t)T * 8) || !al((void**)&bp_time, 4 * (size_t)(nb_time + np) * 8) ||
-        !al((void**)&solve_out, 8 * 8) || !al((void**)&res, RES_SIZE * 8) ||
-        (with_loss && (!al((void**)&wsq, N * 8) || !al((void**)&drho, N * 8) || !al((void**)&drho_c, (size_t)(N + np) * 8) || !al((void**)&wts, N * 8))))
-      return RSBA_ERR_HIP;
-    if (with_loss) {
-      blk_order = order;
-      const std::vector<double> ones(p.observation_weights.empty() ? (size_t)N : 0, 1.0);
+    int cus = 256;
+    { int dev = 0; hipDeviceProp_t prop; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount; }
+    const int rc = PlanMarkerChain(p, loss, cus, MarkerSwitches::FromEnv(), &plan);
+    if (rc != RSBA_OK) return rc;
+    const MarkerPlan& P = plan;
+    const MarkerTables& B = plan.tab;
+    const size_t N = P.N, T = P.T, nr = P.nr, nfull = P.nfull, np = P.np;
+    const size_t nA = (nr + 2) * nr, npart = PartLayout{P.nr}.size();
+    if (np && (prior.Upload(p, B.pcols) != RSBA_OK || !Alloc(&prior_pe, 2 * (size_t)prior.K))) return RSBA_ERR_HIP;
+    bool ok = Alloc(&mo, B.hmo) && Alloc(&ts, B.hts) && Alloc(&chunk_ptr, B.cptr) && Alloc(&time_ptr, B.tptr) && Alloc(&slot_ptr, B.sptr) &&
+              Alloc(&slot_col, B.scol) && Alloc(&time_full, B.tfull) && Alloc(&col_full, B.cf) && Alloc(&ok_flag, 1) && Alloc(&obs8, B.hobs) &&
+              Alloc(&intr, p.intrinsics) && Alloc(&params[0], nfull) && Alloc(&params[1], nfull) && Alloc(&params0, p.parameters) &&
+              Alloc(&posec, nfull / 6 * CC_STRIDE) && Alloc(&posec_c, nfull / 6 * CC_STRIDE) && Alloc(&ss_x, N) && Alloc(&scale_t, 6 * T) &&
+              Alloc(&scale_r, nr) && Alloc(&tdata, 48 * T) && Alloc(&part, (P.G + np) * npart) && Alloc(&red, RedLayout{P.nr}.size()) && Alloc(&A, nA) &&
+              (P.nr <= RSBA_CHOL_MAXN || Alloc(&Wm, nA)) && Alloc(&delta_r, nr) && Alloc(&delta_t, 6 * T) && Alloc(&bp_time, 4 * (P.nb_time + np)) &&
+              Alloc(&solve_out, 8) && Alloc(&res, RES_SIZE) &&
+              (!P.with_loss || (Alloc(&wsq, N) && Alloc(&drho, N) && Alloc(&drho_c, N + np) && Alloc(&wts, N))) &&
+              (!P.with_dist || Alloc(&dist, p.distortion)) &&
+              (!P.has_const || (Alloc(&cs_ptr, B.csptr) && Alloc(&cs_full, B.csfull) && Alloc(&tconst, B.htc) && Alloc(&cpose_full, B.cpf))) &&
+              (!P.with_subset || (Alloc(&tflags, B.htflags) && Alloc(&rmask, B.hrmask))) &&
+              (!P.split || (Alloc(&slot_order, B.h_order) && Alloc(&x_order, B.h_xorder) && Alloc(&slot_time, B.h_slot_time) && Alloc(&sb_ptr, B.h_sb_ptr) &&
+                            Alloc(&sb_blk, B.h_sb_blk) && Alloc(&xi_ptr, B.h_xi_ptr) && Alloc(&xi_blk, B.h_xi_blk) && Alloc(&xi_cc, B.h_xi_cc) &&
+                            Alloc(&xi_cm, B.h_xi_cm) && Alloc(&xc_ptr, B.h_xc_ptr) && Alloc(&sp, (size_t)P.nslots * RSBA_SP_STRIDE) &&
+                            Alloc(&xout, (size_t)P.nx * 36) && Alloc(&tscal, 4 * T))) &&
+              (!P.split_backsub || Alloc(&blk_time, B.h_bt)) &&
+              (P.tc_tiles == 0 || (Alloc(&tc_flags, P.tc_flags) && Alloc(&tc_map, B.tc_map) && Alloc(&tc_hand, P.tc_hand)));
+    if (!ok) return RSBA_ERR_HIP;
+    if (P.with_loss) {
+      const std::vector<double> ones(p.observation_weights.empty() ? N : 0, 1.0);
       if (SetWeights(p.observation_weights.empty() ? ones.data() : p.observation_weights.data()) != RSBA_OK) return RSBA_ERR_HIP;
     }
-    auto up = [](void* d, const void* h, size_t bytes) { return bytes == 0 || hipMemcpy(d, h, bytes, hipMemcpyHostToDevice) == hipSuccess; };
-    if (!up(mo, hmo.data(), N * sizeof(MarkerObs)) || !up(ts, hts.data(), N * sizeof(TimeSlots)) || !up(chunk_ptr, cptr.data(), (G + 1) * 4) ||
-        !up(time_ptr, tptr.data(), (T + 1) * 4) || !up(slot_ptr, sptr.data(), (T + 1) * 4) || !up(slot_col, scol.data(), scol.size() * 4) ||
-        !up(time_full, tfull.data(), T * 4) || !up(col_full, cf.data(), nr * 4) ||
-        !up(obs8, hobs.data(), 8 * (size_t)N * 8) || !up(intr, p.intrinsics.data(), p.intrinsics.size() * 8) ||
-        !up(params0, p.parameters.data(), nfull * 8))
-      return RSBA_ERR_HIP;
     if (hipMemset(res, 0, RES_SIZE * 8) != hipSuccess) return RSBA_ERR_HIP;
-    // the priors' partial system: zeros for good, k_mc_prior_system writes the prior blocks' entries only
-    if (prior_part_zero && hipMemset(part + (size_t)G * PL.size(), 0, PL.size() * 8) != hipSuccess) return RSBA_ERR_HIP;
-    with_dist = p.has_distortion();
-    if (with_dist && (!al((void**)&dist, p.distortion.size() * 8) || !up(dist, p.distortion.data(), p.distortion.size() * 8))) return RSBA_ERR_HIP;
-    if (has_const) {
-      std::vector<int> cpf(6 * (size_t)ncpose, 0);   // (k_pose_constants_reduced's layout: a pose's offset at every sixth entry)
-      for (int k = 0; k < ncpose; ++k) cpf[6 * (size_t)k] = hcpose[k];
-      if (!al((void**)&cs_ptr, (T + 1) * 4) || !al((void**)&cs_full, csfull.size() * 4) || !al((void**)&tconst, T * 4) || !al((void**)&cpose_full, cpf.size() * 4) ||
-          !up(cs_ptr, csptr.data(), (T + 1) * 4) || !up(cs_full, csfull.data(), csfull.size() * 4) || !up(tconst, htc.data(), T * 4) ||
-          !up(cpose_full, cpf.data(), cpf.size() * 4))
-        return RSBA_ERR_HIP;
-    }
-    if (with_subset) {
-      if (!al((void**)&tflags, (size_t)T * 4) || !al((void**)&rmask, hrmask.size()) || !up(tflags, htflags.data(), (size_t)T * 4) || !up(rmask, hrmask.data(), hrmask.size()))
-        return RSBA_ERR_HIP;
-    }
-    if (nr == 0) {
+    // the priors' partial system: zeros for good (which blocks carry a prior is fixed here), k_mc_prior_system writes the prior blocks' entries only
+    if (np && hipMemset(part + P.G * npart, 0, npart * 8) != hipSuccess) return RSBA_ERR_HIP;
+    if (P.nr == 0) {
       // no reduced system: the solve's result block is that of an empty one, once
       const double empty[5] = {0.0, 0.0, 0.0, 0.0, 1.0};
-      if (!up(solve_out, empty, sizeof(empty))) return RSBA_ERR_HIP;
+      if (hipMemcpy(solve_out, empty, sizeof(empty), hipMemcpyHostToDevice) != hipSuccess) return RSBA_ERR_HIP;
     }
-    if (split) {
-      if (!al((void**)&slot_order, (size_t)nslots * 4) || !al((void**)&x_order, (size_t)nx_threads * 4) || !al((void**)&slot_time, (size_t)nslots * 4) || !al((void**)&sb_ptr, ((size_t)nslots + 1) * 4) ||
-          !al((void**)&sb_blk, h_sb_blk.size() * sizeof(int4)) || !al((void**)&xi_ptr, ((size_t)nx + 1) * 4) || !al((void**)&xi_blk, h_xi_blk.size() * sizeof(int4)) ||
-          !al((void**)&xi_cc, (size_t)nx * 4) || !al((void**)&xi_cm, (size_t)nx * 4) || !al((void**)&xc_ptr, ((size_t)G + 1) * 4) ||
-          !al((void**)&sp, (size_t)nslots * RSBA_SP_STRIDE * 8) || !al((void**)&xout, (size_t)nx * 36 * 8) || !al((void**)&tscal, 4 * (size_t)T * 8))
-        return RSBA_ERR_HIP;
-      if (split_backsub) {
-        std::vector<int> h_bt(N);
-        for (int t = 0; t < T; ++t) for (int k = tptr[t]; k < tptr[t + 1]; ++k) h_bt[k] = t;
-        if (!al((void**)&blk_time, (size_t)N * 4) || !up(blk_time, h_bt.data(), (size_t)N * 4)) return RSBA_ERR_HIP;
-      }
-      if (!up(slot_order, h_order.data(), (size_t)nslots * 4) || !up(x_order, h_xorder.data(), (size_t)nx_threads * 4) || !up(slot_time, h_slot_time.data(), (size_t)nslots * 4) ||
-          !up(sb_ptr, h_sb_ptr.data(), ((size_t)nslots + 1) * 4) || !up(sb_blk, h_sb_blk.data(), h_sb_blk.size() * sizeof(int4)) ||
-          !up(xi_ptr, h_xi_ptr.data(), ((size_t)nx + 1) * 4) || !up(xi_blk, h_xi_blk.data(), h_xi_blk.size() * sizeof(int4)) ||
-          !up(xi_cc, h_xi_cc.data(), (size_t)nx * 4) || !up(xi_cm, h_xi_cm.data(), (size_t)nx * 4) || !up(xc_ptr, h_xc_ptr.data(), ((size_t)G + 1) * 4))
-        return RSBA_ERR_HIP;
-      const void* kacc = acc_tiles == 3 ? (acc_tb == 2 ? (const void*)k_mc_accumulate_mfma<3, 2> : (const void*)k_mc_accumulate_mfma<3, 1>) : acc_tiles == 8 ? (const void*)k_mc_accumulate_mfma<8, 1>
-                         : lds_s ? (const void*)k_mc_accumulate<true> : (const void*)k_mc_accumulate<false>;
-      if (lds_acc > 48 * 1024 && hipFuncSetAttribute(kacc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_acc) != hipSuccess) return RSBA_ERR_HIP;
-      if (!(getenv("RSBA_MT_FORK") && atoi(getenv("RSBA_MT_FORK")) == 0)) {
-        bool ok = true;
-        for (auto& q : fork_s) ok = ok && hipStreamCreateWithFlags(&q, hipStreamNonBlocking) == hipSuccess;
-        for (auto& q : fork_ev) ok = ok && hipEventCreateWithFlags(&q, hipEventDisableTiming) == hipSuccess;
-        if (!ok) return RSBA_ERR_HIP;
-      }
+    // the tiled factorisation's flags start at zero, its hand-overs with the sentinel everywhere
+    if (P.tc_tiles > 0 && (hipMemset(tc_flags, 0, P.tc_flags * sizeof(int)) != hipSuccess || hipMemset(tc_hand, 0xff, P.tc_hand * sizeof(double)) != hipSuccess))
+      return RSBA_ERR_HIP;
+    if (P.fork) {
+      for (auto& q : fork_s) ok = ok && hipStreamCreateWithFlags(&q, hipStreamNonBlocking) == hipSuccess;
+      for (auto& q : fork_ev) ok = ok && hipEventCreateWithFlags(&q, hipEventDisableTiming) == hipSuccess;
     }
-    if (backsub_wg) {
-      const size_t lds_bw = (size_t)(pmax + 1) * (CC_STRIDE + 12 + 6) * sizeof(double);
-      const void* kbw = nullptr;
-      RSBA_DIST_SWITCH(kbw = has_const ? (const void*)k_time_backsub_wg<2, 256, true, D> : (const void*)k_time_backsub_wg<2, 256, false, D>);
-      if (lds_bw > 48 * 1024 && hipFuncSetAttribute(kbw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bw) != hipSuccess) return RSBA_ERR_HIP;
+    // dynamic LDS above the default limit, for the kernels the path runs
+    if (P.split) ok = ok && RaiseLds((const void*)AccKernel(), P.lds_acc);
+    else WithElimKernel([&](auto k, auto) { ok = ok && RaiseLds((const void*)k, P.lds_elim); });
+    if (P.backsub_wg) WithBacksubWgKernel([&](auto k, auto) { ok = ok && RaiseLds((const void*)k, P.lds_bw); });
+    if (P.nr > RSBA_CHOL_MAXN) {
+      ok = ok && RaiseLds((const void*)k_chol_step, CholStepLdsDoubles() * sizeof(double));
+      if (P.tc_tiles > 0) ok = ok && RaiseLds((const void*)k_chol_tiles_persistent, TileCholLdsDoubles() * sizeof(double));
+    } else if (P.nr > 0) {
+      ok = ok && RaiseLds((const void*)k_marker_reduced_solve, P.lds_solve);
+      if (P.debug) fprintf(stderr, "rsba: marker reduced system %d columns, solve in LDS: %d (%zu bytes)\n", P.nr, (int)P.solve_lds, P.lds_solve_lds);
+      if (P.solve_lds) ok = ok && RaiseLds((const void*)k_marker_reduced_solve_lds, P.lds_solve_lds);
     }
-    if (!split && lds_elim > 48 * 1024) {
-      const void* kel = nullptr;
-      RSBA_DIST_SWITCH(kel = has_const ? (lds_s ? (const void*)k_time_eliminate<true, true, D> : (const void*)k_time_eliminate<false, true, D>)
-                                       : (lds_s ? (const void*)k_time_eliminate<true, false, D> : (const void*)k_time_eliminate<false, false, D>));
-      if (hipFuncSetAttribute(kel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_elim) != hipSuccess) return RSBA_ERR_HIP;
-    }
-    if (nr == 0) {
-      // (no reduced solve)
-    } else if (nr <= RSBA_CHOL_MAXN) {
-      const size_t lds_c = std::max((size_t)4 * 1024, CholeskyLdsDoubles(nr)) * sizeof(double);
-      if (lds_c > 48 * 1024 &&
-          hipFuncSetAttribute((const void*)k_marker_reduced_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c) != hipSuccess) return RSBA_ERR_HIP;
-      solve_lds = nr <= RSBA_PB * RSBA_MRS_MAXP && MarkerSolveLdsDoubles(nr) * sizeof(double) <= 156 * 1024 && !(getenv("RSBA_MT_SOLVE_LDS") && atoi(getenv("RSBA_MT_SOLVE_LDS")) == 0);
-      if (getenv("RSBA_DEBUG")) fprintf(stderr, "rsba: marker reduced system %d columns, solve in LDS: %d (%zu bytes)\n", nr, (int)solve_lds, MarkerSolveLdsDoubles(nr) * sizeof(double));
-      if (solve_lds && hipFuncSetAttribute((const void*)k_marker_reduced_solve_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(MarkerSolveLdsDoubles(nr) * sizeof(double))) != hipSuccess) return RSBA_ERR_HIP;
-    } else {
-      if (hipFuncSetAttribute((const void*)k_chol_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(CholStepLdsDoubles() * sizeof(double))) != hipSuccess)
-        return RSBA_ERR_HIP;
-      int dev = 0; hipDeviceProp_t prop;
-      const char* e2 = getenv("RSBA_CHOL_TILES");
-      if (!(e2 && atoi(e2) == 0) && hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) {
-        const int m = MultiCholPadded(nr), nrt = (m + 1 + 63) / 64, ntiles = nrt * (nrt + 1) / 2;
-        if (ntiles <= 2 * prop.multiProcessorCount) {
-          tc_np = m / RSBA_PB; tc_nrt = nrt; tc_tiles = ntiles;
-          const size_t nflags = (size_t)tc_np * (nrt + 1) + 1;
-          if (!al((void**)&tc_flags, nflags * sizeof(int)) || hipMemset(tc_flags, 0, nflags * sizeof(int)) != hipSuccess) return RSBA_ERR_HIP;
-          const size_t hand_bytes = (size_t)2 * nrt * kTileHandDoubles * sizeof(double);   // the diagonal chain's hand-overs: the sentinel everywhere
-          {
-            const std::vector<int> order = TileOrder(nrt, prop.multiProcessorCount);
-            if (!al((void**)&tc_map, order.size() * sizeof(int)) || hipMemcpy(tc_map, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return RSBA_ERR_HIP;
-          }
-          if (!al((void**)&tc_hand, hand_bytes) || hipMemset(tc_hand, 0xff, hand_bytes) != hipSuccess) return RSBA_ERR_HIP;
-          if (hipFuncSetAttribute((const void*)k_chol_tiles_persistent, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)(TileCholLdsDoubles() * sizeof(double))) != hipSuccess) return RSBA_ERR_HIP;
-        }
-      }
-    }
-    return RSBA_OK;
+    plan.tab = MarkerTables();
+    return ok ? RSBA_OK : RSBA_ERR_HIP;
   }
   // the blocks' weights, given in the problem's order, into the device's time order (a solver that runs the kLoss instances)
   int SetWeights(const double* w) {
-    std::vector<double> h((size_t)N);
-    for (int k = 0; k < N; ++k) h[k] = w[blk_order[k]];
-    return hipMemcpy(wts, h.data(), (size_t)N * 8, hipMemcpyHostToDevice) == hipSuccess ? RSBA_OK : RSBA_ERR_HIP;
+    std::vector<double> h((size_t)plan.N);
+    for (int k = 0; k < plan.N; ++k) h[k] = w[plan.order[k]];
+    return hipMemcpy(wts, h.data(), (size_t)plan.N * 8, hipMemcpyHostToDevice) == hipSuccess ? RSBA_OK : RSBA_ERR_HIP;
   }
   int Reset(hipStream_t st) {
-    if (hipMemcpyAsync(params[0], params0, nfull * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return RSBA_ERR_HIP;
-    if (hipMemcpyAsync(params[1], params0, nfull * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return RSBA_ERR_HIP;
-    if (ncpose > 0) {
+    if (hipMemcpyAsync(params[0], params0, plan.nfull * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return RSBA_ERR_HIP;
+    if (hipMemcpyAsync(params[1], params0, plan.nfull * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return RSBA_ERR_HIP;
+    if (plan.ncpose > 0) {
       // the constant cameras' and markers' candidate pose constants are those at x, for the whole run
-      k_pose_constants_reduced<<<(ncpose + 63) / 64, 64, 0, st>>>(ncpose, cpose_full, params0, posec_c);
+      k_pose_constants_reduced<<<(plan.ncpose + 63) / 64, 64, 0, st>>>(plan.ncpose, cpose_full, params0, posec_c);
       if (hipGetLastError() != hipSuccess) return RSBA_ERR_HIP;
     }
     cur = 0;
@@ -1766,14 +1450,20 @@ struct MarkerSchurDevice {
   }
   void Accept() { cur = 1 - cur; }
 
+  // A kernel templated on loss, constant blocks, distortion or subset masks is launched once, through Dispatch; the arguments of the
+  // instances that do not read them (wsq, drho_c, wts without a loss; tconst, cs_ptr, cs_full without constant blocks) are the null
+  // pointers those members hold then.
   template <typename Timer>
   int Step(hipStream_t st, const rsba_options& o, double radius, bool first, double* res_host, Timer& Tm) {
+    const MarkerPlan& P = plan;
+    const int N = P.N, T = P.T, nr = P.nr, nfull = P.nfull, G = P.G, np = P.np, nb_time = P.nb_time;
+    const double half_side = P.half_side;
     IterParams ip;
     ip.radius = radius; ip.min_lm_diagonal = o.min_lm_diagonal; ip.max_lm_diagonal = o.max_lm_diagonal; ip.huber_delta = 0.0;
     ip.first = first ? 1 : 0; ip.jacobi_scaling = o.jacobi_scaling;
     // the robust loss, read as the point model reads it (signed: see LossAndScale); Upload was told whether there is one
     // (with_loss and huber_delta = 0: observation weights alone, rho(s) = s)
-    const double loss = with_loss && o.huber_delta > 0.0 ? (o.loss_type == RSBA_LOSS_CAUCHY ? -o.huber_delta : o.huber_delta) : 0.0;
+    const double loss = P.with_loss && o.huber_delta > 0.0 ? (o.loss_type == RSBA_LOSS_CAUCHY ? -o.huber_delta : o.huber_delta) : 0.0;
     const int x = cur, c = 1 - cur;
     if (hipMemcpyAsync(params[c], params[x], nfull * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return RSBA_ERR_HIP;
     auto chk = [&](const char* what) {
@@ -1783,22 +1473,19 @@ struct MarkerSchurDevice {
     };
     if (!chk("(before marker step)")) return RSBA_ERR_HIP;
     const RedLayout RL{nr};
+    auto intr_of = [&](auto D) { return IntrPass<D.value>(intr, dist); };
     Tm.Begin("k_pose_constants", st);
     k_pose_constants<<<(nfull / 6 + 255) / 256, 256, 0, st>>>(nfull / 6, params[x], posec);
     Tm.End(st);
-    ElimArgs ea{nr, dmax, (int)N, chunk_ptr, time_ptr, slot_ptr, slot_col, time_full, col_full, ts, mo, obs8, intr, posec, half_side, params[x], scale_t, tdata, part, ip,
-                cs_ptr, cs_full, tconst, pmax};
-    ElimArgsDist ead; static_cast<ElimArgs&>(ead) = ea; ead.dist = dist;
-    auto elim_args = [&](auto d) -> const typename ElimArgT<decltype(d)::value>::type& { if constexpr (decltype(d)::value) return ead; else return ea; };
-    if (split) {
-      SplitArgs sa{nslots, T, nx, ncam_cols, nx_threads, slot_order, x_order, slot_time, slot_col, sb_ptr, sb_blk, time_ptr, time_full, col_full, ts, mo, obs8, intr, posec, half_side,
+    if (P.split) {
+      SplitArgs sa{P.nslots, T, P.nx, P.ncam_cols, P.nx_threads, slot_order, x_order, slot_time, slot_col, sb_ptr, sb_blk, time_ptr, time_full, col_full, ts, mo, obs8, intr, posec, half_side,
                    xi_ptr, xi_blk, xi_cc, xi_cm, sp, xout, wsq, drho};
       SplitArgsDist sad; static_cast<SplitArgs&>(sad) = sa; sad.dist = dist;
-      auto split_args = [&](auto d) -> const typename SplitArgT<decltype(d)::value>::type& { if constexpr (decltype(d)::value) return sad; else return sa; };
-      if (with_loss) {
+      auto split_args = [&](auto D) -> const typename SplitArgT<D.value>::type& { if constexpr (D.value) return sad; else return sa; };
+      if (P.with_loss) {
         // the corrector's weights at x, wanted by all three product kernels
         Tm.Begin("k_mc_block_weight", st);
-        RSBA_DIST_SWITCH(k_mc_block_weight<D><<<(N + 255) / 256, 256, 0, st>>>(N, ts, mo, obs8, IntrPass<D>(intr, dist), half_side, posec, loss, wts, wsq, drho));
+        Dispatch([&](auto D) { k_mc_block_weight<D.value><<<(N + 255) / 256, 256, 0, st>>>(N, ts, mo, obs8, intr_of(D), half_side, posec, loss, wts, wsq, drho); }, P.with_dist);
         Tm.End(st);
       }
       // the three product kernels are independent and none fills the chip: side by side on three streams (one after the other
@@ -1809,37 +1496,30 @@ struct MarkerSchurDevice {
         if (hipEventRecord(fork_ev[0], st) != hipSuccess || hipStreamWaitEvent(s_time, fork_ev[0], 0) != hipSuccess ||
             hipStreamWaitEvent(s_cross, fork_ev[0], 0) != hipSuccess) return RSBA_ERR_HIP;
       }
-      if (nslots > 0) {   // (none: n_r = 0)
+      if (P.nslots > 0) {   // (none: n_r = 0)
         Tm.Begin("k_mc_slot_products", st);
-        if (with_loss) RSBA_DIST_SWITCH(k_mc_slot_products<true, D><<<(nslots + 255) / 256, 256, 0, st>>>(split_args(std::integral_constant<bool, D>())));
-        else RSBA_DIST_SWITCH(k_mc_slot_products<false, D><<<(nslots + 255) / 256, 256, 0, st>>>(split_args(std::integral_constant<bool, D>())));
+        Dispatch([&](auto L, auto D) { k_mc_slot_products<L.value, D.value><<<(P.nslots + 255) / 256, 256, 0, st>>>(split_args(D)); }, P.with_loss, P.with_dist);
         Tm.End(st);
-        if (with_subset) {
+        if (P.with_subset) {
           Tm.Begin("k_mc_subset_slots", st);
-          k_mc_subset_slots<<<(unsigned)(((size_t)nslots * 64 + 255) / 256), 256, 0, st>>>(nslots, slot_time, slot_col, tflags, rmask, sp);
+          k_mc_subset_slots<<<(unsigned)(((size_t)P.nslots * 64 + 255) / 256), 256, 0, st>>>(P.nslots, slot_time, slot_col, tflags, rmask, sp);
           Tm.End(st);
         }
       }
       Tm.Begin("k_mc_time_products", st);
-      if (with_subset) {
-        if (with_loss) RSBA_DIST_SWITCH(k_mc_time_products<true, true, D, true><<<(T + 3) / 4, 256, 0, s_time>>>(split_args(std::integral_constant<bool, D>()), ip, params[x], scale_t, tdata, tscal, tflags));
-        else RSBA_DIST_SWITCH(k_mc_time_products<false, true, D, true><<<(T + 3) / 4, 256, 0, s_time>>>(split_args(std::integral_constant<bool, D>()), ip, params[x], scale_t, tdata, tscal, tflags));
-      } else if (has_const) {
-        if (with_loss) RSBA_DIST_SWITCH(k_mc_time_products<true, true, D><<<(T + 3) / 4, 256, 0, s_time>>>(split_args(std::integral_constant<bool, D>()), ip, params[x], scale_t, tdata, tscal, tconst));
-        else RSBA_DIST_SWITCH(k_mc_time_products<false, true, D><<<(T + 3) / 4, 256, 0, s_time>>>(split_args(std::integral_constant<bool, D>()), ip, params[x], scale_t, tdata, tscal, tconst));
-      } else {
-        if (with_loss) RSBA_DIST_SWITCH(k_mc_time_products<true, false, D><<<(T + 3) / 4, 256, 0, s_time>>>(split_args(std::integral_constant<bool, D>()), ip, params[x], scale_t, tdata, tscal));
-        else RSBA_DIST_SWITCH(k_mc_time_products<false, false, D><<<(T + 3) / 4, 256, 0, s_time>>>(split_args(std::integral_constant<bool, D>()), ip, params[x], scale_t, tdata, tscal));
-      }
+      Dispatch([&](auto L, auto Cn, auto D, auto Sb) {
+        // (subset masks ride on the constant-block instances: no <*, false, D, true>; the time's flags arrive where tconst does)
+        if constexpr (Cn.value || !Sb.value)
+          k_mc_time_products<L.value, Cn.value, D.value, Sb.value><<<(T + 3) / 4, 256, 0, s_time>>>(split_args(D), ip, params[x], scale_t, tdata, tscal, Sb.value ? tflags : tconst);
+      }, P.with_loss, P.has_const, P.with_dist, P.with_subset);
       Tm.End(st);
-      if (nx > 0) {
+      if (P.nx > 0) {
         Tm.Begin("k_mc_cross", st);
-        if (with_loss) RSBA_DIST_SWITCH(k_mc_cross<true, D><<<(nx_threads + 255) / 256, 256, 0, s_cross>>>(split_args(std::integral_constant<bool, D>())));
-        else RSBA_DIST_SWITCH(k_mc_cross<false, D><<<(nx_threads + 255) / 256, 256, 0, s_cross>>>(split_args(std::integral_constant<bool, D>())));
+        Dispatch([&](auto L, auto D) { k_mc_cross<L.value, D.value><<<(P.nx_threads + 255) / 256, 256, 0, s_cross>>>(split_args(D)); }, P.with_loss, P.with_dist);
         Tm.End(st);
-        if (with_subset) {
+        if (P.with_subset) {
           Tm.Begin("k_mc_subset_cross", st);
-          k_mc_subset_cross<<<(unsigned)(((size_t)nx * 36 + 255) / 256), 256, 0, s_cross>>>(nx, xi_cc, xi_cm, rmask, xout);
+          k_mc_subset_cross<<<(unsigned)(((size_t)P.nx * 36 + 255) / 256), 256, 0, s_cross>>>(P.nx, xi_cc, xi_cm, rmask, xout);
           Tm.End(st);
         }
       }
@@ -1847,26 +1527,20 @@ struct MarkerSchurDevice {
         if (hipEventRecord(fork_ev[1], s_time) != hipSuccess || hipEventRecord(fork_ev[2], s_cross) != hipSuccess ||
             hipStreamWaitEvent(st, fork_ev[1], 0) != hipSuccess || hipStreamWaitEvent(st, fork_ev[2], 0) != hipSuccess) return RSBA_ERR_HIP;
       }
-      AccArgs aa{nr, dmax, chunk_ptr, slot_ptr, slot_col, sp, tdata, tscal, xc_ptr, xi_cc, xi_cm, xout, part};
+      AccArgs aa{nr, P.dmax, chunk_ptr, slot_ptr, slot_col, sp, tdata, tscal, xc_ptr, xi_cc, xi_cm, xout, part};
       Tm.Begin("k_mc_accumulate", st);
-      if (acc_tiles == 3 && acc_tb == 2) k_mc_accumulate_mfma<3, 2><<<G, RSBA_MT_THREADS, lds_acc, st>>>(aa);
-      else if (acc_tiles == 3) k_mc_accumulate_mfma<3, 1><<<G, RSBA_MT_THREADS, lds_acc, st>>>(aa);
-      else if (acc_tiles == 8) k_mc_accumulate_mfma<8, 1><<<G, RSBA_MT_THREADS, lds_acc, st>>>(aa);
-      else if (lds_s) k_mc_accumulate<true><<<G, RSBA_MT_THREADS, lds_acc, st>>>(aa);
-      else k_mc_accumulate<false><<<G, RSBA_MT_THREADS, lds_acc, st>>>(aa);
+      AccKernel()<<<G, RSBA_MT_THREADS, P.lds_acc, st>>>(aa);
       Tm.End(st);
       if (!chk("split elimination")) return RSBA_ERR_HIP;
     } else {
+      ElimArgs ea{nr, P.dmax, N, chunk_ptr, time_ptr, slot_ptr, slot_col, time_full, col_full, ts, mo, obs8, intr, posec, half_side, params[x], scale_t, tdata, part, ip,
+                  cs_ptr, cs_full, tconst, P.pmax};
+      ElimArgsDist ead; static_cast<ElimArgs&>(ead) = ea; ead.dist = dist;
       Tm.Begin("k_time_eliminate", st);
-      if (has_const) {
-        if (lds_s) RSBA_DIST_SWITCH(k_time_eliminate<true, true, D><<<G, RSBA_MT_THREADS, lds_elim, st>>>(elim_args(std::integral_constant<bool, D>())));
-        else RSBA_DIST_SWITCH(k_time_eliminate<false, true, D><<<G, RSBA_MT_THREADS, lds_elim, st>>>(elim_args(std::integral_constant<bool, D>())));
-      } else if (lds_s) RSBA_DIST_SWITCH(k_time_eliminate<true, false, D><<<G, RSBA_MT_THREADS, lds_elim, st>>>(elim_args(std::integral_constant<bool, D>())));
-      else RSBA_DIST_SWITCH(k_time_eliminate<false, false, D><<<G, RSBA_MT_THREADS, lds_elim, st>>>(elim_args(std::integral_constant<bool, D>())));
+      WithElimKernel([&](auto k, auto D) { if constexpr (D.value) k<<<G, RSBA_MT_THREADS, P.lds_elim, st>>>(ead); else k<<<G, RSBA_MT_THREADS, P.lds_elim, st>>>(ea); });
       Tm.End(st);
       if (!chk("k_time_eliminate")) return RSBA_ERR_HIP;
     }
-    const int np = prior.K > 0 ? 1 : 0;
     if (np) {
       Tm.Begin("k_mc_prior_system", st);
       k_mc_prior_system<<<1, 256, 0, st>>>(nr, prior.K, prior.full, prior.col, prior.mask, prior.ab, params[x], part + (size_t)G * PartLayout{nr}.size(), prior_pe);
@@ -1878,19 +1552,18 @@ struct MarkerSchurDevice {
     if (nr == 0) {
       // nothing but time blocks are free: solve_out holds the empty system's result (Upload)
     } else if (nr <= RSBA_CHOL_MAXN) {
-      const size_t lds_c = std::max((size_t)4 * 1024, CholeskyLdsDoubles(nr)) * sizeof(double);
       Tm.Begin("k_marker_reduced_solve", st);
-      if (solve_lds) k_marker_reduced_solve_lds<<<1, 512, MarkerSolveLdsDoubles(nr) * sizeof(double), st>>>(nr, red, A, scale_r, col_full, params[x], params[c], delta_r, solve_out, ip);
-      else k_marker_reduced_solve<<<1, 512, lds_c, st>>>(nr, red, A, scale_r, col_full, params[x], params[c], delta_r, solve_out, ip);
+      if (P.solve_lds) k_marker_reduced_solve_lds<<<1, 512, P.lds_solve_lds, st>>>(nr, red, A, scale_r, col_full, params[x], params[c], delta_r, solve_out, ip);
+      else k_marker_reduced_solve<<<1, 512, P.lds_solve, st>>>(nr, red, A, scale_r, col_full, params[x], params[c], delta_r, solve_out, ip);
       Tm.End(st);
     } else {
       Tm.Begin("k_sys_build", st);
       k_sys_build<<<nr + 1, 256, 0, st>>>(red, RL, Wm, nullptr, nullptr, scale_r, ip, 1, ok_flag);
       Tm.End(st);
-      if (tc_tiles > 0) {
+      if (P.tc_tiles > 0) {
         Tm.Begin("k_chol_tiles_persistent", st);
-        k_chol_tiles_persistent<<<tc_tiles, 256, TileCholLdsDoubles() * sizeof(double), st>>>(
-            nr, Wm, A, ok_flag, TileCholFlags{tc_flags, tc_flags + tc_np, tc_flags + (size_t)tc_np * (tc_nrt + 1), tc_nrt, tc_hand, tc_tag & 1, 0, tc_map}, tc_tag + 1, res, TileSysSource{});
+        k_chol_tiles_persistent<<<P.tc_tiles, 256, TileCholLdsDoubles() * sizeof(double), st>>>(
+            nr, Wm, A, ok_flag, TileCholFlags{tc_flags, tc_flags + P.tc_np, tc_flags + (size_t)P.tc_np * (P.tc_nrt + 1), P.tc_nrt, tc_hand, tc_tag & 1, 0, tc_map}, tc_tag + 1, res, TileSysSource{});
         ++tc_tag;
         Tm.End(st);
       } else {
@@ -1903,78 +1576,69 @@ struct MarkerSchurDevice {
         }
         Tm.End(st);
       }
-      const size_t lds_f = std::max((size_t)4 * 1024, (size_t)((nr + 63) & ~63) + 3 * RSBA_PB * RSBA_PLD + 64) * sizeof(double);
       Tm.Begin("k_marker_chol_finish", st);
-      k_marker_chol_finish<<<1, 1024, lds_f, st>>>(nr, red, A, scale_r, col_full, params[x], params[c], delta_r, solve_out, ok_flag);
+      k_marker_chol_finish<<<1, 1024, P.lds_finish, st>>>(nr, red, A, scale_r, col_full, params[x], params[c], delta_r, solve_out, ok_flag);
       Tm.End(st);
     }
     if (!chk("reduced solve")) return RSBA_ERR_HIP;
     Tm.Begin("k_time_backsub_terms", st);
-    if (split_backsub) {
+    if (P.split_backsub) {
       if (nr > 0) k_pose_constants_reduced<<<(nr / 6 + 63) / 64, 64, 0, st>>>(nr / 6, col_full, params[c], posec_c);
-      if (has_const) k_mc_time_step<true><<<(8 * T + 255) / 256, 256, 0, st>>>(T, slot_ptr, slot_col, time_full, sp, tdata, delta_r, params[x], params[c], delta_t, posec_c, bp_time, tconst);
-      else k_mc_time_step<<<(8 * T + 255) / 256, 256, 0, st>>>(T, slot_ptr, slot_col, time_full, sp, tdata, delta_r, params[x], params[c], delta_t, posec_c, bp_time);
+      Dispatch([&](auto Cn) { k_mc_time_step<Cn.value><<<(8 * T + 255) / 256, 256, 0, st>>>(T, slot_ptr, slot_col, time_full, sp, tdata, delta_r, params[x], params[c], delta_t, posec_c, bp_time, tconst); },
+               P.has_const);
       // the two halves of the candidate's evaluation side by side (one after the other when every kernel is timed)
       const bool fork2 = fork_s[0] != nullptr && !Tm.enabled();
       hipStream_t s_cost = fork2 ? fork_s[0] : st;
       if (fork2 && (hipEventRecord(fork_ev[0], st) != hipSuccess || hipStreamWaitEvent(s_cost, fork_ev[0], 0) != hipSuccess)) return RSBA_ERR_HIP;
-      if (with_loss) {
-        RSBA_DIST_SWITCH(k_mc_candidate<0, true, D><<<ncand_wg, 256, 0, st>>>(N, T, ts, mo, obs8, IntrPass<D>(intr, dist), half_side, posec, posec_c, delta_r, delta_t, blk_time, bp_time, loss, wsq, drho_c));
-        RSBA_DIST_SWITCH(k_mc_candidate<1, true, D><<<ncand_wg, 256, 0, s_cost>>>(N, T, ts, mo, obs8, IntrPass<D>(intr, dist), half_side, posec, posec_c, delta_r, delta_t, blk_time, bp_time, loss, wsq, drho_c, wts));
-      } else {
-        RSBA_DIST_SWITCH(k_mc_candidate<0, false, D><<<ncand_wg, 256, 0, st>>>(N, T, ts, mo, obs8, IntrPass<D>(intr, dist), half_side, posec, posec_c, delta_r, delta_t, blk_time, bp_time));
-        RSBA_DIST_SWITCH(k_mc_candidate<1, false, D><<<ncand_wg, 256, 0, s_cost>>>(N, T, ts, mo, obs8, IntrPass<D>(intr, dist), half_side, posec, posec_c, delta_r, delta_t, blk_time, bp_time));
-      }
+      auto candidate = [&](auto half, hipStream_t s) {   // (the weights: the cost's half only)
+        constexpr int kHalf = decltype(half)::value;
+        Dispatch([&](auto L, auto D) {
+          k_mc_candidate<kHalf, L.value, D.value><<<P.ncand_wg, 256, 0, s>>>(N, T, ts, mo, obs8, intr_of(D), half_side, posec, posec_c, delta_r, delta_t, blk_time, bp_time, loss, wsq, drho_c,
+                                                                                    kHalf == 1 ? wts : nullptr);
+        }, P.with_loss, P.with_dist);
+      };
+      candidate(std::integral_constant<int, 0>(), st);
+      candidate(std::integral_constant<int, 1>(), s_cost);
       if (fork2 && (hipEventRecord(fork_ev[1], s_cost) != hipSuccess || hipStreamWaitEvent(st, fork_ev[1], 0) != hipSuccess)) return RSBA_ERR_HIP;
-    } else if (backsub_wg) {
+    } else if (P.backsub_wg) {
       if (nr > 0) k_pose_constants_reduced<<<(nr / 6 + 63) / 64, 64, 0, st>>>(nr / 6, col_full, params[c], posec_c);
-      const size_t lds_bw = (size_t)(pmax + 1) * (CC_STRIDE + 12 + 6) * sizeof(double);   // the shot's tables (k_time_backsub_wg)
-      if (has_const)
-        RSBA_DIST_SWITCH(k_time_backsub_wg<2, 256, true, D><<<T, 256, lds_bw, st>>>(T, time_ptr, time_full, ts, mo, obs8, IntrPass<D>(intr, dist), half_side, posec, posec_c, tdata, delta_r, params[x],
-                                                           params[c], delta_t, bp_time, slot_ptr, slot_col, col_full, cs_ptr, cs_full, tconst));
-      else
-        RSBA_DIST_SWITCH(k_time_backsub_wg<2, 256, false, D><<<T, 256, lds_bw, st>>>(T, time_ptr, time_full, ts, mo, obs8, IntrPass<D>(intr, dist), half_side, posec, posec_c, tdata, delta_r, params[x],
-                                                     params[c], delta_t, bp_time, slot_ptr, slot_col, col_full));
+      WithBacksubWgKernel([&](auto k, auto D) {
+        k<<<T, 256, P.lds_bw, st>>>(T, time_ptr, time_full, ts, mo, obs8, intr_of(D), half_side, posec, posec_c, tdata, delta_r, params[x], params[c], delta_t, bp_time, slot_ptr, slot_col, col_full,
+                                    cs_ptr, cs_full, tconst);
+      });
     } else {
-      if (with_loss && has_const)
-        RSBA_DIST_SWITCH(k_time_backsub_terms<true, true, D><<<nb_time, 256, 0, st>>>(T, time_ptr, time_full, ts, mo, obs8, IntrPass<D>(intr, dist), half_side, posec, tdata, delta_r, params[x],
-                                                                  params[c], delta_t, bp_time, loss, wsq, drho_c, tconst, wts));
-      else if (with_loss)
-        RSBA_DIST_SWITCH(k_time_backsub_terms<true, false, D><<<nb_time, 256, 0, st>>>(T, time_ptr, time_full, ts, mo, obs8, IntrPass<D>(intr, dist), half_side, posec, tdata, delta_r, params[x],
-                                                            params[c], delta_t, bp_time, loss, wsq, drho_c, nullptr, wts));
-      else if (has_const)
-        RSBA_DIST_SWITCH(k_time_backsub_terms<false, true, D><<<nb_time, 256, 0, st>>>(T, time_ptr, time_full, ts, mo, obs8, IntrPass<D>(intr, dist), half_side, posec, tdata, delta_r, params[x],
-                                                                   params[c], delta_t, bp_time, 0.0, nullptr, nullptr, tconst));
-      else
-        RSBA_DIST_SWITCH(k_time_backsub_terms<false, false, D><<<nb_time, 256, 0, st>>>(T, time_ptr, time_full, ts, mo, obs8, IntrPass<D>(intr, dist), half_side, posec, tdata, delta_r, params[x],
-                                                             params[c], delta_t, bp_time));
+      Dispatch([&](auto L, auto Cn, auto D) {
+        k_time_backsub_terms<L.value, Cn.value, D.value><<<nb_time, 256, 0, st>>>(T, time_ptr, time_full, ts, mo, obs8, intr_of(D), half_side, posec, tdata, delta_r, params[x], params[c], delta_t, bp_time,
+                                                                                  loss, wsq, drho_c, tconst, wts);
+      }, P.with_loss, P.has_const, P.with_dist);
     }
     Tm.End(st);
-    const int nd = split_backsub ? ncand_wg : nb_time;
+    const int nd = P.split_backsub ? P.ncand_wg : nb_time;
     if (np) {
       Tm.Begin("k_mc_prior_candidate", st);
       k_mc_prior_candidate<<<1, 256, 0, st>>>(prior.K, prior.full, prior.col, prior.mask, prior.ab, params[x], params[c], delta_r, prior_pe, bp_time + 4 * (size_t)nb_time, drho_c + nd);
       Tm.End(st);
     }
     Tm.Begin("k_marker_schur_finish", st);
-    if (with_loss) k_marker_schur_finish<true><<<1, 1024, 0, st>>>(nb_time + np, bp_time, red + RL.scal(), solve_out, res, nd + np, drho_c);
+    if (P.with_loss) k_marker_schur_finish<true><<<1, 1024, 0, st>>>(nb_time + np, bp_time, red + RL.scal(), solve_out, res, nd + np, drho_c);
     else k_marker_schur_finish<false><<<1, 1024, 0, st>>>(nb_time, bp_time, red + RL.scal(), solve_out, res);
     Tm.End(st);
     if (!chk("k_marker_schur_finish")) return RSBA_ERR_HIP;
     if (hipMemcpyAsync(res_host, res, RES_SIZE * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess) return RSBA_ERR_HIP;
     { hipError_t e = hipStreamSynchronize(st); if (e != hipSuccess) { fprintf(stderr, "rsba: marker-chain step failed: %s\n", hipGetErrorString(e)); return RSBA_ERR_HIP; } }
-    if (tc_tiles > 0 && res_host[RES_STALL] != 0.0) {
+    if (P.tc_tiles > 0 && res_host[RES_STALL] != 0.0) {
       // the tiles of the persistent factorisation were not all running side by side: the multi-launch path then
       fprintf(stderr, "rsba: persistent tiled Cholesky stalled; using the multi-launch factorisation\n");
-      tc_tiles = 0;
+      plan.tc_tiles = 0;
       if (hipMemset(res, 0, RES_SIZE * sizeof(double)) != hipSuccess) return RSBA_ERR_HIP;
       return Step(st, o, radius, first, res_host, Tm);
     }
     return RSBA_OK;
   }
   int SumSquares(hipStream_t st, double* out) {
+    const int N = plan.N;
     if (Reset(st) != RSBA_OK) return RSBA_ERR_HIP;
-    RSBA_DIST_SWITCH(k_marker_eval<false, D><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[0], IntrPass<D>(intr, dist), half_side, 0, nullptr, nullptr, ss_x));
+    Dispatch([&](auto D) { k_marker_eval<false, D.value><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[0], IntrPass<D.value>(intr, dist), plan.half_side, 0, nullptr, nullptr, ss_x); }, plan.with_dist);
     std::vector<double> h(N);
     if (hipMemcpyAsync(h.data(), ss_x, N * 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return RSBA_ERR_HIP;
     double s = 0; for (double v : h) s += v;
@@ -1982,7 +1646,7 @@ struct MarkerSchurDevice {
     return RSBA_OK;
   }
   int Download(rsba_problem* p) {
-    if (hipMemcpy(p->parameters.data(), params[cur], nfull * 8, hipMemcpyDeviceToHost) != hipSuccess) return RSBA_ERR_HIP;
+    if (hipMemcpy(p->parameters.data(), params[cur], plan.nfull * 8, hipMemcpyDeviceToHost) != hipSuccess) return RSBA_ERR_HIP;
     return RSBA_OK;
   }
 };

@@ -32,8 +32,7 @@ namespace rsba {
 #ifndef RSBA_MC_UNROLL_CAND
 #define RSBA_MC_UNROLL_CAND 1
 #endif
-#define RSBA_SP_STRIDE 64   // doubles of a (time, slot) record: W (time row x, slot column q at 6 x + q: 36) | g_s (6) | U_ss lower triangle (21) | pad
-#define RSBA_SP_LDS 65      // its stride in LDS
+// (RSBA_SP_STRIDE, the doubles of a (time, slot) record, and RSBA_SP_LDS, its stride in LDS: ba_marker_plan.hpp)
 
 struct PoseC {
   double R[9], K[9], T[3];
@@ -543,11 +542,7 @@ struct AccArgs {
 };
 #define RSBA_ACC_PF 11   // record doubles a thread fetches ahead: 170 slots x 64 / 1024 threads
 
-__host__ __device__ inline size_t AccLdsBytes(int dmax, size_t s_doubles) {
-  const int smax = dmax / 6;
-  return (size_t)(2 * smax * RSBA_SP_LDS + 6 * dmax + 96 + s_doubles) * sizeof(double) + (size_t)2 * ((smax + 2) & ~1) * sizeof(int);
-}
-
+// (AccLdsBytes, its LDS: ba_marker_plan.hpp)
 template <bool kLdsS>
 __global__ void __launch_bounds__(RSBA_MT_THREADS) k_mc_accumulate(AccArgs a) {
   extern __shared__ double lds[];
@@ -670,12 +665,7 @@ __global__ void __launch_bounds__(RSBA_MT_THREADS) k_mc_accumulate(AccArgs a) {
 // kTB times per step, two barriers a step: [Y = E W, the small sums, zero the other strips] | [MFMA, the next step's records into the
 // other strips] — the records' trip from memory (~2 us, the whole of a one-time step) is paid once per kTB times.
 typedef double d4_acc __attribute__((ext_vector_type(4)));
-__host__ __device__ inline int AccMfmaTiles(int nr) { const int nt = (nr + 15) / 16; return nt * (nt + 1) / 2; }
-__host__ __device__ inline size_t AccMfmaLdsBytes(int nr, int tb) {
-  const int nrp = ((nr + 15) / 16) * 16;
-  return (size_t)(3 * tb * 8 * nrp + 2 * tb * 48 + 2 * tb * 4 + 2 * tb * (nr / 6) * 21 + 2 * nr + (nr / 6) * 21) * sizeof(double);
-}
-
+// (AccMfmaTiles, AccMfmaLdsBytes: ba_marker_plan.hpp)
 template <int kTiles /* tiles a wavefront owns at most */, int kTB /* times per step */>
 __global__ void __launch_bounds__(RSBA_MT_THREADS) k_mc_accumulate_mfma(AccArgs a) {
   constexpr int kPf = 3;   // record doubles of one time a thread fetches ahead: at most 40 slots (240 columns) x 64 / 1024 threads

@@ -20,24 +20,9 @@
 #include <cfloat>
 #include <cmath>
 
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define RSBA_HD __host__ __device__ __forceinline__
-#else
-#define RSBA_HD inline
-#endif
+#include "ba_common.hpp"   // RSBA_HD, the per-camera constants' layout (CC_*)
 
 namespace rsba {
-
-// Per-camera constants, 32 doubles (256 B) per camera.
-enum {
-  CC_R = 0,      // 9: rotation matrix, row-major (I + [w]x in the small-angle branch)
-  CC_K = 9,      // 9: left Jacobian Jl(w) (identity in the small-angle branch)
-  CC_T = 18,     // 3: translation
-  CC_FX = 21, CC_FY = 22, CC_PPX = 23, CC_PPY = 24,
-  CC_SMALL = 25, // 1.0 when theta^2 <= DBL_EPSILON
-  CC_STRIDE = 32
-};
 
 RSBA_HD void CameraConstants(const double* cam6, const double* intr4, double* cc) {
   const double wx = cam6[0], wy = cam6[1], wz = cam6[2];

@@ -6,6 +6,7 @@
 //
 // The constants and the work-list entry below are shared with the kernels and defined here only.
 #pragma once
+#include <algorithm>
 #include <climits>
 #include <cstddef>
 #include <cstdint>
@@ -26,11 +27,47 @@ namespace rsba {
 #define RSBA_HIT_NONE 0xffffffffu   // an empty entry of a sparse hit list (PairSegmentSparse)
 #define RSBA_CHOL_MAXN 384  // largest reduced system the one-launch factorisations take (64 cameras)
 #define RSBA_PB 32          // panel width of the factorisations
+#define RSBA_PLD (RSBA_PB + 1)   // ... and a panel's LDS leading dimension (bank-conflict padding)
 #define RSBA_CT 64          // trailing-update tile of the multi-launch factorisation (ba_cholesky_large.hpp)
 #define RSBA_BSM_BPG 3      // k_backsub_multi: blocks per workgroup (96 columns)
 constexpr int kTileHandDoubles = 7168;   // doubles of one hand-over buffer of the tiled factorisation's diagonal chain (ba_cholesky_tiles.hpp)
 // the reduced system's dimension padded to whole panels (constexpr: host and device)
 constexpr int MultiCholPadded(int nc) { return (nc + RSBA_PB - 1) / RSBA_PB * RSBA_PB; }
+
+// LDS doubles: (n+2) x 33 shared by the panel and the B strip, 32 x 33 tiles for T and the padded L11, 32 inverse
+// pivots, scratch, the column scale, four 32 x 33 tiles for the look-ahead products of the next diagonal block.
+inline size_t CholeskyLdsDoubles(int n) {
+  const size_t fact = (size_t)(n + 2) * RSBA_PLD + 2 * RSBA_PB * RSBA_PLD + RSBA_PB + 64 + (size_t)n + 4 * RSBA_PB * RSBA_PLD;
+  const size_t back = (size_t)((n + 63) & ~63) + 3 * RSBA_PB * RSBA_PLD + 64;
+  return fact > back ? fact : back;
+}
+
+// Which tile the workgroup with index t works on.  With more tiles than CUs, the workgroups t and t + (number of CUs) end up
+// on the same CU (measured: RSBA_MC_TRACE=1 lists the pairs), and a diagonal tile that shares its CU with a tile busy
+// updating takes ~6 us longer per tile column: row by row, the first eleven diagonal tiles of 256 cameras were paired with
+// tiles of the last three tile rows, busy from the first panel to the last.  So: the first `extra` indices go to tiles that
+// retire early and are off the chain (I >= J + 2 of the first tile columns), their partners at the end of the launch are the
+// tiles of the LAST tile columns (idle until late), everybody else — every early diagonal and sub-diagonal tile — has a CU alone.
+inline std::vector<int> TileOrder(int nrt, int num_cus) {
+  const int ntiles = nrt * (nrt + 1) / 2, extra = std::max(0, std::min(ntiles - num_cus, ntiles / 2));
+  std::vector<int> order;
+  order.reserve(ntiles);
+  if (extra == 0 || nrt > 255) {
+    for (int I = 0; I < nrt; ++I) for (int J = 0; J <= I; ++J) order.push_back(I << 8 | J);
+    return order;
+  }
+  std::vector<char> taken((size_t)nrt * nrt, 0);
+  std::vector<int> first, last;
+  for (int J = 0; J < nrt && (int)first.size() < extra; ++J)
+    for (int I = J + 2; I < nrt && (int)first.size() < extra; ++I) { first.push_back(I << 8 | J); taken[(size_t)I * nrt + J] = 1; }
+  for (int J = nrt - 1; J >= 0 && (int)last.size() < (int)first.size(); --J)
+    for (int I = nrt - 1; I >= J && (int)last.size() < (int)first.size(); --I)
+      if (!taken[(size_t)I * nrt + J]) { last.push_back(I << 8 | J); taken[(size_t)I * nrt + J] = 1; }
+  order = first;
+  for (int I = 0; I < nrt; ++I) for (int J = 0; J <= I; ++J) if (!taken[(size_t)I * nrt + J]) order.push_back(I << 8 | J);
+  order.insert(order.end(), last.begin(), last.end());
+  return order;
+}
 
 // A segment is a range of 64-point mask words of one tile (not necessarily chunk-aligned: small problems get as many
 // workgroups as they have words).

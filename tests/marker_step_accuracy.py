@@ -69,8 +69,9 @@ import solve_accuracy as sa
 U = sa.U
 C_JAC = 37                  # roundings behind one corrected Jacobian entry (tests/test_gpu_jacobian.py's count)
 MIN_LM, MAX_LM = 1e-6, 1e32   # rsba_options_default
-MT_TILE, MT_MAXD, SP_LDS, CHOL_MAXN, PB, MRS_MAXP, PLD = 32, 1020, 65, 384, 32, 5, 33   # ba_marker_schur.hpp / ba_marker_split.hpp / ba_schur_plan.hpp
-LDS_CAP = 156 * 1024
+MT_TILE, MT_MAXD, SP_LDS, MRS_MAXP = 32, 1020, 65, 5   # csrc/ba_marker_plan.hpp: RSBA_MT_TILE, RSBA_MT_MAXD, RSBA_SP_LDS, RSBA_MRS_MAXP
+CHOL_MAXN, PB, PLD = 384, 32, 33                       # csrc/ba_schur_plan.hpp: RSBA_CHOL_MAXN, RSBA_PB, RSBA_PLD
+LDS_CAP = 156 * 1024                                   # RSBA_LDS_CAP
 LOSS_A = 40.0   # px: about the median |r| of a residual block at the jittered start, so that the loss's two branches both occur in one step
 
 
@@ -330,18 +331,22 @@ def _acc_lds_bytes(dmax, s_doubles):
     return (2 * smax * SP_LDS + 6 * dmax + 96 + s_doubles) * 8 + 2 * ((smax + 2) & ~1) * 4
 
 
-def expected_path(case, mc):
-    """What MarkerSchurDevice::Upload decides for the case (ba_marker_schur.hpp), as a dict:
+def expected_path(case, mc, subset=False, priors=False):
+    """What PlanMarkerChain decides for the case (csrc/ba_marker_plan.hpp; tests/test_marker_plan_host.py holds the planner itself to
+    this function), as a dict:
     elim 'dense' | 'split' | 'k_time_eliminate'; acc 'mfma3' | 'mfma8' | 'valu_lds' | 'valu_mem' | ''; solve 'lds' | 'panel' | 'multi' | 'none';
-    backsub 'split' | 'wg' | 'terms'."""
+    backsub 'split' | 'wg' | 'terms'.
+    subset: some block in the program carries a non-zero subset mask (the cases themselves have none) — the split elimination and the
+    split back-substitution then, whatever the switches say, and never k_time_backsub_wg.  priors: the problem carries block priors,
+    which count as a loss."""
     if case.impl == 0:
         return dict(elim="dense", acc="", solve="dense", backsub="")
     env = dict(case.env)
     off = lambda k: k in env and int(env[k]) == 0   # noqa: E731
     nr, dmax, pmax, widest = structure(mc)
     assert 6 * pmax <= MT_MAXD
-    with_loss = case.loss != "none"
-    split = with_loss or not off("RSBA_MT_SPLIT")
+    with_loss = case.loss != "none" or priors
+    split = with_loss or subset or not off("RSBA_MT_SPLIT")
     acc = ""
     if split:
         nt = (nr + 15) // 16
@@ -353,7 +358,7 @@ def expected_path(case, mc):
             lds_s = _acc_lds_bytes(dmax, packed) <= LDS_CAP
             acc = "valu_lds" if lds_s else "valu_mem"
             if _acc_lds_bytes(dmax, packed if lds_s else 0) > LDS_CAP:
-                assert not with_loss
+                assert not with_loss and not subset   # (the planner: RSBA_ERR_UNSUPPORTED, the dense path)
                 split, acc = False, ""
     if nr == 0:
         solve = "none"
@@ -361,8 +366,8 @@ def expected_path(case, mc):
         solve = "lds" if nr <= PB * MRS_MAXP and _marker_solve_lds_doubles(nr) * 8 <= LDS_CAP and not off("RSBA_MT_SOLVE_LDS") else "panel"
     else:
         solve = "multi"
-    backsub_wg = not with_loss and widest <= 128 and not off("RSBA_MT_BACKSUB_WG")
-    split_backsub = split and not off("RSBA_MT_SPLIT_BACKSUB")
+    backsub_wg = not with_loss and not subset and widest <= 128 and not off("RSBA_MT_BACKSUB_WG")
+    split_backsub = split and (subset or not off("RSBA_MT_SPLIT_BACKSUB"))
     return dict(elim="split" if split else "k_time_eliminate", acc=acc, solve=solve, backsub="split" if split_backsub else ("wg" if backsub_wg else "terms"),
                 loss=with_loss)
 

@@ -6,7 +6,7 @@ case runs ONE step through the public API (max_num_iterations = 1, the tolerance
   (a) the path it ran is the path the case names: eliminates_times() and the kernel statistics' names; where two variants share a
       name (the accumulation on the matrix cores with three or eight tiles or on the VALU with its sums in LDS or memory; the
       reduced solve with the triangle in LDS or the panel solver; the three back-substitutions) the expected one is computed from
-      the thresholds of MarkerSchurDevice::Upload (marker_step_accuracy.expected_path) and printed (full_report() names no path: its
+      the thresholds of PlanMarkerChain (csrc/ba_marker_plan.hpp; marker_step_accuracy.expected_path) and printed (full_report() names no path: its
       linear solver line reads DENSE_SCHUR on every one);
   (b) delta = x1 - x0 solves the full damped normal equations of the numpy reference within the derived componentwise
       backward-error bar, row by row;

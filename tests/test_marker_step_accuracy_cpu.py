@@ -120,7 +120,7 @@ def test_every_listed_shape_was_checked():
 
 
 def test_case_list_covers_the_paths():
-    """The path each case names is the one the thresholds of MarkerSchurDevice::Upload give for its structure."""
+    """The path each case names is the one the thresholds of PlanMarkerChain (csrc/ba_marker_plan.hpp) give for its structure."""
     want = {"minimal_2x3x2": (12, "mfma3", "lds"), "minimal_2x3x2_test2": (18, "mfma3", "lds"),
             "width_13x8x13": (144, "mfma3", "lds"), "width_13x8x14": (150, "mfma8", "lds"), "width_21x6x21": (240, "mfma8", "panel"),
             "width_21x6x22": (246, "valu_mem", "panel"), "width_14x8x14": (156, "mfma8", "lds"), "width_14x8x15": (162, "mfma8", "panel"),

@@ -92,7 +92,7 @@ for mode in (0, 1):
             np.savez(KW["dump"], params=p.params.copy(), iterations=s.iterations())
         out.update({"cameras": C_, "times": T_, "markers": M_, "residual_blocks": int(prob["N"]), "generate_s": round(gen, 2), "loss": LOSS, "loss_scale": LOSS_A,
                     "iterations": sm.num_iterations, "initial_cost": sm.initial_cost, "final_cost": sm.final_cost,
-                    "minimizer_ms": 1e3 * sm.minimizer_seconds,
+                    "minimizer_ms": 1e3 * sm.minimizer_seconds, "setup_seconds": sm.setup_seconds,
                     "ms_per_iteration": 1e3 * sm.minimizer_seconds / max(1, sm.num_iterations + 1)})
     else:
         out["kernels_us"] = {k: round(1e3 * ms / n, 1) for k, (n, ms) in s.kernel_stats().items()}
