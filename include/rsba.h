@@ -314,7 +314,8 @@ int rsba_problem_load_correspondence(const char* path, int32_t model, double mar
 /* ------------------------------------------------------------------ initial guesses (the reference's front end)
  * What Correspondencer computes between the ArUco detections and correspondence.txt, without OpenCV.  Poses are
  * 6 doubles (rvec, tvec), p_out = R(rvec) p_in + tvec.  Host code.  The routines see pinhole pixels: detections of a lens with
- * distortion coefficients go through rsba_undistort_points first (include/rsba/correspondencer.h does). */
+ * distortion coefficients go through rsba_undistort_points first (include/rsba/correspondencer.h does); the marker-pose entries at the
+ * end of this section take the coefficients themselves. */
 /* correspondencer.cpp:119-127: the base marker's pose in the main camera from the detection of another marker and
  * that marker's pose in the base marker's frame (my_io GetMarkerGeometry). */
 int rsba_base_pose_from_marker_detection(const double* marker_from_camera, const double* marker_from_base,
@@ -338,6 +339,34 @@ int rsba_solve_pnp_epnp(int32_t n, const double* object_points /* 3n */, const d
  * blocks are filled: camera 0 := identity, every other camera := EPnP over the corners of all markers it detected (undistorted
  * first when the problem carries distortion coefficients). */
 int rsba_problem_initial_camera_poses(rsba_problem* p);
+/* aruco::estimatePoseSingleMarkers for ONE detection (correspondencer.cpp:80): the pose of a square marker of side marker_side from
+ * its four image corners (u, v) in the order top-left, top-right, bottom-right, bottom-left; object points (-s/2, s/2, 0), (s/2, s/2, 0),
+ * (s/2, -s/2, 0), (-s/2, -s/2, 0).  pose6 = (rvec, tvec), p_cam = R(rvec) p_marker + tvec: the local minimiser of the four corners'
+ * reprojection error under the project's camera model (pinhole, or with dist5 = k1 k2 p1 p2 k3), reached by Levenberg-Marquardt from
+ * the homography of the square — what SOLVEPNP_ITERATIVE does for a planar target; no digit-for-digit claim against OpenCV.  *rms: the
+ * RMS of the eight residuals in pixels.  *status: 0 converged; 1 the iteration cap was reached (pose and RMS of the last iterate);
+ * 2 degenerate (singular homography, non-positive depth, a non-finite intermediate, an undistortion that did not converge): pose zeros,
+ * RMS -1, and the call returns RSBA_ERR_UNSUPPORTED as coplanar EPnP does.  RSBA_ERR_ARG: a null pointer, a non-finite value,
+ * marker_side <= 0.  The two-fold ambiguity of a planar target is not resolved: the RMS lets a caller see a poor fit.  Host code. */
+int rsba_marker_pose_from_corners(const double* corners8, const double* intrinsics4, const double* dist5_or_null, double marker_side,
+                                  double* pose6, double* rms_or_null, int32_t* status_or_null);
+/* The same fit for n detections in ONE kernel launch on the GPU, one detection per thread.  camera_index selects each detection's
+ * row of intrinsics (4 per camera) and of dist (5 per camera, or NULL: no distortion); device: a HIP device, -1 = the current one.
+ * RSBA_ERR_NO_DEVICE without a device; n == 0 is RSBA_OK and launches nothing; n < 0, a null required pointer, a camera index outside
+ * [0, num_cameras), a non-finite input or marker_side <= 0: RSBA_ERR_ARG before any device work, nothing written.  A degenerate detection
+ * does not fail the call: it gets status 2 (pose zeros, RMS -1) and its neighbours are unaffected — a detection's result does not depend
+ * on its place in the batch. */
+int rsba_marker_poses_from_corners(int64_t n, const double* corners /* 8n */, const int32_t* camera_index /* n, or NULL = all camera 0 */,
+                                   int32_t num_cameras, const double* intrinsics /* 4 per camera */, const double* dist /* 5 per camera, or NULL */,
+                                   double marker_side, int32_t device /* -1 = current */, double* poses /* 6n */, double* rms /* n, or NULL */,
+                                   int32_t* status /* n, or NULL */);
+/* correspondencer.cpp:100-127 on a marker-chain problem whose marker blocks are filled, the twin of rsba_problem_initial_camera_poses:
+ * at every time, camera 0's detection with the lowest marker index is fitted with the problem's intrinsics (and distortion coefficients,
+ * if it carries any); marker 0's pose is the base pose, another marker's goes through rsba_base_pose_from_marker_detection with the
+ * problem's block of that marker; the result is written into the time block.  A time at which camera 0 detected nothing (the reference
+ * leaves it uninitialised) or only degenerately keeps its bits and is counted in *num_missing_or_null.  The point model:
+ * RSBA_ERR_UNSUPPORTED.  Host code. */
+int rsba_problem_initial_time_poses(rsba_problem* p, int32_t* num_missing_or_null);
 
 void rsba_problem_free(rsba_problem* p);
 

@@ -1,7 +1,9 @@
 // C++ mirror of the OpenCV-free part of RSCalibration::Correspondencer
 // (/root/reference/Main_Calibration/correspondencer.h:17-31, correspondencer.cpp): everything between the ArUco
-// detections and correspondence.txt.  Detection itself (aruco::detectMarkers, estimatePoseSingleMarkers, :74-81) and the
-// image windows stay with OpenCV on the host; this class takes their outputs as plain arrays.
+// detections and correspondence.txt.  Detection itself (aruco::detectMarkers, :74) and the image windows stay with OpenCV on
+// the host; this class takes the detected corners as plain arrays.
+//   EstimatePoseSingleMarkers :80        (one marker's pose from its four corners; a whole batch on the GPU:
+//                                         rsba_marker_poses_from_corners)
 //   Transform            my_struct.h: {rvec, tvec}
 //   GetCornersInCameraWorld   correspondencer.cpp:5-39
 //   BaseFromDetection         :104-127   (the base marker's pose at one time, from the lowest-id marker camera 0 saw)
@@ -40,6 +42,22 @@ class Correspondencer {
     Check(rsba_marker_corners_in_camera(pose, marker_side_, out), "GetCornersInCameraWorld");
     std::vector<Point3d> ret(4);
     for (int i = 0; i < 4; ++i) ret[i] = Point3d{out[3 * i], out[3 * i + 1], out[3 * i + 2]};
+    return ret;
+  }
+  // aruco::estimatePoseSingleMarkers(corners, MARKER_SIDE, camera_matrix, dist_coeffs, rvecs, tvecs) (:80) for the markers camera
+  // `camera` detected: corners[i] = the four corners of detection i, top-left first, clockwise.  rms (optional): each fit's
+  // reprojection RMS in pixels.  A degenerate detection throws.
+  std::vector<Transform> EstimatePoseSingleMarkers(const std::vector<std::array<Point2d, 4>>& corners, size_t camera,
+                                                   std::vector<double>* rms = nullptr) const {
+    std::vector<Transform> ret(corners.size());
+    if (rms) rms->assign(corners.size(), 0.0);
+    for (size_t i = 0; i < corners.size(); ++i) {
+      double pose[6], e;
+      Check(rsba_marker_pose_from_corners(&corners[i][0].x, intrinsics_.at(camera).data(), dist_.empty() ? nullptr : dist_.at(camera).data(),
+                                          marker_side_, pose, &e, nullptr), "EstimatePoseSingleMarkers");
+      ret[i] = Unpack(pose);
+      if (rms) (*rms)[i] = e;
+    }
     return ret;
   }
   // the detected marker IS the base marker: its pose is the base pose (:104-111); otherwise :112-127

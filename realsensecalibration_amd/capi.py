@@ -37,6 +37,7 @@ EXPORTS = [
     "rsba_problem_set_observation_weights", "rsba_problem_observation_weights", "rsba_solver_set_observation_weights",
     "rsba_problem_set_parameter_subset_constant", "rsba_problem_parameter_subset_constant", "rsba_problem_set_distortion", "rsba_problem_distortion", "rsba_read_intrinsics_xml_dist", "rsba_undistort_points",
     "rsba_problem_set_block_prior", "rsba_problem_block_prior", "rsba_problem_num_block_priors", "rsba_solver_set_block_prior",
+    "rsba_marker_pose_from_corners", "rsba_marker_poses_from_corners", "rsba_problem_initial_time_poses",
 ]
 _SYMBOLS = EXPORTS   # (every symbol of include/rsba.h that load() checks)
 
@@ -190,6 +191,9 @@ def load():
     lib.rsba_problem_num_block_priors.argtypes = [C.c_void_p]
     lib.rsba_problem_num_block_priors.restype = C.c_int32
     lib.rsba_solver_set_block_prior.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.rsba_marker_pose_from_corners.argtypes = [C.c_void_p] * 3 + [C.c_double] + [C.c_void_p] * 3
+    lib.rsba_marker_poses_from_corners.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_int32] + [C.c_void_p] * 3
+    lib.rsba_problem_initial_time_poses.argtypes = [C.c_void_p, C.c_void_p]
     _LIB = lib
     return lib
 
@@ -230,6 +234,7 @@ class Problem:
 
     def __init__(self, handle):
         self.h = handle
+        self._fit_constants = None   # (intrinsics C x 4, marker side) of a marker-chain problem: the C ABI has no reader for them
         lib = load()
         n = lib.rsba_problem_num_parameters(self.h)
         self.params = np.ctypeslib.as_array(lib.rsba_problem_parameters(self.h), shape=(n,))
@@ -259,6 +264,7 @@ class Problem:
                                                      _vp(par), _vp(intr), C.c_double(prob["marker_side"]), C.byref(h)),
              "rsba_problem_create_marker_chain")
         p = cls(h)
+        p._fit_constants = (intr.reshape(-1, 4).copy(), float(prob["marker_side"]))
         if prob.get("dist") is not None:
             try:
                 p.set_distortion(prob["dist"])
@@ -280,7 +286,9 @@ class Problem:
         k = np.ascontiguousarray(intrinsics, np.float64)
         _chk(load().rsba_problem_load_correspondence(path.encode(), model, marker_side, _vp(k), C.byref(h)),
              "rsba_problem_load_correspondence")
-        return cls(h)
+        p = cls(h)
+        p._fit_constants = (k.reshape(-1, 4).copy(), float(marker_side))
+        return p
 
     def __getattr__(self, name):
         f = {"model": "rsba_problem_model", "num_cameras": "rsba_problem_num_cameras", "num_points": "rsba_problem_num_points",
@@ -389,6 +397,31 @@ class Problem:
 
     def initial_camera_poses(self):
         _chk(load().rsba_problem_initial_camera_poses(self.h), "rsba_problem_initial_camera_poses")
+
+    def initial_time_poses(self):
+        """Marker-chain models: every time block from camera 0's detection with the lowest marker index at that time
+        (correspondencer.cpp:100-127).  Returns how many times kept their values because camera 0 detected nothing usable there."""
+        missing = C.c_int32(0)
+        _chk(load().rsba_problem_initial_time_poses(self.h, C.byref(missing)), "rsba_problem_initial_time_poses")
+        return int(missing.value)
+
+    def detection_poses(self, device=-1):
+        """Marker-chain models: (poses N x 6, rms N, status N) of every observation's own single-marker fit, one batch on the GPU over
+        the problem's observations, camera indices, intrinsics and distortion coefficients (marker_poses_from_corners)."""
+        lib = load()
+        if self.model == MODEL_POINTS:
+            raise RsbaError(ERR_UNSUPPORTED, "detection_poses")
+        n, nc = self.num_observations, self.num_cameras
+        obs = np.ctypeslib.as_array(lib.rsba_problem_observations(self.h), shape=(n, 8)).copy()
+        cam = np.array([lib.rsba_problem_camera_idx(self.h, i) for i in range(n)], np.int32)
+        intr, side = self._intrinsics_and_side()
+        return marker_poses_from_corners(obs, cam, intr, self.distortion, side, device=device, num_cameras=nc)
+
+    def _intrinsics_and_side(self):
+        if getattr(self, "_fit_constants", None) is None:
+            raise ValueError("detection_poses: the problem's intrinsics and marker side are known for problems made by "
+                             "Problem.marker_chain and Problem.correspondence")
+        return self._fit_constants
 
     def solve(self, opts=None):
         s = Summary()
@@ -878,6 +911,38 @@ def marker_corners_in_camera(pose, marker_side):
     pose, out = np.ascontiguousarray(pose, np.float64), np.zeros((4, 3))
     _chk(load().rsba_marker_corners_in_camera(_vp(pose), C.c_double(marker_side), _vp(out)), "rsba_marker_corners_in_camera")
     return out
+
+
+def marker_pose_from_corners(corners8, intrinsics4, dist5, marker_side):
+    """One detection's pose on the host (aruco::estimatePoseSingleMarkers): corners 4 x (u, v), top-left first, clockwise; dist5 may be
+    None.  Returns (pose6, rms, status); a degenerate detection raises RsbaError with code ERR_UNSUPPORTED."""
+    c = np.ascontiguousarray(corners8, np.float64).reshape(-1)
+    k = np.ascontiguousarray(intrinsics4, np.float64).reshape(-1)
+    d = None if dist5 is None else np.ascontiguousarray(dist5, np.float64).reshape(-1)
+    if c.size != 8 or k.size != 4 or (d is not None and d.size != 5):
+        raise ValueError("marker_pose_from_corners: 8 corner values, 4 intrinsics and 5 coefficients (or None) expected")
+    pose, rms, status = np.zeros(6), C.c_double(), C.c_int32()
+    _chk(load().rsba_marker_pose_from_corners(_vp(c), _vp(k), None if d is None else _vp(d), C.c_double(marker_side), _vp(pose), C.byref(rms),
+                                              C.byref(status)), "rsba_marker_pose_from_corners")
+    return pose, rms.value, int(status.value)
+
+
+def marker_poses_from_corners(corners, camera_index, intrinsics, dist, marker_side, device=-1, num_cameras=None):
+    """A batch of detections on the GPU, one kernel launch: corners n x 8, camera_index n (None: all camera 0), intrinsics C x 4, dist
+    C x 5 or None.  Returns (poses n x 6, rms n, status n); a degenerate detection has status 2, pose zeros and rms -1."""
+    c = np.ascontiguousarray(corners, np.float64).reshape(-1, 8)
+    k = np.ascontiguousarray(intrinsics, np.float64).reshape(-1, 4)
+    nc = len(k) if num_cameras is None else int(num_cameras)
+    d = None if dist is None else np.ascontiguousarray(dist, np.float64).reshape(-1, 5)
+    ci = None if camera_index is None else np.ascontiguousarray(camera_index, np.int32).reshape(-1)
+    if len(k) != nc or (d is not None and len(d) != nc) or (ci is not None and len(ci) != len(c)):
+        raise ValueError("marker_poses_from_corners: one camera index per detection, 4 intrinsics and 5 coefficients per camera expected")
+    n = len(c)
+    poses, rms, status = np.zeros((n, 6)), np.zeros(n), np.zeros(n, np.int32)
+    _chk(load().rsba_marker_poses_from_corners(n, _vp(c), None if ci is None else _vp(ci), nc, _vp(k), None if d is None else _vp(d),
+                                               C.c_double(marker_side), int(device), _vp(poses), _vp(rms), _vp(status)),
+         "rsba_marker_poses_from_corners")
+    return poses, rms, status
 
 
 def solve_pnp_epnp(object_points, image_points, intrinsics4):

@@ -18,6 +18,8 @@
 //   UndistortPoints                      cv::undistortPoints(src, dst, K, dist, noArray(), K) for the five-coefficient model:
 //                                        distorted pixels -> pixels of the ideal pinhole camera with the same K, by fixed-point
 //                                        iteration on the normalised point.  No digit-for-digit claim against OpenCV.
+//   MarkerPoseFromCorners     :80        aruco::estimatePoseSingleMarkers for one detection: ba_marker_pose.hpp's fit on the host
+//   InitialTimePoses          :100-127   the base marker's pose at every time from the main camera's first detection
 //
 // Host code, double precision, no device work: the problem sizes are a few hundred points per camera.
 #include <algorithm>
@@ -26,6 +28,7 @@
 #include <cstring>
 #include <vector>
 
+#include "ba_marker_pose.hpp"
 #include "ba_problem.hpp"
 
 namespace rsba {
@@ -423,6 +426,54 @@ int InitialCameraPoses(rsba_problem* p) {
     const int rc = SolvePnPEPnP(n, obj[c].data(), img[c].data(), &p->intrinsics[4 * (size_t)c], &p->parameters[6 * (size_t)c]);
     if (rc != RSBA_OK) return rc;
   }
+  return RSBA_OK;
+}
+
+// aruco::estimatePoseSingleMarkers for one detection (correspondencer.cpp:80) on the host: FitMarkerPose with its arguments checked.
+// A degenerate detection returns RSBA_ERR_UNSUPPORTED (as coplanar EPnP does) with pose zeros, rms -1 and status 2.
+int MarkerPoseFromCorners(const double* corners8, const double* intrinsics4, const double* dist5, double marker_side, double* pose6,
+                          double* rms, int32_t* status) {
+  if (!corners8 || !intrinsics4 || !pose6 || !(marker_side > 0.0) || !std::isfinite(marker_side)) return RSBA_ERR_ARG;
+  for (int i = 0; i < 8; ++i) if (!std::isfinite(corners8[i])) return RSBA_ERR_ARG;
+  for (int i = 0; i < 4; ++i) if (!std::isfinite(intrinsics4[i])) return RSBA_ERR_ARG;
+  if (!(intrinsics4[0] != 0.0) || !(intrinsics4[1] != 0.0)) return RSBA_ERR_ARG;
+  if (dist5) for (int i = 0; i < 5; ++i) if (!std::isfinite(dist5[i])) return RSBA_ERR_ARG;
+  double e = -1.0;
+  const int st = FitMarkerPose(corners8, intrinsics4, dist5, marker_side, pose6, &e);
+  if (rms) *rms = e;
+  if (status) *status = st;
+  return st == MARKER_POSE_DEGENERATE ? RSBA_ERR_UNSUPPORTED : RSBA_OK;
+}
+
+// correspondencer.cpp:100-127 on a marker-chain problem whose marker blocks hold the board geometry: at every time the main camera's
+// detection with the lowest marker index (:92-97 sorts by id and takes the first) gives the base marker's pose — its own pose when it is
+// the base marker, BaseFromMarkerDetection with the marker's block otherwise.  A time at which the main camera detected nothing, or only
+// degenerately, keeps its bits (the reference leaves it uninitialised) and is counted.
+int InitialTimePoses(rsba_problem* p, int32_t* num_missing) {
+  if (!p) return RSBA_ERR_ARG;
+  if (!p->is_marker_chain()) return RSBA_ERR_UNSUPPORTED;
+  const int C = p->num_cameras, T = p->num_times;
+  std::vector<int64_t> first((size_t)T, -1);
+  for (int64_t i = 0; i < p->num_observations; ++i) {
+    if (p->camera_index[i] != 0) continue;
+    int64_t& f = first[p->time_index[i]];
+    if (f < 0 || p->marker_index[i] < p->marker_index[f]) f = i;
+  }
+  const double* dist = p->has_distortion() ? p->distortion.data() : nullptr;   // the main camera's five come first
+  int32_t missing = 0;
+  for (int t = 0; t < T; ++t) {
+    double pose[6];
+    if (first[t] < 0 || MarkerPoseFromCorners(&p->observations[8 * (size_t)first[t]], p->intrinsics.data(), dist, p->marker_side, pose,
+                                              nullptr, nullptr) != RSBA_OK) {
+      ++missing;
+      continue;
+    }
+    double* out = &p->parameters[6 * (size_t)(C + t)];
+    const int m = p->marker_index[first[t]];
+    if (m == 0) memcpy(out, pose, sizeof(pose));
+    else BaseFromMarkerDetection(pose, &p->parameters[6 * (size_t)(C + T + m)], out);
+  }
+  if (num_missing) *num_missing = missing;
   return RSBA_OK;
 }
 

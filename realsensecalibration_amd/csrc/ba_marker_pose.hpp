@@ -1,0 +1,286 @@
+// Pose of ONE square marker from its four image corners: what aruco::estimatePoseSingleMarkers computes per detection
+// (Main_Calibration/correspondencer.cpp:80 of the reference), the step between the detected corners and the time blocks
+// (:100-127).  Plain C++ for host and device (RSBA_HD), no HIP calls: rsba_marker_pose_from_corners and
+// rsba_problem_initial_time_poses run it on the host, k_marker_pose (ba_solver.hip) one detection per thread.
+//
+//   object points   the marker's corners in its own frame, (-s/2, s/2, 0), (s/2, s/2, 0), (s/2, -s/2, 0), (-s/2, -s/2, 0):
+//                   top-left, top-right, bottom-right, bottom-left, the order of the detections
+//   pose            (rvec, tvec) with p_cam = R(rvec) p_marker + tvec
+//   contract        the local minimiser of the four corners' reprojection error under the project's camera model
+//                   (ProjectCorner<true> / DistortNormalised) reached from the homography of the square: what OpenCV 4.0.1's
+//                   SOLVEPNP_ITERATIVE does for a planar target.  No digit-for-digit claim against OpenCV; the time rows of the
+//                   committed hongo correspondence.txt pin the basin (tests/test_capi_marker_pose_host.py).
+//
+//   1. the corners' normalised points of the ideal pinhole camera: UndistortPoints' fixed-point iteration (ba_initial_guess.cpp);
+//      all-zero coefficients skip it
+//   2. the homography of the square onto them.  Four points fix it exactly, so the null vector of the 8 x 9 DLT system IS the
+//      projective map of the unit square onto the quadrilateral, which has a closed form (Heckbert 1989, "Fundamentals of texture
+//      mapping and image warping", §2.2.3): two 2 x 2 determinant quotients, no decomposition, nothing indexed.  It is normalised so that
+//      the bottom-left corner has depth factor one; the other three must be positive with it.
+//   3. r1 = h1 / |h1|, r2 = h2 / |h2|, t = 2 h3 / (|h1| + |h2|), and the rotation nearest to [r1 r2 r1 x r2]: M'M of that matrix is
+//      [[1 c 0] [c 1 0] [0 0 1 - c^2]], so its polar factor is the symmetric orthonormalisation of the pair — the unit bisectors
+//      of r1 and r2 turned back by 45 degrees — and their cross product
+//   4. Levenberg-Marquardt on (rvec, tvec) with the analytic rows of ba_math.hpp (a pose block's rule: d r / d t = Q,
+//      d r / d w = [w* x Q_i] Jl): damping lambda diag(J'J), lambda0 = 1e-3; a candidate is accepted when the cost does not rise;
+//      lambda /= 10 (floor 1e-15) on acceptance, *= 10 on rejection; stop when the step's max-norm is below 1e-12 (1 + max |p|);
+//      at most kMarkerPoseMaxIterations steps.
+//
+// Everything is scalars and fixed-size arrays indexed by constants once the loops are unrolled: on the device the 21 entries of
+// J'J, the gradient, the pose and the 6 x 6 Cholesky factor live in registers (profiles/marker_pose_kernel_resources.txt: no scratch).
+// A lane that has finished leaves the loop; nothing is exchanged between lanes, so a detection's bits do not depend on its place.
+//
+// Not resolved: the two-fold ambiguity of a planar target (IPPE's second solution) — the RMS is returned so that a caller sees a poor fit.
+#pragma once
+#include <cfloat>
+#include <cmath>
+
+#include "ba_math.hpp"
+
+#if defined(__HIPCC__)
+#define RSBA_UNROLL _Pragma("unroll")
+#else
+#define RSBA_UNROLL
+#endif
+
+namespace rsba {
+
+enum {
+  MARKER_POSE_CONVERGED = 0,    // the step fell below the tolerance
+  MARKER_POSE_ITERATION_CAP = 1,   // the last iterate and its RMS
+  MARKER_POSE_DEGENERATE = 2,   // singular homography, non-positive depth, a non-finite intermediate, an undistortion that did not converge:
+                                // pose zeros, RMS -1
+  kMarkerPoseMaxIterations = 400   // well-posed detections take ~15 steps; frontal 30-pixel markers creep along a flat valley: of 60 000 detections of the
+                                   // 8 x 5000 x 16 problem 165 are unfinished after 100 steps, 38 after 200, 7 after 400 (and hongo has one that takes 191)
+};
+
+RSBA_HD bool FiniteValue(double x) { return fabs(x) <= DBL_MAX; }   // false for NaN too
+
+// One point of UndistortPoints: the distorted normalised point (xd, yd) -> the ideal one, the same iteration and stopping rule (until
+// both updates are below 1e-14 within 50 steps, then up to four more until nothing moves).
+RSBA_HD bool UndistortNormalisedPoint(double xd, double yd, const double k[5], double* xo, double* yo) {
+  const double k1 = k[0], k2 = k[1], p1 = k[2], p2 = k[3], k3 = k[4];
+  double x = xd, y = yd;
+  int polish = 0;
+  for (int it = 0; it < 54; ++it) {
+    const double r2 = x * x + y * y;
+    const double rad = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3));
+    if (!(rad > 0.0)) return false;
+    const double xn = (xd - (2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x))) / rad;
+    const double yn = (yd - (p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y)) / rad;
+    if (!FiniteValue(xn) || !FiniteValue(yn)) return false;
+    const bool same = xn == x && yn == y;
+    const bool small = fabs(xn - x) < 1e-14 && fabs(yn - y) < 1e-14;
+    x = xn; y = yn;
+    if (small) {
+      if (same || ++polish > 4) { *xo = x; *yo = y; return true; }
+    } else if (polish > 0 || it >= 49) {
+      return false;   // no contraction at this radius
+    }
+  }
+  return false;
+}
+
+// Angle-axis of a rotation matrix (row-major) through the quaternion, as ceres::RotationMatrixToAngleAxis goes: stable at every angle, no
+// indexed access.
+RSBA_HD void RotationMatrixToRvec(const double* R, double* w) {
+  const double tr = R[0] + R[4] + R[8];
+  double qw, qx, qy, qz;   // four times the quaternion times its largest component
+  if (tr > 0.0) { qw = 1.0 + tr; qx = R[7] - R[5]; qy = R[2] - R[6]; qz = R[3] - R[1]; }
+  else if (R[0] >= R[4] && R[0] >= R[8]) { qx = 1.0 + R[0] - R[4] - R[8]; qy = R[3] + R[1]; qz = R[6] + R[2]; qw = R[7] - R[5]; }
+  else if (R[4] >= R[8]) { qy = 1.0 + R[4] - R[0] - R[8]; qx = R[1] + R[3]; qz = R[7] + R[5]; qw = R[2] - R[6]; }
+  else { qz = 1.0 + R[8] - R[0] - R[4]; qx = R[2] + R[6]; qy = R[5] + R[7]; qw = R[3] - R[1]; }
+  if (qw < 0.0) { qw = -qw; qx = -qx; qy = -qy; qz = -qz; }
+  const double s = sqrt(qx * qx + qy * qy + qz * qz);
+  const double f = s > 1e-12 * qw ? 2.0 * atan2(s, qw) / s : 2.0 / qw;   // theta / sin(theta / 2) -> 2 at theta = 0
+  w[0] = f * qx; w[1] = f * qy; w[2] = f * qz;
+}
+
+// The start of the fit from the four normalised corners (x[j], y[j]: top-left, top-right, bottom-right, bottom-left).
+RSBA_HD bool MarkerPoseFromHomography(const double x[4], const double y[4], double side, double pose[6]) {
+  // Heckbert's square-to-quadrilateral map, (0,0) (1,0) (1,1) (0,1) -> bottom-left, bottom-right, top-right, top-left:
+  // [a b c; d e f; g h 1] (u, v, 1)' with the marker's X = s (u - 1/2), Y = s (v - 1/2)
+  const double x0 = x[3], y0 = y[3], x1 = x[2], y1 = y[2], x2 = x[1], y2 = y[1], x3 = x[0], y3 = y[0];
+  const double sx = (x0 - x1) + (x2 - x3), sy = (y0 - y1) + (y2 - y3);
+  const double dx1 = x1 - x2, dx2 = x3 - x2, dy1 = y1 - y2, dy2 = y3 - y2;
+  const double m0 = dx1 * dy2, m1 = dx2 * dy1, den = m0 - m1;
+  if (!(fabs(den) > 1e-12 * (fabs(m0) + fabs(m1)))) return false;   // three corners on a line (or all equal; NaN lands here too)
+  const double g = (sx * dy2 - dx2 * sy) / den, h = (dx1 * sy - sx * dy1) / den;
+  // depth factors of the corners (bottom-left: 1): of one sign and none vanishing, or the quadrilateral is no image of a square in front
+  const double w1 = 1.0 + g, w2 = 1.0 + g + h, w3 = 1.0 + h;
+  const double wmax = fmax(fmax(1.0, w1), fmax(w2, w3)), wmin = fmin(fmin(1.0, w1), fmin(w2, w3));
+  if (!(wmin > 1e-9 * wmax) || !FiniteValue(wmax)) return false;
+  const double a = (x1 - x0) + g * x1, b = (x3 - x0) + h * x3, d = (y1 - y0) + g * y1, e = (y3 - y0) + h * y3;
+  const double is = 1.0 / side;
+  const double h1x = a * is, h1y = d * is, h1z = g * is;
+  const double h2x = b * is, h2y = e * is, h2z = h * is;
+  const double h3x = 0.5 * (a + b) + x0, h3y = 0.5 * (d + e) + y0, h3z = 0.5 * (g + h) + 1.0;
+  const double n1 = sqrt(h1x * h1x + h1y * h1y + h1z * h1z), n2 = sqrt(h2x * h2x + h2y * h2y + h2z * h2z);
+  if (!(n1 > 0.0) || !(n2 > 0.0)) return false;
+  const double i1 = 1.0 / n1, i2 = 1.0 / n2, ts = 2.0 / (n1 + n2);
+  const double r1x = h1x * i1, r1y = h1y * i1, r1z = h1z * i1, r2x = h2x * i2, r2y = h2y * i2, r2z = h2z * i2;
+  // unit bisectors of the pair (orthogonal: |r1| = |r2|)
+  const double cx = r1x + r2x, cy = r1y + r2y, cz = r1z + r2z, dx = r1x - r2x, dy = r1y - r2y, dz = r1z - r2z;
+  const double nc = sqrt(cx * cx + cy * cy + cz * cz), nd = sqrt(dx * dx + dy * dy + dz * dz);
+  if (!(nc > 1e-9) || !(nd > 1e-9)) return false;   // h1 and h2 parallel
+  const double ic = 0.70710678118654752440 / nc, id = 0.70710678118654752440 / nd;
+  double R[9];
+  R[0] = cx * ic + dx * id; R[3] = cy * ic + dy * id; R[6] = cz * ic + dz * id;
+  R[1] = cx * ic - dx * id; R[4] = cy * ic - dy * id; R[7] = cz * ic - dz * id;
+  R[2] = R[3] * R[7] - R[6] * R[4]; R[5] = R[6] * R[1] - R[0] * R[7]; R[8] = R[0] * R[4] - R[3] * R[1];
+  RotationMatrixToRvec(R, pose);
+  pose[3] = h3x * ts; pose[4] = h3y * ts; pose[5] = h3z * ts;
+  bool ok = pose[5] > 0.0;
+  RSBA_UNROLL
+  for (int q = 0; q < 6; ++q) ok = ok && FiniteValue(pose[q]);
+  return ok;
+}
+
+// index of (a, b), a <= b, in the packed upper triangle of a symmetric 6 x 6
+RSBA_HD constexpr int Sym6(int a, int b) { return a * 6 - a * (a - 1) / 2 + (b - a); }
+
+// Cost (sum of the eight squared residuals), J'J (packed, 21), J'r and the smallest depth at the pose p.
+RSBA_HD void MarkerPoseLinearise(const double p[6], const double* c8, const double* intr4, const double k5[5], double half,
+                                 double* cost_out, double A[21], double g[6], double* min_depth) {
+  double cc[CC_STRIDE];
+  CameraConstants(p, intr4, cc);
+  const double* R = cc + CC_R;
+  const double* K = cc + CC_K;
+  const bool small = cc[CC_SMALL] != 0.0;
+  const double fx = intr4[0], fy = intr4[1], ppx = intr4[2], ppy = intr4[3];
+  double cost = 0.0, minz = DBL_MAX;
+  RSBA_UNROLL
+  for (int q = 0; q < 21; ++q) A[q] = 0.0;
+  RSBA_UNROLL
+  for (int q = 0; q < 6; ++q) g[q] = 0.0;
+  RSBA_UNROLL
+  for (int j = 0; j < 4; ++j) {
+    const double X = (j == 1 || j == 2) ? half : -half, Y = j < 2 ? half : -half;
+    const double q0 = R[0] * X + R[1] * Y, q1 = R[3] * X + R[4] * Y, q2 = R[6] * X + R[7] * Y;
+    const double P0 = q0 + cc[CC_T], P1 = q1 + cc[CC_T + 1], P2 = q2 + cc[CC_T + 2];
+    double r[2], Q[6];
+    ProjectCorner<true>(P0, P1, P2, fx, fy, ppx, ppy, k5, c8[2 * j], c8[2 * j + 1], r, Q);
+    minz = fmin(minz, P2);
+    const double w0 = small ? X : q0, w1 = small ? Y : q1, w2 = small ? 0.0 : q2;
+    RSBA_UNROLL
+    for (int i = 0; i < 2; ++i) {
+      const double Q0 = Q[3 * i], Q1 = Q[3 * i + 1], Q2 = Q[3 * i + 2];
+      const double a0 = w1 * Q2 - w2 * Q1, a1 = w2 * Q0 - w0 * Q2, a2 = w0 * Q1 - w1 * Q0;   // w* x Q_i
+      double J[6];
+      J[0] = a0 * K[0] + a1 * K[3] + a2 * K[6];
+      J[1] = a0 * K[1] + a1 * K[4] + a2 * K[7];
+      J[2] = a0 * K[2] + a1 * K[5] + a2 * K[8];
+      J[3] = Q0; J[4] = Q1; J[5] = Q2;
+      cost += r[i] * r[i];
+      RSBA_UNROLL
+      for (int a = 0; a < 6; ++a) {
+        g[a] += J[a] * r[i];
+        RSBA_UNROLL
+        for (int b = a; b < 6; ++b) A[Sym6(a, b)] += J[a] * J[b];
+      }
+    }
+  }
+  *cost_out = cost;
+  *min_depth = minz;
+}
+
+// d = -(A + lambda diag(A))^-1 g by Cholesky; false (d zeros) when a pivot is not positive or the step is not finite.
+RSBA_HD bool MarkerPoseStep(const double A[21], const double g[6], double lambda, double d[6]) {
+  double L[21];   // lower triangle by rows: L(i, j) at i (i + 1) / 2 + j
+  bool ok = true;
+  RSBA_UNROLL
+  for (int j = 0; j < 6; ++j) {
+    double s = A[Sym6(j, j)] * (1.0 + lambda);
+    RSBA_UNROLL
+    for (int k = 0; k < j; ++k) s -= L[j * (j + 1) / 2 + k] * L[j * (j + 1) / 2 + k];
+    ok = ok && s > 0.0;
+    const double l = sqrt(ok ? s : 1.0), il = 1.0 / l;
+    L[j * (j + 1) / 2 + j] = l;
+    RSBA_UNROLL
+    for (int i = j + 1; i < 6; ++i) {
+      double t = A[Sym6(j, i)];
+      RSBA_UNROLL
+      for (int k = 0; k < j; ++k) t -= L[i * (i + 1) / 2 + k] * L[j * (j + 1) / 2 + k];
+      L[i * (i + 1) / 2 + j] = t * il;
+    }
+  }
+  double z[6];
+  RSBA_UNROLL
+  for (int i = 0; i < 6; ++i) {
+    double t = -g[i];
+    RSBA_UNROLL
+    for (int k = 0; k < i; ++k) t -= L[i * (i + 1) / 2 + k] * z[k];
+    z[i] = t / L[i * (i + 1) / 2 + i];
+  }
+  RSBA_UNROLL
+  for (int i = 5; i >= 0; --i) {
+    double t = z[i];
+    RSBA_UNROLL
+    for (int k = i + 1; k < 6; ++k) t -= L[k * (k + 1) / 2 + i] * d[k];
+    d[i] = t / L[i * (i + 1) / 2 + i];
+  }
+  RSBA_UNROLL
+  for (int i = 0; i < 6; ++i) ok = ok && FiniteValue(d[i]);
+  RSBA_UNROLL
+  for (int i = 0; i < 6; ++i) d[i] = ok ? d[i] : 0.0;
+  return ok;
+}
+
+// The fit.  corners8: 4 x (u, v); dist5 may be null (no distortion).  Returns the status; pose6 and *rms are always written.
+RSBA_HD int FitMarkerPose(const double* corners8, const double* intr4, const double* dist5, double marker_side, double* pose6, double* rms) {
+  double k5[5];
+  bool any = false;
+  RSBA_UNROLL
+  for (int q = 0; q < 5; ++q) { k5[q] = dist5 ? dist5[q] : 0.0; any = any || k5[q] != 0.0; }
+  const double fx = intr4[0], fy = intr4[1], ppx = intr4[2], ppy = intr4[3];
+  double x[4], y[4], p[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  bool ok = true;
+  RSBA_UNROLL
+  for (int j = 0; j < 4; ++j) {
+    x[j] = (corners8[2 * j] - ppx) / fx;
+    y[j] = (corners8[2 * j + 1] - ppy) / fy;
+    if (any) ok = UndistortNormalisedPoint(x[j], y[j], k5, &x[j], &y[j]) && ok;
+  }
+  ok = ok && MarkerPoseFromHomography(x, y, marker_side, p);
+  const double half = 0.5 * marker_side;
+  double cost = 0.0, A[21], g[6], minz = 0.0;
+  if (ok) {
+    MarkerPoseLinearise(p, corners8, intr4, k5, half, &cost, A, g, &minz);
+    ok = FiniteValue(cost) && minz > 0.0;
+  }
+  int status = MARKER_POSE_ITERATION_CAP;
+  double lambda = 1e-3;
+  for (int it = 0; ok && it < kMarkerPoseMaxIterations; ++it) {
+    double d[6], pn[6], An[21], gn[6], cn, zn;
+    const bool solved = MarkerPoseStep(A, g, lambda, d);
+    double dmax = 0.0, pmax = 0.0;
+    RSBA_UNROLL
+    for (int q = 0; q < 6; ++q) { dmax = fmax(dmax, fabs(d[q])); pmax = fmax(pmax, fabs(p[q])); pn[q] = p[q] + d[q]; }
+    MarkerPoseLinearise(pn, corners8, intr4, k5, half, &cn, An, gn, &zn);
+    const bool accept = solved && FiniteValue(cn) && zn > 0.0 && cn <= cost;
+    if (accept) {
+      cost = cn;
+      RSBA_UNROLL
+      for (int q = 0; q < 6; ++q) { p[q] = pn[q]; g[q] = gn[q]; }
+      RSBA_UNROLL
+      for (int q = 0; q < 21; ++q) A[q] = An[q];
+      lambda = fmax(lambda * 0.1, 1e-15);
+    } else {
+      lambda *= 10.0;
+    }
+    if (solved && dmax < 1e-12 * (1.0 + pmax)) { status = MARKER_POSE_CONVERGED; break; }
+  }
+  RSBA_UNROLL
+  for (int q = 0; q < 6; ++q) ok = ok && FiniteValue(p[q]);
+  if (!ok) {
+    RSBA_UNROLL
+    for (int q = 0; q < 6; ++q) pose6[q] = 0.0;
+    *rms = -1.0;
+    return MARKER_POSE_DEGENERATE;
+  }
+  RSBA_UNROLL
+  for (int q = 0; q < 6; ++q) pose6[q] = p[q];
+  *rms = sqrt(cost * 0.125);
+  return status;
+}
+
+}  // namespace rsba

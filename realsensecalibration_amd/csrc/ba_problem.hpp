@@ -73,6 +73,9 @@ void MarkerFromCamera(const double base_from_camera[6], const double marker_from
 void MarkerCornersInCamera(const double pose[6], double marker_side, double out12[12]);
 int SolvePnPEPnP(int n, const double* object_points, const double* image_points, const double intrinsics4[4], double pose[6]);
 int InitialCameraPoses(rsba_problem* p);
+int MarkerPoseFromCorners(const double* corners8, const double* intrinsics4, const double* dist5, double marker_side, double* pose6,
+                          double* rms, int32_t* status);
+int InitialTimePoses(rsba_problem* p, int32_t* num_missing);
 int WriteOutputs(const rsba_problem& p, const char* camera_transform_xml, const char* extrinsics_dir,
                  const char* point3d_txt);
 

@@ -32,6 +32,7 @@
 #include "ba_evaluate.hpp"
 #include "ba_evaluate_jacobian.hpp"
 #include "ba_marker_kernels.hpp"
+#include "ba_marker_pose.hpp"
 #include "ba_marker_schur.hpp"
 #include "ba_point_kernels.hpp"
 #include "ba_cholesky_large.hpp"
@@ -65,6 +66,27 @@ int DeviceCount() {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
   return n;
+}
+
+// aruco::estimatePoseSingleMarkers for a batch (rsba_marker_poses_from_corners): one detection per thread, the whole fit of
+// ba_marker_pose.hpp in registers.  Lanes share nothing: a wave runs until its slowest lane has left the LM loop, a lane that has
+// finished takes no further part, and its result is the same wherever it sits.  No atomics, no cross-lane operations, plain stores.
+__global__ __launch_bounds__(256) void k_marker_pose(int64_t n, const double* __restrict__ corners, const int32_t* __restrict__ camera_index,
+                                                     const double* __restrict__ intr, const double* __restrict__ dist, double marker_side,
+                                                     double* __restrict__ poses, double* __restrict__ rms, int32_t* __restrict__ status) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int c = camera_index ? camera_index[i] : 0;
+  double c8[8], k4[4], pose[6], e;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) c8[q] = corners[8 * i + q];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) k4[q] = intr[4 * c + q];
+  const int st = FitMarkerPose(c8, k4, dist ? dist + 5 * c : nullptr, marker_side, pose, &e);
+#pragma unroll
+  for (int q = 0; q < 6; ++q) poses[6 * i + q] = pose[q];
+  if (rms) rms[i] = e;
+  if (status) status[i] = st;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3381,6 +3403,60 @@ int rsba_reprojection_error(rsba_problem* p, const rsba_options* o, double* erro
   }
   rsba_solver_destroy(s);
   return rc;
+}
+
+int rsba_marker_poses_from_corners(int64_t n, const double* corners, const int32_t* camera_index, int32_t num_cameras, const double* intrinsics,
+                                   const double* dist, double marker_side, int32_t device, double* poses, double* rms, int32_t* status) {
+  if (n < 0 || num_cameras <= 0 || !intrinsics || !(marker_side > 0.0) || !std::isfinite(marker_side)) return RSBA_ERR_ARG;
+  if (n > 0 && (!corners || !poses)) return RSBA_ERR_ARG;
+  if (n > (int64_t)INT32_MAX * 256) return RSBA_ERR_ARG;   // one launch: the grid's size
+  for (int64_t i = 0; i < 8 * n; ++i) if (!std::isfinite(corners[i])) return RSBA_ERR_ARG;
+  if (camera_index) for (int64_t i = 0; i < n; ++i) if (camera_index[i] < 0 || camera_index[i] >= num_cameras) return RSBA_ERR_ARG;
+  for (int64_t i = 0; i < 4 * (int64_t)num_cameras; ++i) if (!std::isfinite(intrinsics[i])) return RSBA_ERR_ARG;
+  for (int32_t c = 0; c < num_cameras; ++c) if (!(intrinsics[4 * c] != 0.0) || !(intrinsics[4 * c + 1] != 0.0)) return RSBA_ERR_ARG;
+  if (dist) for (int64_t i = 0; i < 5 * (int64_t)num_cameras; ++i) if (!std::isfinite(dist[i])) return RSBA_ERR_ARG;
+  const int ndev = rsba::DeviceCount();
+  if (ndev <= 0) return RSBA_ERR_NO_DEVICE;
+  if (device >= ndev) return RSBA_ERR_ARG;
+  if (n == 0) return RSBA_OK;
+  if (device >= 0 && hipSetDevice(device) != hipSuccess) return RSBA_ERR_HIP;
+  // one allocation: [corners 8n | intrinsics 4C | dist 5C | poses 6n | rms n] doubles, then [camera_index n | status n] int32
+  const size_t C = (size_t)num_cameras, N = (size_t)n;
+  const size_t nd = 8 * N + 4 * C + 5 * C + 6 * N + N;
+  double* d_all = nullptr;
+  if (hipMalloc((void**)&d_all, nd * sizeof(double) + 2 * N * sizeof(int32_t)) != hipSuccess) return RSBA_ERR_HIP;
+  double* d_corners = d_all;
+  double* d_intr = d_corners + 8 * N;
+  double* d_dist = d_intr + 4 * C;
+  double* d_poses = d_dist + 5 * C;
+  double* d_rms = d_poses + 6 * N;
+  int32_t* d_cam = (int32_t*)(d_all + nd);
+  int32_t* d_status = d_cam + N;
+  bool ok = hipMemcpy(d_corners, corners, 8 * N * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
+            hipMemcpy(d_intr, intrinsics, 4 * C * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+  if (ok && dist) ok = hipMemcpy(d_dist, dist, 5 * C * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+  if (ok && camera_index) ok = hipMemcpy(d_cam, camera_index, N * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
+  if (ok) {
+    // RSBA_RUNPROF=1: HIP events around the launch, the interval to stderr (tools/marker_pose_scale.py reads it)
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    const bool prof = getenv("RSBA_RUNPROF") != nullptr && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
+    if (prof) (void)hipEventRecord(e0, 0);
+    rsba::k_marker_pose<<<(unsigned)((N + 255) / 256), 256>>>(n, d_corners, camera_index ? d_cam : nullptr, d_intr, dist ? d_dist : nullptr, marker_side,
+                                                               d_poses, d_rms, d_status);
+    if (prof) (void)hipEventRecord(e1, 0);
+    ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    float ms = 0.0f;
+    if (ok && prof && hipEventElapsedTime(&ms, e0, e1) == hipSuccess)
+      fprintf(stderr, "rsba[runprof] k_marker_pose: %lld detections, %.4f ms between the events around its launch\n", (long long)n, ms);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+  // (the results reach the caller's arrays only when the whole batch ran)
+  if (ok) ok = hipMemcpy(poses, d_poses, 6 * N * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
+  if (ok && rms) ok = hipMemcpy(rms, d_rms, N * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
+  if (ok && status) ok = hipMemcpy(status, d_status, N * sizeof(int32_t), hipMemcpyDeviceToHost) == hipSuccess;
+  (void)hipFree(d_all);
+  return ok ? RSBA_OK : RSBA_ERR_HIP;
 }
 
 int rsba_reprojection_check_files(const char* correspondence_txt, const char* point3d_txt, const char* camera_transform_xml,

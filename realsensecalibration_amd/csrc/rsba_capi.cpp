@@ -189,6 +189,11 @@ int rsba_solve_pnp_epnp(int32_t n, const double* object_points, const double* im
   return rsba::SolvePnPEPnP(n, object_points, image_points, intrinsics4, pose);
 }
 int rsba_problem_initial_camera_poses(rsba_problem* p) { return rsba::InitialCameraPoses(p); }
+int rsba_marker_pose_from_corners(const double* corners8, const double* intrinsics4, const double* dist5_or_null, double marker_side,
+                                  double* pose6, double* rms_or_null, int32_t* status_or_null) {
+  return rsba::MarkerPoseFromCorners(corners8, intrinsics4, dist5_or_null, marker_side, pose6, rms_or_null, status_or_null);
+}
+int rsba_problem_initial_time_poses(rsba_problem* p, int32_t* num_missing_or_null) { return rsba::InitialTimePoses(p, num_missing_or_null); }
 
 int32_t rsba_problem_model(const rsba_problem* p) { return p ? p->model : -1; }
 int32_t rsba_problem_num_cameras(const rsba_problem* p) { return p ? p->num_cameras : 0; }
