@@ -367,6 +367,34 @@ int rsba_marker_poses_from_corners(int64_t n, const double* corners /* 8n */, co
  * leaves it uninitialised) or only degenerately keeps its bits and is counted in *num_missing_or_null.  The point model:
  * RSBA_ERR_UNSUPPORTED.  Host code. */
 int rsba_problem_initial_time_poses(rsba_problem* p, int32_t* num_missing_or_null);
+/* The start of a WHOLE rig from its detections, on the GPU: replaces rsba_problem_initial_time_poses + rsba_problem_initial_camera_poses
+ * where camera 0 does not see every shot.  Marker blocks are inputs (the board geometry), as for those two.
+ *   block resection   one pose block (a time or a camera) is fitted to ALL the detections that name it, the other two blocks of each
+ *                     detection held: the minimiser of their marker-chain reprojection cost (8 residuals each, through the model's functors,
+ *                     base blocks the identity, the problem's distortion coefficients applied) — ceres::Solve with every other block
+ *                     constant.  Levenberg-Marquardt with the rules of rsba_marker_pose_from_corners and one more — a step must realise a
+ *                     quarter of the decrease its damped model predicts, or the damping is raised — from the best of up to four candidate
+ *                     poses: the own fits (that entry's) of the block's detections with the lowest RMS, composed with their known blocks, the
+ *                     block cost evaluated at each.  A second detection so resolves the planar ambiguity of the first.
+ *   propagation       from the known blocks — those flagged in known_blocks (C cameras, then T times), the base camera always — round 0 fits
+ *                     every unknown time some known camera detected, the next round every unknown camera that detected a known time, and so on
+ *                     in turns until nothing is added.  A detection counts for a block only when its other block (the camera of a time's
+ *                     detection, the time of a camera's) is known.  Then refine_sweeps passes: all fitted times, then all fitted cameras, each
+ *                     from its value with every usable detection.  1 is recommended: a block fitted in an early round saw only the
+ *                     neighbours known then; further sweeps are block coordinate descent, which rsba_solve does better.  0 = the rounds alone.
+ * Blocks flagged in known_blocks keep their bits (new shots on a calibrated rig: flag the cameras; new cameras on solved shots: the times).
+ * block_status (C + T): 0 converged; 1 the iteration cap was reached (the last iterate); 2 degenerate — usable detections but no start with
+ * a finite cost and every corner in front — the block keeps its bits; 3 unreached — no usable detection — the block keeps its bits; 4 given,
+ * or the base camera.  block_rms: the RMS of the block's usable residuals in pixels at its last fit, -1 for statuses 2 to 4.  The counters
+ * count the blocks with status 2 or 3.  A block's result does not depend on its place in a launch and is bit-identical between calls.
+ * Observation weights, constant blocks, subset masks and priors of the problem play no part.
+ * RSBA_ERR_ARG (before any device work, nothing written): a null problem, refine_sweeps < 0, device < -1 or >= the device count;
+ * RSBA_ERR_UNSUPPORTED: the point model; RSBA_ERR_NO_DEVICE without a device.  RSBA_RUNPROF=1: each launch's HIP-event time on stderr. */
+int rsba_problem_start_rig(rsba_problem* p, const uint8_t* known_blocks /* C + T, or NULL: only the base camera */,
+                           int32_t refine_sweeps, int32_t device /* -1 = current */,
+                           int32_t* num_missing_times, int32_t* num_missing_cameras,
+                           int32_t* block_status /* C + T, or NULL */,
+                           double* block_rms /* C + T, or NULL */);
 
 void rsba_problem_free(rsba_problem* p);
 

@@ -92,6 +92,23 @@ class BALProblem {
     return rsba_problem_set_block_prior(p_, block - rsba_problem_parameters(p_), A, b) == RSBA_OK;
   }
   // Test1 accessors
+  // the start of the whole rig from its detections, on the GPU (rsba_problem_start_rig): the camera and time blocks by block resection
+  // and propagation over the co-visibility graph; the marker blocks are inputs.  known (optional): num_cameras() + num_times() flags of
+  // blocks that keep their values and serve from the first round.  status / rms (optional) are resized to that many entries.  Returns
+  // the number of blocks left without a value (status 2 or 3), -1 when the call itself fails.
+  int StartRig(const std::vector<uint8_t>* known = nullptr, int refine_sweeps = 1, int device = -1, std::vector<int32_t>* status = nullptr,
+               std::vector<double>* rms = nullptr) {
+    const size_t nb = (size_t)num_cameras() + (size_t)num_times();
+    if (known && known->size() != nb) return -1;
+    if (status) status->assign(nb, 0);
+    if (rms) rms->assign(nb, 0.0);
+    int32_t missing_times = 0, missing_cameras = 0;
+    if (rsba_problem_start_rig(p_, known ? known->data() : nullptr, refine_sweeps, device, &missing_times, &missing_cameras,
+                               status ? status->data() : nullptr, rms ? rms->data() : nullptr) != RSBA_OK)
+      return -1;
+    return missing_times + missing_cameras;
+  }
+
   double* mutable_cameras() { return rsba_problem_parameters(p_); }
   double* mutable_points() { return rsba_problem_parameters(p_) + 6 * num_cameras(); }
   double* mutable_camera_for_observation(int i) { return mutable_cameras() + 6 * rsba_problem_camera_idx(p_, i); }

@@ -37,7 +37,7 @@ EXPORTS = [
     "rsba_problem_set_observation_weights", "rsba_problem_observation_weights", "rsba_solver_set_observation_weights",
     "rsba_problem_set_parameter_subset_constant", "rsba_problem_parameter_subset_constant", "rsba_problem_set_distortion", "rsba_problem_distortion", "rsba_read_intrinsics_xml_dist", "rsba_undistort_points",
     "rsba_problem_set_block_prior", "rsba_problem_block_prior", "rsba_problem_num_block_priors", "rsba_solver_set_block_prior",
-    "rsba_marker_pose_from_corners", "rsba_marker_poses_from_corners", "rsba_problem_initial_time_poses",
+    "rsba_marker_pose_from_corners", "rsba_marker_poses_from_corners", "rsba_problem_initial_time_poses", "rsba_problem_start_rig",
 ]
 _SYMBOLS = EXPORTS   # (every symbol of include/rsba.h that load() checks)
 
@@ -194,6 +194,7 @@ def load():
     lib.rsba_marker_pose_from_corners.argtypes = [C.c_void_p] * 3 + [C.c_double] + [C.c_void_p] * 3
     lib.rsba_marker_poses_from_corners.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_int32] + [C.c_void_p] * 3
     lib.rsba_problem_initial_time_poses.argtypes = [C.c_void_p, C.c_void_p]
+    lib.rsba_problem_start_rig.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4
     _LIB = lib
     return lib
 
@@ -404,6 +405,25 @@ class Problem:
         missing = C.c_int32(0)
         _chk(load().rsba_problem_initial_time_poses(self.h, C.byref(missing)), "rsba_problem_initial_time_poses")
         return int(missing.value)
+
+    def start_rig(self, known=None, refine_sweeps=1, device=-1):
+        """Marker-chain models: the camera and time blocks of the whole rig from its detections, on the GPU (rsba_problem_start_rig):
+        block resection — one block fitted to all its detections, the others held — propagated over the co-visibility graph from the
+        known blocks.  known: C + T flags (cameras, then times) of blocks that keep their values, or None (only the base camera).
+        refine_sweeps: passes over all fitted times, then all fitted cameras, after the rounds (1 is recommended).  Returns
+        (missing_times, missing_cameras, status C + T, rms C + T): status 0 converged, 1 iteration cap, 2 degenerate, 3 unreached, 4 given
+        or the base camera; blocks with status 2 to 4 keep their bits and have rms -1."""
+        nb = self.num_cameras + (self.num_times if self.model != MODEL_POINTS else 0)
+        k = None
+        if known is not None:
+            k = np.ascontiguousarray(known, np.uint8).reshape(-1)
+            if k.size != nb:
+                raise ValueError("start_rig: one flag per camera and time block expected")
+        mt, mc = C.c_int32(0), C.c_int32(0)
+        status, rms = np.zeros(nb, np.int32), np.zeros(nb)
+        _chk(load().rsba_problem_start_rig(self.h, None if k is None else _vp(k), int(refine_sweeps), int(device), C.byref(mt), C.byref(mc),
+                                           _vp(status), _vp(rms)), "rsba_problem_start_rig")
+        return int(mt.value), int(mc.value), status, rms
 
     def detection_poses(self, device=-1):
         """Marker-chain models: (poses N x 6, rms N, status N) of every observation's own single-marker fit, one batch on the GPU over

@@ -23,7 +23,7 @@
 //   4. Levenberg-Marquardt on (rvec, tvec) with the analytic rows of ba_math.hpp (a pose block's rule: d r / d t = Q,
 //      d r / d w = [w* x Q_i] Jl): damping lambda diag(J'J), lambda0 = 1e-3; a candidate is accepted when the cost does not rise;
 //      lambda /= 10 (floor 1e-15) on acceptance, *= 10 on rejection; stop when the step's max-norm is below 1e-12 (1 + max |p|);
-//      at most kMarkerPoseMaxIterations steps.
+//      at most kMarkerPoseMaxIterations steps.  The loop is MarkerPoseMinimise, shared with the block resection (ba_resection.hpp).
 //
 // Everything is scalars and fixed-size arrays indexed by constants once the loops are unrolled: on the device the 21 entries of
 // J'J, the gradient, the pose and the 6 x 6 Cholesky factor live in registers (profiles/marker_pose_kernel_resources.txt: no scratch).
@@ -225,6 +225,65 @@ RSBA_HD bool MarkerPoseStep(const double A[21], const double g[6], double lambda
   return ok;
 }
 
+// The Levenberg-Marquardt loop on six pose parameters, shared by the single-marker fit below and the block resection
+// (ba_resection.hpp): lin(p, &cost, A, g, &min_depth) linearises the objective at p.  From p (when *ok) the loop damps with
+// lambda diag(J'J), accepts a candidate whose cost does not rise and whose points stay in front, and stops on a small step or at the
+// iteration cap.  *ok ends false when the start, or the last iterate, is unusable; p, *cost and *iterations are the last accepted
+// iterate's.  Returns MARKER_POSE_CONVERGED or MARKER_POSE_ITERATION_CAP.
+// kSufficientDecrease (the block resection): a candidate must also realise a quarter of the decrease the damped model predicts,
+// cost - cn >= (-2 g'd - d'Ad) / 4, the usual trust-region threshold below which the damping is raised.  With residuals of several pixels
+// at the minimum J'J underestimates the curvature along a board's tilt by a factor near two; a step twice too long leaves the cost where
+// it was, is accepted under "does not rise", lambda relaxes, the next step is rejected, and the pair repeats at the edge of stability
+// (measured: a factor 0.99 a step, 1.6e-4 from the minimiser after 400 steps).  The single-marker fit, whose eight residuals are noise at
+// its minimum, keeps its rule and its bits: the test is compiled out.
+template <bool kSufficientDecrease = false, class Linearise>
+RSBA_HD int MarkerPoseMinimise(Linearise&& lin, bool* ok_io, double p[6], double* cost_out, int* iterations) {
+  bool ok = *ok_io;
+  double cost = 0.0, A[21], g[6], minz = 0.0;
+  if (ok) {
+    lin(p, &cost, A, g, &minz);
+    ok = FiniteValue(cost) && minz > 0.0;
+  }
+  int status = MARKER_POSE_ITERATION_CAP, it = 0;
+  double lambda = 1e-3;
+  for (; ok && it < kMarkerPoseMaxIterations; ++it) {
+    double d[6], pn[6], An[21], gn[6], cn, zn;
+    const bool solved = MarkerPoseStep(A, g, lambda, d);
+    double dmax = 0.0, pmax = 0.0;
+    RSBA_UNROLL
+    for (int q = 0; q < 6; ++q) { dmax = fmax(dmax, fabs(d[q])); pmax = fmax(pmax, fabs(p[q])); pn[q] = p[q] + d[q]; }
+    lin(pn, &cn, An, gn, &zn);
+    bool accept = solved && FiniteValue(cn) && zn > 0.0 && cn <= cost;
+    if constexpr (kSufficientDecrease) {
+      double gd = 0.0, dAd = 0.0;
+      RSBA_UNROLL
+      for (int a = 0; a < 6; ++a) {
+        gd += g[a] * d[a];
+        RSBA_UNROLL
+        for (int b = 0; b < 6; ++b) dAd += d[a] * A[a <= b ? Sym6(a, b) : Sym6(b, a)] * d[b];
+      }
+      accept = accept && 4.0 * (cost - cn) >= -2.0 * gd - dAd;
+    }
+    if (accept) {
+      cost = cn;
+      RSBA_UNROLL
+      for (int q = 0; q < 6; ++q) { p[q] = pn[q]; g[q] = gn[q]; }
+      RSBA_UNROLL
+      for (int q = 0; q < 21; ++q) A[q] = An[q];
+      lambda = fmax(lambda * 0.1, 1e-15);
+    } else {
+      lambda *= 10.0;
+    }
+    if (solved && dmax < 1e-12 * (1.0 + pmax)) { status = MARKER_POSE_CONVERGED; break; }
+  }
+  RSBA_UNROLL
+  for (int q = 0; q < 6; ++q) ok = ok && FiniteValue(p[q]);
+  *ok_io = ok;
+  *cost_out = cost;
+  *iterations = it;
+  return status;
+}
+
 // The fit.  corners8: 4 x (u, v); dist5 may be null (no distortion).  Returns the status; pose6 and *rms are always written.
 RSBA_HD int FitMarkerPose(const double* corners8, const double* intr4, const double* dist5, double marker_side, double* pose6, double* rms) {
   double k5[5];
@@ -242,35 +301,11 @@ RSBA_HD int FitMarkerPose(const double* corners8, const double* intr4, const dou
   }
   ok = ok && MarkerPoseFromHomography(x, y, marker_side, p);
   const double half = 0.5 * marker_side;
-  double cost = 0.0, A[21], g[6], minz = 0.0;
-  if (ok) {
-    MarkerPoseLinearise(p, corners8, intr4, k5, half, &cost, A, g, &minz);
-    ok = FiniteValue(cost) && minz > 0.0;
-  }
-  int status = MARKER_POSE_ITERATION_CAP;
-  double lambda = 1e-3;
-  for (int it = 0; ok && it < kMarkerPoseMaxIterations; ++it) {
-    double d[6], pn[6], An[21], gn[6], cn, zn;
-    const bool solved = MarkerPoseStep(A, g, lambda, d);
-    double dmax = 0.0, pmax = 0.0;
-    RSBA_UNROLL
-    for (int q = 0; q < 6; ++q) { dmax = fmax(dmax, fabs(d[q])); pmax = fmax(pmax, fabs(p[q])); pn[q] = p[q] + d[q]; }
-    MarkerPoseLinearise(pn, corners8, intr4, k5, half, &cn, An, gn, &zn);
-    const bool accept = solved && FiniteValue(cn) && zn > 0.0 && cn <= cost;
-    if (accept) {
-      cost = cn;
-      RSBA_UNROLL
-      for (int q = 0; q < 6; ++q) { p[q] = pn[q]; g[q] = gn[q]; }
-      RSBA_UNROLL
-      for (int q = 0; q < 21; ++q) A[q] = An[q];
-      lambda = fmax(lambda * 0.1, 1e-15);
-    } else {
-      lambda *= 10.0;
-    }
-    if (solved && dmax < 1e-12 * (1.0 + pmax)) { status = MARKER_POSE_CONVERGED; break; }
-  }
-  RSBA_UNROLL
-  for (int q = 0; q < 6; ++q) ok = ok && FiniteValue(p[q]);
+  double cost = 0.0;
+  int iterations = 0;
+  const int status = MarkerPoseMinimise([&](const double* at, double* c, double* A, double* g, double* z) {
+    MarkerPoseLinearise(at, corners8, intr4, k5, half, c, A, g, z);
+  }, &ok, p, &cost, &iterations);
   if (!ok) {
     RSBA_UNROLL
     for (int q = 0; q < 6; ++q) pose6[q] = 0.0;

@@ -34,6 +34,8 @@
 #include "ba_marker_kernels.hpp"
 #include "ba_marker_pose.hpp"
 #include "ba_marker_schur.hpp"
+#include "ba_resection.hpp"
+#include "ba_rig_start_plan.hpp"
 #include "ba_point_kernels.hpp"
 #include "ba_cholesky_large.hpp"
 #include "ba_cholesky_multi.hpp"
@@ -3457,6 +3459,149 @@ int rsba_marker_poses_from_corners(int64_t n, const double* corners, const int32
   if (ok && status) ok = hipMemcpy(status, d_status, N * sizeof(int32_t), hipMemcpyDeviceToHost) == hipSuccess;
   (void)hipFree(d_all);
   return ok ? RSBA_OK : RSBA_ERR_HIP;
+}
+
+// The whole-rig start: every detection's own fit (k_marker_pose), then the launches of the plan (ba_rig_start_plan.hpp) on the default
+// stream, one after the other: a launch reads the flags and blocks the one before it wrote.
+int rsba_problem_start_rig(rsba_problem* p, const uint8_t* known_blocks, int32_t refine_sweeps, int32_t device, int32_t* num_missing_times,
+                           int32_t* num_missing_cameras, int32_t* block_status, double* block_rms) {
+  if (!p || refine_sweeps < 0 || device < -1) return RSBA_ERR_ARG;
+  if (!p->is_marker_chain()) return RSBA_ERR_UNSUPPORTED;
+  const int ndev = rsba::DeviceCount();
+  if (ndev <= 0) return RSBA_ERR_NO_DEVICE;
+  if (device >= ndev) return RSBA_ERR_ARG;
+  const int C = p->num_cameras, T = p->num_times, M = p->num_markers;
+  const size_t N = (size_t)p->num_observations, nb = (size_t)C + T;
+  const bool with_dist = p->has_distortion();
+  rsba::RigStartPlan plan;
+  if (!rsba::PlanRigStart(C, T, M, p->num_observations, p->camera_index.data(), p->time_index.data(), known_blocks, refine_sweeps, with_dist, &plan))
+    return RSBA_ERR_ARG;
+  std::vector<int32_t> status(nb);
+  std::vector<double> rms(nb, -1.0);
+  for (size_t b = 0; b < nb; ++b) status[b] = plan.given[b] ? rsba::BLOCK_GIVEN : rsba::BLOCK_UNREACHED;
+  std::vector<int32_t> iterations(nb, 0);
+  bool ok = true;
+  if (N > 0 && !plan.launches.empty()) {
+    if (device >= 0 && hipSetDevice(device) != hipSuccess) return RSBA_ERR_HIP;
+    char* d_all = nullptr;
+    if (hipMalloc((void**)&d_all, plan.buffers.total) != hipSuccess) return RSBA_ERR_HIP;
+    const rsba::RigStartBuffers& bf = plan.buffers;
+    auto up = [&](size_t off, const void* src, size_t bytes) {
+      if (ok && bytes > 0) ok = hipMemcpy(d_all + off, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+    };
+    up(bf.observations, p->observations.data(), 8 * N * sizeof(double));
+    up(bf.intrinsics, p->intrinsics.data(), 4 * (size_t)C * sizeof(double));
+    if (with_dist) up(bf.distortion, p->distortion.data(), 5 * (size_t)C * sizeof(double));
+    up(bf.parameters, p->parameters.data(), 6 * (nb + (size_t)M) * sizeof(double));
+    up(bf.block_rms, rms.data(), nb * sizeof(double));
+    up(bf.camera_index, p->camera_index.data(), N * sizeof(int32_t));
+    up(bf.time_index, p->time_index.data(), N * sizeof(int32_t));
+    up(bf.marker_index, p->marker_index.data(), N * sizeof(int32_t));
+    up(bf.time_ptr, plan.time_ptr.data(), plan.time_ptr.size() * sizeof(int));
+    up(bf.time_obs, plan.time_obs.data(), N * sizeof(int));
+    up(bf.camera_ptr, plan.camera_ptr.data(), plan.camera_ptr.size() * sizeof(int));
+    up(bf.camera_obs, plan.camera_obs.data(), N * sizeof(int));
+    up(bf.blocks, plan.blocks.data(), plan.blocks.size() * sizeof(int));
+    up(bf.block_status, status.data(), nb * sizeof(int32_t));
+    up(bf.block_iterations, iterations.data(), nb * sizeof(int32_t));
+    up(bf.known, plan.given.data(), nb);
+    rsba::ResectionArgs a{};
+    a.all_markers = p->model == RSBA_MODEL_MARKER_CHAIN_TEST2 ? 1 : 0;
+    a.C = C; a.T = T;
+    a.half = 0.5 * p->marker_side;
+    a.camera_index = (const int32_t*)(d_all + bf.camera_index);
+    a.time_index = (const int32_t*)(d_all + bf.time_index);
+    a.marker_index = (const int32_t*)(d_all + bf.marker_index);
+    a.observations = (const double*)(d_all + bf.observations);
+    a.intrinsics = (const double*)(d_all + bf.intrinsics);
+    a.distortion = with_dist ? (const double*)(d_all + bf.distortion) : nullptr;
+    a.own_pose = (const double*)(d_all + bf.own_pose);
+    a.own_rms = (const double*)(d_all + bf.own_rms);
+    a.own_status = (const int32_t*)(d_all + bf.own_status);
+    a.parameters = (double*)(d_all + bf.parameters);
+    a.known = (uint8_t*)(d_all + bf.known);
+    a.status = (int32_t*)(d_all + bf.block_status);
+    a.rms = (double*)(d_all + bf.block_rms);
+    a.iterations = (int32_t*)(d_all + bf.block_iterations);
+    if (ok) {
+      // RSBA_RUNPROF=1: HIP events between the launches, the intervals to stderr (tools/rig_start_scale.py reads them)
+      const bool prof = getenv("RSBA_RUNPROF") != nullptr;
+      std::vector<hipEvent_t> ev;
+      if (prof) {
+        ev.resize(plan.launches.size() + 2, nullptr);
+        for (hipEvent_t& e : ev) if (hipEventCreate(&e) != hipSuccess) e = nullptr;
+      }
+      auto mark = [&](size_t k) { if (prof && ev[k]) (void)hipEventRecord(ev[k], 0); };
+      mark(0);
+      rsba::k_marker_pose<<<(unsigned)((N + 255) / 256), 256>>>((int64_t)N, a.observations, a.camera_index, a.intrinsics, a.distortion, p->marker_side,
+                                                                 (double*)(d_all + bf.own_pose), (double*)(d_all + bf.own_rms), (int32_t*)(d_all + bf.own_status));
+      mark(1);
+      for (size_t k = 0; k < plan.launches.size(); ++k) {
+        const rsba::RigStartLaunch& l = plan.launches[k];
+        a.blocks = (const int*)(d_all + bf.blocks) + l.first;
+        a.num_blocks = l.count;
+        if (l.which == rsba::kRigStartTime) {
+          a.list_ptr = (const int*)(d_all + bf.time_ptr);
+          a.list_obs = (const int*)(d_all + bf.time_obs);
+          rsba::k_block_resection<false><<<l.grid, 256>>>(a, rsba::RESECT_TIME);
+        } else {
+          a.list_ptr = (const int*)(d_all + bf.camera_ptr);
+          a.list_obs = (const int*)(d_all + bf.camera_obs);
+          rsba::k_block_resection<true><<<l.grid, 256>>>(a, rsba::RESECT_CAMERA);
+        }
+        mark(k + 2);
+      }
+      ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+      if (ok && prof) {
+        float ms = 0.0f;
+        if (ev[0] && ev[1] && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
+          fprintf(stderr, "rsba[runprof] start_rig k_marker_pose: %lld detections, %.4f ms\n", (long long)N, ms);
+        for (size_t k = 0; k < plan.launches.size(); ++k) {
+          const rsba::RigStartLaunch& l = plan.launches[k];
+          if (ev[k + 1] && ev[k + 2] && hipEventElapsedTime(&ms, ev[k + 1], ev[k + 2]) == hipSuccess)
+            fprintf(stderr, "rsba[runprof] start_rig launch %d: %s %s %d, %d blocks, %lld detections, %.4f ms\n", (int)k, l.which == rsba::kRigStartTime ? "times" : "cameras",
+                    l.sweep ? "sweep" : "round", l.sweep ? l.sweep : (int)k, l.count, (long long)l.observations, ms);
+        }
+      }
+      for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    }
+    // (the results reach the problem only when every launch ran)
+    std::vector<double> blocks6(6 * nb);
+    auto down = [&](void* dst, size_t off, size_t bytes) {
+      if (ok && bytes > 0) ok = hipMemcpy(dst, d_all + off, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+    };
+    down(blocks6.data(), bf.parameters, 6 * nb * sizeof(double));
+    down(status.data(), bf.block_status, nb * sizeof(int32_t));
+    down(rms.data(), bf.block_rms, nb * sizeof(double));
+    down(iterations.data(), bf.block_iterations, nb * sizeof(int32_t));
+    (void)hipFree(d_all);
+    if (!ok) return RSBA_ERR_HIP;
+    // a block that was fitted carries its new value; every other block keeps its bits
+    for (size_t b = 0; b < nb; ++b)
+      if (status[b] == rsba::BLOCK_CONVERGED || status[b] == rsba::BLOCK_ITERATION_CAP) memcpy(&p->parameters[6 * b], &blocks6[6 * b], 6 * sizeof(double));
+    if (getenv("RSBA_RUNPROF")) {
+      // the iteration counts of the blocks' last fits, in bins of 25, and the fits that ended at the cap
+      int hist[17] = {0}, capped = 0;
+      for (size_t b = 0; b < nb; ++b) {
+        if (status[b] > rsba::BLOCK_ITERATION_CAP) continue;
+        ++hist[std::min(16, iterations[b] / 25)];
+        capped += status[b] == rsba::BLOCK_ITERATION_CAP;
+      }
+      fprintf(stderr, "rsba[runprof] start_rig iterations by 25:");
+      for (int h : hist) fprintf(stderr, " %d", h);
+      fprintf(stderr, "; at the cap: %d\n", capped);
+    }
+  }
+  int32_t missing_t = 0, missing_c = 0;
+  for (size_t b = 0; b < nb; ++b) {
+    const bool missing = status[b] == rsba::BLOCK_DEGENERATE || status[b] == rsba::BLOCK_UNREACHED;
+    if (missing) ++(b < (size_t)C ? missing_c : missing_t);
+  }
+  if (num_missing_times) *num_missing_times = missing_t;
+  if (num_missing_cameras) *num_missing_cameras = missing_c;
+  if (block_status) memcpy(block_status, status.data(), nb * sizeof(int32_t));
+  if (block_rms) memcpy(block_rms, rms.data(), nb * sizeof(double));
+  return RSBA_OK;
 }
 
 int rsba_reprojection_check_files(const char* correspondence_txt, const char* point3d_txt, const char* camera_transform_xml,
