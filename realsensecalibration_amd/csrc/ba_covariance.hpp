@@ -18,6 +18,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "ba_covariance_plan.hpp"   // CovReq, COV_REQ_*, CovMcRow, RSBA_COV_MC_MAXBLK: shared with the host plan
 #include "ba_math.hpp"
 #include "ba_point_kernels.hpp"
 
@@ -432,9 +433,7 @@ k_cov_points(int P, const double* __restrict__ obs_u, const double* __restrict__
 
 
 // ---- marker-chain models ------------------------------------------------------------------------------------------------
-// One row of the marker-chain problem in time order: pose-block indices into [C | T | M] (-1: not a parameter of this row) and
-// the camera whose intrinsics project it.
-struct CovMcRow { int cam_block, time_block, marker_block, camera; };
+// (CovMcRow, a row of the marker-chain problem in time order: ba_covariance_plan.hpp)
 
 // pose constants (CC_R, CC_K, CC_T, CC_SMALL) of every block of [C | T | M]
 __global__ void __launch_bounds__(256) k_cov_pose_constants(int nb, const double* __restrict__ params, double* __restrict__ pc) {
@@ -729,8 +728,7 @@ k_cov_mc_lin(int T, const int* __restrict__ tptr, const CovMcRow* __restrict__ r
 //                   the blocks; (t, t') walks the rows of t with G = sum_d Sigma_{p, p_d} Y'_d per row block, M += W' G, and
 //                   cov = V_t^-1 M (+ V_t^-1 for t = t')
 //   k_cov_pt_cross  (camera, point j) and (point j, point k), on the pattern of k_cov_points
-struct CovReq { int a, b, kind, out; };   // out: the request's 36 doubles in the staging buffer
-enum { COV_REQ_SINV = 0, COV_REQ_POINT = 1, COV_REQ_TIME_TIME = 2, COV_REQ_TIME_X = 3, COV_REQ_CAM_POINT = 4, COV_REQ_POINT_POINT = 5 };
+// (CovReq and its kinds: ba_covariance_plan.hpp, where the host plans the lists)
 
 // a, b: row and column of the block in S^-1 (COV_REQ_SINV); a: the point, the problem's order (COV_REQ_POINT)
 __global__ void __launch_bounds__(64)
@@ -746,7 +744,6 @@ k_cov_gather(int nreq, const CovReq* __restrict__ req, int n, const double* __re
   }
 }
 
-#define RSBA_COV_MC_MAXBLK 170   // distinct camera / marker blocks with columns that one time touches: 170 x 36 doubles of LDS
 #define RSBA_COV_MC_STAGE 37     // doubles per staged row (+1: bank padding)
 
 // The marker chain's snapshot (the compute's arena) and the host's slot tables: the distinct blocks of time t are

@@ -14,6 +14,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "ba_problem.hpp"
+
 namespace rsba {
 
 // Which blocks' gradient slots are computed (1) and which are 0.0 by definition (0: constant or referenced by no residual).  Point
@@ -33,10 +35,18 @@ EvalCameraIndex BuildEvalCameraIndex(int C, int P, const std::vector<int64_t>& o
 
 // Marker-chain models: one row per observation in the problem's order, the blocks of [C | T | M] it names as PARAMETERS (-1: the
 // functor has no such block — camera 0, and marker 0 of RSBA_MODEL_MARKER_CHAIN) and the camera whose intrinsics project it.
-// (The fields of ba_covariance.hpp's CovMcRow; that header is device code, and this unit compiles without HIP.)
+// (The covariance reads the same rows in time order: ba_covariance_plan.hpp's CovMcRow is this struct.)
 struct EvalMarkerRow {
   int cam_block, time_block, marker_block, camera;
 };
+inline EvalMarkerRow EvalMarkerRowOf(const rsba_problem& p, int64_t i) {
+  return EvalMarkerRow{p.uses_camera(i) ? p.camera_block(i) : -1, p.time_block(i), p.uses_marker(i) ? p.marker_block(i) : -1, p.camera_index[i]};
+}
+inline std::vector<EvalMarkerRow> EvalMarkerRows(const rsba_problem& p) {
+  std::vector<EvalMarkerRow> rows((size_t)p.num_observations);
+  for (int64_t i = 0; i < p.num_observations; ++i) rows[i] = EvalMarkerRowOf(p, i);
+  return rows;
+}
 // Block b owns entries [ptr[b], ptr[b + 1]): `obs` ascending; `slot` 0 / 1 / 2.  An observation is in the list of every block it names.
 struct EvalMarkerLists {
   std::vector<int> ptr, obs;

@@ -308,9 +308,8 @@ struct rsba_solver {
   // ---- covariance (rsba_solver_covariance_compute, ba_covariance.hpp): buffers of its own, the LM state is not touched
   bool cov_valid = false;
   int cov_n = 0;
-  std::vector<int> cov_pos;                    // per camera (point model) / per block of [C | T | M] (marker chain): 6 x its index in the
-                                               // covariance system, -1: constant, unreferenced or eliminated
-  std::vector<uint8_t> cov_ref_cam, cov_ref_pt;   // referenced by a residual (marker chain: cov_ref_cam per block of [C | T | M])
+  CovLayout cov_layout;                        // the last compute's column map (ba_covariance_plan.hpp): referenced flags, positions in the
+                                               // system, eliminated times; the point order's inverse, built by the first query that needs it
   double* cov_sinv = nullptr;                  // cov_n x cov_n, full symmetric
   size_t cov_sinv_cap = 0;
   double* cov_pts = nullptr;                   // P x 9, the problem's point order
@@ -326,7 +325,6 @@ struct rsba_solver {
     int* sub18 = nullptr;                      // the rows' constant columns (a solver with constant components; else nullptr)
     double loss = 0.0, rcond = 0.0, half_side = 0.0;
     bool use_w = false;
-    std::vector<unsigned char> elim;           // per time: eliminated by this compute (free, referenced, time-eliminating path)
   } cov_mc;
   struct CovPointSnapshot {
     double *camc = nullptr, *pts = nullptr;    // pts: the compute's own copy of the points (the solver's point order)
@@ -343,7 +341,6 @@ struct rsba_solver {
   double* cov_times = nullptr;                 // T x 36 time marginals, formed by the first rsba_solver_time_covariances after a compute
   size_t cov_times_cap = 0;
   uint64_t cov_times_epoch = 0;
-  std::vector<int> cov_pt_dev;                 // point model: a point's index in the problem -> its position on the device
 
   // ---- evaluate (rsba_solver_evaluate, ba_evaluate.hpp): tables and arena of its own, the LM state is not touched
   EvalDevice eval;
@@ -1866,6 +1863,17 @@ static int CovGrow(T** p, size_t* cap, size_t n) {
   *cap = n;
   return RSBA_OK;
 }
+// The two passes: `carve` runs over a sizing carve, the arena grows to that, `carve` runs again and hands out.
+template <typename F>
+static int CovCarveArena(char** arena, size_t* cap, F&& carve) {
+  CovCarve sizing;
+  carve(sizing);
+  if (int rc = CovGrow(arena, cap, sizing.off)) return rc;
+  CovCarve cv;
+  cv.base = *arena;
+  carve(cv);
+  return RSBA_OK;
+}
 
 struct CovSystem {   // the reduced system's buffers (carved) and its size
   int n = 0, np = 0;
@@ -1900,14 +1908,10 @@ static int CovRun(rsba_solver* s, int n, double rcond, Extra&& extra, Launch&& l
   s->cov_n = n;
   CovSystem y;
   y.n = n; y.np = std::max(RSBA_COV_NB, (n + RSBA_COV_NB - 1) / RSBA_COV_NB * RSBA_COV_NB);
-  CovCarve sizing;
-  y.Carve(sizing); extra(sizing);
   int rc;
-  if ((rc = CovGrow(&s->cov_arena, &s->cov_arena_cap, sizing.off)) || (rc = CovGrow(&s->cov_sinv, &s->cov_sinv_cap, (size_t)n * n))) return rc;
-  CovCarve cv;
-  cv.base = s->cov_arena;
-  y.Carve(cv); extra(cv);
-  rc = RSBA_OK;
+  if ((rc = CovCarveArena(&s->cov_arena, &s->cov_arena_cap, [&](CovCarve& cv) { y.Carve(cv); extra(cv); })) ||
+      (rc = CovGrow(&s->cov_sinv, &s->cov_sinv_cap, (size_t)n * n)))
+    return rc;
   auto hip = [&](hipError_t e) { if (e != hipSuccess && rc == RSBA_OK) rc = RSBA_ERR_HIP; };
   hip(hipMemsetAsync(y.flags, 0, COV_FLAG_WORDS * sizeof(int), st));
   hip(hipMemsetAsync(y.S, 0, std::max<size_t>((size_t)n * n, 1) * sizeof(double), st));
@@ -1931,27 +1935,23 @@ static int CovRun(rsba_solver* s, int n, double rcond, Extra&& extra, Launch&& l
 static int CovariancePoints(rsba_solver* s, const rsba_covariance_options& co, Comm* comm) {
   const rsba_problem& p = *s->prob;
   const int C = s->C, P = s->P;
-  s->cov_ref_cam.assign(C, 0);
-  s->cov_ref_pt.assign(P, 0);
-  for (int64_t i = 0; i < s->N; ++i) { s->cov_ref_cam[p.camera_index[i]] = 1; s->cov_ref_pt[p.point_index[i]] = 1; }
+  CovLayout& L = s->cov_layout;
+  std::vector<uint8_t> ref_cam;
+  CovPointReferenced(C, P, s->N, p.camera_index.data(), p.point_index.data(), s->eval_const_pt, &ref_cam, &L);
   if (comm) {
     ShardedQuery q{s, comm};
-    std::vector<double> f(std::max(C, 1), 0.0);
-    for (int c = 0; c < C; ++c) f[c] = s->cov_ref_cam[c] ? 1.0 : 0.0;
+    std::vector<double> f(ref_cam.begin(), ref_cam.end());
+    f.resize(std::max(C, 1), 0.0);
     int rc = q.Reserve(f.size());
     if (rc != RSBA_OK) return rc;
     HIPCHK(hipMemcpyAsync(s->query_buf, f.data(), f.size() * sizeof(double), hipMemcpyHostToDevice, s->stream));
     COMMCHK(comm->SumDoubles(s->query_buf, f.size(), s->stream));
     COMMCHK(comm->WaitStream(s->stream));
     HIPCHK(hipMemcpy(f.data(), s->query_buf, f.size() * sizeof(double), hipMemcpyDeviceToHost));
-    for (int c = 0; c < C; ++c) s->cov_ref_cam[c] = f[c] > 0.0;
+    for (int c = 0; c < C; ++c) ref_cam[c] = f[c] > 0.0;
   }
-  s->cov_pos.assign(C, -1);
-  int n = 0;
-  for (int c = 0; c < C; ++c) {
-    const bool constant = c < (int)p.camera_constant.size() && p.camera_constant[c];
-    if (s->cov_ref_cam[c] && !constant) { s->cov_pos[c] = n; n += 6; }
-  }
+  CovPointColumns(ref_cam, p.camera_constant, &L);
+  const int n = L.n;
   if (!s->cov_pts) { int rc = DevAlloc(&s->cov_pts, 9 * (size_t)P); if (rc) return rc; }
   double *camc = nullptr, *tri = nullptr, *pts_snap = nullptr;
   int *pos = nullptr, *perm = nullptr;
@@ -1969,7 +1969,7 @@ static int CovariancePoints(rsba_solver* s, const rsba_covariance_options& co, C
   const int grid_pts = std::max(1, std::min((P + 3) / 4, 8192));
   hipStream_t st = s->stream;
   int rc = CovRun(s, n, rcond, extra, [&](CovSystem& y, auto& hip) {
-    hip(hipMemcpyAsync(pos, s->cov_pos.data(), C * sizeof(int), hipMemcpyHostToDevice, st));
+    hip(hipMemcpyAsync(pos, L.pos.data(), C * sizeof(int), hipMemcpyHostToDevice, st));
     if (perm) hip(hipMemcpyAsync(perm, s->pt_perm.data(), P * sizeof(int), hipMemcpyHostToDevice, st));
     if (P > 0) hip(hipMemcpyAsync(pts_snap, pts, 3 * (size_t)P * sizeof(double), hipMemcpyDeviceToDevice, st));
     k_camera_constants<<<(C + 63) / 64, 64, 0, st>>>(C, cam, s->intr, camc);
@@ -1995,74 +1995,36 @@ static int CovariancePoints(rsba_solver* s, const rsba_covariance_options& co, C
   return RSBA_OK;
 }
 
+// k_cov_mc_lin's intrinsics argument: the array alone, with the distortion coefficients, or — the kSub instances — with both and the rows' masks
+template <bool kDist, bool kSub>
+static typename CovIntrArg<kDist, kSub>::type CovIntrPass(const double* intr, const double* dist, const int* sub18) {
+  if constexpr (kSub) { IntrDistSub a; a.intr = intr; a.dist = dist; a.sub18 = sub18; return a; }
+  else return IntrPass<kDist>(intr, dist);
+}
+
 // Marker-chain models: S^-1 of the free referenced camera / marker blocks.  The dense path keeps the free time blocks in the system
 // (the inverse of its whole active system); the time-eliminating path eliminates them first, as its solve does.  The solve's loss
 // corrector with apply_loss_function, on both paths (the eliminated time blocks included).
 static int CovarianceMarker(rsba_solver* s, const rsba_covariance_options& co) {
   const rsba_problem& p = *s->prob;
-  const int C = p.num_cameras, T = p.num_times, M = p.num_markers, nb = C + T + M;
-  const int64_t N = p.num_observations;
   const bool elim_path = s->eliminate_times;
-  s->cov_ref_cam.assign(nb, 0);
-  for (int64_t i = 0; i < N; ++i) {
-    if (p.uses_camera(i)) s->cov_ref_cam[p.camera_block(i)] = 1;
-    s->cov_ref_cam[p.time_block(i)] = 1;
-    if (p.uses_marker(i)) s->cov_ref_cam[p.marker_block(i)] = 1;
-  }
-  auto is_free = [&](int b) { return s->cov_ref_cam[b] && !(b < (int)p.block_constant.size() && p.block_constant[b]); };
-  s->cov_pos.assign(nb, -1);
-  std::vector<unsigned char> elim(std::max(T, 1), 0);
-  int n = 0;
-  for (int b = 0; b < nb; ++b) {
-    const bool time = b >= C && b < C + T;
-    if (!is_free(b)) continue;
-    if (time && elim_path) { elim[b - C] = 1; continue; }
-    s->cov_pos[b] = n; n += 6;
-  }
-  // rows in time order
-  std::vector<int> tptr(T + 1, 0);
-  for (int64_t i = 0; i < N; ++i) tptr[p.time_index[i] + 1]++;
-  for (int t = 0; t < T; ++t) tptr[t + 1] += tptr[t];
-  std::vector<int> fill(tptr.begin(), tptr.end() - 1);
-  std::vector<CovMcRow> rows(std::max<int64_t>(N, 1));
-  std::vector<double> obs(8 * (size_t)std::max<int64_t>(N, 1));
-  for (int64_t i = 0; i < N; ++i) {
-    const int q = fill[p.time_index[i]]++;
-    rows[q] = CovMcRow{p.uses_camera(i) ? p.camera_block(i) : -1, p.time_block(i), p.uses_marker(i) ? p.marker_block(i) : -1, p.camera_index[i]};
-    for (int e = 0; e < 8; ++e) obs[8 * (size_t)q + e] = p.observations[8 * i + e];
-  }
-  double *pc = nullptr, *obs_d = nullptr, *intr = nullptr;
-  int *pos = nullptr, *tptr_d = nullptr;
-  CovMcRow* rows_d = nullptr;
-  unsigned char* elim_d = nullptr;
+  // the plan (ba_covariance_plan.hpp): the problem's constant blocks as they are now, the component masks as taken at create
+  CovLayout& L = s->cov_layout;
+  CovMarkerColumns(p, p.block_constant, elim_path, &L);
+  const int T = L.T, nb = L.blocks(), n = L.n;
   // the rows' weights ride on the loss corrector: ignored with it (apply_loss_function = 0), as Ceres ignores the whole LossFunction
   const bool use_w = s->weights_given && co.apply_loss_function;
-  std::vector<double> wrow;
-  if (use_w) {
-    wrow.resize(rows.size(), 1.0);
-    std::vector<int> fw(tptr.begin(), tptr.end() - 1);
-    for (int64_t i = 0; i < N; ++i) wrow[fw[p.time_index[i]]++] = s->obs_w[i];
-  }
-  // constant components (eval_subset) of the blocks with columns or eliminated: the rows' 18-bit column masks, the blocks' masks
-  std::vector<unsigned char> bsub(nb, 0);
-  bool with_sub = false;
-  for (int b = 0; b < nb && b < (int)s->eval_subset.size(); ++b) if (is_free(b)) { bsub[b] = s->eval_subset[b]; with_sub = with_sub || bsub[b] != 0; }
-  std::vector<int> sub18;
-  if (with_sub) {
-    sub18.resize(rows.size(), 0);
-    for (size_t q = 0; q < (size_t)N; ++q) {
-      const CovMcRow& rw = rows[q];
-      sub18[q] = (rw.cam_block >= 0 ? bsub[rw.cam_block] : 0) | (bsub[rw.time_block] << 6) | (rw.marker_block >= 0 ? bsub[rw.marker_block] << 12 : 0);
-    }
-  }
-  int* sub18_d = nullptr;
-  unsigned char* bsub_d = nullptr;
-  double* wrow_d = nullptr;
+  const CovMarkerRows R = CovPlanMarkerRows(p, L, use_w ? s->obs_w.data() : nullptr, s->eval_subset);
+  const bool with_sub = R.with_sub;
+  double *pc = nullptr, *obs_d = nullptr, *intr = nullptr, *wrow_d = nullptr;
+  int *pos = nullptr, *tptr_d = nullptr, *sub18_d = nullptr;
+  CovMcRow* rows_d = nullptr;
+  unsigned char *elim_d = nullptr, *bsub_d = nullptr;
   auto extra = [&](CovCarve& cv) {
-    if (with_sub) { sub18_d = cv.take<int>(sub18.size()); bsub_d = cv.take<unsigned char>(nb); }
-    if (use_w) wrow_d = cv.take<double>(wrow.size());
-    pc = cv.take<double>((size_t)CC_STRIDE * nb); obs_d = cv.take<double>(obs.size()); intr = cv.take<double>(p.intrinsics.size());
-    pos = cv.take<int>(nb); tptr_d = cv.take<int>(T + 1); rows_d = cv.take<CovMcRow>(rows.size()); elim_d = cv.take<unsigned char>(elim.size());
+    if (with_sub) { sub18_d = cv.take<int>(R.sub18.size()); bsub_d = cv.take<unsigned char>(nb); }
+    if (use_w) wrow_d = cv.take<double>(R.wrow.size());
+    pc = cv.take<double>((size_t)CC_STRIDE * nb); obs_d = cv.take<double>(R.obs.size()); intr = cv.take<double>(p.intrinsics.size());
+    pos = cv.take<int>(nb); tptr_d = cv.take<int>(T + 1); rows_d = cv.take<CovMcRow>(R.rows.size()); elim_d = cv.take<unsigned char>(L.elim.size());
   };
   const double* params = elim_path ? (s->has_run ? s->marker_schur.params[s->marker_schur.cur] : s->marker_schur.params0)
                                    : (s->has_run ? s->marker.params[s->marker.cur] : s->marker.params0);
@@ -2070,32 +2032,16 @@ static int CovarianceMarker(rsba_solver* s, const rsba_covariance_options& co) {
   const double loss = !co.apply_loss_function || !(s->opt.huber_delta > 0.0) ? 0.0 : (s->opt.loss_type == RSBA_LOSS_CAUCHY ? -s->opt.huber_delta : s->opt.huber_delta);
   hipStream_t st = s->stream;
   const int rc = CovRun(s, n, rcond, extra, [&](CovSystem& y, auto& hip) {
-    hip(hipMemcpyAsync(obs_d, obs.data(), obs.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    hip(hipMemcpyAsync(intr, p.intrinsics.data(), p.intrinsics.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    hip(hipMemcpyAsync(pos, s->cov_pos.data(), nb * sizeof(int), hipMemcpyHostToDevice, st));
-    hip(hipMemcpyAsync(tptr_d, tptr.data(), (T + 1) * sizeof(int), hipMemcpyHostToDevice, st));
-    hip(hipMemcpyAsync(rows_d, rows.data(), rows.size() * sizeof(CovMcRow), hipMemcpyHostToDevice, st));
-    hip(hipMemcpyAsync(elim_d, elim.data(), elim.size(), hipMemcpyHostToDevice, st));
-    if (use_w) hip(hipMemcpyAsync(wrow_d, wrow.data(), wrow.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    auto upload = [&](auto* dst, const auto& v) { hip(hipMemcpyAsync(dst, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice, st)); };
+    upload(obs_d, R.obs); upload(intr, p.intrinsics); upload(pos, L.pos); upload(tptr_d, R.tptr); upload(rows_d, R.rows); upload(elim_d, L.elim);
+    if (use_w) upload(wrow_d, R.wrow);
     k_cov_pose_constants<<<(nb + 255) / 256, 256, 0, st>>>(nb, params, pc);
-    if (with_sub) {
-      hip(hipMemcpyAsync(sub18_d, sub18.data(), sub18.size() * sizeof(int), hipMemcpyHostToDevice, st));
-      hip(hipMemcpyAsync(bsub_d, bsub.data(), nb, hipMemcpyHostToDevice, st));
-      IntrDistSub ids; ids.intr = intr; ids.dist = s->dist_dev; ids.sub18 = sub18_d;
-      const int grid = std::max(1, std::min(T, 4096));
-      const bool lossy = loss != 0.0 || use_w;
-      if (lossy && s->dist_dev) k_cov_mc_lin<true, true, true><<<grid, 64, 0, st>>>(T, tptr_d, rows_d, obs_d, ids, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags, loss, wrow_d);
-      else if (lossy) k_cov_mc_lin<true, false, true><<<grid, 64, 0, st>>>(T, tptr_d, rows_d, obs_d, ids, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags, loss, wrow_d);
-      else if (s->dist_dev) k_cov_mc_lin<false, true, true><<<grid, 64, 0, st>>>(T, tptr_d, rows_d, obs_d, ids, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags);
-      else k_cov_mc_lin<false, false, true><<<grid, 64, 0, st>>>(T, tptr_d, rows_d, obs_d, ids, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags);
-    } else if (loss != 0.0 || use_w) {
-      if (s->dist_dev) k_cov_mc_lin<true, true><<<std::max(1, std::min(T, 4096)), 64, 0, st>>>(T, tptr_d, rows_d, obs_d, IntrDist{intr, s->dist_dev}, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags, loss, wrow_d);
-      else k_cov_mc_lin<true><<<std::max(1, std::min(T, 4096)), 64, 0, st>>>(T, tptr_d, rows_d, obs_d, intr, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags, loss, wrow_d);
-    } else if (s->dist_dev) {
-      k_cov_mc_lin<false, true><<<std::max(1, std::min(T, 4096)), 64, 0, st>>>(T, tptr_d, rows_d, obs_d, IntrDist{intr, s->dist_dev}, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags);
-    } else {
-      k_cov_mc_lin<false><<<std::max(1, std::min(T, 4096)), 64, 0, st>>>(T, tptr_d, rows_d, obs_d, intr, pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags);
-    }
+    if (with_sub) { upload(sub18_d, R.sub18); upload(bsub_d, R.bsub); }
+    // (the instances without a loss take loss = 0 and no weights, those without distortion or masks a null pointer in their place)
+    Dispatch([&](auto Ls, auto D, auto Sb) {
+      k_cov_mc_lin<Ls.value, D.value, Sb.value><<<std::max(1, std::min(T, 4096)), 64, 0, st>>>(
+          T, tptr_d, rows_d, obs_d, CovIntrPass<D.value, Sb.value>(intr, s->dist_dev, sub18_d), pc, pos, elim_d, p.marker_side / 2, rcond, y.n, y.S, y.flags, loss, wrow_d);
+    }, loss != 0.0 || use_w, s->dist_dev != nullptr, with_sub);
     if (s->num_priors > 0 && y.n > 0) {
       // the priors: S += A'A on their blocks' diagonals (in front of the constant components' unit diagonal and the scaling)
       const PriorDevice& pd = elim_path ? s->marker_schur.prior : s->marker.prior;
@@ -2113,145 +2059,65 @@ static int CovarianceMarker(rsba_solver* s, const rsba_covariance_options& co) {
   // the snapshot of the pair queries: the carved pointers and what the linearisation was told
   s->cov_mc.pc = pc; s->cov_mc.obs = obs_d; s->cov_mc.intr = intr; s->cov_mc.wrow = wrow_d; s->cov_mc.tptr = tptr_d; s->cov_mc.rows = rows_d;
   s->cov_mc.loss = loss; s->cov_mc.rcond = rcond; s->cov_mc.half_side = p.marker_side / 2; s->cov_mc.use_w = use_w;
-  s->cov_mc.elim = elim;
   return rc;
 }
 
 
 // ------------------------------------------------------------------------------------------------
 // Any pair of blocks of a covariance result (rsba_solver_covariance_blocks, rsba_solver_time_covariances; kernels and maths:
-// ba_covariance.hpp).  Local on a sharded solver: no collective.  Everything is read from the compute's snapshot.
+// ba_covariance.hpp, resolution and the plan of a query: ba_covariance_plan.hpp).  Local on a sharded solver: no collective.
+// Everything is read from the compute's snapshot.
 // ------------------------------------------------------------------------------------------------
-// One block of a pair: what it is in the result.
-struct CovBlockRef {
-  enum Kind { CONSTANT, REDUCED, TIME, POINT } kind = CONSTANT;
-  int idx = 0;    // REDUCED: position in S^-1; TIME: the time; POINT: the point (the problem's index)
-  int size = 6;
-};
-
-// RSBA_ERR_ARG: the offset starts no block, or names a block no residual references (the fixed base blocks included)
-static int CovResolve(const rsba_solver* s, int64_t off, CovBlockRef* r) {
-  const rsba_problem& p = *s->prob;
-  if (p.model != RSBA_MODEL_POINTS) {
-    const int C = p.num_cameras, T = p.num_times, nb = C + T + p.num_markers;
-    if (off < 0 || off >= 6LL * nb || off % 6) return RSBA_ERR_ARG;
-    const int blk = (int)(off / 6);
-    if (!s->cov_ref_cam[blk]) return RSBA_ERR_ARG;
-    r->size = 6;
-    if (s->cov_pos[blk] >= 0) { r->kind = CovBlockRef::REDUCED; r->idx = s->cov_pos[blk]; }
-    else if (blk >= C && blk < C + T && s->cov_mc.elim[blk - C]) { r->kind = CovBlockRef::TIME; r->idx = blk - C; }
-    else r->kind = CovBlockRef::CONSTANT;
-    return RSBA_OK;
-  }
-  const int64_t cam_end = 6LL * s->C, end = cam_end + 3LL * s->P;
-  if (off < 0 || off >= end) return RSBA_ERR_ARG;
-  if (off < cam_end) {
-    if (off % 6) return RSBA_ERR_ARG;
-    const int c = (int)(off / 6);
-    if (!s->cov_ref_cam[c]) return RSBA_ERR_ARG;
-    r->size = 6;
-    if (s->cov_pos[c] >= 0) { r->kind = CovBlockRef::REDUCED; r->idx = s->cov_pos[c]; } else r->kind = CovBlockRef::CONSTANT;
-    return RSBA_OK;
-  }
-  if ((off - cam_end) % 3) return RSBA_ERR_ARG;
-  const int j = (int)((off - cam_end) / 3);
-  if (!s->cov_ref_pt[j]) return RSBA_ERR_ARG;
-  r->size = 3;
-  const bool constant = j < (int)s->eval_const_pt.size() && s->eval_const_pt[j];
-  r->kind = constant ? CovBlockRef::CONSTANT : CovBlockRef::POINT;
-  r->idx = j;
-  return RSBA_OK;
-}
-
-// Marker chain, time-eliminating path: per time the distinct camera / marker blocks with columns that its rows touch, and every
-// row's two slots among them — the rows in the compute's order (time order, the problem's order within a time).  Built by the first
-// query after a compute, from the compute's column map.
+// Marker chain, time-eliminating path: the distinct blocks of every time and the rows' slots among them (CovPlanCrossTables), built
+// by the first query after a compute, from the compute's column map.
 static int CovMarkerTables(rsba_solver* s) {
   if (s->cov_tables && s->cov_tables_epoch == s->cov_epoch) return RSBA_OK;
-  const rsba_problem& p = *s->prob;
-  const int T = p.num_times;
-  const int64_t N = p.num_observations;
-  std::vector<int> tptr(T + 1, 0);
-  for (int64_t i = 0; i < N; ++i) tptr[p.time_index[i] + 1]++;
-  for (int t = 0; t < T; ++t) tptr[t + 1] += tptr[t];
-  std::vector<int> fill(tptr.begin(), tptr.end() - 1);
-  std::vector<int> rpos(2 * (size_t)std::max<int64_t>(N, 1), -1);
-  for (int64_t i = 0; i < N; ++i) {
-    const size_t q = (size_t)fill[p.time_index[i]]++;
-    rpos[2 * q] = p.uses_camera(i) ? s->cov_pos[p.camera_block(i)] : -1;
-    rpos[2 * q + 1] = p.uses_marker(i) ? s->cov_pos[p.marker_block(i)] : -1;
-  }
-  std::vector<int> dptr(T + 1, 0), dpos, rslot(rpos.size(), -1);
-  for (int t = 0; t < T; ++t) {
-    const size_t d0 = dpos.size();
-    for (size_t e = 2 * (size_t)tptr[t]; e < 2 * (size_t)tptr[t + 1]; ++e) {
-      if (rpos[e] < 0) continue;
-      size_t d = d0;
-      while (d < dpos.size() && dpos[d] != rpos[e]) ++d;
-      if (d == dpos.size()) dpos.push_back(rpos[e]);
-      rslot[e] = (int)(d - d0);
-    }
-    if (dpos.size() - d0 > RSBA_COV_MC_MAXBLK) return RSBA_ERR_UNSUPPORTED;
-    dptr[t + 1] = (int)dpos.size();
-  }
-  if (dpos.empty()) dpos.push_back(0);
-  int *dptr_d = nullptr, *dpos_d = nullptr, *rslot_d = nullptr;
-  auto carve = [&](CovCarve& cv) { dptr_d = cv.take<int>(dptr.size()); dpos_d = cv.take<int>(dpos.size()); rslot_d = cv.take<int>(rslot.size()); };
-  CovCarve sizing;
-  carve(sizing);
+  CovCrossTables X;
   int rc;
-  if ((rc = CovGrow(&s->cov_tables, &s->cov_tables_cap, sizing.off))) return rc;
-  CovCarve cv;
-  cv.base = s->cov_tables;
-  carve(cv);
+  if ((rc = CovPlanCrossTables(*s->prob, s->cov_layout, &X))) return rc;
+  int *dptr_d = nullptr, *dpos_d = nullptr, *rslot_d = nullptr;
+  if ((rc = CovCarveArena(&s->cov_tables, &s->cov_tables_cap, [&](CovCarve& cv) {
+         dptr_d = cv.take<int>(X.dptr.size()); dpos_d = cv.take<int>(X.dpos.size()); rslot_d = cv.take<int>(X.rslot.size());
+       })))
+    return rc;
   hipStream_t st = s->stream;
-  HIPCHK(hipMemcpyAsync(dptr_d, dptr.data(), dptr.size() * sizeof(int), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(dpos_d, dpos.data(), dpos.size() * sizeof(int), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(rslot_d, rslot.data(), rslot.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dptr_d, X.dptr.data(), X.dptr.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dpos_d, X.dpos.data(), X.dpos.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(rslot_d, X.rslot.data(), X.rslot.size() * sizeof(int), hipMemcpyHostToDevice, st));
   HIPCHK(hipStreamSynchronize(st));
   s->cov_dptr = dptr_d; s->cov_dpos = dpos_d; s->cov_rslot = rslot_d;
   s->cov_tables_epoch = s->cov_epoch;
   return RSBA_OK;
 }
 
-// The requests of one query, by kernel.  Queues them on the solver's stream: the list into cov_query, the blocks into `dst` (36
-// doubles per request slot; nullptr: a staging area behind the list, returned through *staging).  The caller synchronises.
-struct CovRequests { std::vector<CovReq> gather, marker, point; };
-
+// Queues the requests of one query on the solver's stream: the list into cov_query, the blocks into `dst` (36 doubles per request
+// slot; nullptr: a staging area behind the list, returned through *staging).  The caller synchronises.
 static int CovQueue(rsba_solver* s, const CovRequests& rq, size_t slots, double* dst, double** staging) {
-  const size_t ng = rq.gather.size(), nm = rq.marker.size(), np = rq.point.size(), nreq = ng + nm + np;
-  if (nm > 0) { int rc = CovMarkerTables(s); if (rc != RSBA_OK) return rc; }
+  const size_t ng = rq.gather.size(), nm = rq.marker.size(), np = rq.point.size(), nreq = rq.size();
+  int rc;
+  if (nm > 0 && (rc = CovMarkerTables(s))) return rc;
   CovReq* req_d = nullptr;
   double* stage_d = nullptr;
-  auto carve = [&](CovCarve& cv) { req_d = cv.take<CovReq>(nreq); stage_d = dst ? dst : cv.take<double>(36 * slots); };
-  CovCarve sizing;
-  carve(sizing);
-  int rc;
-  if ((rc = CovGrow(&s->cov_query, &s->cov_query_cap, sizing.off))) return rc;
-  CovCarve cv;
-  cv.base = s->cov_query;
-  carve(cv);
+  if ((rc = CovCarveArena(&s->cov_query, &s->cov_query_cap, [&](CovCarve& cv) { req_d = cv.take<CovReq>(nreq); stage_d = dst ? dst : cv.take<double>(36 * slots); })))
+    return rc;
   if (staging) *staging = stage_d;
   if (nreq == 0) return RSBA_OK;
-  std::vector<CovReq> all;
-  all.reserve(nreq);
-  all.insert(all.end(), rq.gather.begin(), rq.gather.end());
-  all.insert(all.end(), rq.marker.begin(), rq.marker.end());
-  all.insert(all.end(), rq.point.begin(), rq.point.end());
+  const std::vector<CovReq> all = rq.All();
   hipStream_t st = s->stream;
   HIPCHK(hipMemcpyAsync(req_d, all.data(), nreq * sizeof(CovReq), hipMemcpyHostToDevice, st));
   if (ng > 0) k_cov_gather<<<(int)std::min<size_t>(ng, 8192), 64, 0, st>>>((int)ng, req_d, s->cov_n, s->cov_sinv, s->cov_pts, stage_d);
   if (nm > 0) {
     const auto& m = s->cov_mc;
-    CovMcSnap sn{m.tptr, m.rows, m.obs, m.intr, m.pc, m.use_w ? m.wrow : nullptr, s->cov_dptr, s->cov_dpos, s->cov_rslot,
-                 m.half_side, m.rcond, m.loss, m.loss != 0.0 || m.use_w ? 1 : 0, s->cov_n};
-    CovMcSnapDist snd; static_cast<CovMcSnap&>(snd) = sn; snd.dist = s->dist_dev;
-    if (m.sub18) {
-      CovMcSnapSub sns; static_cast<CovMcSnapDist&>(sns) = snd; sns.sub18 = m.sub18;
-      if (s->dist_dev) k_cov_mc_cross<true, true><<<(int)std::min<size_t>(nm, 4096), 64, 0, st>>>((int)nm, req_d + ng, sns, s->cov_sinv, stage_d);
-      else k_cov_mc_cross<false, true><<<(int)std::min<size_t>(nm, 4096), 64, 0, st>>>((int)nm, req_d + ng, sns, s->cov_sinv, stage_d);
-    } else if (s->dist_dev) k_cov_mc_cross<true><<<(int)std::min<size_t>(nm, 4096), 64, 0, st>>>((int)nm, req_d + ng, snd, s->cov_sinv, stage_d);
-    else k_cov_mc_cross<false><<<(int)std::min<size_t>(nm, 4096), 64, 0, st>>>((int)nm, req_d + ng, sn, s->cov_sinv, stage_d);
+    const CovMcSnap sn{m.tptr, m.rows, m.obs, m.intr, m.pc, m.use_w ? m.wrow : nullptr, s->cov_dptr, s->cov_dpos, s->cov_rslot,
+                       m.half_side, m.rcond, m.loss, m.loss != 0.0 || m.use_w ? 1 : 0, s->cov_n};
+    // (the instances with masks carry the distortion pointer too, null without distortion)
+    Dispatch([&](auto D, auto Sb) {
+      typename CovMcSnapT<D.value, Sb.value>::type arg;
+      static_cast<CovMcSnap&>(arg) = sn;
+      if constexpr (D.value || Sb.value) arg.dist = s->dist_dev;
+      if constexpr (Sb.value) arg.sub18 = m.sub18;
+      k_cov_mc_cross<D.value, Sb.value><<<(int)std::min<size_t>(nm, 4096), 64, 0, st>>>((int)nm, req_d + ng, arg, s->cov_sinv, stage_d);
+    }, s->dist_dev != nullptr, m.sub18 != nullptr);
   }
   if (np > 0) {
     const auto& m = s->cov_pt;
@@ -2264,86 +2130,30 @@ static int CovQueue(rsba_solver* s, const CovRequests& rq, size_t slots, double*
 }
 
 static int CovarianceBlocks(rsba_solver* s, int64_t num_pairs, const int64_t* offsets_a, const int64_t* offsets_b, double* out) {
+  CovLayout& L = s->cov_layout;
   // every pair is resolved before anything is written or launched: one bad offset refuses the whole call
-  struct Pair { CovBlockRef a, b; };
-  std::vector<Pair> pairs((size_t)num_pairs);
-  for (int64_t i = 0; i < num_pairs; ++i) {
-    int rc;
-    if ((rc = CovResolve(s, offsets_a[i], &pairs[i].a)) != RSBA_OK || (rc = CovResolve(s, offsets_b[i], &pairs[i].b)) != RSBA_OK) return rc;
-  }
-  if (s->prob->model == RSBA_MODEL_POINTS && s->cov_pt_dev.empty() && !s->pt_perm.empty()) {
-    s->cov_pt_dev.resize(s->pt_perm.size());
-    for (size_t jn = 0; jn < s->pt_perm.size(); ++jn) s->cov_pt_dev[s->pt_perm[jn]] = (int)jn;
-  }
-  auto dev = [&](int j) { return s->cov_pt_dev.empty() ? j : s->cov_pt_dev[j]; };
-  // ONE orientation of every pair is computed (rows x cols below); the other is its transpose on output
-  struct Plan { bool zero, transposed; int rows, cols; };
-  std::vector<Plan> plan((size_t)num_pairs);
-  CovRequests rq;
-  for (int64_t i = 0; i < num_pairs; ++i) {
-    const CovBlockRef &a = pairs[i].a, &b = pairs[i].b;
-    Plan& pl = plan[i];
-    pl = Plan{false, false, a.size, b.size};
-    const int slot = (int)i;
-    if (a.kind == CovBlockRef::CONSTANT || b.kind == CovBlockRef::CONSTANT) { pl.zero = true; continue; }
-    if (a.kind == CovBlockRef::REDUCED && b.kind == CovBlockRef::REDUCED) { rq.gather.push_back(CovReq{a.idx, b.idx, COV_REQ_SINV, slot}); continue; }
-    if (a.kind == CovBlockRef::POINT && b.kind == CovBlockRef::POINT) {
-      if (a.idx == b.idx) { rq.gather.push_back(CovReq{a.idx, a.idx, COV_REQ_POINT, slot}); continue; }
-      pl.transposed = a.idx > b.idx;
-      rq.point.push_back(CovReq{dev(std::min(a.idx, b.idx)), dev(std::max(a.idx, b.idx)), COV_REQ_POINT_POINT, slot});
-      continue;
-    }
-    if (a.kind == CovBlockRef::TIME && b.kind == CovBlockRef::TIME) {
-      pl.transposed = a.idx > b.idx;
-      rq.marker.push_back(CovReq{std::min(a.idx, b.idx), std::max(a.idx, b.idx), COV_REQ_TIME_TIME, slot});
-      continue;
-    }
-    // a reduced block with an eliminated one: computed as (time, x) / (camera, point)
-    const bool a_reduced = a.kind == CovBlockRef::REDUCED;
-    const CovBlockRef &x = a_reduced ? a : b, &e = a_reduced ? b : a;
-    if (e.kind == CovBlockRef::TIME) {
-      pl.transposed = a_reduced; pl.rows = 6; pl.cols = 6;
-      rq.marker.push_back(CovReq{e.idx, x.idx, COV_REQ_TIME_X, slot});
-    } else {
-      pl.transposed = !a_reduced; pl.rows = 6; pl.cols = 3;
-      rq.point.push_back(CovReq{x.idx, dev(e.idx), COV_REQ_CAM_POINT, slot});
-    }
-  }
+  std::vector<CovPair> pairs;
+  int rc;
+  if ((rc = CovResolvePairs(L, num_pairs, offsets_a, offsets_b, &pairs))) return rc;
+  if (L.points() && L.pt_dev.empty() && !s->pt_perm.empty()) L.BuildPointDev(s->pt_perm);
+  const CovQueryPlan Q = CovPlanPairs(L, pairs);
   double* stage_d = nullptr;
-  int rc = CovQueue(s, rq, (size_t)num_pairs, nullptr, &stage_d);
-  if (rc != RSBA_OK) return rc;
+  if ((rc = CovQueue(s, Q.rq, (size_t)num_pairs, nullptr, &stage_d))) return rc;
   std::vector<double> h(36 * (size_t)num_pairs, 0.0);
-  if (!rq.gather.empty() || !rq.marker.empty() || !rq.point.empty())
-    HIPCHK(hipMemcpy(h.data(), stage_d, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-  for (int64_t i = 0; i < num_pairs; ++i) {
-    const Plan& pl = plan[i];
-    double* o = out + 36 * (size_t)i;
-    const double* g = h.data() + 36 * (size_t)i;
-    const int na = pairs[i].a.size, nb = pairs[i].b.size;
-    for (int e = 0; e < 36; ++e) o[e] = 0.0;
-    if (pl.zero) continue;
-    for (int r = 0; r < na; ++r)
-      for (int c = 0; c < nb; ++c) o[r * nb + c] = pl.transposed ? g[c * pl.cols + r] : g[r * pl.cols + c];
-  }
+  if (Q.rq.size() > 0) HIPCHK(hipMemcpy(h.data(), stage_d, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+  CovUnpackPairs(Q, h.data(), out);
   return RSBA_OK;
 }
 
 // T x 36 marginals of the time blocks, formed once per compute into cov_times (zeros for constant and unreferenced times): the
 // request list {(t, t)} — on the dense path the diagonal blocks of S^-1.
 static int CovarianceTimes(rsba_solver* s, double* out) {
-  const rsba_problem& p = *s->prob;
-  const int C = p.num_cameras, T = p.num_times;
+  const int T = s->cov_layout.T;
   if (!(s->cov_times && s->cov_times_epoch == s->cov_epoch)) {
     int rc;
     if ((rc = CovGrow(&s->cov_times, &s->cov_times_cap, 36 * (size_t)std::max(T, 1)))) return rc;
     HIPCHK(hipMemsetAsync(s->cov_times, 0, 36 * (size_t)std::max(T, 1) * sizeof(double), s->stream));
-    CovRequests rq;
-    for (int t = 0; t < T; ++t) {
-      if (!s->cov_ref_cam[C + t]) continue;
-      if (s->cov_pos[C + t] >= 0) rq.gather.push_back(CovReq{s->cov_pos[C + t], s->cov_pos[C + t], COV_REQ_SINV, t});
-      else if (s->cov_mc.elim[t]) rq.marker.push_back(CovReq{t, t, COV_REQ_TIME_TIME, t});
-    }
-    if ((rc = CovQueue(s, rq, 0, s->cov_times, nullptr)) != RSBA_OK) return rc;
+    if ((rc = CovQueue(s, CovPlanTimes(s->cov_layout), 0, s->cov_times, nullptr)) != RSBA_OK) return rc;
     HIPCHK(hipStreamSynchronize(s->stream));
     s->cov_times_epoch = s->cov_epoch;
   }
@@ -2360,13 +2170,6 @@ static int EvalUpload(T** dst, const std::vector<T>& v) {
   if (rc != RSBA_OK) return rc;
   if (!v.empty() && hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return RSBA_ERR_HIP;
   return RSBA_OK;
-}
-
-static std::vector<EvalMarkerRow> EvalMarkerRows(const rsba_problem& p) {
-  std::vector<EvalMarkerRow> rows((size_t)p.num_observations);
-  for (int64_t i = 0; i < p.num_observations; ++i)
-    rows[i] = EvalMarkerRow{p.uses_camera(i) ? p.camera_block(i) : -1, p.time_block(i), p.uses_marker(i) ? p.marker_block(i) : -1, p.camera_index[i]};
-  return rows;
 }
 
 // The tables of the first call.  They depend on the problem's index arrays and on the constant flags AS THE SOLVER TOOK THEM at
@@ -2442,12 +2245,7 @@ static int EvaluateOnDevice(rsba_solver* s, bool apply_loss, double* cost, doubl
     if (s->num_priors > 0) prior_pe = cv.take<double>(s->num_priors);
     if (comm) pay = cv.take<double>(7 * (size_t)C + 1);
   };
-  CovCarve sizing;
-  carve(sizing);
-  if ((rc = CovGrow(&e.arena, &e.arena_cap, sizing.off))) return rc;
-  CovCarve cv;
-  cv.base = e.arena;
-  carve(cv);
+  if ((rc = CovCarveArena(&e.arena, &e.arena_cap, carve))) return rc;
   hipStream_t st = s->stream;
   // the current device state: the last run's accepted point, or the uploaded / set start before any run
   if (points) {
@@ -2606,12 +2404,7 @@ static int JacobianOnDevice(rsba_solver* s, bool apply_loss, double* values) {
     posec = cv.take<double>((size_t)CC_STRIDE * (points ? C : nb));
     values_d = cv.take<double>(nnz);
   };
-  CovCarve sizing;
-  carve(sizing);
-  if ((rc = CovGrow(&e.arena, &e.arena_cap, sizing.off))) return rc;
-  CovCarve cv;
-  cv.base = e.arena;
-  carve(cv);
+  if ((rc = CovCarveArena(&e.arena, &e.arena_cap, carve))) return rc;
   hipStream_t st = s->stream;
   if (points) {
     const double* cam = s->has_run ? s->cam[s->cur] : s->cam0;
@@ -3112,49 +2905,16 @@ int rsba_solver_covariance_block(const rsba_solver* s, int64_t offset_a, int64_t
   if (!s || !out) return RSBA_ERR_ARG;
   if (!s->cov_valid) return RSBA_ERR_ARG;
   rsba::CommScope device_turn(s->comm.get());   // (local, no collective; a loopback rank copies on its turn only)
-  const size_t n = (size_t)s->cov_n;
-  auto copy6 = [&](int pa, int pb) {
-    if (pa < 0 || pb < 0) { memset(out, 0, 36 * sizeof(double)); return RSBA_OK; }   // a constant block
-    if (hipSetDevice(s->device) != hipSuccess) return RSBA_ERR_HIP;
-    return hipMemcpy2D(out, 6 * sizeof(double), s->cov_sinv + (size_t)pa * n + pb, n * sizeof(double), 6 * sizeof(double), 6, hipMemcpyDeviceToHost) == hipSuccess
-               ? RSBA_OK : RSBA_ERR_HIP;
-  };
-  if (s->prob->model != RSBA_MODEL_POINTS) {
-    // [C | T | M] x 6: camera and marker blocks; time blocks are not offered (eliminated on one path)
-    const rsba_problem& p = *s->prob;
-    const int C = p.num_cameras, T = p.num_times, nb = C + T + p.num_markers;
-    int blk[2];
-    const int64_t offs[2] = {offset_a, offset_b};
-    for (int e = 0; e < 2; ++e) {
-      if (offs[e] < 0 || offs[e] >= 6LL * nb || offs[e] % 6) return RSBA_ERR_ARG;
-      blk[e] = (int)(offs[e] / 6);
-    }
-    for (int e = 0; e < 2; ++e) if (blk[e] >= C && blk[e] < C + T) return RSBA_ERR_UNSUPPORTED;
-    for (int e = 0; e < 2; ++e) if (!s->cov_ref_cam[blk[e]]) return RSBA_ERR_ARG;
-    return copy6(s->cov_pos[blk[0]], s->cov_pos[blk[1]]);
-  }
-  const rsba_problem& p = *s->prob;
-  const int64_t cam_end = 6LL * s->C, end = cam_end + 3LL * s->P;
-  // -> (is camera, index); RSBA_ERR_ARG for an offset that starts no block or names a block no residual references
-  auto block = [&](int64_t off, bool* is_cam, int* idx) {
-    if (off < 0 || off >= end) return RSBA_ERR_ARG;
-    if (off < cam_end) {
-      if (off % 6) return RSBA_ERR_ARG;
-      *is_cam = true; *idx = (int)(off / 6);
-      return s->cov_ref_cam[*idx] ? RSBA_OK : RSBA_ERR_ARG;
-    }
-    if ((off - cam_end) % 3) return RSBA_ERR_ARG;
-    *is_cam = false; *idx = (int)((off - cam_end) / 3);
-    return s->cov_ref_pt[*idx] ? RSBA_OK : RSBA_ERR_ARG;
-  };
-  bool ca = false, cb = false;
-  int ia = 0, ib = 0, rc;
-  if ((rc = block(offset_a, &ca, &ia)) != RSBA_OK || (rc = block(offset_b, &cb, &ib)) != RSBA_OK) return rc;
+  // which blocks, and every refusal in its order: CovLayout::Single (time blocks, camera x point and cross-point blocks are not offered)
+  rsba::CovSingle q;
+  if (int rc = s->cov_layout.Single(offset_a, offset_b, &q)) return rc;
+  if (q.what == rsba::CovSingle::ZEROS) { memset(out, 0, 36 * sizeof(double)); return RSBA_OK; }   // a constant block
   if (hipSetDevice(s->device) != hipSuccess) return RSBA_ERR_HIP;
-  if (ca && cb) return copy6(s->cov_pos[ia], s->cov_pos[ib]);
-  if (ca || cb || ia != ib) return RSBA_ERR_UNSUPPORTED;   // camera x point and cross-point blocks
-  // (a constant point's marginal is written as zeros by k_cov_points)
-  return hipMemcpy(out, s->cov_pts + 9 * (size_t)ia, 9 * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess ? RSBA_OK : RSBA_ERR_HIP;
+  const size_t n = (size_t)s->cov_n;
+  const hipError_t e = q.what == rsba::CovSingle::SINV
+      ? hipMemcpy2D(out, 6 * sizeof(double), s->cov_sinv + (size_t)q.a * n + q.b, n * sizeof(double), 6 * sizeof(double), 6, hipMemcpyDeviceToHost)
+      : hipMemcpy(out, s->cov_pts + 9 * (size_t)q.a, 9 * sizeof(double), hipMemcpyDeviceToHost);
+  return e == hipSuccess ? RSBA_OK : RSBA_ERR_HIP;
 }
 
 int rsba_solver_point_covariances(const rsba_solver* s, double* out) {
