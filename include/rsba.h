@@ -368,7 +368,8 @@ int rsba_marker_poses_from_corners(int64_t n, const double* corners /* 8n */, co
  * RSBA_ERR_UNSUPPORTED.  Host code. */
 int rsba_problem_initial_time_poses(rsba_problem* p, int32_t* num_missing_or_null);
 /* The start of a WHOLE rig from its detections, on the GPU: replaces rsba_problem_initial_time_poses + rsba_problem_initial_camera_poses
- * where camera 0 does not see every shot.  Marker blocks are inputs (the board geometry), as for those two.
+ * where camera 0 does not see every shot.  Marker blocks are inputs (the board geometry), as for those two; rsba_problem_start_scene
+ * below fits them too.
  *   block resection   one pose block (a time or a camera) is fitted to ALL the detections that name it, the other two blocks of each
  *                     detection held: the minimiser of their marker-chain reprojection cost (8 residuals each, through the model's functors,
  *                     base blocks the identity, the problem's distortion coefficients applied) — ceres::Solve with every other block
@@ -395,6 +396,27 @@ int rsba_problem_start_rig(rsba_problem* p, const uint8_t* known_blocks /* C + T
                            int32_t* num_missing_times, int32_t* num_missing_cameras,
                            int32_t* block_status /* C + T, or NULL */,
                            double* block_rms /* C + T, or NULL */);
+/* rsba_problem_start_rig for a scene whose board geometry nobody measured (markers on a wall, a floor, a folded board): the marker blocks
+ * are a third kind of block to be fitted, by the same block resection.
+ *   a marker's fit    the points entering the fitted transform are the raw corners (+-half, +-half, 0), the known transform behind it is
+ *                     camera o time (the time alone for the base camera); a candidate is the detection's own fit D = camera o time o marker
+ *                     solved for the marker.  A marker is a block per 256-lane workgroup, as a camera.
+ *   propagation       known_blocks flags C cameras, T times, then M markers; the base camera is always known, and so is marker 0 of
+ *                     RSBA_MODEL_MARKER_CHAIN (the base marker, the identity; it gets status 4).  In RSBA_MODEL_MARKER_CHAIN_TEST2 marker 0
+ *                     is an ordinary block, known only if flagged — with nothing flagged that model has no gauge and nothing is reached.
+ *                     A detection counts for a block only when BOTH its other blocks are known.  Rounds go time, marker, camera in turn; a
+ *                     round that would fit nothing is not launched, three empty rounds in a row end the propagation.  Then refine_sweeps
+ *                     passes: all fitted times, then markers, then cameras.  With every marker flagged the call launches and computes
+ *                     what rsba_problem_start_rig does, bit for bit.
+ * The gauge is the base camera's frame and, at every time, the base marker's: a scene in which the base camera never sees the base marker
+ * (or a flagged one) has no first round, and every block comes back unreached.  A planar board seen by few cameras has a mirrored pose
+ * that is a true local minimum of the whole problem; the candidates' block cost resolves it where a block has enough detections, not
+ * always.  Statuses, RMS, errors and RSBA_RUNPROF as for rsba_problem_start_rig, over C + T + M blocks. */
+int rsba_problem_start_scene(rsba_problem* p, const uint8_t* known_blocks /* C + T + M, or NULL */,
+                             int32_t refine_sweeps, int32_t device /* -1 = current */,
+                             int32_t* num_missing_times, int32_t* num_missing_cameras, int32_t* num_missing_markers,
+                             int32_t* block_status /* C + T + M, or NULL */,
+                             double* block_rms /* C + T + M, or NULL */);
 
 void rsba_problem_free(rsba_problem* p);
 

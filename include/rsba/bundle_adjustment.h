@@ -108,6 +108,21 @@ class BALProblem {
       return -1;
     return missing_times + missing_cameras;
   }
+  // the start of a scene whose board geometry is not known (rsba_problem_start_scene): StartRig with the marker blocks fitted too, from the
+  // base camera and the base marker alone.  known (optional): num_cameras() + num_times() + num_markers flags; status / rms (optional) are
+  // resized to that many entries.  Returns the number of blocks left without a value (status 2 or 3), -1 when the call itself fails.
+  int StartScene(const std::vector<uint8_t>* known = nullptr, int refine_sweeps = 1, int device = -1, std::vector<int32_t>* status = nullptr,
+                 std::vector<double>* rms = nullptr) {
+    const size_t nb = (size_t)num_cameras() + (size_t)num_times() + (size_t)rsba_problem_num_markers(p_);
+    if (known && known->size() != nb) return -1;
+    if (status) status->assign(nb, 0);
+    if (rms) rms->assign(nb, 0.0);
+    int32_t missing_times = 0, missing_cameras = 0, missing_markers = 0;
+    if (rsba_problem_start_scene(p_, known ? known->data() : nullptr, refine_sweeps, device, &missing_times, &missing_cameras, &missing_markers,
+                                 status ? status->data() : nullptr, rms ? rms->data() : nullptr) != RSBA_OK)
+      return -1;
+    return missing_times + missing_cameras + missing_markers;
+  }
 
   double* mutable_cameras() { return rsba_problem_parameters(p_); }
   double* mutable_points() { return rsba_problem_parameters(p_) + 6 * num_cameras(); }

@@ -37,7 +37,7 @@ EXPORTS = [
     "rsba_problem_set_observation_weights", "rsba_problem_observation_weights", "rsba_solver_set_observation_weights",
     "rsba_problem_set_parameter_subset_constant", "rsba_problem_parameter_subset_constant", "rsba_problem_set_distortion", "rsba_problem_distortion", "rsba_read_intrinsics_xml_dist", "rsba_undistort_points",
     "rsba_problem_set_block_prior", "rsba_problem_block_prior", "rsba_problem_num_block_priors", "rsba_solver_set_block_prior",
-    "rsba_marker_pose_from_corners", "rsba_marker_poses_from_corners", "rsba_problem_initial_time_poses", "rsba_problem_start_rig",
+    "rsba_marker_pose_from_corners", "rsba_marker_poses_from_corners", "rsba_problem_initial_time_poses", "rsba_problem_start_rig", "rsba_problem_start_scene",
 ]
 _SYMBOLS = EXPORTS   # (every symbol of include/rsba.h that load() checks)
 
@@ -195,6 +195,7 @@ def load():
     lib.rsba_marker_poses_from_corners.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_int32] + [C.c_void_p] * 3
     lib.rsba_problem_initial_time_poses.argtypes = [C.c_void_p, C.c_void_p]
     lib.rsba_problem_start_rig.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4
+    lib.rsba_problem_start_scene.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5
     _LIB = lib
     return lib
 
@@ -424,6 +425,24 @@ class Problem:
         _chk(load().rsba_problem_start_rig(self.h, None if k is None else _vp(k), int(refine_sweeps), int(device), C.byref(mt), C.byref(mc),
                                            _vp(status), _vp(rms)), "rsba_problem_start_rig")
         return int(mt.value), int(mc.value), status, rms
+
+    def start_scene(self, known=None, refine_sweeps=1, device=-1):
+        """Marker-chain models: start_rig for a scene whose board geometry is not known (rsba_problem_start_scene): the marker blocks are
+        fitted by block resection too, in rounds of times, markers, cameras from the known blocks.  known: C + T + M flags (cameras, times,
+        markers) of blocks that keep their values, or None (the base camera, and the base marker of MODEL_MARKER_CHAIN).  A detection
+        counts for a block only when both its other blocks are known.  Returns (missing_times, missing_cameras, missing_markers,
+        status C + T + M, rms C + T + M) with start_rig's statuses; 4 also for the base marker."""
+        nb = self.num_cameras + (self.num_times + self.num_markers if self.model != MODEL_POINTS else 0)
+        k = None
+        if known is not None:
+            k = np.ascontiguousarray(known, np.uint8).reshape(-1)
+            if k.size != nb:
+                raise ValueError("start_scene: one flag per camera, time and marker block expected")
+        mt, mc, mm = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        status, rms = np.zeros(nb, np.int32), np.zeros(nb)
+        _chk(load().rsba_problem_start_scene(self.h, None if k is None else _vp(k), int(refine_sweeps), int(device), C.byref(mt), C.byref(mc),
+                                             C.byref(mm), _vp(status), _vp(rms)), "rsba_problem_start_scene")
+        return int(mt.value), int(mc.value), int(mm.value), status, rms
 
     def detection_poses(self, device=-1):
         """Marker-chain models: (poses N x 6, rms N, status N) of every observation's own single-marker fit, one batch on the GPU over

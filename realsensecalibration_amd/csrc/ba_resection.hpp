@@ -1,12 +1,14 @@
-// Block resection: ONE pose block of a marker-chain problem (a time or a camera) fitted to all the detections that name it, the other
-// two blocks of each detection held at their current values — ceres::Solve with every other block constant, one block at a time, and the
-// step of the whole-rig start (rsba_problem_start_rig; the rounds are planned in ba_rig_start_plan.hpp).
+// Block resection: ONE pose block of a marker-chain problem (a time, a camera or a marker) fitted to all the detections that name it, the
+// other two blocks of each detection held at their current values — ceres::Solve with every other block constant, one block at a time, and
+// the step of the whole-rig start (rsba_problem_start_rig; the rounds are planned in ba_rig_start_plan.hpp) and of the scene start, which
+// fits the marker blocks too (rsba_problem_start_scene; ba_scene_start_plan.hpp).
 //
 //   objective   the marker-chain reprojection cost of the block's usable detections, eight residuals each, through the functor the model
 //               selects: corner --marker--> --time--> --camera--> projection, a base block (camera 0; marker 0 of RSBA_MODEL_MARKER_CHAIN)
 //               acting as the identity, ProjectCorner<true> with the detecting camera's coefficients (zeros: the pinhole camera)
 //   usable      a detection whose OTHER variable block (a time's detecting camera, a camera's time) is flagged in known[]; marker blocks are
-//               inputs and always known
+//               inputs and always known.  The scene start flags the marker blocks too, known[C + T + M]:
+//               a detection is usable for a block when BOTH its other blocks are flagged, and a marker block is fitted like the others
 //   rows        a pose block's rule of ba_math.hpp, as MarkerPoseLinearise applies it to a single marker: with Q the sensitivity of the
 //               residual to the point leaving the fitted transform, d r / d t = Q, d r / d w = [w* x Q_i] Jl
 //   step        MarkerPoseMinimise (ba_marker_pose.hpp): FitMarkerPose's loop, step, accept / reject / lambda and convergence rule, with its
@@ -35,6 +37,7 @@ namespace rsba {
 enum {
   RESECT_TIME = 0,
   RESECT_CAMERA = 1,
+  RESECT_MARKER = 2,         // the scene start only
   BLOCK_CONVERGED = 0,       // MARKER_POSE_CONVERGED
   BLOCK_ITERATION_CAP = 1,   // MARKER_POSE_ITERATION_CAP
   BLOCK_DEGENERATE = 2,      // usable detections, but no candidate with a finite cost and every point in front: the block keeps its bits
@@ -60,12 +63,13 @@ struct ResectionArgs {
   const double* own_rms;           // [N]
   const int32_t* own_status;       // [N]
   double* parameters;
-  uint8_t* known;                  // [C + T]
+  uint8_t* known;                  // [C + T]; the scene start: [C + T + M] and one more that is never set; so the three arrays below
   int32_t* status;                 // [C + T]
   double* rms;                     // [C + T]
   int32_t* iterations;             // [C + T]
-  const int* blocks;               // the launch's blocks: time or camera indices
+  const int* blocks;               // the launch's blocks: time, camera or marker indices
   int num_blocks;
+  int markers_flagged;             // the host: 0: marker blocks are inputs, always known (the whole-rig start); 1: known[C + T + m] says so
 };
 
 // Rotation matrix (row-major) and translation of a pose block as the functors apply it (CameraConstants: the first-order form at
@@ -119,14 +123,34 @@ RSBA_HD void ObservationBlocks(const ResectionArgs& a, int o, const double** cam
 
 // What one detection contributes that does not move with the fitted pose: the four points ENTERING the fitted transform and the known
 // transform behind it.  A time: the corners through the marker block, then the camera block behind (absent for the base camera).  A camera:
-// the corners through marker and time, nothing behind.
+// the corners through marker and time, nothing behind.  A marker: the raw corners, camera o time behind (the time alone for the base camera).
 struct ResectionFrame {
   double x[12];
   double Ro[9], to[3];
   bool outer;
 };
 
+// (kMarkerToo = false: the caller never asks for a marker, and the instance carries no code of that kind)
+template <bool kMarkerToo = true>
 RSBA_HD void ResectionFrameOf(int which, const double* cam6, const double* time6, const double* marker6, double half, ResectionFrame* f) {
+  if (kMarkerToo && which == RESECT_MARKER) {
+    RSBA_UNROLL
+    for (int j = 0; j < 4; ++j) {
+      f->x[3 * j] = (j == 1 || j == 2) ? half : -half; f->x[3 * j + 1] = j < 2 ? half : -half; f->x[3 * j + 2] = 0.0;
+    }
+    f->outer = true;
+    if (cam6) {   // Ro = Rc Rt, to = Rc tt + tc
+      double Rc[9], tc[3], Rt[9], tt[3], s[3];
+      PoseRotationTranslation(cam6, Rc, tc);
+      PoseRotationTranslation(time6, Rt, tt);
+      Mat3Mul(Rc, Rt, f->Ro);
+      Mat3Vec(Rc, tt, s);
+      f->to[0] = s[0] + tc[0]; f->to[1] = s[1] + tc[1]; f->to[2] = s[2] + tc[2];
+    } else {
+      PoseRotationTranslation(time6, f->Ro, f->to);
+    }
+    return;
+  }
   double Rm[9], tm[3];
   PoseRotationTranslation(marker6, Rm, tm);
   double Rt[9], tt[3];
@@ -202,12 +226,31 @@ RSBA_HD void ResectionAccumulate(const double* cc, const ResectionFrame& f, cons
 }
 
 // The candidate a detection gives for the fitted block: its own-fit pose D (marker frame -> detecting camera's frame) composed with its two
-// known blocks, D = camera o time o marker solved for the time or for the camera.
+// known blocks, D = camera o time o marker solved for the time, for the camera or for the marker.
+template <bool kMarkerToo = true>
 RSBA_HD void ResectionCandidate(int which, const double* own6, const double* cam6, const double* time6, const double* marker6, double pose[6]) {
   double Rd[9], td[3], Rm[9], tm[3];
   PoseRotationTranslation(own6, Rd, td);
-  PoseRotationTranslation(marker6, Rm, tm);
   double R[9], t[3];
+  if (kMarkerToo && which == RESECT_MARKER) {
+    double Rc[9], tc[3], Rt[9], tt[3], Rct[9], s[3], d[3];
+    PoseRotationTranslation(cam6, Rc, tc);
+    PoseRotationTranslation(time6, Rt, tt);
+    // R_m = (R_c R_t)' R_d,  t_m = (R_c R_t)' (t_d - R_c t_t - t_c)
+    Mat3Mul(Rc, Rt, Rct);
+    RSBA_UNROLL
+    for (int i = 0; i < 3; ++i) {
+      RSBA_UNROLL
+      for (int j = 0; j < 3; ++j) R[3 * i + j] = Rct[i] * Rd[j] + Rct[3 + i] * Rd[3 + j] + Rct[6 + i] * Rd[6 + j];
+    }
+    Mat3Vec(Rc, tt, s);
+    d[0] = td[0] - s[0] - tc[0]; d[1] = td[1] - s[1] - tc[1]; d[2] = td[2] - s[2] - tc[2];
+    Mat3TransposedVec(Rct, d, t);
+    RotationMatrixToRvec(R, pose);
+    pose[3] = t[0]; pose[4] = t[1]; pose[5] = t[2];
+    return;
+  }
+  PoseRotationTranslation(marker6, Rm, tm);
   if (which == RESECT_TIME) {
     double Rc[9], tc[3], RcD[9], d[3], e[3], s[3];
     PoseRotationTranslation(cam6, Rc, tc);
@@ -246,14 +289,30 @@ struct SerialLanes {
   RSBA_HD void ArgMin(double*, int*) const {}
 };
 
-// The fit of one block (a.blocks[] entry `block`: a time or a camera index).  Every lane of `lanes` calls it with the same arguments and
-// leaves with the same result; the lane whose first() is 0 writes it.
-template <class Lanes>
-RSBA_HD void ResectBlock(const ResectionArgs& a, int which, int block, Lanes& lanes) {
-  const int pb = which == RESECT_TIME ? a.C + block : block;   // the block's place in [C | T | M]
+// The fit of one block (a.blocks[] entry `block`: a time, a camera or a marker index).  Every lane of `lanes` calls it with the same
+// arguments and leaves with the same result; the lane whose first() is 0 writes it.  kKinds says which kinds the caller can ask for, so
+// that a kernel carries the code of its own kinds only:
+//   RESECT_ANY              the host: three kinds, markers_flagged read
+//   RESECT_TIME_OR_CAMERA   the two kernels BOTH starts launch for times and cameras — the whole-rig start's code as it was before markers
+//                           were fitted, instruction for instruction, so that start keeps its bits and the scene start with every marker
+//                           flagged gives the same ones.  markers_flagged is not read: the scene start hides a detection whose marker is
+//                           not known behind the index of a flag that is never set (k_scene_mask_index below)
+//   RESECT_MARKER           the marker launches
+enum { RESECT_ANY = -1, RESECT_TIME_OR_CAMERA = -2 };
+template <int kKinds, class Lanes>
+RSBA_HD void ResectBlockOf(const ResectionArgs& a, int which, int block, Lanes& lanes) {
+  constexpr bool kMarkerToo = kKinds != RESECT_TIME_OR_CAMERA;
+  const bool marker = kKinds == RESECT_MARKER || (kKinds == RESECT_ANY && which == RESECT_MARKER);
+  const int kind = marker ? RESECT_MARKER : which;
+  const bool flagged = kKinds == RESECT_ANY && a.markers_flagged != 0;
+  const int pb = marker ? a.C + a.T + block : which == RESECT_TIME ? a.C + block : block;   // the block's place in [C | T | M]
   const int lo = a.list_ptr[block], hi = a.list_ptr[block + 1];
   const bool refit = a.known[pb] != 0;
-  auto usable = [&](int o) { return a.known[which == RESECT_TIME ? a.camera_index[o] : a.C + a.time_index[o]] != 0; };
+  auto usable = [&](int o) {
+    if (marker) return a.known[a.camera_index[o]] != 0 && a.known[a.C + a.time_index[o]] != 0;
+    const bool other = a.known[which == RESECT_TIME ? a.camera_index[o] : a.C + a.time_index[o]] != 0;
+    return flagged ? other && a.known[a.C + a.T + a.marker_index[o]] != 0 : other;
+  };
 
   double counted[1] = {0.0};   // the usable detections: how many
   for (int k = lo + lanes.first(); k < hi; k += lanes.stride()) counted[0] += usable(a.list_obs[k]) ? 1.0 : 0.0;
@@ -273,7 +332,7 @@ RSBA_HD void ResectBlock(const ResectionArgs& a, int which, int block, Lanes& la
       const double *cam, *tim, *mar;
       ObservationBlocks(a, o, &cam, &tim, &mar);
       ResectionFrame f;
-      ResectionFrameOf(which, cam, tim, mar, a.half, &f);
+      ResectionFrameOf<kMarkerToo>(kind, cam, tim, mar, a.half, &f);
       const int c = a.camera_index[o];
       double k5[5], c8[8];
       RSBA_UNROLL
@@ -322,7 +381,7 @@ RSBA_HD void ResectBlock(const ResectionArgs& a, int which, int block, Lanes& la
       double own[6], cand[6], c0, A[21], g[6], z;
       RSBA_UNROLL
       for (int q = 0; q < 6; ++q) own[q] = a.own_pose[6 * (size_t)idx + q];
-      ResectionCandidate(which, own, cam, tim, mar, cand);
+      ResectionCandidate<kMarkerToo>(kind, own, cam, tim, mar, cand);
       bool fine = true;
       RSBA_UNROLL
       for (int q = 0; q < 6; ++q) fine = fine && FiniteValue(cand[q]);
@@ -353,6 +412,11 @@ RSBA_HD void ResectBlock(const ResectionArgs& a, int which, int block, Lanes& la
     a.rms[pb] = -1.0;
     a.iterations[pb] = 0;
   }
+}
+
+template <class Lanes>
+RSBA_HD void ResectBlock(const ResectionArgs& a, int which, int block, Lanes& lanes) {
+  ResectBlockOf<RESECT_ANY>(a, which, block, lanes);
 }
 
 #if defined(__HIPCC__)
@@ -422,14 +486,26 @@ struct DeviceLanes {
 
 // kWorkgroup = false: a block per wavefront, four to a workgroup (times: tens of detections each); true: a block per workgroup (cameras:
 // tens of thousands).  A wavefront past the launch's last block leaves at once; inside a workgroup-wide block every barrier is reached by
-// all four wavefronts, since they hold the same sums and take the same branches.
-template <bool kWorkgroup>
+// all four wavefronts, since they hold the same sums and take the same branches.  kMarker = true: the scene start's marker launches — a
+// marker, like a camera, is a block per workgroup (in a large rig it is named by up to C x T detections).
+template <bool kWorkgroup, bool kMarker = false>
 __global__ __launch_bounds__(256) void k_block_resection(ResectionArgs a, int which) {
   __shared__ double lds[kWorkgroup ? 4 * kResectionSums : 1];
   const int i = kWorkgroup ? (int)blockIdx.x : (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
   if (i >= a.num_blocks) return;
   DeviceLanes<kWorkgroup> lanes{lds};
-  ResectBlock(a, which, a.blocks[i], lanes);
+  ResectBlockOf<kMarker ? RESECT_MARKER : RESECT_TIME_OR_CAMERA>(a, which, a.blocks[i], lanes);
+}
+
+// The scene start's rule for a time or a camera block — a detection counts only when its marker is known too — without another
+// instruction in the two kernels above: before such a launch, out[o] is index[o] (the camera index for a time launch, the time index for
+// a camera launch) where the detection's marker is flagged, and `hidden` where it is not — the index at which those kernels find the
+// one flag of known[] that no launch sets.  They read an index further only for a usable detection.  A thread per detection.
+__global__ __launch_bounds__(256) void k_scene_mask_index(int64_t n, const int32_t* index, const int32_t* marker_index, const uint8_t* marker_known,
+                                                          int32_t hidden, int32_t* out) {
+  const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (o >= n) return;
+  out[o] = marker_known[marker_index[o]] != 0 ? index[o] : hidden;
 }
 #endif
 

@@ -36,6 +36,7 @@
 #include "ba_marker_schur.hpp"
 #include "ba_resection.hpp"
 #include "ba_rig_start_plan.hpp"
+#include "ba_scene_start_plan.hpp"
 #include "ba_point_kernels.hpp"
 #include "ba_cholesky_large.hpp"
 #include "ba_cholesky_multi.hpp"
@@ -3221,8 +3222,173 @@ int rsba_marker_poses_from_corners(int64_t n, const double* corners, const int32
   return ok ? RSBA_OK : RSBA_ERR_HIP;
 }
 
-// The whole-rig start: every detection's own fit (k_marker_pose), then the launches of the plan (ba_rig_start_plan.hpp) on the default
-// stream, one after the other: a launch reads the flags and blocks the one before it wrote.
+}  // extern "C"
+
+namespace {
+
+// The whole-rig start and the scene start: every detection's own fit (k_marker_pose), then the launches of the plan (ba_rig_start_plan.hpp,
+// ba_scene_start_plan.hpp) on the default stream, one after the other: a launch reads the flags and blocks the one before it wrote.
+// kScene = false launches what rsba_problem_start_rig always launched: times and cameras, flags over C + T.  kScene = true: markers are a
+// third kind of block with a kernel instance of their own, flags, statuses and RMS over C + T + M; times and cameras go through the same
+// two kernel instances as without, so with every marker flagged the call computes the whole-rig start's bits.  status and rms come in with the plan's initial values.
+template <bool kScene, class Plan>
+int RunStartPlan(rsba_problem* p, const Plan& plan, int32_t device, const char* name, std::vector<int32_t>* status_io, std::vector<double>* rms_io) {
+  const int C = p->num_cameras, T = p->num_times, M = p->num_markers;
+  const size_t N = (size_t)p->num_observations, nb = (size_t)C + T + (kScene ? (size_t)M : 0), all = (size_t)C + T + M;
+  const bool with_dist = p->has_distortion();
+  std::vector<int32_t>& status = *status_io;
+  std::vector<double>& rms = *rms_io;
+  std::vector<int32_t> iterations(nb, 0);
+  bool ok = true;
+  if (N == 0 || plan.launches.empty()) return RSBA_OK;
+  if (device >= 0 && hipSetDevice(device) != hipSuccess) return RSBA_ERR_HIP;
+  char* d_all = nullptr;
+  if (hipMalloc((void**)&d_all, plan.buffers.total) != hipSuccess) return RSBA_ERR_HIP;
+  const auto& bf = plan.buffers;
+  auto up = [&](size_t off, const void* src, size_t bytes) {
+    if (ok && bytes > 0) ok = hipMemcpy(d_all + off, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+  };
+  up(bf.observations, p->observations.data(), 8 * N * sizeof(double));
+  up(bf.intrinsics, p->intrinsics.data(), 4 * (size_t)C * sizeof(double));
+  if (with_dist) up(bf.distortion, p->distortion.data(), 5 * (size_t)C * sizeof(double));
+  up(bf.parameters, p->parameters.data(), 6 * all * sizeof(double));
+  up(bf.block_rms, rms.data(), nb * sizeof(double));
+  up(bf.camera_index, p->camera_index.data(), N * sizeof(int32_t));
+  up(bf.time_index, p->time_index.data(), N * sizeof(int32_t));
+  up(bf.marker_index, p->marker_index.data(), N * sizeof(int32_t));
+  up(bf.time_ptr, plan.time_ptr.data(), plan.time_ptr.size() * sizeof(int));
+  up(bf.time_obs, plan.time_obs.data(), N * sizeof(int));
+  up(bf.camera_ptr, plan.camera_ptr.data(), plan.camera_ptr.size() * sizeof(int));
+  up(bf.camera_obs, plan.camera_obs.data(), N * sizeof(int));
+  if constexpr (kScene) {
+    up(bf.marker_ptr, plan.marker_ptr.data(), plan.marker_ptr.size() * sizeof(int));
+    up(bf.marker_obs, plan.marker_obs.data(), N * sizeof(int));
+  }
+  up(bf.blocks, plan.blocks.data(), plan.blocks.size() * sizeof(int));
+  up(bf.block_status, status.data(), nb * sizeof(int32_t));
+  up(bf.block_iterations, iterations.data(), nb * sizeof(int32_t));
+  if constexpr (kScene) {
+    std::vector<uint8_t> flags(plan.given);
+    flags.push_back(0);   // the flag no launch sets: where k_scene_mask_index sends a detection whose marker is not known
+    up(bf.known, flags.data(), nb + 1);
+  } else {
+    up(bf.known, plan.given.data(), nb);
+  }
+  rsba::ResectionArgs a{};
+  a.all_markers = p->model == RSBA_MODEL_MARKER_CHAIN_TEST2 ? 1 : 0;
+  a.C = C; a.T = T;
+  a.half = 0.5 * p->marker_side;
+  a.camera_index = (const int32_t*)(d_all + bf.camera_index);
+  a.time_index = (const int32_t*)(d_all + bf.time_index);
+  a.marker_index = (const int32_t*)(d_all + bf.marker_index);
+  a.observations = (const double*)(d_all + bf.observations);
+  a.intrinsics = (const double*)(d_all + bf.intrinsics);
+  a.distortion = with_dist ? (const double*)(d_all + bf.distortion) : nullptr;
+  a.own_pose = (const double*)(d_all + bf.own_pose);
+  a.own_rms = (const double*)(d_all + bf.own_rms);
+  a.own_status = (const int32_t*)(d_all + bf.own_status);
+  a.parameters = (double*)(d_all + bf.parameters);
+  a.known = (uint8_t*)(d_all + bf.known);
+  a.status = (int32_t*)(d_all + bf.block_status);
+  a.rms = (double*)(d_all + bf.block_rms);
+  a.iterations = (int32_t*)(d_all + bf.block_iterations);
+  auto kind_name = [](int which) { return which == rsba::kRigStartTime ? "times" : which == rsba::kRigStartCamera ? "cameras" : "markers"; };
+  if (ok) {
+    // RSBA_RUNPROF=1: HIP events between the launches, the intervals to stderr (tools/rig_start_scale.py, tools/scene_start_scale.py read them)
+    const bool prof = getenv("RSBA_RUNPROF") != nullptr;
+    std::vector<hipEvent_t> ev;
+    if (prof) {
+      ev.resize(plan.launches.size() + 2, nullptr);
+      for (hipEvent_t& e : ev) if (hipEventCreate(&e) != hipSuccess) e = nullptr;
+    }
+    auto mark = [&](size_t k) { if (prof && ev[k]) (void)hipEventRecord(ev[k], 0); };
+    const int32_t* camera_index = a.camera_index;
+    const int32_t* time_index = a.time_index;
+    mark(0);
+    rsba::k_marker_pose<<<(unsigned)((N + 255) / 256), 256>>>((int64_t)N, a.observations, a.camera_index, a.intrinsics, a.distortion, p->marker_side,
+                                                               (double*)(d_all + bf.own_pose), (double*)(d_all + bf.own_rms), (int32_t*)(d_all + bf.own_status));
+    mark(1);
+    for (size_t k = 0; k < plan.launches.size(); ++k) {
+      const rsba::RigStartLaunch& l = plan.launches[k];
+      a.blocks = (const int*)(d_all + bf.blocks) + l.first;
+      a.num_blocks = l.count;
+      if constexpr (kScene) {
+        // a time or camera launch sees a detection only where its marker is known: its camera (time) indices through k_scene_mask_index
+        a.camera_index = camera_index;
+        a.time_index = time_index;
+        if (l.which != rsba::kSceneStartMarker) {
+          int32_t* masked = (int32_t*)(d_all + bf.masked_index);
+          rsba::k_scene_mask_index<<<(unsigned)((N + 255) / 256), 256>>>((int64_t)N, l.which == rsba::kRigStartTime ? camera_index : time_index, a.marker_index,
+                                                                          a.known + (size_t)C + T, rsba::SceneStartHiddenIndex(l.which, C, T, M), masked);
+          (l.which == rsba::kRigStartTime ? a.camera_index : a.time_index) = masked;
+        }
+      }
+      if (l.which == rsba::kRigStartTime) {
+        a.list_ptr = (const int*)(d_all + bf.time_ptr);
+        a.list_obs = (const int*)(d_all + bf.time_obs);
+        rsba::k_block_resection<false><<<l.grid, 256>>>(a, rsba::RESECT_TIME);
+      } else if (l.which == rsba::kRigStartCamera) {
+        a.list_ptr = (const int*)(d_all + bf.camera_ptr);
+        a.list_obs = (const int*)(d_all + bf.camera_obs);
+        rsba::k_block_resection<true><<<l.grid, 256>>>(a, rsba::RESECT_CAMERA);
+      } else if constexpr (kScene) {
+        a.list_ptr = (const int*)(d_all + bf.marker_ptr);
+        a.list_obs = (const int*)(d_all + bf.marker_obs);
+        rsba::k_block_resection<true, true><<<l.grid, 256>>>(a, rsba::RESECT_MARKER);
+      }
+      mark(k + 2);
+    }
+    ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    if (ok && prof) {
+      float ms = 0.0f;
+      if (ev[0] && ev[1] && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
+        fprintf(stderr, "rsba[runprof] %s k_marker_pose: %lld detections, %.4f ms\n", name, (long long)N, ms);
+      for (size_t k = 0; k < plan.launches.size(); ++k) {
+        const rsba::RigStartLaunch& l = plan.launches[k];
+        if (ev[k + 1] && ev[k + 2] && hipEventElapsedTime(&ms, ev[k + 1], ev[k + 2]) == hipSuccess)
+          fprintf(stderr, "rsba[runprof] %s launch %d: %s %s %d, %d blocks, %lld detections, %.4f ms\n", name, (int)k, kind_name(l.which),
+                  l.sweep ? "sweep" : "round", l.sweep ? l.sweep : (int)k, l.count, (long long)l.observations, ms);
+      }
+    }
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+  }
+  // (the results reach the problem only when every launch ran)
+  std::vector<double> blocks6(6 * nb);
+  std::vector<int32_t> status_d(nb);
+  std::vector<double> rms_d(nb);
+  auto down = [&](void* dst, size_t off, size_t bytes) {
+    if (ok && bytes > 0) ok = hipMemcpy(dst, d_all + off, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+  };
+  down(blocks6.data(), bf.parameters, 6 * nb * sizeof(double));
+  down(status_d.data(), bf.block_status, nb * sizeof(int32_t));
+  down(rms_d.data(), bf.block_rms, nb * sizeof(double));
+  down(iterations.data(), bf.block_iterations, nb * sizeof(int32_t));
+  (void)hipFree(d_all);
+  if (!ok) return RSBA_ERR_HIP;
+  status = status_d;
+  rms = rms_d;
+  // a block that was fitted carries its new value; every other block keeps its bits
+  for (size_t b = 0; b < nb; ++b)
+    if (status[b] == rsba::BLOCK_CONVERGED || status[b] == rsba::BLOCK_ITERATION_CAP) memcpy(&p->parameters[6 * b], &blocks6[6 * b], 6 * sizeof(double));
+  if (getenv("RSBA_RUNPROF")) {
+    // the iteration counts of the blocks' last fits, in bins of 25, and the fits that ended at the cap
+    int hist[17] = {0}, capped = 0;
+    for (size_t b = 0; b < nb; ++b) {
+      if (status[b] > rsba::BLOCK_ITERATION_CAP) continue;
+      ++hist[std::min(16, iterations[b] / 25)];
+      capped += status[b] == rsba::BLOCK_ITERATION_CAP;
+    }
+    fprintf(stderr, "rsba[runprof] %s iterations by 25:", name);
+    for (int h : hist) fprintf(stderr, " %d", h);
+    fprintf(stderr, "; at the cap: %d\n", capped);
+  }
+  return RSBA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 int rsba_problem_start_rig(rsba_problem* p, const uint8_t* known_blocks, int32_t refine_sweeps, int32_t device, int32_t* num_missing_times,
                            int32_t* num_missing_cameras, int32_t* block_status, double* block_rms) {
   if (!p || refine_sweeps < 0 || device < -1) return RSBA_ERR_ARG;
@@ -3231,127 +3397,15 @@ int rsba_problem_start_rig(rsba_problem* p, const uint8_t* known_blocks, int32_t
   if (ndev <= 0) return RSBA_ERR_NO_DEVICE;
   if (device >= ndev) return RSBA_ERR_ARG;
   const int C = p->num_cameras, T = p->num_times, M = p->num_markers;
-  const size_t N = (size_t)p->num_observations, nb = (size_t)C + T;
-  const bool with_dist = p->has_distortion();
+  const size_t nb = (size_t)C + T;
   rsba::RigStartPlan plan;
-  if (!rsba::PlanRigStart(C, T, M, p->num_observations, p->camera_index.data(), p->time_index.data(), known_blocks, refine_sweeps, with_dist, &plan))
+  if (!rsba::PlanRigStart(C, T, M, p->num_observations, p->camera_index.data(), p->time_index.data(), known_blocks, refine_sweeps, p->has_distortion(), &plan))
     return RSBA_ERR_ARG;
   std::vector<int32_t> status(nb);
   std::vector<double> rms(nb, -1.0);
   for (size_t b = 0; b < nb; ++b) status[b] = plan.given[b] ? rsba::BLOCK_GIVEN : rsba::BLOCK_UNREACHED;
-  std::vector<int32_t> iterations(nb, 0);
-  bool ok = true;
-  if (N > 0 && !plan.launches.empty()) {
-    if (device >= 0 && hipSetDevice(device) != hipSuccess) return RSBA_ERR_HIP;
-    char* d_all = nullptr;
-    if (hipMalloc((void**)&d_all, plan.buffers.total) != hipSuccess) return RSBA_ERR_HIP;
-    const rsba::RigStartBuffers& bf = plan.buffers;
-    auto up = [&](size_t off, const void* src, size_t bytes) {
-      if (ok && bytes > 0) ok = hipMemcpy(d_all + off, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
-    };
-    up(bf.observations, p->observations.data(), 8 * N * sizeof(double));
-    up(bf.intrinsics, p->intrinsics.data(), 4 * (size_t)C * sizeof(double));
-    if (with_dist) up(bf.distortion, p->distortion.data(), 5 * (size_t)C * sizeof(double));
-    up(bf.parameters, p->parameters.data(), 6 * (nb + (size_t)M) * sizeof(double));
-    up(bf.block_rms, rms.data(), nb * sizeof(double));
-    up(bf.camera_index, p->camera_index.data(), N * sizeof(int32_t));
-    up(bf.time_index, p->time_index.data(), N * sizeof(int32_t));
-    up(bf.marker_index, p->marker_index.data(), N * sizeof(int32_t));
-    up(bf.time_ptr, plan.time_ptr.data(), plan.time_ptr.size() * sizeof(int));
-    up(bf.time_obs, plan.time_obs.data(), N * sizeof(int));
-    up(bf.camera_ptr, plan.camera_ptr.data(), plan.camera_ptr.size() * sizeof(int));
-    up(bf.camera_obs, plan.camera_obs.data(), N * sizeof(int));
-    up(bf.blocks, plan.blocks.data(), plan.blocks.size() * sizeof(int));
-    up(bf.block_status, status.data(), nb * sizeof(int32_t));
-    up(bf.block_iterations, iterations.data(), nb * sizeof(int32_t));
-    up(bf.known, plan.given.data(), nb);
-    rsba::ResectionArgs a{};
-    a.all_markers = p->model == RSBA_MODEL_MARKER_CHAIN_TEST2 ? 1 : 0;
-    a.C = C; a.T = T;
-    a.half = 0.5 * p->marker_side;
-    a.camera_index = (const int32_t*)(d_all + bf.camera_index);
-    a.time_index = (const int32_t*)(d_all + bf.time_index);
-    a.marker_index = (const int32_t*)(d_all + bf.marker_index);
-    a.observations = (const double*)(d_all + bf.observations);
-    a.intrinsics = (const double*)(d_all + bf.intrinsics);
-    a.distortion = with_dist ? (const double*)(d_all + bf.distortion) : nullptr;
-    a.own_pose = (const double*)(d_all + bf.own_pose);
-    a.own_rms = (const double*)(d_all + bf.own_rms);
-    a.own_status = (const int32_t*)(d_all + bf.own_status);
-    a.parameters = (double*)(d_all + bf.parameters);
-    a.known = (uint8_t*)(d_all + bf.known);
-    a.status = (int32_t*)(d_all + bf.block_status);
-    a.rms = (double*)(d_all + bf.block_rms);
-    a.iterations = (int32_t*)(d_all + bf.block_iterations);
-    if (ok) {
-      // RSBA_RUNPROF=1: HIP events between the launches, the intervals to stderr (tools/rig_start_scale.py reads them)
-      const bool prof = getenv("RSBA_RUNPROF") != nullptr;
-      std::vector<hipEvent_t> ev;
-      if (prof) {
-        ev.resize(plan.launches.size() + 2, nullptr);
-        for (hipEvent_t& e : ev) if (hipEventCreate(&e) != hipSuccess) e = nullptr;
-      }
-      auto mark = [&](size_t k) { if (prof && ev[k]) (void)hipEventRecord(ev[k], 0); };
-      mark(0);
-      rsba::k_marker_pose<<<(unsigned)((N + 255) / 256), 256>>>((int64_t)N, a.observations, a.camera_index, a.intrinsics, a.distortion, p->marker_side,
-                                                                 (double*)(d_all + bf.own_pose), (double*)(d_all + bf.own_rms), (int32_t*)(d_all + bf.own_status));
-      mark(1);
-      for (size_t k = 0; k < plan.launches.size(); ++k) {
-        const rsba::RigStartLaunch& l = plan.launches[k];
-        a.blocks = (const int*)(d_all + bf.blocks) + l.first;
-        a.num_blocks = l.count;
-        if (l.which == rsba::kRigStartTime) {
-          a.list_ptr = (const int*)(d_all + bf.time_ptr);
-          a.list_obs = (const int*)(d_all + bf.time_obs);
-          rsba::k_block_resection<false><<<l.grid, 256>>>(a, rsba::RESECT_TIME);
-        } else {
-          a.list_ptr = (const int*)(d_all + bf.camera_ptr);
-          a.list_obs = (const int*)(d_all + bf.camera_obs);
-          rsba::k_block_resection<true><<<l.grid, 256>>>(a, rsba::RESECT_CAMERA);
-        }
-        mark(k + 2);
-      }
-      ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
-      if (ok && prof) {
-        float ms = 0.0f;
-        if (ev[0] && ev[1] && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
-          fprintf(stderr, "rsba[runprof] start_rig k_marker_pose: %lld detections, %.4f ms\n", (long long)N, ms);
-        for (size_t k = 0; k < plan.launches.size(); ++k) {
-          const rsba::RigStartLaunch& l = plan.launches[k];
-          if (ev[k + 1] && ev[k + 2] && hipEventElapsedTime(&ms, ev[k + 1], ev[k + 2]) == hipSuccess)
-            fprintf(stderr, "rsba[runprof] start_rig launch %d: %s %s %d, %d blocks, %lld detections, %.4f ms\n", (int)k, l.which == rsba::kRigStartTime ? "times" : "cameras",
-                    l.sweep ? "sweep" : "round", l.sweep ? l.sweep : (int)k, l.count, (long long)l.observations, ms);
-        }
-      }
-      for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    }
-    // (the results reach the problem only when every launch ran)
-    std::vector<double> blocks6(6 * nb);
-    auto down = [&](void* dst, size_t off, size_t bytes) {
-      if (ok && bytes > 0) ok = hipMemcpy(dst, d_all + off, bytes, hipMemcpyDeviceToHost) == hipSuccess;
-    };
-    down(blocks6.data(), bf.parameters, 6 * nb * sizeof(double));
-    down(status.data(), bf.block_status, nb * sizeof(int32_t));
-    down(rms.data(), bf.block_rms, nb * sizeof(double));
-    down(iterations.data(), bf.block_iterations, nb * sizeof(int32_t));
-    (void)hipFree(d_all);
-    if (!ok) return RSBA_ERR_HIP;
-    // a block that was fitted carries its new value; every other block keeps its bits
-    for (size_t b = 0; b < nb; ++b)
-      if (status[b] == rsba::BLOCK_CONVERGED || status[b] == rsba::BLOCK_ITERATION_CAP) memcpy(&p->parameters[6 * b], &blocks6[6 * b], 6 * sizeof(double));
-    if (getenv("RSBA_RUNPROF")) {
-      // the iteration counts of the blocks' last fits, in bins of 25, and the fits that ended at the cap
-      int hist[17] = {0}, capped = 0;
-      for (size_t b = 0; b < nb; ++b) {
-        if (status[b] > rsba::BLOCK_ITERATION_CAP) continue;
-        ++hist[std::min(16, iterations[b] / 25)];
-        capped += status[b] == rsba::BLOCK_ITERATION_CAP;
-      }
-      fprintf(stderr, "rsba[runprof] start_rig iterations by 25:");
-      for (int h : hist) fprintf(stderr, " %d", h);
-      fprintf(stderr, "; at the cap: %d\n", capped);
-    }
-  }
+  const int rc = RunStartPlan<false>(p, plan, device, "start_rig", &status, &rms);
+  if (rc != RSBA_OK) return rc;
   int32_t missing_t = 0, missing_c = 0;
   for (size_t b = 0; b < nb; ++b) {
     const bool missing = status[b] == rsba::BLOCK_DEGENERATE || status[b] == rsba::BLOCK_UNREACHED;
@@ -3359,6 +3413,36 @@ int rsba_problem_start_rig(rsba_problem* p, const uint8_t* known_blocks, int32_t
   }
   if (num_missing_times) *num_missing_times = missing_t;
   if (num_missing_cameras) *num_missing_cameras = missing_c;
+  if (block_status) memcpy(block_status, status.data(), nb * sizeof(int32_t));
+  if (block_rms) memcpy(block_rms, rms.data(), nb * sizeof(double));
+  return RSBA_OK;
+}
+
+// The scene start: the whole-rig start with the marker blocks fitted too (ba_scene_start_plan.hpp).
+int rsba_problem_start_scene(rsba_problem* p, const uint8_t* known_blocks, int32_t refine_sweeps, int32_t device, int32_t* num_missing_times,
+                             int32_t* num_missing_cameras, int32_t* num_missing_markers, int32_t* block_status, double* block_rms) {
+  if (!p || refine_sweeps < 0 || device < -1) return RSBA_ERR_ARG;
+  if (!p->is_marker_chain()) return RSBA_ERR_UNSUPPORTED;
+  const int ndev = rsba::DeviceCount();
+  if (ndev <= 0) return RSBA_ERR_NO_DEVICE;
+  if (device >= ndev) return RSBA_ERR_ARG;
+  const int C = p->num_cameras, T = p->num_times, M = p->num_markers;
+  const size_t nb = (size_t)C + T + M;
+  rsba::SceneStartPlan plan;
+  if (!rsba::PlanSceneStart(C, T, M, p->num_observations, p->camera_index.data(), p->time_index.data(), p->marker_index.data(), known_blocks,
+                            p->model != RSBA_MODEL_MARKER_CHAIN_TEST2, refine_sweeps, p->has_distortion(), &plan))
+    return RSBA_ERR_ARG;
+  std::vector<int32_t> status(nb);
+  std::vector<double> rms(nb, -1.0);
+  for (size_t b = 0; b < nb; ++b) status[b] = plan.given[b] ? rsba::BLOCK_GIVEN : rsba::BLOCK_UNREACHED;
+  const int rc = RunStartPlan<true>(p, plan, device, "start_scene", &status, &rms);
+  if (rc != RSBA_OK) return rc;
+  int32_t missing[3] = {0, 0, 0};   // cameras, times, markers
+  for (size_t b = 0; b < nb; ++b)
+    if (status[b] == rsba::BLOCK_DEGENERATE || status[b] == rsba::BLOCK_UNREACHED) ++missing[b < (size_t)C ? 0 : b < (size_t)C + T ? 1 : 2];
+  if (num_missing_times) *num_missing_times = missing[1];
+  if (num_missing_cameras) *num_missing_cameras = missing[0];
+  if (num_missing_markers) *num_missing_markers = missing[2];
   if (block_status) memcpy(block_status, status.data(), nb * sizeof(int32_t));
   if (block_rms) memcpy(block_rms, rms.data(), nb * sizeof(double));
   return RSBA_OK;
