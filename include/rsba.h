@@ -347,9 +347,26 @@ int rsba_problem_initial_camera_poses(rsba_problem* p);
  * RMS of the eight residuals in pixels.  *status: 0 converged; 1 the iteration cap was reached (pose and RMS of the last iterate);
  * 2 degenerate (singular homography, non-positive depth, a non-finite intermediate, an undistortion that did not converge): pose zeros,
  * RMS -1, and the call returns RSBA_ERR_UNSUPPORTED as coplanar EPnP does.  RSBA_ERR_ARG: a null pointer, a non-finite value,
- * marker_side <= 0.  The two-fold ambiguity of a planar target is not resolved: the RMS lets a caller see a poor fit.  Host code. */
+ * marker_side <= 0.  A planar target has TWO such minimisers, the pose and its mirror image about the line of sight; this entry returns
+ * the one in whose basin the homography start falls — for a small or nearly frontal marker the wrong one in a quarter to a third of the
+ * cases, at an RMS that does not give it away.  rsba_marker_pose_from_corners_both returns both.  Host code. */
 int rsba_marker_pose_from_corners(const double* corners8, const double* intrinsics4, const double* dist5_or_null, double marker_side,
                                   double* pose6, double* rms_or_null, int32_t* status_or_null);
+/* Both poses of the planar marker.  poses12 = solution 0, then solution 1; rms2 and status2 likewise.  The order is fixed, not sorted.
+ *   solution 0   rsba_marker_pose_from_corners, bit for bit
+ *   solution 1   exists when solution 0 has status 0 or 1: the same Levenberg-Marquardt loop started from the mirror image of solution 0,
+ *                R' = (I - 2 v v') R diag(1, 1, -1), t' = t with v = t / |t| — the marker's in-plane axes reflected in the plane
+ *                perpendicular to the line of sight.  (Not IPPE's closed form: a minimiser of the same reprojection error.)
+ *                status 0, 1 as above; 2: no solution 0, or the mirrored start is unusable (not finite, a corner behind the camera);
+ *                3 (RSBA_MARKER_POSE_SAME): the fit ended at solution 0 — no entry of the two rotation matrices or translations differs
+ *                by 1e-5 — as for a close-up, where perspective leaves one minimum.  Statuses 2 and 3: pose zeros, RMS -1.
+ * What is and is not resolved: both candidates are returned; WHICH is the marker's pose four corners cannot say (the two RMS values differ
+ * by less than the noise for a small marker; compare them only for a large or strongly tilted one).  A block's cost over several detections
+ * does say: rsba_problem_start_rig2 / _scene2 with RSBA_START_BOTH_SOLUTIONS.
+ * Return codes as rsba_marker_pose_from_corners: RSBA_ERR_UNSUPPORTED only when solution 0 is degenerate.  Host code. */
+#define RSBA_MARKER_POSE_SAME 3
+int rsba_marker_pose_from_corners_both(const double* corners8, const double* intrinsics4, const double* dist5_or_null, double marker_side,
+                                       double* poses12, double* rms2_or_null, int32_t* status2_or_null);
 /* The same fit for n detections in ONE kernel launch on the GPU, one detection per thread.  camera_index selects each detection's
  * row of intrinsics (4 per camera) and of dist (5 per camera, or NULL: no distortion); device: a HIP device, -1 = the current one.
  * RSBA_ERR_NO_DEVICE without a device; n == 0 is RSBA_OK and launches nothing; n < 0, a null required pointer, a camera index outside
@@ -360,6 +377,15 @@ int rsba_marker_poses_from_corners(int64_t n, const double* corners /* 8n */, co
                                    int32_t num_cameras, const double* intrinsics /* 4 per camera */, const double* dist /* 5 per camera, or NULL */,
                                    double marker_side, int32_t device /* -1 = current */, double* poses /* 6n */, double* rms /* n, or NULL */,
                                    int32_t* status /* n, or NULL */);
+/* rsba_marker_pose_from_corners_both for n detections on the GPU, in TWO launches: k_marker_pose (solution 0: the bits of
+ * rsba_marker_poses_from_corners), then k_marker_pose_mirror (solution 1 from solution 0), one detection per thread each.  Arguments,
+ * checks in the same order and error codes as rsba_marker_poses_from_corners; detection i's results are poses[12 i .. 12 i + 11],
+ * rms[2 i], rms[2 i + 1], status[2 i], status[2 i + 1].  A degenerate detection gets statuses (2, 2).  RSBA_RUNPROF=1: each launch's
+ * HIP-event time on stderr. */
+int rsba_marker_poses_from_corners_both(int64_t n, const double* corners /* 8n */, const int32_t* camera_index /* n, or NULL = all camera 0 */,
+                                        int32_t num_cameras, const double* intrinsics /* 4 per camera */, const double* dist /* 5 per camera, or NULL */,
+                                        double marker_side, int32_t device /* -1 = current */, double* poses /* 12n */, double* rms /* 2n, or NULL */,
+                                        int32_t* status /* 2n, or NULL */);
 /* correspondencer.cpp:100-127 on a marker-chain problem whose marker blocks are filled, the twin of rsba_problem_initial_camera_poses:
  * at every time, camera 0's detection with the lowest marker index is fitted with the problem's intrinsics (and distortion coefficients,
  * if it carries any); marker 0's pose is the base pose, another marker's goes through rsba_base_pose_from_marker_detection with the
@@ -376,7 +402,10 @@ int rsba_problem_initial_time_poses(rsba_problem* p, int32_t* num_missing_or_nul
  *                     constant.  Levenberg-Marquardt with the rules of rsba_marker_pose_from_corners and one more — a step must realise a
  *                     quarter of the decrease its damped model predicts, or the damping is raised — from the best of up to four candidate
  *                     poses: the own fits (that entry's) of the block's detections with the lowest RMS, composed with their known blocks, the
- *                     block cost evaluated at each.  A second detection so resolves the planar ambiguity of the first.
+ *                     block cost evaluated at each.  A second detection so resolves the planar ambiguity of the first — when its own fit
+ *                     fell into the right basin.  A block whose detections all fell into the wrong one, or that has a single detection,
+ *                     starts mirrored: rsba_problem_start_rig2 with RSBA_START_BOTH_SOLUTIONS puts both poses of each candidate detection
+ *                     on the list.
  *   propagation       from the known blocks — those flagged in known_blocks (C cameras, then T times), the base camera always — round 0 fits
  *                     every unknown time some known camera detected, the next round every unknown camera that detected a known time, and so on
  *                     in turns until nothing is added.  A detection counts for a block only when its other block (the camera of a time's
@@ -396,6 +425,22 @@ int rsba_problem_start_rig(rsba_problem* p, const uint8_t* known_blocks /* C + T
                            int32_t* num_missing_times, int32_t* num_missing_cameras,
                            int32_t* block_status /* C + T, or NULL */,
                            double* block_rms /* C + T, or NULL */);
+/* rsba_problem_start_rig with flags.  flags = 0 IS rsba_problem_start_rig (that entry calls this one: the same host path, the same kernel
+ * instances, the same bits).  RSBA_START_BOTH_SOLUTIONS: k_marker_pose_mirror runs once after the own fits, and a block that is not yet
+ * known takes its start from up to EIGHT candidates — the same up-to-four detections in the same (solution-0 RMS, observation index) order,
+ * each contributing its solution 0 and then, where it has status 0 or 1, its solution 1 (rsba_marker_pose_from_corners_both), the lowest
+ * block cost taken, the earlier candidate on a tie.  The unflagged list is contained in the flagged one in the same order, so the chosen
+ * start's block cost is never higher with the flag.  What that resolves: a time, camera or marker block whose own fits are all mirrored,
+ * provided the block's cost tells the two apart (two detections, or one beside known neighbours).  What it does not: a WHOLE board that
+ * is mirrored consistently, which is a true local minimum of the scene; a block with one detection of one marker, where
+ * both candidates cost almost the same and the lower one wins by noise.  Refits, sweeps, statuses and RMS are unchanged.  The flagged
+ * launches are kernel instances of their own.  Any other bit of flags: RSBA_ERR_ARG before any device work. */
+#define RSBA_START_BOTH_SOLUTIONS 1u
+int rsba_problem_start_rig2(rsba_problem* p, const uint8_t* known_blocks /* C + T, or NULL: only the base camera */,
+                            int32_t refine_sweeps, int32_t device /* -1 = current */, uint32_t flags,
+                            int32_t* num_missing_times, int32_t* num_missing_cameras,
+                            int32_t* block_status /* C + T, or NULL */,
+                            double* block_rms /* C + T, or NULL */);
 /* rsba_problem_start_rig for a scene whose board geometry nobody measured (markers on a wall, a floor, a folded board): the marker blocks
  * are a third kind of block to be fitted, by the same block resection.
  *   a marker's fit    the points entering the fitted transform are the raw corners (+-half, +-half, 0), the known transform behind it is
@@ -411,12 +456,19 @@ int rsba_problem_start_rig(rsba_problem* p, const uint8_t* known_blocks /* C + T
  * The gauge is the base camera's frame and, at every time, the base marker's: a scene in which the base camera never sees the base marker
  * (or a flagged one) has no first round, and every block comes back unreached.  A planar board seen by few cameras has a mirrored pose
  * that is a true local minimum of the whole problem; the candidates' block cost resolves it where a block has enough detections, not
- * always.  Statuses, RMS, errors and RSBA_RUNPROF as for rsba_problem_start_rig, over C + T + M blocks. */
+ * always; rsba_problem_start_scene2's RSBA_START_BOTH_SOLUTIONS widens the candidates, and does not promise it either.  Statuses, RMS, errors and RSBA_RUNPROF as for rsba_problem_start_rig, over C + T + M blocks. */
 int rsba_problem_start_scene(rsba_problem* p, const uint8_t* known_blocks /* C + T + M, or NULL */,
                              int32_t refine_sweeps, int32_t device /* -1 = current */,
                              int32_t* num_missing_times, int32_t* num_missing_cameras, int32_t* num_missing_markers,
                              int32_t* block_status /* C + T + M, or NULL */,
                              double* block_rms /* C + T + M, or NULL */);
+/* rsba_problem_start_scene with flags, as rsba_problem_start_rig2 is to rsba_problem_start_rig: 0 is that entry bit for bit,
+ * RSBA_START_BOTH_SOLUTIONS widens the candidates of time, marker and camera blocks alike, any other bit is RSBA_ERR_ARG. */
+int rsba_problem_start_scene2(rsba_problem* p, const uint8_t* known_blocks /* C + T + M, or NULL */,
+                              int32_t refine_sweeps, int32_t device /* -1 = current */, uint32_t flags,
+                              int32_t* num_missing_times, int32_t* num_missing_cameras, int32_t* num_missing_markers,
+                              int32_t* block_status /* C + T + M, or NULL */,
+                              double* block_rms /* C + T + M, or NULL */);
 
 void rsba_problem_free(rsba_problem* p);
 

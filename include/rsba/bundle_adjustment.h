@@ -95,31 +95,34 @@ class BALProblem {
   // the start of the whole rig from its detections, on the GPU (rsba_problem_start_rig): the camera and time blocks by block resection
   // and propagation over the co-visibility graph; the marker blocks are inputs.  known (optional): num_cameras() + num_times() flags of
   // blocks that keep their values and serve from the first round.  status / rms (optional) are resized to that many entries.  Returns
-  // the number of blocks left without a value (status 2 or 3), -1 when the call itself fails.
+  // the number of blocks left without a value (status 2 or 3), -1 when the call itself fails.  both_solutions
+  // (RSBA_START_BOTH_SOLUTIONS): both poses of each candidate detection's planar marker are among a block's starts.
   int StartRig(const std::vector<uint8_t>* known = nullptr, int refine_sweeps = 1, int device = -1, std::vector<int32_t>* status = nullptr,
-               std::vector<double>* rms = nullptr) {
+               std::vector<double>* rms = nullptr, bool both_solutions = false) {
     const size_t nb = (size_t)num_cameras() + (size_t)num_times();
     if (known && known->size() != nb) return -1;
     if (status) status->assign(nb, 0);
     if (rms) rms->assign(nb, 0.0);
     int32_t missing_times = 0, missing_cameras = 0;
-    if (rsba_problem_start_rig(p_, known ? known->data() : nullptr, refine_sweeps, device, &missing_times, &missing_cameras,
-                               status ? status->data() : nullptr, rms ? rms->data() : nullptr) != RSBA_OK)
+    if (rsba_problem_start_rig2(p_, known ? known->data() : nullptr, refine_sweeps, device, both_solutions ? RSBA_START_BOTH_SOLUTIONS : 0u,
+                                &missing_times, &missing_cameras, status ? status->data() : nullptr, rms ? rms->data() : nullptr) != RSBA_OK)
       return -1;
     return missing_times + missing_cameras;
   }
   // the start of a scene whose board geometry is not known (rsba_problem_start_scene): StartRig with the marker blocks fitted too, from the
   // base camera and the base marker alone.  known (optional): num_cameras() + num_times() + num_markers flags; status / rms (optional) are
   // resized to that many entries.  Returns the number of blocks left without a value (status 2 or 3), -1 when the call itself fails.
+  // both_solutions: as for StartRig.
   int StartScene(const std::vector<uint8_t>* known = nullptr, int refine_sweeps = 1, int device = -1, std::vector<int32_t>* status = nullptr,
-                 std::vector<double>* rms = nullptr) {
+                 std::vector<double>* rms = nullptr, bool both_solutions = false) {
     const size_t nb = (size_t)num_cameras() + (size_t)num_times() + (size_t)rsba_problem_num_markers(p_);
     if (known && known->size() != nb) return -1;
     if (status) status->assign(nb, 0);
     if (rms) rms->assign(nb, 0.0);
     int32_t missing_times = 0, missing_cameras = 0, missing_markers = 0;
-    if (rsba_problem_start_scene(p_, known ? known->data() : nullptr, refine_sweeps, device, &missing_times, &missing_cameras, &missing_markers,
-                                 status ? status->data() : nullptr, rms ? rms->data() : nullptr) != RSBA_OK)
+    if (rsba_problem_start_scene2(p_, known ? known->data() : nullptr, refine_sweeps, device, both_solutions ? RSBA_START_BOTH_SOLUTIONS : 0u,
+                                  &missing_times, &missing_cameras, &missing_markers, status ? status->data() : nullptr,
+                                  rms ? rms->data() : nullptr) != RSBA_OK)
       return -1;
     return missing_times + missing_cameras + missing_markers;
   }

@@ -60,6 +60,19 @@ class Correspondencer {
     }
     return ret;
   }
+  // Both poses of ONE detection's planar marker (rsba_marker_pose_from_corners_both): {solution 0, solution 1}, solution 0 being what
+  // EstimatePoseSingleMarkers returns.  status[1] is 0 or 1 where a second solution exists; 2 or RSBA_MARKER_POSE_SAME where it does not
+  // (a zero Transform, rms -1).  A degenerate solution 0 throws.
+  std::array<Transform, 2> EstimatePoseSingleMarkerBoth(const std::array<Point2d, 4>& corners, size_t camera, std::array<double, 2>* rms = nullptr,
+                                                        std::array<int32_t, 2>* status = nullptr) const {
+    double poses[12], e[2];
+    int32_t st[2];
+    Check(rsba_marker_pose_from_corners_both(&corners[0].x, intrinsics_.at(camera).data(), dist_.empty() ? nullptr : dist_.at(camera).data(),
+                                             marker_side_, poses, e, st), "EstimatePoseSingleMarkerBoth");
+    if (rms) *rms = {{e[0], e[1]}};
+    if (status) *status = {{st[0], st[1]}};
+    return {{Unpack(poses), Unpack(poses + 6)}};
+  }
   // the detected marker IS the base marker: its pose is the base pose (:104-111); otherwise :112-127
   static Transform BaseFromDetection(const Transform& marker_from_camera, const Transform& marker_from_base) {
     double a[6], b[6], out[6];

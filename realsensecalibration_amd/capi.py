@@ -38,7 +38,10 @@ EXPORTS = [
     "rsba_problem_set_parameter_subset_constant", "rsba_problem_parameter_subset_constant", "rsba_problem_set_distortion", "rsba_problem_distortion", "rsba_read_intrinsics_xml_dist", "rsba_undistort_points",
     "rsba_problem_set_block_prior", "rsba_problem_block_prior", "rsba_problem_num_block_priors", "rsba_solver_set_block_prior",
     "rsba_marker_pose_from_corners", "rsba_marker_poses_from_corners", "rsba_problem_initial_time_poses", "rsba_problem_start_rig", "rsba_problem_start_scene",
+    "rsba_marker_pose_from_corners_both", "rsba_marker_poses_from_corners_both", "rsba_problem_start_rig2", "rsba_problem_start_scene2",
 ]
+START_BOTH_SOLUTIONS = 1   # RSBA_START_BOTH_SOLUTIONS
+MARKER_POSE_SAME = 3       # RSBA_MARKER_POSE_SAME
 _SYMBOLS = EXPORTS   # (every symbol of include/rsba.h that load() checks)
 
 
@@ -196,6 +199,10 @@ def load():
     lib.rsba_problem_initial_time_poses.argtypes = [C.c_void_p, C.c_void_p]
     lib.rsba_problem_start_rig.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4
     lib.rsba_problem_start_scene.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5
+    lib.rsba_marker_pose_from_corners_both.argtypes = lib.rsba_marker_pose_from_corners.argtypes
+    lib.rsba_marker_poses_from_corners_both.argtypes = lib.rsba_marker_poses_from_corners.argtypes
+    lib.rsba_problem_start_rig2.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32] + [C.c_void_p] * 4
+    lib.rsba_problem_start_scene2.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32] + [C.c_void_p] * 5
     _LIB = lib
     return lib
 
@@ -407,13 +414,15 @@ class Problem:
         _chk(load().rsba_problem_initial_time_poses(self.h, C.byref(missing)), "rsba_problem_initial_time_poses")
         return int(missing.value)
 
-    def start_rig(self, known=None, refine_sweeps=1, device=-1):
+    def start_rig(self, known=None, refine_sweeps=1, device=-1, both_solutions=False):
         """Marker-chain models: the camera and time blocks of the whole rig from its detections, on the GPU (rsba_problem_start_rig):
         block resection — one block fitted to all its detections, the others held — propagated over the co-visibility graph from the
         known blocks.  known: C + T flags (cameras, then times) of blocks that keep their values, or None (only the base camera).
         refine_sweeps: passes over all fitted times, then all fitted cameras, after the rounds (1 is recommended).  Returns
         (missing_times, missing_cameras, status C + T, rms C + T): status 0 converged, 1 iteration cap, 2 degenerate, 3 unreached, 4 given
-        or the base camera; blocks with status 2 to 4 keep their bits and have rms -1."""
+        or the base camera; blocks with status 2 to 4 keep their bits and have rms -1.
+        both_solutions (rsba_problem_start_rig2, RSBA_START_BOTH_SOLUTIONS): a block's start is taken from both poses of each candidate
+        detection (marker_pose_from_corners_both), so a block whose own fits are all the mirror image can still start right."""
         nb = self.num_cameras + (self.num_times if self.model != MODEL_POINTS else 0)
         k = None
         if known is not None:
@@ -422,16 +431,21 @@ class Problem:
                 raise ValueError("start_rig: one flag per camera and time block expected")
         mt, mc = C.c_int32(0), C.c_int32(0)
         status, rms = np.zeros(nb, np.int32), np.zeros(nb)
+        if both_solutions:
+            _chk(load().rsba_problem_start_rig2(self.h, None if k is None else _vp(k), int(refine_sweeps), int(device), START_BOTH_SOLUTIONS,
+                                                C.byref(mt), C.byref(mc), _vp(status), _vp(rms)), "rsba_problem_start_rig2")
+            return int(mt.value), int(mc.value), status, rms
         _chk(load().rsba_problem_start_rig(self.h, None if k is None else _vp(k), int(refine_sweeps), int(device), C.byref(mt), C.byref(mc),
                                            _vp(status), _vp(rms)), "rsba_problem_start_rig")
         return int(mt.value), int(mc.value), status, rms
 
-    def start_scene(self, known=None, refine_sweeps=1, device=-1):
+    def start_scene(self, known=None, refine_sweeps=1, device=-1, both_solutions=False):
         """Marker-chain models: start_rig for a scene whose board geometry is not known (rsba_problem_start_scene): the marker blocks are
         fitted by block resection too, in rounds of times, markers, cameras from the known blocks.  known: C + T + M flags (cameras, times,
         markers) of blocks that keep their values, or None (the base camera, and the base marker of MODEL_MARKER_CHAIN).  A detection
         counts for a block only when both its other blocks are known.  Returns (missing_times, missing_cameras, missing_markers,
-        status C + T + M, rms C + T + M) with start_rig's statuses; 4 also for the base marker."""
+        status C + T + M, rms C + T + M) with start_rig's statuses; 4 also for the base marker.  both_solutions: as for start_rig
+        (rsba_problem_start_scene2)."""
         nb = self.num_cameras + (self.num_times + self.num_markers if self.model != MODEL_POINTS else 0)
         k = None
         if known is not None:
@@ -440,6 +454,10 @@ class Problem:
                 raise ValueError("start_scene: one flag per camera, time and marker block expected")
         mt, mc, mm = C.c_int32(0), C.c_int32(0), C.c_int32(0)
         status, rms = np.zeros(nb, np.int32), np.zeros(nb)
+        if both_solutions:
+            _chk(load().rsba_problem_start_scene2(self.h, None if k is None else _vp(k), int(refine_sweeps), int(device), START_BOTH_SOLUTIONS,
+                                                  C.byref(mt), C.byref(mc), C.byref(mm), _vp(status), _vp(rms)), "rsba_problem_start_scene2")
+            return int(mt.value), int(mc.value), int(mm.value), status, rms
         _chk(load().rsba_problem_start_scene(self.h, None if k is None else _vp(k), int(refine_sweeps), int(device), C.byref(mt), C.byref(mc),
                                              C.byref(mm), _vp(status), _vp(rms)), "rsba_problem_start_scene")
         return int(mt.value), int(mc.value), int(mm.value), status, rms
@@ -964,6 +982,40 @@ def marker_pose_from_corners(corners8, intrinsics4, dist5, marker_side):
     _chk(load().rsba_marker_pose_from_corners(_vp(c), _vp(k), None if d is None else _vp(d), C.c_double(marker_side), _vp(pose), C.byref(rms),
                                               C.byref(status)), "rsba_marker_pose_from_corners")
     return pose, rms.value, int(status.value)
+
+
+def marker_pose_from_corners_both(corners8, intrinsics4, dist5, marker_side):
+    """Both poses of one planar marker on the host (rsba_marker_pose_from_corners_both): solution 0 is marker_pose_from_corners', solution
+    1 the minimiser reached from its mirror image.  Returns (poses 2 x 6, rms 2, status 2), in that fixed order; solution 1 has status 2
+    (unusable start) or 3 (MARKER_POSE_SAME: it ended at solution 0) with pose zeros and rms -1 where there is no second solution.  A
+    degenerate solution 0 raises RsbaError with code ERR_UNSUPPORTED."""
+    c = np.ascontiguousarray(corners8, np.float64).reshape(-1)
+    k = np.ascontiguousarray(intrinsics4, np.float64).reshape(-1)
+    d = None if dist5 is None else np.ascontiguousarray(dist5, np.float64).reshape(-1)
+    if c.size != 8 or k.size != 4 or (d is not None and d.size != 5):
+        raise ValueError("marker_pose_from_corners_both: 8 corner values, 4 intrinsics and 5 coefficients (or None) expected")
+    poses, rms, status = np.zeros((2, 6)), np.zeros(2), np.zeros(2, np.int32)
+    _chk(load().rsba_marker_pose_from_corners_both(_vp(c), _vp(k), None if d is None else _vp(d), C.c_double(marker_side), _vp(poses), _vp(rms),
+                                                   _vp(status)), "rsba_marker_pose_from_corners_both")
+    return poses, rms, status
+
+
+def marker_poses_from_corners_both(corners, camera_index, intrinsics, dist, marker_side, device=-1, num_cameras=None):
+    """marker_pose_from_corners_both for a batch on the GPU, two kernel launches.  Arguments as marker_poses_from_corners.  Returns
+    (poses n x 2 x 6, rms n x 2, status n x 2); a degenerate detection has statuses (2, 2)."""
+    c = np.ascontiguousarray(corners, np.float64).reshape(-1, 8)
+    k = np.ascontiguousarray(intrinsics, np.float64).reshape(-1, 4)
+    nc = len(k) if num_cameras is None else int(num_cameras)
+    d = None if dist is None else np.ascontiguousarray(dist, np.float64).reshape(-1, 5)
+    ci = None if camera_index is None else np.ascontiguousarray(camera_index, np.int32).reshape(-1)
+    if len(k) != nc or (d is not None and len(d) != nc) or (ci is not None and len(ci) != len(c)):
+        raise ValueError("marker_poses_from_corners_both: one camera index per detection, 4 intrinsics and 5 coefficients per camera expected")
+    n = len(c)
+    poses, rms, status = np.zeros((n, 2, 6)), np.zeros((n, 2)), np.zeros((n, 2), np.int32)
+    _chk(load().rsba_marker_poses_from_corners_both(n, _vp(c), None if ci is None else _vp(ci), nc, _vp(k), None if d is None else _vp(d),
+                                                    C.c_double(marker_side), int(device), _vp(poses), _vp(rms), _vp(status)),
+         "rsba_marker_poses_from_corners_both")
+    return poses, rms, status
 
 
 def marker_poses_from_corners(corners, camera_index, intrinsics, dist, marker_side, device=-1, num_cameras=None):

@@ -19,6 +19,7 @@
 //                                        distorted pixels -> pixels of the ideal pinhole camera with the same K, by fixed-point
 //                                        iteration on the normalised point.  No digit-for-digit claim against OpenCV.
 //   MarkerPoseFromCorners     :80        aruco::estimatePoseSingleMarkers for one detection: ba_marker_pose.hpp's fit on the host
+//   MarkerPoseFromCornersBoth            that fit and the planar target's other pose (FitMarkerPoseBoth)
 //   InitialTimePoses          :100-127   the base marker's pose at every time from the main camera's first detection
 //
 // Host code, double precision, no device work: the problem sizes are a few hundred points per camera.
@@ -443,6 +444,22 @@ int MarkerPoseFromCorners(const double* corners8, const double* intrinsics4, con
   if (rms) *rms = e;
   if (status) *status = st;
   return st == MARKER_POSE_DEGENERATE ? RSBA_ERR_UNSUPPORTED : RSBA_OK;
+}
+
+// Both poses of the planar marker (FitMarkerPoseBoth): the checks and return codes of the entry above, which decide on solution 0 alone.
+int MarkerPoseFromCornersBoth(const double* corners8, const double* intrinsics4, const double* dist5, double marker_side, double* poses12,
+                              double* rms2, int32_t* status2) {
+  if (!corners8 || !intrinsics4 || !poses12 || !(marker_side > 0.0) || !std::isfinite(marker_side)) return RSBA_ERR_ARG;
+  for (int i = 0; i < 8; ++i) if (!std::isfinite(corners8[i])) return RSBA_ERR_ARG;
+  for (int i = 0; i < 4; ++i) if (!std::isfinite(intrinsics4[i])) return RSBA_ERR_ARG;
+  if (!(intrinsics4[0] != 0.0) || !(intrinsics4[1] != 0.0)) return RSBA_ERR_ARG;
+  if (dist5) for (int i = 0; i < 5; ++i) if (!std::isfinite(dist5[i])) return RSBA_ERR_ARG;
+  double e[2] = {-1.0, -1.0};
+  int st[2] = {MARKER_POSE_DEGENERATE, MARKER_POSE_DEGENERATE};
+  FitMarkerPoseBoth(corners8, intrinsics4, dist5, marker_side, poses12, e, st);
+  if (rms2) { rms2[0] = e[0]; rms2[1] = e[1]; }
+  if (status2) { status2[0] = st[0]; status2[1] = st[1]; }
+  return st[0] == MARKER_POSE_DEGENERATE ? RSBA_ERR_UNSUPPORTED : RSBA_OK;
 }
 
 // correspondencer.cpp:100-127 on a marker-chain problem whose marker blocks hold the board geometry: at every time the main camera's

@@ -29,7 +29,10 @@
 // J'J, the gradient, the pose and the 6 x 6 Cholesky factor live in registers (profiles/marker_pose_kernel_resources.txt: no scratch).
 // A lane that has finished leaves the loop; nothing is exchanged between lanes, so a detection's bits do not depend on its place.
 //
-// Not resolved: the two-fold ambiguity of a planar target (IPPE's second solution) — the RMS is returned so that a caller sees a poor fit.
+// The two-fold ambiguity of a planar target: FitMarkerPose returns the minimiser of the basin its homography start falls into, which for
+// a small or nearly frontal marker is the mirror image in a quarter to a third of the cases, at an RMS that does not give it away.
+// FitMarkerPoseBoth (below) returns the other minimiser too, reached from the mirrored start (MirrorMarkerPose; no IPPE closed form).
+// Which of the two is the marker's pose one detection cannot say: the block resection decides by a block's cost over several detections.
 #pragma once
 #include <cfloat>
 #include <cmath>
@@ -316,6 +319,95 @@ RSBA_HD int FitMarkerPose(const double* corners8, const double* intr4, const dou
   for (int q = 0; q < 6; ++q) pose6[q] = p[q];
   *rms = sqrt(cost * 0.125);
   return status;
+}
+
+// The other pose of a planar target.  With R = R(rvec), t = tvec and v = t / |t| (the line of sight to the marker's centre):
+//   R' = (I - 2 v v') R diag(1, 1, -1),   t' = t
+// The marker's two in-plane axes are reflected in the plane perpendicular to the line of sight (its normal follows as their cross
+// product: the third column changes sign once more), so the tilt about the line of sight changes sign and the corners' image under
+// weak perspective stays where it was.  Two reflections: a proper rotation; applied twice it returns the pose up to rounding.
+// out6 may be pose6.  t = 0 gives a non-finite pose (the caller's start check refuses it).
+RSBA_HD void MirrorMarkerPose(const double* pose6, double* out6) {
+  const double none[4] = {0.0, 0.0, 0.0, 0.0};
+  double cc[CC_STRIDE];
+  CameraConstants(pose6, none, cc);
+  const double* R = cc + CC_R;
+  const double t0 = pose6[3], t1 = pose6[4], t2 = pose6[5];
+  const double in = 1.0 / sqrt(t0 * t0 + t1 * t1 + t2 * t2);
+  const double v0 = t0 * in, v1 = t1 * in, v2 = t2 * in;
+  double M[9];   // R diag(1, 1, -1), then M - 2 v (v' M)
+  RSBA_UNROLL
+  for (int i = 0; i < 3; ++i) { M[3 * i] = R[3 * i]; M[3 * i + 1] = R[3 * i + 1]; M[3 * i + 2] = -R[3 * i + 2]; }
+  RSBA_UNROLL
+  for (int j = 0; j < 3; ++j) {
+    const double s = 2.0 * (v0 * M[j] + v1 * M[3 + j] + v2 * M[6 + j]);
+    M[j] -= v0 * s; M[3 + j] -= v1 * s; M[6 + j] -= v2 * s;
+  }
+  double w[3];
+  RotationMatrixToRvec(M, w);
+  out6[0] = w[0]; out6[1] = w[1]; out6[2] = w[2];
+  out6[3] = t0; out6[4] = t1; out6[5] = t2;
+}
+
+enum {
+  MARKER_POSE_SAME = 3   // the second solution only: the fit from the mirrored start ended at the first solution; pose zeros, RMS -1
+};
+
+// Two fits of one detection count as one solution when no entry of their rotation matrices or translations differs by this much.  A
+// definition: the stopping rule leaves about 1e-9 between two runs into the same minimiser, and a mirror image is about 0.1 rad away.
+constexpr double kMarkerPoseSameBelow = 1e-5;
+
+// The second solution of a detection whose first one (pose0, status0: FitMarkerPose's) is at hand: MarkerPoseMinimise — FitMarkerPose's
+// instance and its linearisation — started from MirrorMarkerPose(pose0).  Returns its status, pose1 and *rms1 are always written:
+//   0, 1   as FitMarkerPose: the minimiser reached from the mirrored start (1: the last iterate at the cap)
+//   2      there is no first solution (status0 = 2), or the mirrored start is unusable (not finite, or a corner behind the camera):
+//          pose zeros, RMS -1
+//   3      MARKER_POSE_SAME: the fit slid back to the first solution (a close-up, where perspective leaves one minimum): pose zeros, RMS -1
+// Shared by FitMarkerPoseBoth (the host) and k_marker_pose_mirror (ba_solver.hip), so both run the same arithmetic.
+RSBA_HD int SecondMarkerPose(const double* corners8, const double* intr4, const double* dist5, double marker_side, const double* pose0, int status0,
+                             double* pose1, double* rms1) {
+  double k5[5], p[6];
+  RSBA_UNROLL
+  for (int q = 0; q < 5; ++q) k5[q] = dist5 ? dist5[q] : 0.0;
+  bool ok = status0 == MARKER_POSE_CONVERGED || status0 == MARKER_POSE_ITERATION_CAP;
+  int status = MARKER_POSE_DEGENERATE;
+  double cost = 0.0;
+  if (ok) {
+    MirrorMarkerPose(pose0, p);
+    RSBA_UNROLL
+    for (int q = 0; q < 6; ++q) ok = ok && FiniteValue(p[q]);
+    const double half = 0.5 * marker_side;
+    int iterations = 0;
+    status = MarkerPoseMinimise([&](const double* at, double* c, double* A, double* g, double* z) {
+      MarkerPoseLinearise(at, corners8, intr4, k5, half, c, A, g, z);
+    }, &ok, p, &cost, &iterations);
+    if (!ok) status = MARKER_POSE_DEGENERATE;
+  }
+  if (ok) {
+    const double none[4] = {0.0, 0.0, 0.0, 0.0};
+    double ca[CC_STRIDE], cb[CC_STRIDE], far = 0.0;
+    CameraConstants(pose0, none, ca);
+    CameraConstants(p, none, cb);
+    RSBA_UNROLL
+    for (int q = 0; q < 9; ++q) far = fmax(far, fabs(ca[CC_R + q] - cb[CC_R + q]));
+    RSBA_UNROLL
+    for (int q = 0; q < 3; ++q) far = fmax(far, fabs(pose0[3 + q] - p[3 + q]));
+    if (far < kMarkerPoseSameBelow) { ok = false; status = MARKER_POSE_SAME; }
+  }
+  RSBA_UNROLL
+  for (int q = 0; q < 6; ++q) pose1[q] = ok ? p[q] : 0.0;
+  *rms1 = ok ? sqrt(cost * 0.125) : -1.0;
+  return status;
+}
+
+// Both poses of a planar marker.  Solution 0 is FitMarkerPose, called as it is (its bits are that routine's); solution 1 is
+// SecondMarkerPose.  poses12 = (solution 0, solution 1), rms2 and status2 likewise, in that fixed order: not sorted — a caller compares
+// the two RMS values, or, better, the cost of a block over several detections (ba_resection.hpp), since one marker's RMS does not
+// tell a small, nearly frontal marker's pose from its mirror image.
+RSBA_HD void FitMarkerPoseBoth(const double* corners8, const double* intr4, const double* dist5, double marker_side, double* poses12, double* rms2,
+                               int* status2) {
+  status2[0] = FitMarkerPose(corners8, intr4, dist5, marker_side, poses12, &rms2[0]);
+  status2[1] = SecondMarkerPose(corners8, intr4, dist5, marker_side, poses12, status2[0], poses12 + 6, &rms2[1]);
 }
 
 }  // namespace rsba

@@ -75,6 +75,8 @@ int SolvePnPEPnP(int n, const double* object_points, const double* image_points,
 int InitialCameraPoses(rsba_problem* p);
 int MarkerPoseFromCorners(const double* corners8, const double* intrinsics4, const double* dist5, double marker_side, double* pose6,
                           double* rms, int32_t* status);
+int MarkerPoseFromCornersBoth(const double* corners8, const double* intrinsics4, const double* dist5, double marker_side, double* poses12,
+                              double* rms2, int32_t* status2);
 int InitialTimePoses(rsba_problem* p, int32_t* num_missing);
 int WriteOutputs(const rsba_problem& p, const char* camera_transform_xml, const char* extrinsics_dir,
                  const char* point3d_txt);

@@ -18,10 +18,19 @@
 //               own-fit pose composed with the detection's two known blocks, the block cost evaluated at each, the lowest taken.  A second
 //               detection therefore resolves the planar two-fold ambiguity of the first: the wrong basin of a small frontal marker fits
 //               that marker almost as well as the right one, and the rest of the board not at all.
+//   both        kBoth (RSBA_START_BOTH_SOLUTIONS): the same up-to-four detections, chosen in the same order, each contributing its own fit
+//               and then, where it has one (own_status2 0 or 1), its second solution (k_marker_pose_mirror's: ba_marker_pose.hpp) — up to
+//               eight candidates, the strict < keeping the earlier one on a tie.  The list without the flag is a sublist of the list with
+//               it, in the same order, and the cost of each candidate is the same function of the same pose, so THE CHOSEN START'S BLOCK
+//               COST WITH THE FLAG IS NEVER HIGHER THAN WITHOUT IT (tests/marker_pose_both_driver.cpp holds the host to that).  A block
+//               whose detections all fell into the wrong basin, or that has a single detection, so has the right one among its starts.
+//               Refits, the minimiser, statuses and RMS are the same code with and without.
 //
 // ResectBlock is plain host / device code over a `Lanes` policy: which of a block's detections this caller accumulates (first(), stride())
 // and how partial sums meet (Sum, Min, ArgMin).  SerialLanes is one caller summing in observation order (the host: tests/
-// rig_start_plan_driver.cpp); DeviceLanes<false> is a wavefront, DeviceLanes<true> a 256-lane workgroup.  Every lane of the device forms
+// rig_start_plan_driver.cpp); DeviceLanes<false> is a wavefront, DeviceLanes<true> a 256-lane workgroup.  ChosenStart(have, cost, pose) is
+// told the start a block that is not yet known takes from its candidates and that start's block cost: nothing on the device, what a host
+// test records (tests/marker_pose_both_driver.cpp).  Every lane of the device forms
 // the same reduced system — an xor butterfly adds the same pairs in every lane, and the four wavefronts' sums meet in LDS in wavefront
 // order — and solves the 6 x 6 redundantly, so control flow is uniform, nothing is broadcast, and a block's bits depend on its own list
 // alone: not on its place in the launch, not on the call.  No atomics, no spin waits: the flags a launch sets are read by the next launch
@@ -70,6 +79,8 @@ struct ResectionArgs {
   const int* blocks;               // the launch's blocks: time, camera or marker indices
   int num_blocks;
   int markers_flagged;             // the host: 0: marker blocks are inputs, always known (the whole-rig start); 1: known[C + T + m] says so
+  const double* own_pose2;         // [N][6] kBoth only: each detection's second solution (k_marker_pose_mirror's), zeros where there is none
+  const int32_t* own_status2;      // [N]    kBoth only: 0 or 1 where there is one
 };
 
 // Rotation matrix (row-major) and translation of a pose block as the functors apply it (CameraConstants: the first-order form at
@@ -287,6 +298,7 @@ struct SerialLanes {
   template <int N> RSBA_HD void Sum(double (&)[N]) const {}
   RSBA_HD void Min(double*) const {}
   RSBA_HD void ArgMin(double*, int*) const {}
+  RSBA_HD void ChosenStart(bool, double, const double*) const {}
 };
 
 // The fit of one block (a.blocks[] entry `block`: a time, a camera or a marker index).  Every lane of `lanes` calls it with the same
@@ -299,7 +311,7 @@ struct SerialLanes {
 //                           not known behind the index of a flag that is never set (k_scene_mask_index below)
 //   RESECT_MARKER           the marker launches
 enum { RESECT_ANY = -1, RESECT_TIME_OR_CAMERA = -2 };
-template <int kKinds, class Lanes>
+template <int kKinds, bool kBoth = false, class Lanes>
 RSBA_HD void ResectBlockOf(const ResectionArgs& a, int which, int block, Lanes& lanes) {
   constexpr bool kMarkerToo = kKinds != RESECT_TIME_OR_CAMERA;
   const bool marker = kKinds == RESECT_MARKER || (kKinds == RESECT_ANY && which == RESECT_MARKER);
@@ -378,6 +390,32 @@ RSBA_HD void ResectBlockOf(const ResectionArgs& a, int which, int block, Lanes& 
       prev_key = key; prev_o = idx;
       const double *cam, *tim, *mar;
       ObservationBlocks(a, idx, &cam, &tim, &mar);
+      if constexpr (kBoth) {
+        // the detection's own fit, then its second solution where it has one
+        for (int sol = 0; sol < 2; ++sol) {
+          if (sol == 1 && a.own_status2[idx] > MARKER_POSE_ITERATION_CAP) break;
+          const double* from = sol == 1 ? a.own_pose2 : a.own_pose;
+          double own[6], cand[6], c0, A[21], g[6], z;
+          RSBA_UNROLL
+          for (int q = 0; q < 6; ++q) own[q] = from[6 * (size_t)idx + q];
+          ResectionCandidate<kMarkerToo>(kind, own, cam, tim, mar, cand);
+          bool fine = true;
+          RSBA_UNROLL
+          for (int q = 0; q < 6; ++q) fine = fine && FiniteValue(cand[q]);
+          if (!fine) continue;
+          lin(cand, &c0, A, g, &z);
+          if (FiniteValue(c0) && z > 0.0 && (!have || c0 < best)) {
+            have = true;
+            best = c0;
+            RSBA_UNROLL
+            for (int q = 0; q < 6; ++q) p[q] = cand[q];
+          }
+        }
+        continue;
+      }
+      // Without kBoth: these lines as they always were, NOT folded into the loop above as its one-trip case.  Folded, the three unflagged
+      // kernels came out with other register names and two moves in another order — the same arithmetic, but no longer the code that
+      // the whole-rig start's bits were recorded with; as they stand, those kernels match their earlier code instruction for instruction.
       double own[6], cand[6], c0, A[21], g[6], z;
       RSBA_UNROLL
       for (int q = 0; q < 6; ++q) own[q] = a.own_pose[6 * (size_t)idx + q];
@@ -395,6 +433,7 @@ RSBA_HD void ResectBlockOf(const ResectionArgs& a, int which, int block, Lanes& 
       }
     }
   }
+  if (!refit) lanes.ChosenStart(have, best, p);
   bool ok = have;
   double cost = 0.0;
   int iterations = 0;
@@ -414,9 +453,9 @@ RSBA_HD void ResectBlockOf(const ResectionArgs& a, int which, int block, Lanes& 
   }
 }
 
-template <class Lanes>
+template <bool kBoth = false, class Lanes>
 RSBA_HD void ResectBlock(const ResectionArgs& a, int which, int block, Lanes& lanes) {
-  ResectBlockOf<RESECT_ANY>(a, which, block, lanes);
+  ResectBlockOf<RESECT_ANY, kBoth>(a, which, block, lanes);
 }
 
 #if defined(__HIPCC__)
@@ -428,6 +467,7 @@ struct DeviceLanes {
   double* lds;   // kWorkgroup: 4 x kResectionSums doubles
   __device__ int first() const { return kWorkgroup ? (int)threadIdx.x : (int)(threadIdx.x & 63); }
   __device__ int stride() const { return kWorkgroup ? 256 : 64; }
+  __device__ void ChosenStart(bool, double, const double*) const {}
   template <int N> __device__ void Sum(double (&v)[N]) const {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) {
@@ -487,14 +527,15 @@ struct DeviceLanes {
 // kWorkgroup = false: a block per wavefront, four to a workgroup (times: tens of detections each); true: a block per workgroup (cameras:
 // tens of thousands).  A wavefront past the launch's last block leaves at once; inside a workgroup-wide block every barrier is reached by
 // all four wavefronts, since they hold the same sums and take the same branches.  kMarker = true: the scene start's marker launches — a
-// marker, like a camera, is a block per workgroup (in a large rig it is named by up to C x T detections).
-template <bool kWorkgroup, bool kMarker = false>
+// marker, like a camera, is a block per workgroup (in a large rig it is named by up to C x T detections).  kBoth = true: the three
+// instances of the flagged start, with both solutions of a detection among a block's candidates; the three without it carry none of that.
+template <bool kWorkgroup, bool kMarker = false, bool kBoth = false>
 __global__ __launch_bounds__(256) void k_block_resection(ResectionArgs a, int which) {
   __shared__ double lds[kWorkgroup ? 4 * kResectionSums : 1];
   const int i = kWorkgroup ? (int)blockIdx.x : (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
   if (i >= a.num_blocks) return;
   DeviceLanes<kWorkgroup> lanes{lds};
-  ResectBlockOf<kMarker ? RESECT_MARKER : RESECT_TIME_OR_CAMERA>(a, which, a.blocks[i], lanes);
+  ResectBlockOf<kMarker ? RESECT_MARKER : RESECT_TIME_OR_CAMERA, kBoth>(a, which, a.blocks[i], lanes);
 }
 
 // The scene start's rule for a time or a camera block — a detection counts only when its marker is known too — without another

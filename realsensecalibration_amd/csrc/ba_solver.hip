@@ -92,6 +92,32 @@ __global__ __launch_bounds__(256) void k_marker_pose(int64_t n, const double* __
   if (status) status[i] = st;
 }
 
+// The second solution of every detection of a batch (rsba_marker_poses_from_corners_both, the flagged starts): launched after
+// k_marker_pose, it reads a detection's first solution (pose and status) and writes the minimiser reached from its mirror image
+// (SecondMarkerPose, ba_marker_pose.hpp: the same loop, without the undistortion and the homography).  One detection per thread as there:
+// no LDS, no atomics, nothing exchanged between lanes, plain stores; a lane without a first solution, and a lane that has finished,
+// takes no further part.  poses0 and status0 must not alias the outputs.
+__global__ __launch_bounds__(256) void k_marker_pose_mirror(int64_t n, const double* __restrict__ corners, const int32_t* __restrict__ camera_index,
+                                                            const double* __restrict__ intr, const double* __restrict__ dist, double marker_side,
+                                                            const double* __restrict__ poses0, const int32_t* __restrict__ status0,
+                                                            double* __restrict__ poses1, double* __restrict__ rms1, int32_t* __restrict__ status1) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int c = camera_index ? camera_index[i] : 0;
+  double c8[8], k4[4], first[6], pose[6], e;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) c8[q] = corners[8 * i + q];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) k4[q] = intr[4 * c + q];
+#pragma unroll
+  for (int q = 0; q < 6; ++q) first[q] = poses0[6 * i + q];
+  const int st = SecondMarkerPose(c8, k4, dist ? dist + 5 * c : nullptr, marker_side, first, status0[i], pose, &e);
+#pragma unroll
+  for (int q = 0; q < 6; ++q) poses1[6 * i + q] = pose[q];
+  if (rms1) rms1[i] = e;
+  status1[i] = st;
+}
+
 // ------------------------------------------------------------------------------------------------
 class KernelTimer {
  public:
@@ -3168,8 +3194,14 @@ int rsba_reprojection_error(rsba_problem* p, const rsba_options* o, double* erro
   return rc;
 }
 
-int rsba_marker_poses_from_corners(int64_t n, const double* corners, const int32_t* camera_index, int32_t num_cameras, const double* intrinsics,
-                                   const double* dist, double marker_side, int32_t device, double* poses, double* rms, int32_t* status) {
+}  // extern "C"
+
+namespace {
+
+// rsba_marker_poses_from_corners (both = false: one launch, poses 6n, rms n, status n) and rsba_marker_poses_from_corners_both (two
+// launches, k_marker_pose then k_marker_pose_mirror; poses 12n, rms 2n, status 2n: solution 0 then solution 1 of each detection).
+int MarkerPosesBatch(bool both, int64_t n, const double* corners, const int32_t* camera_index, int32_t num_cameras, const double* intrinsics,
+                     const double* dist, double marker_side, int32_t device, double* poses, double* rms, int32_t* status) {
   if (n < 0 || num_cameras <= 0 || !intrinsics || !(marker_side > 0.0) || !std::isfinite(marker_side)) return RSBA_ERR_ARG;
   if (n > 0 && (!corners || !poses)) return RSBA_ERR_ARG;
   if (n > (int64_t)INT32_MAX * 256) return RSBA_ERR_ARG;   // one launch: the grid's size
@@ -3183,43 +3215,91 @@ int rsba_marker_poses_from_corners(int64_t n, const double* corners, const int32
   if (device >= ndev) return RSBA_ERR_ARG;
   if (n == 0) return RSBA_OK;
   if (device >= 0 && hipSetDevice(device) != hipSuccess) return RSBA_ERR_HIP;
-  // one allocation: [corners 8n | intrinsics 4C | dist 5C | poses 6n | rms n] doubles, then [camera_index n | status n] int32
+  // one allocation: [corners 8n | intrinsics 4C | dist 5C | poses 6n | rms n | both: poses 6n | rms n] doubles, then
+  // [camera_index n | status n | both: status n] int32
   const size_t C = (size_t)num_cameras, N = (size_t)n;
-  const size_t nd = 8 * N + 4 * C + 5 * C + 6 * N + N;
+  const size_t nd = 8 * N + 4 * C + 5 * C + 6 * N + N + (both ? 6 * N + N : 0);
   double* d_all = nullptr;
-  if (hipMalloc((void**)&d_all, nd * sizeof(double) + 2 * N * sizeof(int32_t)) != hipSuccess) return RSBA_ERR_HIP;
+  if (hipMalloc((void**)&d_all, nd * sizeof(double) + (both ? 3 : 2) * N * sizeof(int32_t)) != hipSuccess) return RSBA_ERR_HIP;
   double* d_corners = d_all;
   double* d_intr = d_corners + 8 * N;
   double* d_dist = d_intr + 4 * C;
   double* d_poses = d_dist + 5 * C;
   double* d_rms = d_poses + 6 * N;
+  double* d_poses1 = d_rms + N;      // (both only)
+  double* d_rms1 = d_poses1 + 6 * N;
   int32_t* d_cam = (int32_t*)(d_all + nd);
   int32_t* d_status = d_cam + N;
+  int32_t* d_status1 = d_status + N;   // (both only)
   bool ok = hipMemcpy(d_corners, corners, 8 * N * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
             hipMemcpy(d_intr, intrinsics, 4 * C * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
   if (ok && dist) ok = hipMemcpy(d_dist, dist, 5 * C * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
   if (ok && camera_index) ok = hipMemcpy(d_cam, camera_index, N * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
   if (ok) {
     // RSBA_RUNPROF=1: HIP events around the launch, the interval to stderr (tools/marker_pose_scale.py reads it)
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    const bool prof = getenv("RSBA_RUNPROF") != nullptr && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
+    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+    const bool prof = getenv("RSBA_RUNPROF") != nullptr && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess &&
+                      (!both || hipEventCreate(&e2) == hipSuccess);
     if (prof) (void)hipEventRecord(e0, 0);
     rsba::k_marker_pose<<<(unsigned)((N + 255) / 256), 256>>>(n, d_corners, camera_index ? d_cam : nullptr, d_intr, dist ? d_dist : nullptr, marker_side,
                                                                d_poses, d_rms, d_status);
     if (prof) (void)hipEventRecord(e1, 0);
+    if (both) {
+      rsba::k_marker_pose_mirror<<<(unsigned)((N + 255) / 256), 256>>>(n, d_corners, camera_index ? d_cam : nullptr, d_intr, dist ? d_dist : nullptr,
+                                                                        marker_side, d_poses, d_status, d_poses1, d_rms1, d_status1);
+      if (prof) (void)hipEventRecord(e2, 0);
+    }
     ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
     float ms = 0.0f;
     if (ok && prof && hipEventElapsedTime(&ms, e0, e1) == hipSuccess)
       fprintf(stderr, "rsba[runprof] k_marker_pose: %lld detections, %.4f ms between the events around its launch\n", (long long)n, ms);
+    if (ok && prof && both && hipEventElapsedTime(&ms, e1, e2) == hipSuccess)
+      fprintf(stderr, "rsba[runprof] k_marker_pose_mirror: %lld detections, %.4f ms between the events around its launch\n", (long long)n, ms);
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
+    if (e2) (void)hipEventDestroy(e2);
   }
   // (the results reach the caller's arrays only when the whole batch ran)
-  if (ok) ok = hipMemcpy(poses, d_poses, 6 * N * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
-  if (ok && rms) ok = hipMemcpy(rms, d_rms, N * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
-  if (ok && status) ok = hipMemcpy(status, d_status, N * sizeof(int32_t), hipMemcpyDeviceToHost) == hipSuccess;
+  if (!both) {
+    if (ok) ok = hipMemcpy(poses, d_poses, 6 * N * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
+    if (ok && rms) ok = hipMemcpy(rms, d_rms, N * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
+    if (ok && status) ok = hipMemcpy(status, d_status, N * sizeof(int32_t), hipMemcpyDeviceToHost) == hipSuccess;
+  } else {
+    // the device holds the two solutions in arrays of their own (k_marker_pose writes what it always wrote); the caller's are interleaved
+    std::vector<double> h_poses(12 * N), h_rms(2 * N);
+    std::vector<int32_t> h_status(2 * N);
+    if (ok) ok = hipMemcpy(h_poses.data(), d_poses, 6 * N * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess &&
+                 hipMemcpy(h_poses.data() + 6 * N, d_poses1, 6 * N * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess &&
+                 hipMemcpy(h_rms.data(), d_rms, N * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess &&
+                 hipMemcpy(h_rms.data() + N, d_rms1, N * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess &&
+                 hipMemcpy(h_status.data(), d_status, N * sizeof(int32_t), hipMemcpyDeviceToHost) == hipSuccess &&
+                 hipMemcpy(h_status.data() + N, d_status1, N * sizeof(int32_t), hipMemcpyDeviceToHost) == hipSuccess;
+    if (ok) {
+      for (size_t i = 0; i < N; ++i) {
+        for (int s = 0; s < 2; ++s) {
+          memcpy(poses + 12 * i + 6 * (size_t)s, &h_poses[6 * N * (size_t)s + 6 * i], 6 * sizeof(double));
+          if (rms) rms[2 * i + (size_t)s] = h_rms[N * (size_t)s + i];
+          if (status) status[2 * i + (size_t)s] = h_status[N * (size_t)s + i];
+        }
+      }
+    }
+  }
   (void)hipFree(d_all);
   return ok ? RSBA_OK : RSBA_ERR_HIP;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rsba_marker_poses_from_corners(int64_t n, const double* corners, const int32_t* camera_index, int32_t num_cameras, const double* intrinsics,
+                                   const double* dist, double marker_side, int32_t device, double* poses, double* rms, int32_t* status) {
+  return MarkerPosesBatch(false, n, corners, camera_index, num_cameras, intrinsics, dist, marker_side, device, poses, rms, status);
+}
+
+int rsba_marker_poses_from_corners_both(int64_t n, const double* corners, const int32_t* camera_index, int32_t num_cameras, const double* intrinsics,
+                                        const double* dist, double marker_side, int32_t device, double* poses, double* rms, int32_t* status) {
+  return MarkerPosesBatch(true, n, corners, camera_index, num_cameras, intrinsics, dist, marker_side, device, poses, rms, status);
 }
 
 }  // extern "C"
@@ -3232,7 +3312,7 @@ namespace {
 // third kind of block with a kernel instance of their own, flags, statuses and RMS over C + T + M; times and cameras go through the same
 // two kernel instances as without, so with every marker flagged the call computes the whole-rig start's bits.  status and rms come in with the plan's initial values.
 template <bool kScene, class Plan>
-int RunStartPlan(rsba_problem* p, const Plan& plan, int32_t device, const char* name, std::vector<int32_t>* status_io, std::vector<double>* rms_io) {
+int RunStartPlan(rsba_problem* p, const Plan& plan, int32_t device, bool both, const char* name, std::vector<int32_t>* status_io, std::vector<double>* rms_io) {
   const int C = p->num_cameras, T = p->num_times, M = p->num_markers;
   const size_t N = (size_t)p->num_observations, nb = (size_t)C + T + (kScene ? (size_t)M : 0), all = (size_t)C + T + M;
   const bool with_dist = p->has_distortion();
@@ -3244,6 +3324,9 @@ int RunStartPlan(rsba_problem* p, const Plan& plan, int32_t device, const char* 
   if (device >= 0 && hipSetDevice(device) != hipSuccess) return RSBA_ERR_HIP;
   char* d_all = nullptr;
   if (hipMalloc((void**)&d_all, plan.buffers.total) != hipSuccess) return RSBA_ERR_HIP;
+  // both (RSBA_START_BOTH_SOLUTIONS): every detection's second solution beside the plan's buffers, [pose 6N doubles | status N int32]
+  char* d_second = nullptr;
+  if (both && hipMalloc((void**)&d_second, 6 * N * sizeof(double) + N * sizeof(int32_t)) != hipSuccess) { (void)hipFree(d_all); return RSBA_ERR_HIP; }
   const auto& bf = plan.buffers;
   auto up = [&](size_t off, const void* src, size_t bytes) {
     if (ok && bytes > 0) ok = hipMemcpy(d_all + off, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
@@ -3287,6 +3370,8 @@ int RunStartPlan(rsba_problem* p, const Plan& plan, int32_t device, const char* 
   a.own_pose = (const double*)(d_all + bf.own_pose);
   a.own_rms = (const double*)(d_all + bf.own_rms);
   a.own_status = (const int32_t*)(d_all + bf.own_status);
+  a.own_pose2 = both ? (const double*)d_second : nullptr;
+  a.own_status2 = both ? (const int32_t*)(d_second + 6 * N * sizeof(double)) : nullptr;
   a.parameters = (double*)(d_all + bf.parameters);
   a.known = (uint8_t*)(d_all + bf.known);
   a.status = (int32_t*)(d_all + bf.block_status);
@@ -3298,7 +3383,7 @@ int RunStartPlan(rsba_problem* p, const Plan& plan, int32_t device, const char* 
     const bool prof = getenv("RSBA_RUNPROF") != nullptr;
     std::vector<hipEvent_t> ev;
     if (prof) {
-      ev.resize(plan.launches.size() + 2, nullptr);
+      ev.resize(plan.launches.size() + 3, nullptr);   // (the last one: after k_marker_pose_mirror)
       for (hipEvent_t& e : ev) if (hipEventCreate(&e) != hipSuccess) e = nullptr;
     }
     auto mark = [&](size_t k) { if (prof && ev[k]) (void)hipEventRecord(ev[k], 0); };
@@ -3308,6 +3393,13 @@ int RunStartPlan(rsba_problem* p, const Plan& plan, int32_t device, const char* 
     rsba::k_marker_pose<<<(unsigned)((N + 255) / 256), 256>>>((int64_t)N, a.observations, a.camera_index, a.intrinsics, a.distortion, p->marker_side,
                                                                (double*)(d_all + bf.own_pose), (double*)(d_all + bf.own_rms), (int32_t*)(d_all + bf.own_status));
     mark(1);
+    const size_t mirrored = plan.launches.size() + 2;
+    if (both) {
+      rsba::k_marker_pose_mirror<<<(unsigned)((N + 255) / 256), 256>>>((int64_t)N, a.observations, a.camera_index, a.intrinsics, a.distortion, p->marker_side,
+                                                                        a.own_pose, a.own_status, (double*)d_second, nullptr,
+                                                                        (int32_t*)(d_second + 6 * N * sizeof(double)));
+      mark(mirrored);
+    }
     for (size_t k = 0; k < plan.launches.size(); ++k) {
       const rsba::RigStartLaunch& l = plan.launches[k];
       a.blocks = (const int*)(d_all + bf.blocks) + l.first;
@@ -3326,15 +3418,18 @@ int RunStartPlan(rsba_problem* p, const Plan& plan, int32_t device, const char* 
       if (l.which == rsba::kRigStartTime) {
         a.list_ptr = (const int*)(d_all + bf.time_ptr);
         a.list_obs = (const int*)(d_all + bf.time_obs);
-        rsba::k_block_resection<false><<<l.grid, 256>>>(a, rsba::RESECT_TIME);
+        if (both) rsba::k_block_resection<false, false, true><<<l.grid, 256>>>(a, rsba::RESECT_TIME);
+        else rsba::k_block_resection<false><<<l.grid, 256>>>(a, rsba::RESECT_TIME);
       } else if (l.which == rsba::kRigStartCamera) {
         a.list_ptr = (const int*)(d_all + bf.camera_ptr);
         a.list_obs = (const int*)(d_all + bf.camera_obs);
-        rsba::k_block_resection<true><<<l.grid, 256>>>(a, rsba::RESECT_CAMERA);
+        if (both) rsba::k_block_resection<true, false, true><<<l.grid, 256>>>(a, rsba::RESECT_CAMERA);
+        else rsba::k_block_resection<true><<<l.grid, 256>>>(a, rsba::RESECT_CAMERA);
       } else if constexpr (kScene) {
         a.list_ptr = (const int*)(d_all + bf.marker_ptr);
         a.list_obs = (const int*)(d_all + bf.marker_obs);
-        rsba::k_block_resection<true, true><<<l.grid, 256>>>(a, rsba::RESECT_MARKER);
+        if (both) rsba::k_block_resection<true, true, true><<<l.grid, 256>>>(a, rsba::RESECT_MARKER);
+        else rsba::k_block_resection<true, true><<<l.grid, 256>>>(a, rsba::RESECT_MARKER);
       }
       mark(k + 2);
     }
@@ -3343,9 +3438,12 @@ int RunStartPlan(rsba_problem* p, const Plan& plan, int32_t device, const char* 
       float ms = 0.0f;
       if (ev[0] && ev[1] && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
         fprintf(stderr, "rsba[runprof] %s k_marker_pose: %lld detections, %.4f ms\n", name, (long long)N, ms);
+      if (both && ev[1] && ev[mirrored] && hipEventElapsedTime(&ms, ev[1], ev[mirrored]) == hipSuccess)
+        fprintf(stderr, "rsba[runprof] %s k_marker_pose_mirror: %lld detections, %.4f ms\n", name, (long long)N, ms);
       for (size_t k = 0; k < plan.launches.size(); ++k) {
         const rsba::RigStartLaunch& l = plan.launches[k];
-        if (ev[k + 1] && ev[k + 2] && hipEventElapsedTime(&ms, ev[k + 1], ev[k + 2]) == hipSuccess)
+        const size_t since = both && k == 0 ? mirrored : k + 1;
+        if (ev[since] && ev[k + 2] && hipEventElapsedTime(&ms, ev[since], ev[k + 2]) == hipSuccess)
           fprintf(stderr, "rsba[runprof] %s launch %d: %s %s %d, %d blocks, %lld detections, %.4f ms\n", name, (int)k, kind_name(l.which),
                   l.sweep ? "sweep" : "round", l.sweep ? l.sweep : (int)k, l.count, (long long)l.observations, ms);
       }
@@ -3364,6 +3462,7 @@ int RunStartPlan(rsba_problem* p, const Plan& plan, int32_t device, const char* 
   down(rms_d.data(), bf.block_rms, nb * sizeof(double));
   down(iterations.data(), bf.block_iterations, nb * sizeof(int32_t));
   (void)hipFree(d_all);
+  if (d_second) (void)hipFree(d_second);
   if (!ok) return RSBA_ERR_HIP;
   status = status_d;
   rms = rms_d;
@@ -3391,7 +3490,14 @@ extern "C" {
 
 int rsba_problem_start_rig(rsba_problem* p, const uint8_t* known_blocks, int32_t refine_sweeps, int32_t device, int32_t* num_missing_times,
                            int32_t* num_missing_cameras, int32_t* block_status, double* block_rms) {
-  if (!p || refine_sweeps < 0 || device < -1) return RSBA_ERR_ARG;
+  return rsba_problem_start_rig2(p, known_blocks, refine_sweeps, device, 0, num_missing_times, num_missing_cameras, block_status, block_rms);
+}
+
+// flags = 0: the whole-rig start as it always ran (the entry above IS this one); RSBA_START_BOTH_SOLUTIONS: k_marker_pose_mirror after the
+// own fits and the kBoth instances of the block resection.
+int rsba_problem_start_rig2(rsba_problem* p, const uint8_t* known_blocks, int32_t refine_sweeps, int32_t device, uint32_t flags,
+                            int32_t* num_missing_times, int32_t* num_missing_cameras, int32_t* block_status, double* block_rms) {
+  if (!p || refine_sweeps < 0 || device < -1 || (flags & ~(uint32_t)RSBA_START_BOTH_SOLUTIONS) != 0) return RSBA_ERR_ARG;
   if (!p->is_marker_chain()) return RSBA_ERR_UNSUPPORTED;
   const int ndev = rsba::DeviceCount();
   if (ndev <= 0) return RSBA_ERR_NO_DEVICE;
@@ -3404,7 +3510,7 @@ int rsba_problem_start_rig(rsba_problem* p, const uint8_t* known_blocks, int32_t
   std::vector<int32_t> status(nb);
   std::vector<double> rms(nb, -1.0);
   for (size_t b = 0; b < nb; ++b) status[b] = plan.given[b] ? rsba::BLOCK_GIVEN : rsba::BLOCK_UNREACHED;
-  const int rc = RunStartPlan<false>(p, plan, device, "start_rig", &status, &rms);
+  const int rc = RunStartPlan<false>(p, plan, device, (flags & RSBA_START_BOTH_SOLUTIONS) != 0, "start_rig", &status, &rms);
   if (rc != RSBA_OK) return rc;
   int32_t missing_t = 0, missing_c = 0;
   for (size_t b = 0; b < nb; ++b) {
@@ -3421,7 +3527,14 @@ int rsba_problem_start_rig(rsba_problem* p, const uint8_t* known_blocks, int32_t
 // The scene start: the whole-rig start with the marker blocks fitted too (ba_scene_start_plan.hpp).
 int rsba_problem_start_scene(rsba_problem* p, const uint8_t* known_blocks, int32_t refine_sweeps, int32_t device, int32_t* num_missing_times,
                              int32_t* num_missing_cameras, int32_t* num_missing_markers, int32_t* block_status, double* block_rms) {
-  if (!p || refine_sweeps < 0 || device < -1) return RSBA_ERR_ARG;
+  return rsba_problem_start_scene2(p, known_blocks, refine_sweeps, device, 0, num_missing_times, num_missing_cameras, num_missing_markers, block_status,
+                                   block_rms);
+}
+
+int rsba_problem_start_scene2(rsba_problem* p, const uint8_t* known_blocks, int32_t refine_sweeps, int32_t device, uint32_t flags,
+                              int32_t* num_missing_times, int32_t* num_missing_cameras, int32_t* num_missing_markers, int32_t* block_status,
+                              double* block_rms) {
+  if (!p || refine_sweeps < 0 || device < -1 || (flags & ~(uint32_t)RSBA_START_BOTH_SOLUTIONS) != 0) return RSBA_ERR_ARG;
   if (!p->is_marker_chain()) return RSBA_ERR_UNSUPPORTED;
   const int ndev = rsba::DeviceCount();
   if (ndev <= 0) return RSBA_ERR_NO_DEVICE;
@@ -3435,7 +3548,7 @@ int rsba_problem_start_scene(rsba_problem* p, const uint8_t* known_blocks, int32
   std::vector<int32_t> status(nb);
   std::vector<double> rms(nb, -1.0);
   for (size_t b = 0; b < nb; ++b) status[b] = plan.given[b] ? rsba::BLOCK_GIVEN : rsba::BLOCK_UNREACHED;
-  const int rc = RunStartPlan<true>(p, plan, device, "start_scene", &status, &rms);
+  const int rc = RunStartPlan<true>(p, plan, device, (flags & RSBA_START_BOTH_SOLUTIONS) != 0, "start_scene", &status, &rms);
   if (rc != RSBA_OK) return rc;
   int32_t missing[3] = {0, 0, 0};   // cameras, times, markers
   for (size_t b = 0; b < nb; ++b)

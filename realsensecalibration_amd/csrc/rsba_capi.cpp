@@ -193,6 +193,10 @@ int rsba_marker_pose_from_corners(const double* corners8, const double* intrinsi
                                   double* pose6, double* rms_or_null, int32_t* status_or_null) {
   return rsba::MarkerPoseFromCorners(corners8, intrinsics4, dist5_or_null, marker_side, pose6, rms_or_null, status_or_null);
 }
+int rsba_marker_pose_from_corners_both(const double* corners8, const double* intrinsics4, const double* dist5_or_null, double marker_side,
+                                       double* poses12, double* rms2_or_null, int32_t* status2_or_null) {
+  return rsba::MarkerPoseFromCornersBoth(corners8, intrinsics4, dist5_or_null, marker_side, poses12, rms2_or_null, status2_or_null);
+}
 int rsba_problem_initial_time_poses(rsba_problem* p, int32_t* num_missing_or_null) { return rsba::InitialTimePoses(p, num_missing_or_null); }
 
 int32_t rsba_problem_model(const rsba_problem* p) { return p ? p->model : -1; }
