@@ -299,6 +299,35 @@ int rsba_problem_set_distortion(rsba_problem* p, const double* dist /* 5 per cam
 /* the problem's copy of the coefficients; NULL when it has none */
 const double* rsba_problem_distortion(const rsba_problem* p);
 
+/* Free intrinsics on the marker-chain models: the solve refines a camera's fx fy cx cy k1 k2 (in Ceres: one more parameter block of six
+ * per camera handed to the functor, a SubsetParameterization holding the components that stay fixed).
+ * camera_idx: the detecting camera, indexed as the intrinsics and the coefficients are, the base camera included.  free_mask: bit q set =
+ * component q of (fx, fy, cx, cy, k1, k2) is refined; 0 (the default): the camera has no block, its values are constants of the
+ * problem.  p1 p2 k3 always are.  The projection is the five-coefficient model of rsba_problem_set_distortion; nothing about it changes.
+ * Host only.  camera_idx out of range, or bits above 5: RSBA_ERR_ARG.  The point model: RSBA_ERR_UNSUPPORTED.
+ * The masks are read at rsba_solver_create / rsba_solve and fixed for that solver.  With any mask non-zero:
+ *   - the solver takes the dense path whatever schur_impl says (rsba_solver_time_elimination reports 0); the columns of its linear
+ *     system are the pose columns in their order, then the intrinsics blocks in ascending camera index, six columns each.  A held
+ *     component of a block is treated as a constant component of a pose block is (rsba_problem_set_parameter_subset_constant): zero
+ *     rows, a zero step, its bits kept, and it counts in |x| — the parameter-tolerance test sees all six values of every block;
+ *   - a non-zero mask on a camera no observation names, or a dense system of more than 8192 columns: RSBA_ERR_UNSUPPORTED from
+ *     rsba_solver_create / rsba_solve, before anything is allocated;
+ *   - rsba_solve and rsba_solver_download write the refined values into the problem's intrinsics and distortion arrays (the problem
+ *     gets a distortion array, zeros elsewhere, when k1 or k2 is free and it had none): rsba_reprojection_error, rsba_write_outputs
+ *     and a later solver see them.  The parameter array, rsba_problem_num_parameters and every offset stay as they are;
+ *   - rsba_solver_run restarts from the uploaded state, intrinsics included; the summary, the iteration log, the progress table and
+ *     the full report (whose parameter counts include the blocks) work as before; so do rsba_solver_set_observation_weights and
+ *     rsba_solver_set_block_prior, a robust loss, constant blocks, constant components and priors on pose blocks;
+ *   - rsba_solver_evaluate, rsba_solver_evaluate_jacobian, rsba_solver_jacobian_structure, rsba_solver_covariance_compute and
+ *     rsba_solver_set_parameters return RSBA_ERR_UNSUPPORTED: their outputs are indexed by parameter offset and have no place for the
+ *     intrinsics blocks.
+ * All masks zero: the kernels and the bits of a problem on which this was never called. */
+int rsba_problem_set_intrinsics_free(rsba_problem* p, int32_t camera_idx, int32_t free_mask);
+/* the camera's mask; 0 when none was set */
+int32_t rsba_problem_intrinsics_free(const rsba_problem* p, int32_t camera_idx);
+/* the problem's intrinsics, 4 per camera (fx fy ppx ppy): the values it was created with, or a solve's refined ones */
+const double* rsba_problem_intrinsics(const rsba_problem* p);
+
 /* Test1 file "two_cam_data.txt": `C P`, P rows `cam pt u v` (one observation per point,
  * bundle_adjustmenter.cpp:62-64), C x (rvec row, tvec row), P rows xyz.  Also accepts the extended
  * first line `C P N` with N observation rows.  One intrinsics 4-vector is used for every

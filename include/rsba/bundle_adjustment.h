@@ -77,6 +77,19 @@ class BALProblem {
   // lens distortion (rsba_problem_set_distortion): 5 per camera, nullptr removes them / none set
   bool set_distortion(const double* dist) { return rsba_problem_set_distortion(p_, dist) == RSBA_OK; }
   const double* distortion() const { return rsba_problem_distortion(p_); }
+  // problem.AddParameterBlock(intrinsics_of_camera, 6) handed to the functor, with a SubsetParameterization for what stays fixed
+  // (rsba_problem_set_intrinsics_free): the listed components of the camera's (fx, fy, cx, cy, k1, k2), indices 0..5, are refined by
+  // the solve; an empty list makes them constants again.  False for a camera or an index out of range.  After a solve, intrinsics()
+  // and distortion() hold the refined values.
+  bool SetIntrinsicsFree(int camera_idx, const std::vector<int>& free_components) {
+    int mask = 0;
+    for (int q : free_components) { if (q < 0 || q > 5) return false; mask |= 1 << q; }
+    return rsba_problem_set_intrinsics_free(p_, camera_idx, mask) == RSBA_OK;
+  }
+  // the camera's fx, fy, ppx, ppy (nullptr for a camera out of range)
+  const double* intrinsics(int camera_idx) const {
+    return camera_idx >= 0 && camera_idx < num_cameras() ? rsba_problem_intrinsics(p_) + 4 * camera_idx : nullptr;
+  }
   // problem.SetParameterization(block, new ceres::SubsetParameterization(6, constant_parameters)) on a pose block handed out by the
   // mutable_* accessors above: the listed components of (rvec, tvec) are held (rsba_problem_set_parameter_subset_constant); an empty
   // list removes the subset.  False for a pointer that starts no pose block, an index outside 0..5 or all six components.

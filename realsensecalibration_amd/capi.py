@@ -39,7 +39,9 @@ EXPORTS = [
     "rsba_problem_set_block_prior", "rsba_problem_block_prior", "rsba_problem_num_block_priors", "rsba_solver_set_block_prior",
     "rsba_marker_pose_from_corners", "rsba_marker_poses_from_corners", "rsba_problem_initial_time_poses", "rsba_problem_start_rig", "rsba_problem_start_scene",
     "rsba_marker_pose_from_corners_both", "rsba_marker_poses_from_corners_both", "rsba_problem_start_rig2", "rsba_problem_start_scene2",
+    "rsba_problem_set_intrinsics_free", "rsba_problem_intrinsics_free", "rsba_problem_intrinsics",
 ]
+INTRINSICS_COMPONENTS = ("fx", "fy", "cx", "cy", "k1", "k2")   # bit q of rsba_problem_set_intrinsics_free's mask
 START_BOTH_SOLUTIONS = 1   # RSBA_START_BOTH_SOLUTIONS
 MARKER_POSE_SAME = 3       # RSBA_MARKER_POSE_SAME
 _SYMBOLS = EXPORTS   # (every symbol of include/rsba.h that load() checks)
@@ -187,6 +189,11 @@ def load():
     lib.rsba_problem_set_distortion.argtypes = [C.c_void_p, C.c_void_p]
     lib.rsba_problem_distortion.argtypes = [C.c_void_p]
     lib.rsba_problem_distortion.restype = C.POINTER(C.c_double)
+    lib.rsba_problem_set_intrinsics_free.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+    lib.rsba_problem_intrinsics_free.argtypes = [C.c_void_p, C.c_int32]
+    lib.rsba_problem_intrinsics_free.restype = C.c_int32
+    lib.rsba_problem_intrinsics.argtypes = [C.c_void_p]
+    lib.rsba_problem_intrinsics.restype = C.POINTER(C.c_double)
     lib.rsba_read_intrinsics_xml_dist.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p]
     lib.rsba_undistort_points.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.rsba_problem_set_block_prior.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
@@ -385,6 +392,31 @@ class Problem:
         """A copy of the problem's distortion coefficients (C x 5), or None when it has none."""
         q = load().rsba_problem_distortion(self.h)
         return np.ctypeslib.as_array(q, shape=(self.num_cameras, 5)).copy() if q else None
+
+    def set_intrinsics_free(self, camera, components):
+        """Marker-chain models: let the solve refine components of camera index `camera`'s intrinsics block fx fy cx cy k1 k2
+        (rsba_problem_set_intrinsics_free).  components: a 6-bit mask (bit q = component q is refined) or an iterable of names among
+        "fx", "fy", "cx", "cy", "k1", "k2"; 0 / empty: the camera's values are constants again.  Solvers created afterwards take the
+        dense path and write the refined values back into the problem (intrinsics, distortion) on download."""
+        if isinstance(components, (int, np.integer)):
+            mask = int(components)
+        else:
+            mask = 0
+            for name in ([components] if isinstance(components, str) else components):
+                if name not in INTRINSICS_COMPONENTS:
+                    raise ValueError("set_intrinsics_free: %r is not one of %s" % (name, ", ".join(INTRINSICS_COMPONENTS)))
+                mask |= 1 << INTRINSICS_COMPONENTS.index(name)
+        _chk(load().rsba_problem_set_intrinsics_free(self.h, int(camera), mask), "rsba_problem_set_intrinsics_free")
+
+    def intrinsics_free(self, camera):
+        """The camera's mask of refined intrinsics components; 0 when it has none."""
+        return int(load().rsba_problem_intrinsics_free(self.h, int(camera)))
+
+    @property
+    def intrinsics(self):
+        """A copy of the problem's intrinsics (C x 4: fx fy ppx ppy): the values it was created with, or a solve's refined ones."""
+        q = load().rsba_problem_intrinsics(self.h)
+        return np.ctypeslib.as_array(q, shape=(self.num_cameras, 4)).copy()
 
     def set_block_prior(self, parameter_offset, A, b=None):
         """Marker-chain models: a Gaussian prior (ceres::NormalPrior) on the camera or marker block at `parameter_offset`: the

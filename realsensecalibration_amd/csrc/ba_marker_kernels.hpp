@@ -393,6 +393,269 @@ __global__ void __launch_bounds__(64) k_marker_prior_rows(int K, int N, const Ma
   rho[N + k] = ss;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Free intrinsics (rsba_problem_set_intrinsics_free): a fourth block per residual, the detecting camera's six values
+// fx fy cx cy k1 k2.  Kernels of their own: a solver without free intrinsics runs the instances above, untouched.
+//   state:  the vectors params[2] / params0 continue behind the nfull pose values with six values per camera (every camera, free
+//           or not), camera k at nfull + 6 k; p1 p2 k3 stay in dist [C][5] (zeros where the problem has no coefficients)
+//   rows:   8 x 24 per residual block, columns camera | time | marker | intrinsics; the 18 pose columns by dual numbers as
+//           k_marker_eval<., true> forms them, the six others analytic:
+//             du / d (fx cx k1 k2) = xd, 1, fx x r2, fx x r2^2     dv / d (fy cy k1 k2) = yd, 1, fy y r2, fy y r2^2
+//   icol:   [C] the first column of a camera's intrinsics block in the linear system, -1: the camera has none
+//   pad:    bits 18..23 of MarkerObs::pad mark the held components of the block (all six where the camera has none)
+// ------------------------------------------------------------------------------------------------
+#define RSBA_INTR_MAX_COLUMNS 8192   // active columns of the dense system above which a solver with free intrinsics is refused
+
+// the constant columns of the stored 8 x 24 rows as exact zeros (k_marker_subset_rows at this width).  Thread per entry.
+__global__ void __launch_bounds__(256) k_marker_intr_subset_rows(int N, const MarkerObs* __restrict__ mo, double* __restrict__ Jbuf) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (size_t)N * 192) return;
+  const int i = (int)(e / 192), q = (int)(e - (size_t)i * 192) % 24;
+  if ((mo[i].pad >> q) & 1) Jbuf[e] = 0.0;
+}
+
+// Always with the corrector and the weights (k_marker_eval<true, true>): loss = 0 and weights of one change no bit, so a solver
+// without either passes those.
+__global__ void __launch_bounds__(64) k_marker_intr_eval(int N, const MarkerObs* __restrict__ mo, const double* __restrict__ obs8,
+                              const double* __restrict__ params, int nfull, const double* __restrict__ dist, double half_side,
+                              int with_jacobian, double* __restrict__ Jbuf, double* __restrict__ rbuf,
+                              double* __restrict__ sumsq_per_obs, double loss, double* __restrict__ rho_per_obs,
+                              const double* __restrict__ wts) {
+  __shared__ double stage[64 * 49];   // (k_marker_eval's staging, 48 doubles per corner and the corrector's word)
+  const int i0 = blockIdx.x * blockDim.x, i = i0 + threadIdx.x;
+  const bool live = i < N;
+  const int ii = live ? i : N - 1;
+  const MarkerObs o = mo[ii];
+  const double* __restrict__ sv = params + nfull + 6 * (size_t)o.camera;
+  const double fx = sv[0], fy = sv[1], ppx = sv[2], ppy = sv[3];
+  const double kd5[5] = {sv[4], sv[5], dist[5 * o.camera + 2], dist[5 * o.camera + 3], dist[5 * o.camera + 4]};
+  const double cx[4] = {-half_side, half_side, half_side, -half_side};
+  const double cy[4] = {half_side, half_side, -half_side, -half_side};
+  double ss = 0.0;
+  if (!with_jacobian) {
+    for (int k = 0; k < 4; ++k) {
+      double p[3] = {cx[k], cy[k], 0.0};
+      if (o.full_marker >= 0) { const double* m = params + o.full_marker; RotateD(m, p); p[0] += m[3]; p[1] += m[4]; p[2] += m[5]; }
+      { const double* t = params + o.full_time; RotateD(t, p); p[0] += t[3]; p[1] += t[4]; p[2] += t[5]; }
+      if (o.full_cam >= 0) { const double* c = params + o.full_cam; RotateD(c, p); p[0] += c[3]; p[1] += c[4]; p[2] += c[5]; }
+      double r0, r1;
+      ProjectCornerResidual<true>(p[0], p[1], p[2], fx, fy, ppx, ppy, kd5, obs8[8 * (size_t)ii + 2 * k], obs8[8 * (size_t)ii + 2 * k + 1], &r0, &r1);
+      ss += r0 * r0 + r1 * r1;
+    }
+  } else {
+    typedef DJet<18> J;
+    J cam[6], tim[6], mar[6];
+    for (int q = 0; q < 6; ++q) {
+      cam[q] = o.full_cam >= 0 ? JVar<18>(params[o.full_cam + q], q) : JConst<18>(0.0);
+      tim[q] = JVar<18>(params[o.full_time + q], 6 + q);
+      mar[q] = o.full_marker >= 0 ? JVar<18>(params[o.full_marker + q], 12 + q) : JConst<18>(0.0);
+    }
+    for (int k = 0; k < 4; ++k) {
+      J p[3] = {JConst<18>(cx[k]), JConst<18>(cy[k]), JConst<18>(0.0)};
+      if (o.full_marker >= 0) { RotateJet<18>(mar, p); p[0] = p[0] + mar[3]; p[1] = p[1] + mar[4]; p[2] = p[2] + mar[5]; }
+      RotateJet<18>(tim, p); p[0] = p[0] + tim[3]; p[1] = p[1] + tim[4]; p[2] = p[2] + tim[5];
+      if (o.full_cam >= 0) { RotateJet<18>(cam, p); p[0] = p[0] + cam[3]; p[1] = p[1] + cam[4]; p[2] = p[2] + cam[5]; }
+      J kd[5], xd, yd;
+      for (int q = 0; q < 5; ++q) kd[q] = JConst<18>(kd5[q]);
+      const J xn = p[0] / p[2], yn = p[1] / p[2];
+      DistortNormalised(xn, yn, kd, JConst<18>(1.0), JConst<18>(2.0), &xd, &yd);
+      const J xp = JConst<18>(fx) * xd + JConst<18>(ppx);
+      const J yp = JConst<18>(fy) * yd + JConst<18>(ppy);
+      const double r0 = xp.a - obs8[8 * (size_t)ii + 2 * k], r1 = yp.a - obs8[8 * (size_t)ii + 2 * k + 1];
+      if (live) { rbuf[8 * (size_t)i + 2 * k] = r0; rbuf[8 * (size_t)i + 2 * k + 1] = r1; }
+      double* __restrict__ su = stage + threadIdx.x * 49;
+      double* __restrict__ sw = su + 24;
+      for (int q = 0; q < 18; ++q) { su[q] = xp.v[q]; sw[q] = yp.v[q]; }
+      {
+        // the intrinsics columns: the projection is linear in each of the six
+        const double r2 = xn.a * xn.a + yn.a * yn.a;
+        const double gx = fx * xn.a * r2, gy = fy * yn.a * r2;
+        su[18] = xd.a; su[19] = 0.0; su[20] = 1.0; su[21] = 0.0; su[22] = gx; su[23] = gx * r2;
+        sw[18] = 0.0; sw[19] = yd.a; sw[20] = 0.0; sw[21] = 1.0; sw[22] = gy; sw[23] = gy * r2;
+      }
+      __syncthreads();
+      {
+        const int nlive = min(64, N - i0);
+        for (int e = threadIdx.x; e < nlive * 48; e += 64) { const int t = e / 48, q = e - 48 * t; Jbuf[(size_t)(i0 + t) * 192 + 48 * k + q] = stage[t * 49 + q]; }
+      }
+      __syncthreads();
+      ss += r0 * r0 + r1 * r1;
+    }
+    {
+      // (k_marker_eval's corrector and weight, over all 24 columns)
+      double sq;
+      const double a = wts[ii];
+      const double rho = a * LossAndScale(loss, ss, &sq);
+      sq *= sqrt(a);
+      if (live) {
+        rho_per_obs[i] = rho;
+        for (int e = 0; e < 8; ++e) rbuf[8 * (size_t)i + e] *= sq;
+      }
+      stage[threadIdx.x * 49 + 48] = sq;
+      __threadfence_block();
+      __syncthreads();
+      const int nlive = min(64, N - i0);
+      for (int e = threadIdx.x; e < nlive * 192; e += 64) Jbuf[(size_t)i0 * 192 + e] *= stage[(e / 192) * 49 + 48];
+    }
+  }
+  if (!with_jacobian && live) { double sq; rho_per_obs[i] = wts[i] * LossAndScale(loss, ss, &sq); }
+  if (live) sumsq_per_obs[i] = ss;
+}
+
+// the first column of local column q (0..23) of residual block ob; blocks N.. are the priors' pseudo-blocks: no intrinsics columns
+__device__ __forceinline__ int MarkerIntrColumn(const MarkerObs& o, int q, int ob, int N, const int* __restrict__ icol) {
+  const int b = q / 6;
+  const int base = b == 0 ? o.act_cam : (b == 1 ? o.act_time : (b == 2 ? o.act_marker : (ob < N ? icol[o.camera] : -1)));
+  return base < 0 ? -1 : base + (q - 6 * b);
+}
+
+// k_marker_system<., true> over the 24 columns.  N: the observations, NK: with the priors' pseudo-blocks behind them.
+template <int kThreads>
+__global__ void __launch_bounds__(kThreads)
+k_marker_intr_system(int N, int NK, int n, const MarkerObs* __restrict__ mo, const int* __restrict__ icol, const double* __restrict__ Jbuf,
+                     const double* __restrict__ rbuf, const double* __restrict__ sumsq_per_obs, double* __restrict__ A,
+                     double* __restrict__ scale, double* __restrict__ grad, const int* __restrict__ act_to_full,
+                     const double* __restrict__ params_x, double* __restrict__ params_c, double* __restrict__ delta_act,
+                     double* __restrict__ res, IterParams ip) {
+  extern __shared__ double lds[];
+  const int tid = threadIdx.x, nt = blockDim.x;
+  __shared__ int s_ok;
+  for (size_t e = tid; e < (size_t)n * n; e += nt) A[e] = 0.0;
+  for (int i = tid; i < n; i += nt) { A[(size_t)n * n + i] = 0.0; }
+  __syncthreads();
+  for (int ob = 0; ob < NK; ++ob) {
+    const MarkerObs o = mo[ob];
+    // 24 x 24 local block, 576 entries over the threads
+    for (int e = tid; e < 576; e += nt) {
+      const int a = e / 24, b = e - 24 * a;
+      const int ca = MarkerIntrColumn(o, a, ob, N, icol), cb = MarkerIntrColumn(o, b, ob, N, icol);
+      if (ca < 0 || cb < 0) continue;
+      double s = 0.0;
+      for (int r = 0; r < 8; ++r) s += Jbuf[(size_t)(8 * ob + r) * 24 + a] * Jbuf[(size_t)(8 * ob + r) * 24 + b];
+      A[(size_t)ca * n + cb] += s;
+    }
+    for (int a = tid; a < 24; a += nt) {
+      const int ca = MarkerIntrColumn(o, a, ob, N, icol);
+      if (ca < 0) continue;
+      double s = 0.0;
+      for (int r = 0; r < 8; ++r) s += Jbuf[(size_t)(8 * ob + r) * 24 + a] * rbuf[8 * (size_t)ob + r];
+      A[(size_t)n * n + ca] += s;
+    }
+    __threadfence_block();
+    __syncthreads();
+  }
+  for (int i = tid; i < n; i += nt) if (act_to_full[i] & RSBA_SUBSET_BIT) A[(size_t)i * n + i] = 1.0;
+  __threadfence_block();
+  __syncthreads();
+  for (int i = tid; i < n; i += nt) {
+    grad[i] = A[(size_t)n * n + i];
+    if (ip.first) scale[i] = ip.jacobi_scaling ? 1.0 / (1.0 + sqrt(A[(size_t)i * n + i])) : 1.0;
+  }
+  __threadfence_block();
+  __syncthreads();
+  for (size_t e = tid; e < (size_t)n * n; e += nt) {
+    const int i = (int)(e / n), j = (int)(e - (size_t)i * n);
+    double v = A[e] * (scale[i] * scale[j]);
+    if (i == j) v += fmin(fmax(v, ip.min_lm_diagonal), ip.max_lm_diagonal) / ip.radius;
+    A[e] = v;
+  }
+  for (int i = tid; i < n; i += nt) A[(size_t)n * n + i] *= scale[i];
+  __threadfence_block();
+  __syncthreads();
+  double* ysol = A + (size_t)n * n;
+  if (kThreads == 512) CholeskySolvePanelLDS(n, A, ysol, &s_ok, lds, PanelSource{nullptr, nullptr, nullptr, 0.0, 0.0, 0.0, nullptr, nullptr, 0});
+  else CholeskySolveBlocked<2>(n, A, ysol, &s_ok, lds);   // (a copy of its own: see CholeskySolveBlocked)
+  __syncthreads();
+  double* scr = lds;
+  double d2 = 0, x2 = 0, xc2 = 0, gm = 0;
+  for (int i = tid; i < n; i += nt) {
+    const double d = -scale[i] * ysol[i];
+    delta_act[i] = d;
+    const int fi = act_to_full[i] & ~RSBA_SUBSET_BIT;
+    const double x = params_x[fi], xc = x + d;
+    params_c[fi] = xc;
+    d2 += d * d; x2 += x * x; xc2 += xc * xc; gm = fmax(gm, fabs(grad[i]));
+  }
+  double cs = 0;
+  for (int i = tid; i < NK; i += nt) cs += sumsq_per_obs[i];
+  scr[tid] = d2; scr[nt + tid] = x2; scr[2 * nt + tid] = xc2; scr[3 * nt + tid] = gm; scr[4 * nt + tid] = cs;
+  __syncthreads();
+  for (int off = nt / 2; off > 0; off >>= 1) {
+    if (tid < off) {
+      scr[tid] += scr[tid + off]; scr[nt + tid] += scr[nt + tid + off]; scr[2 * nt + tid] += scr[2 * nt + tid + off];
+      scr[3 * nt + tid] = fmax(scr[3 * nt + tid], scr[3 * nt + tid + off]); scr[4 * nt + tid] += scr[4 * nt + tid + off];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    res[RES_COST_X] = 0.5 * scr[4 * nt]; res[RES_GMAX] = scr[3 * nt]; res[RES_XNORM2] = scr[nt];
+    res[RES_CHOL_OK] = s_ok ? 1.0 : 0.0; res[RES_STEP2] = scr[0]; res[RES_XCNORM2] = scr[2 * nt]; res[RES_POINT_FAIL] = 0.0;
+  }
+}
+
+// k_marker_candidate<true> over the 24 columns
+__global__ void __launch_bounds__(256)
+k_marker_intr_candidate(int N, int NK, const MarkerObs* __restrict__ mo, const int* __restrict__ icol, const double* __restrict__ Jbuf,
+                        const double* __restrict__ rbuf, const double* __restrict__ delta_act, const double* __restrict__ sumsq_c,
+                        double* __restrict__ res, const double* __restrict__ rho_c) {
+  __shared__ double s[3][256];
+  const int tid = threadIdx.x;
+  double mcc = 0, cc = 0, rc = 0;
+  for (int i = tid; i < NK; i += blockDim.x) {
+    const MarkerObs o = mo[i];
+    int col[24];
+    for (int q = 0; q < 24; ++q) col[q] = MarkerIntrColumn(o, q, i, N, icol);
+    for (int r = 0; r < 8; ++r) {
+      double mr = 0.0;
+      for (int q = 0; q < 24; ++q) if (col[q] >= 0) mr += Jbuf[(size_t)(8 * i + r) * 24 + q] * delta_act[col[q]];
+      mcc -= mr * (rbuf[8 * (size_t)i + r] + 0.5 * mr);
+    }
+    cc += sumsq_c[i];
+    rc += rho_c[i];
+  }
+  s[0][tid] = mcc; s[1][tid] = cc;
+  s[2][tid] = rc;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (tid < off) { s[0][tid] += s[0][tid + off]; s[1][tid] += s[1][tid + off]; s[2][tid] += s[2][tid + off]; }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    res[RES_MCC] = s[0][0];
+    double c = 0.5 * s[2][0];
+    if (!(c == c) || !(fabs(c) <= DBL_MAX)) c = DBL_MAX;
+    res[RES_COST_C] = c; res[RES_SUMSQ_C] = s[1][0];
+  }
+}
+
+// k_marker_prior_rows at 24 columns: the six intrinsics columns of a prior's pseudo-block are zeros
+__global__ void __launch_bounds__(64) k_marker_intr_prior_rows(int K, int N, const MarkerObs* __restrict__ mo, const int* __restrict__ mask,
+                                                               const double* __restrict__ ab, const double* __restrict__ params, int with_rows,
+                                                               double* __restrict__ Jbuf, double* __restrict__ rbuf, double* __restrict__ sumsq,
+                                                               double* __restrict__ rho) {
+  const int k = blockIdx.x * 64 + threadIdx.x;
+  if (k >= K) return;
+  const MarkerObs o = mo[N + k];
+  const int g = o.full_cam >= 0 ? 0 : 12;
+  const double* __restrict__ A = ab + 42 * (size_t)k;
+  const double* __restrict__ x = params + (o.full_cam >= 0 ? o.full_cam : o.full_marker);
+  double d[6], ss = 0.0;
+  for (int q = 0; q < 6; ++q) d[q] = x[q] - A[36 + q];
+  for (int i = 0; i < 8; ++i) {
+    double r = 0.0;
+    if (i < 6) for (int q = 0; q < 6; ++q) r += A[6 * i + q] * d[q];
+    ss += r * r;
+    if (with_rows) {
+      rbuf[8 * (size_t)(N + k) + i] = r;
+      double* __restrict__ row = Jbuf + ((size_t)(N + k) * 8 + i) * 24;
+      for (int q = 0; q < 24; ++q) row[q] = 0.0;
+      if (i < 6) for (int q = 0; q < 6; ++q) row[g + q] = ((mask[k] >> q) & 1) ? 0.0 : A[6 * i + q];
+    }
+  }
+  sumsq[N + k] = 0.0;
+  rho[N + k] = ss;
+}
+
 
 struct MarkerDevice {
   int N = 0, n = 0, nfull = 0;
@@ -410,10 +673,16 @@ struct MarkerDevice {
   bool with_dist = false;   // the kDist instances (Upload): some distortion coefficient of the problem is not zero
   double* dist = nullptr;   // [C][5], indexed as intr
   PriorDevice prior;        // K priors: K pseudo residual blocks behind the N observations' (k_marker_prior_rows); with_loss then
+  // free intrinsics (rsba_problem_set_intrinsics_free): the k_marker_intr_* kernels, rows of 24 columns, with_loss always (ones for the
+  // weights, loss 0 where the solver has neither) and dist always there (zeros where the problem has no coefficients)
+  bool with_intr = false;
+  int nstate = 0;           // doubles of params[2] / params0: nfull, with_intr: + 6 per camera (fx fy cx cy k1 k2)
+  int* icol = nullptr;      // [C] first column of the camera's intrinsics block, -1: none (with_intr only)
+  std::vector<int> intr_mask;   // [C] the masks this solver was created with (with_intr only)
 
   void Free() {
     prior.Free();
-    void* ptrs[] = {mo, obs8, intr, params[0], params[1], params0, Jbuf, rbuf, ss_x, ss_c, A, scale, grad, delta, res, act_to_full, rho_x, rho_c, wts, dist};
+    void* ptrs[] = {mo, obs8, intr, params[0], params[1], params0, Jbuf, rbuf, ss_x, ss_c, A, scale, grad, delta, res, act_to_full, rho_x, rho_c, wts, dist, icol};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     mo = nullptr;
   }
@@ -437,6 +706,28 @@ struct MarkerDevice {
       for (int q = 0; q < 6; ++q) a2f.push_back((6 * b + q) | (((mask >> q) & 1) ? RSBA_SUBSET_BIT : 0));
     }
     n = 6 * na;
+    // free intrinsics: the blocks behind the pose columns, ascending camera index; a held component is a marked column, as a pose block's.
+    // Refusals come before anything is allocated.
+    const int C = p.num_cameras;
+    with_intr = p.has_free_intrinsics();
+    std::vector<int> hicol(C, -1);
+    intr_mask.assign(with_intr ? C : 0, 0);
+    if (with_intr) {
+      std::vector<char> named(C, 0);
+      for (int i = 0; i < N; ++i) named[p.camera_index[i]] = 1;
+      for (int k = 0; k < C; ++k) {
+        const int mask = p.intrinsics_free_mask(k);
+        if (mask == 0) continue;
+        if (!named[k]) return RSBA_ERR_UNSUPPORTED;   // (like a prior on a block no observation names)
+        if (n + 6 > RSBA_INTR_MAX_COLUMNS) return RSBA_ERR_UNSUPPORTED;   // one workgroup factors the dense system
+        intr_mask[k] = mask; hicol[k] = n; n += 6;
+        for (int q = 0; q < 6; ++q) a2f.push_back((nfull + 6 * k + q) | (((mask >> q) & 1) ? 0 : RSBA_SUBSET_BIT));
+      }
+      if (n > RSBA_INTR_MAX_COLUMNS) return RSBA_ERR_UNSUPPORTED;
+      with_loss = true;
+    }
+    nstate = nfull + (with_intr ? 6 * C : 0);
+    const int ncols = with_intr ? 24 : 18;   // columns of a stored row
     const int K = (int)p.block_priors.size();
     std::vector<int> pcols;
     std::vector<MarkerObs> h(N + K);
@@ -462,11 +753,12 @@ struct MarkerDevice {
       if (o.act_cam >= 0) o.pad |= p.subset_mask(p.camera_block(i));
       if (o.act_time >= 0) o.pad |= p.subset_mask(p.time_block(i)) << 6;
       if (o.act_marker >= 0) o.pad |= p.subset_mask(p.marker_block(i)) << 12;
+      if (with_intr) o.pad |= (hicol[o.camera] >= 0 ? (~intr_mask[o.camera] & 63) : 63) << 18;
     }
     auto al = [](void** q, size_t bytes) { return hipMalloc(q, std::max<size_t>(bytes, 8)) == hipSuccess; };
     if (!al((void**)&mo, NK * sizeof(MarkerObs)) || !al((void**)&obs8, 8 * (size_t)N * 8) || !al((void**)&intr, p.intrinsics.size() * 8) ||
-        !al((void**)&params[0], nfull * 8) || !al((void**)&params[1], nfull * 8) || !al((void**)&params0, nfull * 8) ||
-        !al((void**)&Jbuf, (size_t)NK * 8 * 18 * 8) || !al((void**)&rbuf, (size_t)NK * 8 * 8) || !al((void**)&ss_x, NK * 8) || !al((void**)&ss_c, NK * 8) ||
+        !al((void**)&params[0], (size_t)nstate * 8) || !al((void**)&params[1], (size_t)nstate * 8) || !al((void**)&params0, (size_t)nstate * 8) ||
+        !al((void**)&Jbuf, (size_t)NK * 8 * ncols * 8) || !al((void**)&rbuf, (size_t)NK * 8 * 8) || !al((void**)&ss_x, NK * 8) || !al((void**)&ss_c, NK * 8) ||
         !al((void**)&A, (size_t)(n + 2) * n * 8) || !al((void**)&scale, n * 8) || !al((void**)&grad, n * 8) || !al((void**)&delta, n * 8) ||
         !al((void**)&res, RES_SIZE * 8) || !al((void**)&act_to_full, n * sizeof(int)) || !al((void**)&rho_x, NK * 8) || !al((void**)&rho_c, NK * 8))
       return RSBA_ERR_HIP;
@@ -477,6 +769,19 @@ struct MarkerDevice {
     if (hipMemcpy(params0, p.parameters.data(), nfull * 8, hipMemcpyHostToDevice) != hipSuccess) return RSBA_ERR_HIP;
     if (hipMemcpy(act_to_full, a2f.data(), n * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return RSBA_ERR_HIP;
     with_dist = p.has_distortion();
+    if (with_intr) {
+      // the state behind the poses, and the coefficients as an array that is always there
+      std::vector<double> hs(6 * (size_t)C), hd(5 * (size_t)C, 0.0);
+      if (!p.distortion.empty()) hd = p.distortion;
+      for (int k = 0; k < C; ++k) {
+        for (int q = 0; q < 4; ++q) hs[6 * (size_t)k + q] = p.intrinsics[4 * (size_t)k + q];
+        hs[6 * (size_t)k + 4] = hd[5 * (size_t)k]; hs[6 * (size_t)k + 5] = hd[5 * (size_t)k + 1];
+      }
+      if (!al((void**)&icol, C * sizeof(int)) || !al((void**)&dist, hd.size() * 8) ||
+          hipMemcpy(icol, hicol.data(), C * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
+          hipMemcpy(dist, hd.data(), hd.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
+          hipMemcpy(params0 + nfull, hs.data(), hs.size() * 8, hipMemcpyHostToDevice) != hipSuccess) return RSBA_ERR_HIP;
+    } else
     if (with_dist && (!al((void**)&dist, p.distortion.size() * 8) ||
                       hipMemcpy(dist, p.distortion.data(), p.distortion.size() * 8, hipMemcpyHostToDevice) != hipSuccess)) return RSBA_ERR_HIP;
     if (with_loss) {
@@ -491,8 +796,8 @@ struct MarkerDevice {
     return N == 0 || hipMemcpy(wts, w, (size_t)N * 8, hipMemcpyHostToDevice) == hipSuccess ? RSBA_OK : RSBA_ERR_HIP;
   }
   int Reset(hipStream_t st) {
-    if (hipMemcpyAsync(params[0], params0, nfull * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return RSBA_ERR_HIP;
-    if (hipMemcpyAsync(params[1], params0, nfull * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return RSBA_ERR_HIP;
+    if (hipMemcpyAsync(params[0], params0, (size_t)nstate * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return RSBA_ERR_HIP;
+    if (hipMemcpyAsync(params[1], params0, (size_t)nstate * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return RSBA_ERR_HIP;
     cur = 0;
     return RSBA_OK;
   }
@@ -507,13 +812,14 @@ struct MarkerDevice {
     const double loss = o.huber_delta > 0.0 ? (o.loss_type == RSBA_LOSS_CAUCHY ? -o.huber_delta : o.huber_delta) : 0.0;
     const int x = cur, c = 1 - cur;
     // the candidate array must carry the untouched blocks too
-    if (hipMemcpyAsync(params[c], params[x], nfull * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return RSBA_ERR_HIP;
+    if (hipMemcpyAsync(params[c], params[x], (size_t)nstate * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return RSBA_ERR_HIP;
     auto chk = [&](const char* what) {
       hipError_t e = hipGetLastError();
       if (e != hipSuccess) { fprintf(stderr, "rsba: %s launch failed: %s\n", what, hipGetErrorString(e)); return false; }
       return true;
     };
     if (!chk("(before marker step)")) return RSBA_ERR_HIP;
+    if (with_intr) return StepIntr(st, ip, loss, res_host, T);
     T.Begin("k_marker_eval", st);
     if (with_dist) {
       if (with_loss) k_marker_eval<true, true><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[x], IntrDist{intr, dist}, half_side, 1, Jbuf, rbuf, ss_x, loss, rho_x, wts);
@@ -573,6 +879,54 @@ struct MarkerDevice {
     { hipError_t e = hipStreamSynchronize(st); if (e != hipSuccess) { fprintf(stderr, "rsba: marker-chain step failed: %s\n", hipGetErrorString(e)); return RSBA_ERR_HIP; } }
     return RSBA_OK;
   }
+  // The step of a solver with free intrinsics: the same five stages on rows of 24 columns, every one reading the state's intrinsics.
+  template <typename Timer>
+  int StepIntr(hipStream_t st, const IterParams& ip, double loss, double* res_host, Timer& T) {
+    const int x = cur, c = 1 - cur, NK = N + prior.K;
+    auto chk = [&](const char* what) {
+      hipError_t e = hipGetLastError();
+      if (e != hipSuccess) { fprintf(stderr, "rsba: %s launch failed: %s\n", what, hipGetErrorString(e)); return false; }
+      return true;
+    };
+    T.Begin("k_marker_intr_eval", st);
+    k_marker_intr_eval<<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[x], nfull, dist, half_side, 1, Jbuf, rbuf, ss_x, loss, rho_x, wts);
+    T.End(st);
+    if (!chk("k_marker_intr_eval")) return RSBA_ERR_HIP;
+    T.Begin("k_marker_intr_subset_rows", st);
+    k_marker_intr_subset_rows<<<(unsigned)(((size_t)N * 192 + 255) / 256), 256, 0, st>>>(N, mo, Jbuf);
+    T.End(st);
+    if (prior.K > 0) {
+      T.Begin("k_marker_intr_prior_rows", st);
+      k_marker_intr_prior_rows<<<(prior.K + 63) / 64, 64, 0, st>>>(prior.K, N, mo, prior.mask, prior.ab, params[x], 1, Jbuf, rbuf, ss_x, rho_x);
+      T.End(st);
+    }
+    size_t lds = (size_t)std::max(2 * RSBA_TB * (RSBA_NB + 1) + RSBA_NB * (RSBA_NB + 1), 5 * 1024) * sizeof(double);
+    if (n <= RSBA_CHOL_MAXN) lds = std::max(lds, CholeskyLdsDoubles(n) * sizeof(double));
+    T.Begin("k_marker_intr_system", st);
+    if (n <= RSBA_CHOL_MAXN) {
+      if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k_marker_intr_system<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      k_marker_intr_system<512><<<1, 512, lds, st>>>(N, NK, n, mo, icol, Jbuf, rbuf, rho_x, A, scale, grad, act_to_full, params[x], params[c], delta, res, ip);
+    } else {
+      k_marker_intr_system<1024><<<1, 1024, lds, st>>>(N, NK, n, mo, icol, Jbuf, rbuf, rho_x, A, scale, grad, act_to_full, params[x], params[c], delta, res, ip);
+    }
+    T.End(st);
+    if (!chk("k_marker_intr_system")) return RSBA_ERR_HIP;
+    T.Begin("k_marker_intr_eval", st);
+    k_marker_intr_eval<<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[c], nfull, dist, half_side, 0, nullptr, nullptr, ss_c, loss, rho_c, wts);
+    T.End(st);
+    if (prior.K > 0) {
+      T.Begin("k_marker_intr_prior_rows", st);
+      k_marker_intr_prior_rows<<<(prior.K + 63) / 64, 64, 0, st>>>(prior.K, N, mo, prior.mask, prior.ab, params[c], 0, nullptr, nullptr, ss_c, rho_c);
+      T.End(st);
+    }
+    T.Begin("k_marker_intr_candidate", st);
+    k_marker_intr_candidate<<<1, 256, 0, st>>>(N, NK, mo, icol, Jbuf, rbuf, delta, ss_c, res, rho_c);
+    T.End(st);
+    if (!chk("k_marker_intr_candidate")) return RSBA_ERR_HIP;
+    if (hipMemcpyAsync(res_host, res, RES_SIZE * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess) return RSBA_ERR_HIP;
+    { hipError_t e = hipStreamSynchronize(st); if (e != hipSuccess) { fprintf(stderr, "rsba: marker-chain step failed: %s\n", hipGetErrorString(e)); return RSBA_ERR_HIP; } }
+    return RSBA_OK;
+  }
   int SumSquares(hipStream_t st, double* out) {
     if (Reset(st) != RSBA_OK) return RSBA_ERR_HIP;
     if (with_dist) k_marker_eval<false, true><<<(N + 63) / 64, 64, 0, st>>>(N, mo, obs8, params[0], IntrDist{intr, dist}, half_side, 0, nullptr, nullptr, ss_x);
@@ -585,6 +939,19 @@ struct MarkerDevice {
   }
   int Download(rsba_problem* p) {
     if (hipMemcpy(p->parameters.data(), params[cur], nfull * 8, hipMemcpyDeviceToHost) != hipSuccess) return RSBA_ERR_HIP;
+    if (with_intr) {
+      // the refined values into the problem's own arrays (a camera without a block, and a held component, keep their bits: the
+      // state started from them); a distortion array appears when k1 or k2 was free and the problem had none
+      const int C = (int)intr_mask.size();
+      std::vector<double> hs(6 * (size_t)C);
+      if (hipMemcpy(hs.data(), params[cur] + nfull, hs.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return RSBA_ERR_HIP;
+      for (int k = 0; k < C; ++k) {
+        if (intr_mask[k] == 0) continue;
+        for (int q = 0; q < 4; ++q) p->intrinsics[4 * (size_t)k + q] = hs[6 * (size_t)k + q];
+        if ((intr_mask[k] & 0x30) && p->distortion.empty()) p->distortion.assign(5 * (size_t)C, 0.0);
+        if (!p->distortion.empty()) { p->distortion[5 * (size_t)k] = hs[6 * (size_t)k + 4]; p->distortion[5 * (size_t)k + 1] = hs[6 * (size_t)k + 5]; }
+      }
+    }
     return RSBA_OK;
   }
 };

@@ -34,6 +34,8 @@ struct rsba_problem {
                                          // constant (ceres::SubsetParameterization); empty = none
   std::vector<double> observation_weights;   // marker-chain models: a_i >= 0 per residual block (ceres::ScaledLoss); empty = none
   std::vector<double> distortion;     // marker-chain models: 5 per camera (k1 k2 p1 p2 k3, OpenCV), indexed as intrinsics; empty = none
+  std::vector<uint8_t> intrinsics_free;   // marker-chain models: per camera a 6-bit mask, bit q set = component q of (fx fy cx cy k1 k2) is
+                                          // refined by the solve (the camera's intrinsics block); empty = none
   std::map<int, std::array<double, 42>> block_priors;   // marker-chain models: block of [C | T | M] -> A (6 x 6 row-major) then b (6): the
                                                         // residual A (x - b) with no loss (ceres::NormalPrior); camera and marker blocks only
 
@@ -44,6 +46,9 @@ struct rsba_problem {
   bool has_distortion() const { for (double v : distortion) if (v != 0.0) return true; return false; }
   // some block carries a non-zero subset mask: a solver then masks those components' columns (none, or all zero: today's kernels)
   bool has_subset() const { for (uint8_t v : block_subset) if (v != 0) return true; return false; }
+  // some camera has free intrinsics: a solver then takes the dense path with the intrinsics blocks behind the pose columns
+  bool has_free_intrinsics() const { for (uint8_t v : intrinsics_free) if (v != 0) return true; return false; }
+  int intrinsics_free_mask(int camera) const { return camera >= 0 && camera < (int)intrinsics_free.size() ? intrinsics_free[camera] : 0; }
   int subset_mask(int block) const { return block >= 0 && block < (int)block_subset.size() ? block_subset[block] : 0; }
   // wiring rules of bundle_adjustment_manager.cpp:26-87 / Test2 main.cpp:64-96
   bool uses_camera(int64_t i) const { return camera_index[i] != 0; }

@@ -375,6 +375,8 @@ struct rsba_solver {
   std::vector<uint8_t> eval_const_cam, eval_const_pt, eval_const_block;   // the problem's constant flags as they were at create
   std::vector<uint8_t> eval_subset;   // marker chain: the blocks' masks of constant components as they were at create (empty: none set)
   int num_priors = 0;                 // marker chain: the priors (rsba_problem_set_block_prior) the solver was created with
+  bool free_intrinsics = false;       // marker chain: some camera's intrinsics are refined (rsba_problem_set_intrinsics_free): the dense path with
+                                      // MarkerDevice's k_marker_intr_* kernels; evaluate, the Jacobian, the covariance and set_parameters are refused
 
   // ---- the three above on a solver with a communicator (ShardedQuery): the request word and the camera check travel from here
   double* query_buf = nullptr;                 // device scratch, kept between calls (grows only)
@@ -2588,7 +2590,11 @@ int rsba_solver_create(rsba_problem* p, const rsba_options* o, rsba_solver** out
     rc = rsba::UploadPoints(s);
     if (rc == RSBA_OK && s->tiled.tree_error) s->tiled.error_flag = reinterpret_cast<int*>(s->res_host + RES_SIZE + 4);   // (zeroed above)
   } else {
-    s->eliminate_times = rsba::MarkerSchurDevice::Wanted(*p, opt.schur_impl);
+    // free intrinsics (rsba_problem_set_intrinsics_free): the dense path whatever schur_impl says — the time-eliminating kernels have
+    // two slots per residual block; read here and fixed for this solver, like the masks of constant components
+    if (!p->intrinsics_free.empty() && p->intrinsics_free.size() != (size_t)p->num_cameras) { rsba::FreeSolver(s); return RSBA_ERR_ARG; }
+    s->free_intrinsics = p->has_free_intrinsics();
+    s->eliminate_times = !s->free_intrinsics && rsba::MarkerSchurDevice::Wanted(*p, opt.schur_impl);
     // the loss instances: a robust loss, or a problem that carries observation weights (all ones included: how a caller asks for
     // rsba_solver_set_observation_weights); once, here
     // ... or block priors: their cost travels where rho(s) does and stays out of the raw sum of squares (k_marker_prior_rows,
@@ -2773,6 +2779,8 @@ int rsba_solver_full_report(const rsba_solver* s, char* buf, int32_t capacity) {
     for (int b = 0; b < nb && b < (int)p.block_constant.size(); ++b) nconst += (used[b] && p.block_constant[b]) ? 1 : 0;
     // blocks no residual touches never enter the ceres::Problem (camera 0 / marker 0 of the reference's wiring); constant ones leave the reduced program
     blocks0 = nu; params0 = 6LL * nu; blocks1 = nu - nconst; params1 = 6LL * (nu - nconst);
+    // the intrinsics blocks this solver refines: parameter blocks of six (held components stay in the count, as Ceres' ambient sizes do)
+    for (int m : s->marker.intr_mask) if (m != 0) { ++blocks0; ++blocks1; params0 += 6; params1 += 6; }
     rblocks = p.num_observations + s->num_priors; residuals = 8 * p.num_observations + 6LL * s->num_priors;
   }
   static const char* kTerm[] = {"CONVERGENCE", "NO_CONVERGENCE", "FAILURE"};
@@ -2921,6 +2929,7 @@ int rsba_solver_covariance_compute(rsba_solver* s, const rsba_covariance_options
     return rsba::ShardedLeave(s, rc);
   }
   if (bad) return RSBA_ERR_ARG;
+  if (s->free_intrinsics) return RSBA_ERR_UNSUPPORTED;   // (no place for the intrinsics blocks: rsba.h)
   s->cov_valid = false;
   ++s->cov_epoch;
   if (hipSetDevice(s->device) != hipSuccess) return RSBA_ERR_HIP;
@@ -2979,6 +2988,7 @@ int rsba_solver_evaluate(rsba_solver* s, const rsba_evaluate_options* o, double*
   if (!s) return RSBA_ERR_ARG;
   rsba_evaluate_options eo;
   if (o) eo = *o; else rsba_evaluate_options_default(&eo);
+  if (s->free_intrinsics) return RSBA_ERR_UNSUPPORTED;   // (the gradient is indexed by parameter offset: no place for the intrinsics blocks)
   if (!cost && !residuals && !gradient) return RSBA_OK;
   if (s->comm) {
     if (s->prob->model != RSBA_MODEL_POINTS) return RSBA_ERR_UNSUPPORTED;   // (a marker-chain solver has one rank: nobody waits)
@@ -2999,11 +3009,13 @@ int rsba_solver_evaluate(rsba_solver* s, const rsba_evaluate_options* o, double*
 
 int rsba_solver_jacobian_structure(rsba_solver* s, int64_t* num_rows, int64_t* num_cols, int64_t* num_nonzeros, int64_t* row_ptr, int32_t* cols) {
   if (!s) return RSBA_ERR_ARG;
+  if (s->free_intrinsics) return RSBA_ERR_UNSUPPORTED;
   return rsba::JacobianStructure(s, num_rows, num_cols, num_nonzeros, row_ptr, cols);   // (host only: no device turn to take)
 }
 
 int rsba_solver_evaluate_jacobian(rsba_solver* s, const rsba_evaluate_options* o, double* values) {
   if (!s || !values) return RSBA_ERR_ARG;
+  if (s->free_intrinsics) return RSBA_ERR_UNSUPPORTED;
   rsba_evaluate_options eo;
   if (o) eo = *o; else rsba_evaluate_options_default(&eo);
   if (s->comm && s->prob->model != RSBA_MODEL_POINTS) return RSBA_ERR_UNSUPPORTED;   // (as rsba_solver_evaluate)
@@ -3050,6 +3062,7 @@ int rsba_solver_set_block_prior(rsba_solver* s, int64_t parameter_offset, const 
 
 int rsba_solver_set_parameters(rsba_solver* s, const double* parameters) {
   if (!s) return RSBA_ERR_ARG;
+  if (s->free_intrinsics) return RSBA_ERR_UNSUPPORTED;   // (the array has no place for the intrinsics blocks)
   const size_t n = s->prob->parameters.size();
   if (s->comm) {
     // collective (rsba.h): NULL or a non-finite value on this rank alone travels in the request word, the group refuses together

@@ -134,6 +134,18 @@ int rsba_problem_set_distortion(rsba_problem* p, const double* dist) {
 const double* rsba_problem_distortion(const rsba_problem* p) {
   return (p && !p->distortion.empty()) ? p->distortion.data() : nullptr;
 }
+int rsba_problem_set_intrinsics_free(rsba_problem* p, int32_t camera_idx, int32_t free_mask) {
+  if (!p) return RSBA_ERR_ARG;
+  if (!p->is_marker_chain()) return RSBA_ERR_UNSUPPORTED;   // like distortion: the point model's projection sits in the headline kernels
+  if (camera_idx < 0 || camera_idx >= p->num_cameras || free_mask < 0 || free_mask > 63) return RSBA_ERR_ARG;
+  if (p->intrinsics_free.empty()) p->intrinsics_free.assign((size_t)p->num_cameras, 0);
+  p->intrinsics_free[(size_t)camera_idx] = (uint8_t)free_mask;
+  return RSBA_OK;
+}
+int32_t rsba_problem_intrinsics_free(const rsba_problem* p, int32_t camera_idx) {
+  return (p && p->is_marker_chain()) ? p->intrinsics_free_mask(camera_idx) : 0;
+}
+const double* rsba_problem_intrinsics(const rsba_problem* p) { return p ? p->intrinsics.data() : nullptr; }
 // the block a prior may sit on: a camera or marker block that is a parameter block of the model's wiring (-1 - code otherwise)
 static int PriorBlock(const rsba_problem* p, int64_t parameter_offset) {
   if (!p) return -1 - RSBA_ERR_ARG;
