@@ -155,6 +155,9 @@ def _case(name, prob, variant=0, impl=2, loss="none", const="", env=None, radius
     return Case(name, prob, variant, impl, loss, const, tuple(sorted((env or {}).items())), radius, state, force)
 
 
+make_case = _case   # (public: tests/step_sequence.py builds its sequence cases on these)
+
+
 def _cases():
     out = []
     S = lambda C, T, M, keep=0.9: ("syn", C, T, M, keep)   # noqa: E731
@@ -236,15 +239,16 @@ def _longdouble_normal_equations(mc, rt, Jt):
 
 
 class System:
-    """The full damped normal equations at x (the free blocks' vector), their conditioning and the bar's row-independent part."""
+    """The full damped normal equations at x (the free blocks' vector), their conditioning and the bar's row-independent part.
+    scale: the Jacobi scale s (n) of iteration 0, or None to take it here (x is iteration 0's state)."""
 
-    def __init__(self, mc, x, radius, dense, min_lm=MIN_LM, max_lm=MAX_LM):
+    def __init__(self, mc, x, radius, dense, min_lm=MIN_LM, max_lm=MAX_LM, scale=None):
         assert sa.longdouble_ok()
         self.mc, self.x, self.radius, self.n = mc, np.asarray(x, float).copy(), radius, mc.n
         self.cost, self.rt, self.Jt, H64, g64, _ = mc.linearise(self.x)
         self.H, self.g = _longdouble_normal_equations(mc, self.rt, self.Jt)
         dH = np.diagonal(self.H).astype(np.float64)
-        self.s = 1.0 / (1.0 + np.sqrt(dH))
+        self.s = 1.0 / (1.0 + np.sqrt(dH)) if scale is None else np.asarray(scale, float).copy()
         self.D = np.clip(dH * self.s ** 2, min_lm, max_lm) / radius
         self.A = self.H + np.diag((self.D / self.s ** 2).astype(np.longdouble))
         self.b = -self.g

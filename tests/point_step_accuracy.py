@@ -176,12 +176,13 @@ def problem(shape, outliers=False, views=None, zero_cam=None):
 
 
 # ------------------------------------------------------------------------------------------------ cases
-Case = namedtuple("Case", "name shape huber const zero radius views")
+# perturb: sigma of a seeded perturbation of the start (perturbed_start); 0: the problem's own start, bit for bit
+Case = namedtuple("Case", "name shape huber const zero radius views perturb", defaults=(0.0,))
 ZERO_CAM = 3
 
 
-def _case(shape, tag="", huber=0.0, const=False, zero=False, radius=1e4, views=None):
-    return Case(shape + ("_" + tag if tag else ""), shape, huber, const, zero, radius, views)
+def _case(shape, tag="", huber=0.0, const=False, zero=False, radius=1e4, views=None, perturb=0.0):
+    return Case(shape + ("_" + tag if tag else ""), shape, huber, const, zero, radius, views, perturb)
 
 
 def _cases():
@@ -214,10 +215,24 @@ SETTINGS = [
 ]
 
 
+def perturbed_start(prob, sigma):
+    """prob with its start moved away from the minimum: a seeded normal of scale sigma on translations and points, 0.2 sigma on
+    rotations (the stock starts are so close that every step's relative decrease is 1.0001 whatever the radius)."""
+    C = prob["C"]
+    par = np.asarray(prob["params"], float).copy()
+    rng = np.random.default_rng([911, C])
+    cams = par[:6 * C].reshape(C, 6)
+    cams[:, :3] += 0.2 * sigma * rng.normal(size=(C, 3))
+    cams[:, 3:] += sigma * rng.normal(size=(C, 3))
+    par[6 * C:] += sigma * rng.normal(size=par.size - 6 * C)
+    return dict(prob, params=par)
+
+
 def case_problem(case):
     C = SHAPES[case.shape][0]
     assert ZERO_CAM not in (0, C - 1)
-    return problem(case.shape, case.huber > 0.0, case.views, ZERO_CAM if case.zero else None)
+    p = problem(case.shape, case.huber > 0.0, case.views, ZERO_CAM if case.zero else None)
+    return perturbed_start(p, case.perturb) if case.perturb else p
 
 
 def constants(case, prob):

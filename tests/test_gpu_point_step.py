@@ -16,8 +16,9 @@ One child process per setting (tests/point_step_worker.py).  Every case prints t
 tests/test_step_plan_host.py holds: the kernel statistics name all forms alike), n, m, kappa, and eta, bar and eta / bar of both
 row classes and steps; profiles/point_step_backward_error.txt is that table from an MI355X.
 
-Still held per solve only: a step after a REJECTED one (the public API cannot observe it), radius updates beyond the second step,
-termination."""
+A step after a REJECTED one, and the radius updates behind it, are observable through the public API too (min_relative_decrease set
+between the reference's relative decreases): tests/test_gpu_point_sequence.py holds them.  Still held per solve only: a step after an
+INVALID one (a failed factorisation or a non-positive model cost change), termination."""
 import json
 import os
 import subprocess
