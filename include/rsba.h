@@ -83,7 +83,10 @@ typedef struct rsba_options {
   int32_t device;          /* HIP device ordinal, -1 = current                                  */
   int32_t schur_impl;      /* point model: 0 = reference kernel (global atomics), 1 = tiled (default).          */
                            /* marker-chain: 0 = dense normal equations in one workgroup, 1 = eliminate the time */
-                           /* blocks when the dense system has more than 384 unknowns, 2 = always eliminate     */
+                           /* blocks when the dense system has more than 384 unknowns, 2 = always eliminate,    */
+                           /* 3 = as 2, and a solver with free intrinsics (rsba_problem_set_intrinsics_free)    */
+                           /* eliminates the time blocks too: its intrinsics blocks join the reduced system.    */
+                           /* Without free intrinsics 3 is 2 bit for bit; on the point model 3 means "not 0"    */
   int32_t profile_kernels; /* HIP events on the solver stream (rsba_solver_kernel_stats): 1 = around every kernel,
                               2 = only around the Schur pair kernel and the reduced-system solve */
   int32_t rank;            /* multi-GPU: this process' rank, 0..world_size-1                     */
@@ -306,11 +309,16 @@ const double* rsba_problem_distortion(const rsba_problem* p);
  * problem.  p1 p2 k3 always are.  The projection is the five-coefficient model of rsba_problem_set_distortion; nothing about it changes.
  * Host only.  camera_idx out of range, or bits above 5: RSBA_ERR_ARG.  The point model: RSBA_ERR_UNSUPPORTED.
  * The masks are read at rsba_solver_create / rsba_solve and fixed for that solver.  With any mask non-zero:
- *   - the solver takes the dense path whatever schur_impl says (rsba_solver_time_elimination reports 0); the columns of its linear
- *     system are the pose columns in their order, then the intrinsics blocks in ascending camera index, six columns each.  A held
+ *   - under schur_impl 0, 1 and 2 the solver takes the dense path (rsba_solver_time_elimination reports 0); the columns of its linear
+ *     system are the pose columns in their order, then the intrinsics blocks in ascending camera index, six columns each.  Under
+ *     schur_impl = 3 the time blocks are eliminated (rsba_solver_time_elimination reports 1) and the intrinsics blocks are the last
+ *     blocks of the reduced system, in the same order; the limit of 8192 columns below, which guards the dense matrix, does not
+ *     apply.  Where the planner refuses the problem (duplicate detections, a time too wide for the split accumulation — the
+ *     intrinsics blocks of the cameras that detect in a time count in its width) the solver falls back to the dense path silently,
+ *     with that path's rules.  Everything below holds on both paths.  A held
  *     component of a block is treated as a constant component of a pose block is (rsba_problem_set_parameter_subset_constant): zero
  *     rows, a zero step, its bits kept, and it counts in |x| — the parameter-tolerance test sees all six values of every block;
- *   - a non-zero mask on a camera no observation names, or a dense system of more than 8192 columns: RSBA_ERR_UNSUPPORTED from
+ *   - a non-zero mask on a camera no observation names, or (dense path) a dense system of more than 8192 columns: RSBA_ERR_UNSUPPORTED from
  *     rsba_solver_create / rsba_solve, before anything is allocated;
  *   - rsba_solve and rsba_solver_download write the refined values into the problem's intrinsics and distortion arrays (the problem
  *     gets a distortion array, zeros elsewhere, when k1 or k2 is free and it had none): rsba_reprojection_error, rsba_write_outputs
@@ -788,8 +796,9 @@ int rsba_solver_comm_abort(rsba_solver* s);
 /* The schedule in effect and the stalls / fallbacks so far (rsba_schedule_info).  The reference has no counterpart: Ceres runs
  * one thread (bundle_adjustment_manager.cpp:90-92). */
 int rsba_solver_schedule_info(const rsba_solver* s, rsba_schedule_info* out);
-/* Marker-chain models: which path the solver runs.  *eliminates_times = 1 when the time blocks are eliminated (rsba_options.schur_impl 2,
- * or 1 above RSBA_CHOL_MAXN unknowns), 0 on the dense one-workgroup path — the choice falls back to it silently for duplicate
+/* Marker-chain models: which path the solver runs.  *eliminates_times = 1 when the time blocks are eliminated (rsba_options.schur_impl 2
+ * or 3, or 1 above RSBA_CHOL_MAXN unknowns; with free intrinsics, rsba_problem_set_intrinsics_free: schur_impl 3 only), 0 on the dense
+ * one-workgroup path — the choice falls back to it silently for duplicate
  * detections, a time that touches more than 170 camera / marker blocks, or a solver that needs the split elimination (a robust
  * loss, observation weights, priors or subset masks) with times too wide for the split accumulation (about 120 camera / marker
  * blocks).  The rules, and the RSBA_MT_* environment switches of the time-eliminating path (RSBA_MT_SPLIT, RSBA_MT_ACC_MFMA,

@@ -60,6 +60,10 @@ struct TimeSlots {  // per residual block, in time order: where its camera / mar
 struct BlockRef { int x, y, z, w; };
 static_assert(sizeof(BlockRef) == 16, "BlockRef is uploaded as int4");
 
+// Free intrinsics on this path (with_intr): a residual block's THIRD slot — the intrinsics block of its detecting camera — in its
+// time's slot list, and that block's first reduced column; -1 both: the camera has no block.  Beside TimeSlots, which stays as it is.
+struct IntrSlots { int slot_intr, col_intr; };
+
 inline size_t AccLdsBytes(int dmax, size_t s_doubles) {
   const int smax = dmax / 6;
   return (size_t)(2 * smax * RSBA_SP_LDS + 6 * dmax + 96 + s_doubles) * sizeof(double) + (size_t)2 * ((smax + 2) & ~1) * sizeof(int);
@@ -126,6 +130,19 @@ struct MarkerTables {
   std::vector<int> h_bt;          // [N] the time of a residual block (split_backsub)
   std::vector<int> pcols;         // per prior of the problem (ascending block) its first reduced column, -1: constant as a whole
   std::vector<int> tc_map;        // the tiled factorisation's placement of its workgroups (TileOrder; tc_tiles > 0)
+  // free intrinsics (with_intr; all empty otherwise).  An intrinsics slot j = one (time, camera with a block):
+  std::vector<IntrSlots> hti;     // [N] the residual blocks' third slot and column
+  std::vector<int> h_is_slot;     // [nislots] its slot S (slot order: ascending time, ascending camera)
+  std::vector<int> h_is_cam;      // [nislots] its camera
+  std::vector<int> h_ib_ptr;      // [nislots + 1] its residual blocks ...
+  std::vector<int> h_ib_blk;      // ... in block order (nib entries: every residual block of a camera with a block, once)
+  // the pair items (camera pose x own intrinsics) and (marker x detecting camera's intrinsics) of every chunk lie behind the chunk's
+  // camera x marker items in h_xi_cc (the column block: camera or marker) / h_xi_cm (the row block: intrinsics), with an empty list
+  // in h_xi_ptr and no thread in h_xorder.  Each is the sum, in list order, of source records of 36 doubles: record j < nislots is
+  // J_i' J_c of intrinsics slot j, record nislots + e is J_i' J_m of entry e of h_ib_blk.
+  std::vector<int> h_xs_item;     // [nxs] the item
+  std::vector<int> h_xs_ptr;      // [nxs + 1] its sources ...
+  std::vector<int> h_xs_src;      // ... ascending (= time order)
 };
 
 struct MarkerPlan {
@@ -139,6 +156,10 @@ struct MarkerPlan {
   bool with_subset = false;  // some block in the program has a non-zero subset mask
   bool has_const = false;    // the kConst instances: a residual names a constant camera, marker or time block, or subset masks
   bool with_dist = false;    // the kDist instances: some distortion coefficient is not zero; no path rule reads it
+  bool with_intr = false;    // free intrinsics ride on this plan: a third slot per residual block, the kDist instances always
+  int nr_pose = 0;           // reduced columns of the pose blocks (= nr without free intrinsics; the intrinsics blocks lie behind)
+  int nislots = 0, nib = 0, nxs = 0;   // (with_intr) intrinsics slots, entries of h_ib_blk, pair items summed from source records
+  int nslots_pose = 0;       // (split) slots of pose blocks = threads of k_mc_slot_products (= nslots without free intrinsics)
   // ---- the path
   bool split = true;            // the split elimination (ba_marker_split.hpp); false: k_time_eliminate
   int acc_tiles = 0;            // > 0: k_mc_accumulate_mfma with that many tiles a wavefront
@@ -170,7 +191,13 @@ struct MarkerPlan {
 // the split accumulation returns RSBA_ERR_UNSUPPORTED (the solver takes the dense path).  Subset masks: the same, and the split
 // back-substitution whatever the switches say (the masks are applied to the split kernels' small products).
 // cus: the chip's compute units (one chunk per CU where the chunk sums live in LDS; the resident tiles fit two per CU).
-inline int PlanMarkerChain(const rsba_problem& p, bool loss, int cus, const MarkerSwitches& sw, MarkerPlan* out) {
+// intr: the caller wants the problem's free intrinsics (rsba_problem_set_intrinsics_free) in the plan; without a mask set it changes
+// nothing.  One block of six reduced columns per camera with a mask, ascending camera, behind the markers' (the dense path's order
+// without the time columns; the base camera and a camera with a constant pose may have one); column c of camera k is state value
+// nfull + 6 k + c.  A time's slot list gains the blocks of the cameras that detect in it — last, their columns being the highest — and
+// the width rules count them.  Held components (the complement of the mask) go into hrmask like a pose block's constant components.
+// Such a plan always runs the split elimination and the split back-substitution: the other forms have no place for the third block.
+inline int PlanMarkerChain(const rsba_problem& p, bool loss, int cus, const MarkerSwitches& sw, MarkerPlan* out, bool intr = false) {
   MarkerPlan& P = *out;
   P = MarkerPlan();
   MarkerTables& B = P.tab;
@@ -194,9 +221,23 @@ inline int PlanMarkerChain(const rsba_problem& p, bool loss, int cus, const Mark
     const int full = 6 * (b < C ? b : Tn + b);   // [C | T | M] x 6
     for (int q = 0; q < 6; ++q) B.cf.push_back(full + q);
   }
+  P.nr_pose = 6 * K;
+  std::vector<int> icol(C, -1);   // a camera's intrinsics block
+  P.with_intr = intr && p.has_free_intrinsics();
+  if (P.with_intr) {
+    P.with_dist = true;
+    std::vector<char> named(C, 0);
+    for (int i = 0; i < N; ++i) named[p.camera_index[i]] = 1;
+    for (int k = 0; k < C; ++k) if (p.intrinsics_free_mask(k) != 0) {
+      if (!named[k]) return RSBA_ERR_UNSUPPORTED;   // (a mask on a camera no observation names: the dense path refuses it too)
+      icol[k] = 6 * K++;
+      for (int q = 0; q < 6; ++q) B.cf.push_back(P.nfull + 6 * k + q);
+    }
+  }
   const int nr = P.nr = 6 * K;   // (0: nothing but time blocks are free)
   // constant components: of the blocks in the program only (a constant, base or unreferenced block's mask is ignored)
   for (int b = 0; b < C + M; ++b) if (red_col[b] >= 0) B.hrmask.push_back((unsigned char)p.subset_mask(b < C ? b : Tn + b));
+  for (int k = 0; k < C; ++k) if (icol[k] >= 0) B.hrmask.push_back((unsigned char)(~p.intrinsics_free_mask(k) & 0x3F));
   P.with_subset = std::find_if(B.hrmask.begin(), B.hrmask.end(), [](unsigned char v) { return v != 0; }) != B.hrmask.end();
   std::vector<int> tid_of(Tn, -1);
   int T = 0;
@@ -217,6 +258,7 @@ inline int PlanMarkerChain(const rsba_problem& p, bool loss, int cus, const Mark
   std::vector<TimeSlots>& hts = B.hts;
   tptr.assign(T + 1, 0); sptr.assign(T + 1, 0); csptr.assign(T + 1, 0);
   hmo.resize(N); hts.resize(N);
+  if (P.with_intr) B.hti.resize(N);
   B.hobs.resize(8 * (size_t)N);
   for (int k = 0; k < N; ++k) tptr[tid_of[p.time_index[order[k]]] + 1]++;
   for (int t = 0; t < T; ++t) tptr[t + 1] += tptr[t];
@@ -237,6 +279,7 @@ inline int PlanMarkerChain(const rsba_problem& p, bool loss, int cus, const Mark
         if (red_col[b] >= 0) cols.push_back(red_col[b]);
         else { cfl.push_back(6 * p.marker_block(i)); if (!cpose_seen[b]) { cpose_seen[b] = 1; hcpose.push_back(6 * p.marker_block(i)); } }
       }
+      if (icol[p.camera_index[i]] >= 0) cols.push_back(icol[p.camera_index[i]]);
     }
     std::sort(cols.begin(), cols.end());
     cols.erase(std::unique(cols.begin(), cols.end()), cols.end());
@@ -264,6 +307,11 @@ inline int PlanMarkerChain(const rsba_problem& p, bool loss, int cus, const Mark
       s.slot_cam = s.col_cam >= 0 ? (int)(std::lower_bound(cols.begin(), cols.end(), s.col_cam) - cols.begin()) : (o.full_cam >= 0 ? const_slot(o.full_cam) : -1);
       s.slot_marker = s.col_marker >= 0 ? (int)(std::lower_bound(cols.begin(), cols.end(), s.col_marker) - cols.begin())
                                         : (o.full_marker >= 0 ? const_slot(o.full_marker) : -1);
+      if (P.with_intr) {
+        IntrSlots& u = B.hti[k];
+        u.col_intr = icol[p.camera_index[i]];
+        u.slot_intr = u.col_intr >= 0 ? (int)(std::lower_bound(cols.begin(), cols.end(), u.col_intr) - cols.begin()) : -1;
+      }
       memcpy(&B.hobs[8 * (size_t)k], &p.observations[8 * (size_t)i], 8 * sizeof(double));
     }
     sptr[t + 1] = sptr[t] + (int)cols.size();
@@ -291,7 +339,7 @@ inline int PlanMarkerChain(const rsba_problem& p, bool loss, int cus, const Mark
   P.lds_s = P.lds_elim + s_doubles * sizeof(double) <= RSBA_LDS_CAP;
   if (P.lds_s) P.lds_elim += s_doubles * sizeof(double);
   const bool lds_s_elim = P.lds_s;   // (k_time_eliminate's own choice, should the split kernels not take the problem)
-  P.split = P.with_loss || P.with_subset || sw.split;
+  P.split = P.with_loss || P.with_subset || P.with_intr || sw.split;
   if (P.split) {
     const int per_wave = (AccMfmaTiles(nr) + 15) / 16;
     P.acc_tiles = (per_wave <= 8 && sw.acc_mfma) ? (per_wave <= 3 ? 3 : 8) : 0;
@@ -306,7 +354,7 @@ inline int PlanMarkerChain(const rsba_problem& p, bool loss, int cus, const Mark
     if (P.lds_acc > RSBA_LDS_CAP) {
       // times that touch more blocks than the accumulation's double-buffered records hold in LDS (~110 of the 170 the model allows):
       // k_time_eliminate, which stages 32 residual blocks at a time whatever the width
-      if (P.with_loss || P.with_subset) return RSBA_ERR_UNSUPPORTED;
+      if (P.with_loss || P.with_subset || P.with_intr) return RSBA_ERR_UNSUPPORTED;
       P.split = false; P.acc_tiles = 0; P.lds_s = lds_s_elim;
     }
   }
@@ -365,8 +413,8 @@ inline int PlanMarkerChain(const rsba_problem& p, bool loss, int cus, const Mark
           if (hts[k].slot_marker >= 0) h_sb_blk[fill[sptr[t] + hts[k].slot_marker]++] = BlockRef{k, pose_of_full(hmo[k].full_cam), hts[k].camera, 0};
         }
     }
-    h_order.resize(nslots);
-    for (int S = 0; S < nslots; ++S) h_order[S] = S;
+    for (int S = 0; S < nslots; ++S) if (scol[S] < P.nr_pose) h_order.push_back(S);   // (an intrinsics slot has its own kernel)
+    P.nslots_pose = (int)h_order.size();
     std::stable_sort(h_order.begin(), h_order.end(), [&](int x, int y) {
       const bool cx = scol[x] < ncam_cols, cy = scol[y] < ncam_cols;
       if (cx != cy) return cx;
@@ -388,7 +436,46 @@ inline int PlanMarkerChain(const rsba_problem& p, bool loss, int cus, const Mark
         h_xi_blk.push_back(BlockRef{items[i].second, hmo[items[i].second].full_time / 6, hts[items[i].second].camera, 0});
       }
       if (!items.empty()) h_xi_ptr.push_back((int)h_xi_blk.size());
+      if (P.with_intr) {
+        // the chunk's intrinsics slots and their residual blocks, then its items with an intrinsics row: ((row, column), source)
+        // A (camera, own intrinsics) block is formed per intrinsics slot, by the thread that walks exactly those residual blocks, and
+        // a (marker, intrinsics) block per residual block; an item sums its records in time order.  (A thread per item walking the
+        // residual blocks, as k_mc_cross has it, would give a (camera, intrinsics) item every block of the camera in the chunk.)
+        std::vector<std::pair<std::pair<int, int>, int>> xs;
+        for (int t = cptr[g]; t < cptr[g + 1]; ++t) {
+          for (int S = sptr[t]; S < sptr[t + 1]; ++S) if (scol[S] >= P.nr_pose) {
+            const int j = (int)B.h_is_slot.size();
+            B.h_is_slot.push_back(S);
+            B.h_is_cam.push_back((int)(std::find(icol.begin(), icol.end(), scol[S]) - icol.begin()));
+            B.h_ib_ptr.push_back((int)B.h_ib_blk.size());
+            bool with_cam = false;
+            int cam_col = -1;
+            for (int k = tptr[t]; k < tptr[t + 1]; ++k) if (B.hti[k].col_intr == scol[S]) {
+              if (hts[k].col_cam >= 0) { with_cam = true; cam_col = hts[k].col_cam; }
+              if (hts[k].col_marker >= 0) xs.push_back({{scol[S], hts[k].col_marker}, -1 - (int)B.h_ib_blk.size()});   // (entry e as -1 - e: nislots is not known yet)
+              B.h_ib_blk.push_back(k);
+            }
+            if (with_cam) xs.push_back({{scol[S], cam_col}, j});
+          }
+        }
+        std::stable_sort(xs.begin(), xs.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
+        for (size_t i = 0; i < xs.size(); ++i) {
+          if (i == 0 || xs[i].first != xs[i - 1].first) {
+            B.h_xs_item.push_back((int)h_xi_cc.size());
+            B.h_xs_ptr.push_back((int)B.h_xs_src.size());
+            h_xi_cm.push_back(xs[i].first.first); h_xi_cc.push_back(xs[i].first.second);
+            h_xi_ptr.push_back((int)h_xi_blk.size());   // (no residual block of its own: k_mc_cross has no thread for it)
+          }
+          B.h_xs_src.push_back(xs[i].second);
+        }
+      }
       h_xc_ptr[g + 1] = (int)h_xi_cc.size();
+    }
+    if (P.with_intr) {
+      P.nislots = (int)B.h_is_slot.size(); P.nib = (int)B.h_ib_blk.size(); P.nxs = (int)B.h_xs_item.size();
+      B.h_ib_ptr.push_back(P.nib);
+      B.h_xs_ptr.push_back((int)B.h_xs_src.size());
+      for (int& src : B.h_xs_src) if (src < 0) src = P.nislots + (-1 - src);
     }
     const int nx = P.nx = (int)h_xi_cc.size();
     {
@@ -397,16 +484,16 @@ inline int PlanMarkerChain(const rsba_problem& p, bool loss, int cus, const Mark
       auto len = [&](int it) { return h_xi_ptr[it + 1] - h_xi_ptr[it]; };
       std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return len(x) > len(y); });
       for (int it : ord) if (len(it) >= kShareFrom) { h_xorder.push_back(4 * it + 2); h_xorder.push_back(4 * it + 3); }
-      for (int it : ord) if (len(it) < kShareFrom) h_xorder.push_back(4 * it);
+      for (int it : ord) if (len(it) < kShareFrom && len(it) > 0) h_xorder.push_back(4 * it);   // (an empty list: an item summed from source records)
       P.nx_threads = (int)h_xorder.size();
     }
     P.fork = sw.fork;
   }
   // (k_time_backsub_wg: a corner of a residual block per lane, two per lane at most; wider times take the wavefront-per-time kernel)
-  P.backsub_wg = !P.with_loss && !P.with_subset && P.widest <= 128 /* 4 x 128 corners = 512 lanes */ && sw.backsub_wg;
+  P.backsub_wg = !P.with_loss && !P.with_subset && !P.with_intr && P.widest <= 128 /* 4 x 128 corners = 512 lanes */ && sw.backsub_wg;
   P.lds_bw = (size_t)(pmax + 1) * (CC_STRIDE + 12 + 6) * sizeof(double);   // the shot's tables (k_time_backsub_wg)
   P.nb_time = P.backsub_wg ? T : (T + 3) / 4;
-  P.split_backsub = P.split && (P.with_subset || sw.split_backsub);
+  P.split_backsub = P.split && (P.with_subset || P.with_intr || sw.split_backsub);
   if (P.split_backsub) {
     P.ncand_wg = (N + 255) / 256; P.nb_time = T + P.ncand_wg;
     B.h_bt.resize(N);

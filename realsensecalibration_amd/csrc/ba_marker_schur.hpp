@@ -1275,6 +1275,7 @@ __global__ void __launch_bounds__(256) k_mc_prior_candidate(int K, const int* __
 
 }  // namespace rsba
 #include "ba_marker_split.hpp"
+#include "ba_marker_intr_split.hpp"
 namespace rsba {
 
 // Runtime flags as template arguments: Dispatch(f, a, b) calls f(std::integral_constant<bool, a>(), std::integral_constant<bool, b>()).
@@ -1322,6 +1323,15 @@ struct MarkerSchurDevice {
   unsigned char* rmask = nullptr;   // [nr / 6] the reduced blocks' constant components (with_subset only)
   PriorDevice prior;                // K priors: one more partial system and one more bp_time / drho_c entry (with_loss then)
   double* prior_pe = nullptr;       // [2 K] the priors' terms, summed in order by thread 0
+  // free intrinsics (plan.with_intr only; ba_marker_intr_split.hpp): params[2] / params0 continue behind the nfull pose values with six
+  // values per camera, as MarkerDevice has them; intr / dist above stay the problem's values (dist then always there, zeros where the
+  // problem has none), the kernels read the current (x) and candidate (c) copies, scattered from the state in every step
+  int nstate = 0;                   // doubles of params[2] / params0
+  std::vector<int> intr_mask;       // [C] the masks this solver was created with
+  double *intr_x = nullptr, *dist_x = nullptr, *intr_c = nullptr, *dist_c = nullptr;
+  IntrSlots* ti = nullptr;
+  int *is_slot = nullptr, *is_cam = nullptr, *ib_ptr = nullptr, *ib_blk = nullptr, *xs_item = nullptr, *xs_ptr = nullptr, *xs_src = nullptr;
+  double* xsrc = nullptr;           // [nislots + nib][36] the source records of the pair items with an intrinsics row
 
   // Every device buffer above has one owner: Alloc records the member it fills, Free releases what was recorded.
   std::vector<void**> owned;
@@ -1369,25 +1379,44 @@ struct MarkerSchurDevice {
 
   // loss: a robust loss is set, or the problem carries observation weights or priors (PlanMarkerChain).  RSBA_ERR_UNSUPPORTED: the
   // solver takes the dense path.
-  int Upload(const rsba_problem& p, bool loss = false) {
+  // want_intr: the problem's free intrinsics join the reduced system (schur_impl = 3)
+  int Upload(const rsba_problem& p, bool loss = false, bool want_intr = false) {
     int cus = 256;
     { int dev = 0; hipDeviceProp_t prop; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount; }
-    const int rc = PlanMarkerChain(p, loss, cus, MarkerSwitches::FromEnv(), &plan);
+    const int rc = want_intr ? PlanMarkerChain(p, loss, cus, MarkerSwitches::FromEnv(), &plan, true) : PlanMarkerChain(p, loss, cus, MarkerSwitches::FromEnv(), &plan);
     if (rc != RSBA_OK) return rc;
     const MarkerPlan& P = plan;
     const MarkerTables& B = plan.tab;
     const size_t N = P.N, T = P.T, nr = P.nr, nfull = P.nfull, np = P.np;
     const size_t nA = (nr + 2) * nr, npart = PartLayout{P.nr}.size();
+    const size_t C = (size_t)p.num_cameras;
+    nstate = (int)(nfull + (P.with_intr ? 6 * C : 0));
+    // the state: the poses, then (with_intr) fx fy cx cy k1 k2 of every camera; the coefficients as an array that is always there then
+    std::vector<double> hstate(p.parameters), hdist(p.distortion);
+    if (P.with_intr) {
+      if (hdist.empty()) hdist.assign(5 * C, 0.0);
+      hstate.resize((size_t)nstate);
+      intr_mask.assign(C, 0);
+      for (size_t k = 0; k < C; ++k) {
+        intr_mask[k] = p.intrinsics_free_mask((int)k);
+        for (int q = 0; q < 4; ++q) hstate[nfull + 6 * k + q] = p.intrinsics[4 * k + q];
+        hstate[nfull + 6 * k + 4] = hdist[5 * k]; hstate[nfull + 6 * k + 5] = hdist[5 * k + 1];
+      }
+    }
     if (np && (prior.Upload(p, B.pcols) != RSBA_OK || !Alloc(&prior_pe, 2 * (size_t)prior.K))) return RSBA_ERR_HIP;
     bool ok = Alloc(&mo, B.hmo) && Alloc(&ts, B.hts) && Alloc(&chunk_ptr, B.cptr) && Alloc(&time_ptr, B.tptr) && Alloc(&slot_ptr, B.sptr) &&
               Alloc(&slot_col, B.scol) && Alloc(&time_full, B.tfull) && Alloc(&col_full, B.cf) && Alloc(&ok_flag, 1) && Alloc(&obs8, B.hobs) &&
-              Alloc(&intr, p.intrinsics) && Alloc(&params[0], nfull) && Alloc(&params[1], nfull) && Alloc(&params0, p.parameters) &&
+              Alloc(&intr, p.intrinsics) && Alloc(&params[0], (size_t)nstate) && Alloc(&params[1], (size_t)nstate) && Alloc(&params0, hstate) &&
               Alloc(&posec, nfull / 6 * CC_STRIDE) && Alloc(&posec_c, nfull / 6 * CC_STRIDE) && Alloc(&ss_x, N) && Alloc(&scale_t, 6 * T) &&
               Alloc(&scale_r, nr) && Alloc(&tdata, 48 * T) && Alloc(&part, (P.G + np) * npart) && Alloc(&red, RedLayout{P.nr}.size()) && Alloc(&A, nA) &&
               (P.nr <= RSBA_CHOL_MAXN || Alloc(&Wm, nA)) && Alloc(&delta_r, nr) && Alloc(&delta_t, 6 * T) && Alloc(&bp_time, 4 * (P.nb_time + np)) &&
               Alloc(&solve_out, 8) && Alloc(&res, RES_SIZE) &&
               (!P.with_loss || (Alloc(&wsq, N) && Alloc(&drho, N) && Alloc(&drho_c, N + np) && Alloc(&wts, N))) &&
-              (!P.with_dist || Alloc(&dist, p.distortion)) &&
+              (!P.with_dist || Alloc(&dist, hdist)) &&
+              (!P.with_intr || (Alloc(&intr_x, p.intrinsics) && Alloc(&intr_c, p.intrinsics) && Alloc(&dist_x, hdist) && Alloc(&dist_c, hdist) && Alloc(&ti, B.hti) &&
+                                Alloc(&is_slot, B.h_is_slot) && Alloc(&is_cam, B.h_is_cam) && Alloc(&ib_ptr, B.h_ib_ptr) && Alloc(&ib_blk, B.h_ib_blk) &&
+                                Alloc(&xs_item, B.h_xs_item) && Alloc(&xs_ptr, B.h_xs_ptr) && Alloc(&xs_src, B.h_xs_src) &&
+                                Alloc(&xsrc, ((size_t)P.nislots + P.nib) * 36))) &&
               (!P.has_const || (Alloc(&cs_ptr, B.csptr) && Alloc(&cs_full, B.csfull) && Alloc(&tconst, B.htc) && Alloc(&cpose_full, B.cpf))) &&
               (!P.with_subset || (Alloc(&tflags, B.htflags) && Alloc(&rmask, B.hrmask))) &&
               (!P.split || (Alloc(&slot_order, B.h_order) && Alloc(&x_order, B.h_xorder) && Alloc(&slot_time, B.h_slot_time) && Alloc(&sb_ptr, B.h_sb_ptr) &&
@@ -1438,8 +1467,8 @@ struct MarkerSchurDevice {
     return hipMemcpy(wts, h.data(), (size_t)plan.N * 8, hipMemcpyHostToDevice) == hipSuccess ? RSBA_OK : RSBA_ERR_HIP;
   }
   int Reset(hipStream_t st) {
-    if (hipMemcpyAsync(params[0], params0, plan.nfull * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return RSBA_ERR_HIP;
-    if (hipMemcpyAsync(params[1], params0, plan.nfull * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return RSBA_ERR_HIP;
+    if (hipMemcpyAsync(params[0], params0, (size_t)nstate * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return RSBA_ERR_HIP;
+    if (hipMemcpyAsync(params[1], params0, (size_t)nstate * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return RSBA_ERR_HIP;
     if (plan.ncpose > 0) {
       // the constant cameras' and markers' candidate pose constants are those at x, for the whole run
       k_pose_constants_reduced<<<(plan.ncpose + 63) / 64, 64, 0, st>>>(plan.ncpose, cpose_full, params0, posec_c);
@@ -1465,7 +1494,7 @@ struct MarkerSchurDevice {
     // (with_loss and huber_delta = 0: observation weights alone, rho(s) = s)
     const double loss = P.with_loss && o.huber_delta > 0.0 ? (o.loss_type == RSBA_LOSS_CAUCHY ? -o.huber_delta : o.huber_delta) : 0.0;
     const int x = cur, c = 1 - cur;
-    if (hipMemcpyAsync(params[c], params[x], nfull * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return RSBA_ERR_HIP;
+    if (hipMemcpyAsync(params[c], params[x], (size_t)nstate * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return RSBA_ERR_HIP;
     auto chk = [&](const char* what) {
       hipError_t e = hipGetLastError();
       if (e != hipSuccess) { fprintf(stderr, "rsba: %s launch failed: %s\n", what, hipGetErrorString(e)); return false; }
@@ -1473,14 +1502,26 @@ struct MarkerSchurDevice {
     };
     if (!chk("(before marker step)")) return RSBA_ERR_HIP;
     const RedLayout RL{nr};
-    auto intr_of = [&](auto D) { return IntrPass<D.value>(intr, dist); };
+    // free intrinsics: every kernel at x reads the state's values through the current copies (so a rejected candidate's values are
+    // never seen by a linearisation), the candidate's residuals the candidate copies
+    const int ncams = (int)intr_mask.size();
+    const double* intr_u = P.with_intr ? intr_x : intr;
+    const double* dist_u = P.with_intr ? dist_x : dist;
+    if (P.with_intr) {
+      Tm.Begin("k_mc_intr_state", st);
+      k_mc_intr_state<<<(ncams + 63) / 64, 64, 0, st>>>(ncams, nfull, params[x], intr_x, dist_x);
+      Tm.End(st);
+    }
+    auto intr_of = [&](auto D) { return IntrPass<D.value>(intr_u, dist_u); };
     Tm.Begin("k_pose_constants", st);
     k_pose_constants<<<(nfull / 6 + 255) / 256, 256, 0, st>>>(nfull / 6, params[x], posec);
     Tm.End(st);
     if (P.split) {
-      SplitArgs sa{P.nslots, T, P.nx, P.ncam_cols, P.nx_threads, slot_order, x_order, slot_time, slot_col, sb_ptr, sb_blk, time_ptr, time_full, col_full, ts, mo, obs8, intr, posec, half_side,
+      // (nslots: the threads of k_mc_slot_products, the only kernel that reads it — the pose slots; an intrinsics slot has its own kernel)
+      SplitArgs sa{P.nslots_pose, T, P.nx, P.ncam_cols, P.nx_threads, slot_order, x_order, slot_time, slot_col, sb_ptr, sb_blk, time_ptr, time_full, col_full, ts, mo, obs8, intr_u, posec, half_side,
                    xi_ptr, xi_blk, xi_cc, xi_cm, sp, xout, wsq, drho};
-      SplitArgsDist sad; static_cast<SplitArgs&>(sad) = sa; sad.dist = dist;
+      SplitArgsDist sad; static_cast<SplitArgs&>(sad) = sa; sad.dist = dist_u;
+      const IntrSplitArgs ia{P.nislots, P.nib, is_slot, is_cam, ib_ptr, ib_blk, slot_time, time_full, mo, obs8, intr_x, dist_x, posec, half_side, P.with_loss ? wsq : nullptr, sp, xsrc};
       auto split_args = [&](auto D) -> const typename SplitArgT<D.value>::type& { if constexpr (D.value) return sad; else return sa; };
       if (P.with_loss) {
         // the corrector's weights at x, wanted by all three product kernels
@@ -1497,9 +1538,16 @@ struct MarkerSchurDevice {
             hipStreamWaitEvent(s_cross, fork_ev[0], 0) != hipSuccess) return RSBA_ERR_HIP;
       }
       if (P.nslots > 0) {   // (none: n_r = 0)
-        Tm.Begin("k_mc_slot_products", st);
-        Dispatch([&](auto L, auto D) { k_mc_slot_products<L.value, D.value><<<(P.nslots + 255) / 256, 256, 0, st>>>(split_args(D)); }, P.with_loss, P.with_dist);
-        Tm.End(st);
+        if (P.nslots_pose > 0) {
+          Tm.Begin("k_mc_slot_products", st);
+          Dispatch([&](auto L, auto D) { k_mc_slot_products<L.value, D.value><<<(P.nslots_pose + 255) / 256, 256, 0, st>>>(split_args(D)); }, P.with_loss, P.with_dist);
+          Tm.End(st);
+        }
+        if (P.nislots > 0) {
+          Tm.Begin("k_mc_intr_slot_products", st);
+          k_mc_intr_slot_products<<<(P.nislots + 255) / 256, 256, 0, st>>>(ia);
+          Tm.End(st);
+        }
         if (P.with_subset) {
           Tm.Begin("k_mc_subset_slots", st);
           k_mc_subset_slots<<<(unsigned)(((size_t)P.nslots * 64 + 255) / 256), 256, 0, st>>>(P.nslots, slot_time, slot_col, tflags, rmask, sp);
@@ -1514,9 +1562,21 @@ struct MarkerSchurDevice {
       }, P.with_loss, P.has_const, P.with_dist, P.with_subset);
       Tm.End(st);
       if (P.nx > 0) {
-        Tm.Begin("k_mc_cross", st);
-        Dispatch([&](auto L, auto D) { k_mc_cross<L.value, D.value><<<(P.nx_threads + 255) / 256, 256, 0, s_cross>>>(split_args(D)); }, P.with_loss, P.with_dist);
-        Tm.End(st);
+        if (P.nx_threads > 0) {
+          Tm.Begin("k_mc_cross", st);
+          Dispatch([&](auto L, auto D) { k_mc_cross<L.value, D.value><<<(P.nx_threads + 255) / 256, 256, 0, s_cross>>>(split_args(D)); }, P.with_loss, P.with_dist);
+          Tm.End(st);
+        }
+        if (P.nxs > 0) {
+          // the items with an intrinsics row: the (camera, intrinsics) records come from k_mc_intr_slot_products, on the solver's stream
+          if (fork && (hipEventRecord(fork_ev[1], st) != hipSuccess || hipStreamWaitEvent(s_cross, fork_ev[1], 0) != hipSuccess)) return RSBA_ERR_HIP;
+          Tm.Begin("k_mc_intr_marker_cross", st);
+          k_mc_intr_marker_cross<<<(P.nib + 255) / 256, 256, 0, s_cross>>>(ia);
+          Tm.End(st);
+          Tm.Begin("k_mc_intr_cross_sum", st);
+          k_mc_intr_cross_sum<<<(unsigned)(((size_t)P.nxs * 36 + 255) / 256), 256, 0, s_cross>>>(P.nxs, xs_item, xs_ptr, xs_src, xsrc, xout);
+          Tm.End(st);
+        }
         if (P.with_subset) {
           Tm.Begin("k_mc_subset_cross", st);
           k_mc_subset_cross<<<(unsigned)(((size_t)P.nx * 36 + 255) / 256), 256, 0, s_cross>>>(P.nx, xi_cc, xi_cm, rmask, xout);
@@ -1583,7 +1643,8 @@ struct MarkerSchurDevice {
     if (!chk("reduced solve")) return RSBA_ERR_HIP;
     Tm.Begin("k_time_backsub_terms", st);
     if (P.split_backsub) {
-      if (nr > 0) k_pose_constants_reduced<<<(nr / 6 + 63) / 64, 64, 0, st>>>(nr / 6, col_full, params[c], posec_c);
+      if (P.nr_pose > 0) k_pose_constants_reduced<<<(P.nr_pose / 6 + 63) / 64, 64, 0, st>>>(P.nr_pose / 6, col_full, params[c], posec_c);
+      if (P.with_intr) k_mc_intr_state<<<(ncams + 63) / 64, 64, 0, st>>>(ncams, nfull, params[c], intr_c, dist_c);
       Dispatch([&](auto Cn) { k_mc_time_step<Cn.value><<<(8 * T + 255) / 256, 256, 0, st>>>(T, slot_ptr, slot_col, time_full, sp, tdata, delta_r, params[x], params[c], delta_t, posec_c, bp_time, tconst); },
                P.has_const);
       // the two halves of the candidate's evaluation side by side (one after the other when every kernel is timed)
@@ -1592,6 +1653,14 @@ struct MarkerSchurDevice {
       if (fork2 && (hipEventRecord(fork_ev[0], st) != hipSuccess || hipStreamWaitEvent(s_cost, fork_ev[0], 0) != hipSuccess)) return RSBA_ERR_HIP;
       auto candidate = [&](auto half, hipStream_t s) {   // (the weights: the cost's half only)
         constexpr int kHalf = decltype(half)::value;
+        if (P.with_intr) {
+          // the model cost change with the third block; the candidate's residuals at the candidate's intrinsics through the existing part 1
+          if constexpr (kHalf == 0) k_mc_intr_candidate<<<P.ncand_wg, 256, 0, s>>>(N, T, ts, ti, mo, obs8, intr_x, dist_x, half_side, posec, delta_r, delta_t, blk_time, bp_time, P.with_loss ? wsq : nullptr);
+          else Dispatch([&](auto L) {
+            k_mc_candidate<1, L.value, true><<<P.ncand_wg, 256, 0, s>>>(N, T, ts, mo, obs8, IntrDist{intr_c, dist_c}, half_side, posec, posec_c, delta_r, delta_t, blk_time, bp_time, loss, wsq, drho_c, wts);
+          }, P.with_loss);
+          return;
+        }
         Dispatch([&](auto L, auto D) {
           k_mc_candidate<kHalf, L.value, D.value><<<P.ncand_wg, 256, 0, s>>>(N, T, ts, mo, obs8, intr_of(D), half_side, posec, posec_c, delta_r, delta_t, blk_time, bp_time, loss, wsq, drho_c,
                                                                                     kHalf == 1 ? wts : nullptr);
@@ -1647,6 +1716,19 @@ struct MarkerSchurDevice {
   }
   int Download(rsba_problem* p) {
     if (hipMemcpy(p->parameters.data(), params[cur], plan.nfull * 8, hipMemcpyDeviceToHost) != hipSuccess) return RSBA_ERR_HIP;
+    if (plan.with_intr) {
+      // the refined values into the problem's own arrays, as MarkerDevice::Download writes them (a camera without a block, and a held
+      // component, keep their bits: the state started from them); a distortion array appears when k1 or k2 was free
+      const int C = (int)intr_mask.size();
+      std::vector<double> hs(6 * (size_t)C);
+      if (hipMemcpy(hs.data(), params[cur] + plan.nfull, hs.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return RSBA_ERR_HIP;
+      for (int k = 0; k < C; ++k) {
+        if (intr_mask[k] == 0) continue;
+        for (int q = 0; q < 4; ++q) p->intrinsics[4 * (size_t)k + q] = hs[6 * (size_t)k + q];
+        if ((intr_mask[k] & 0x30) && p->distortion.empty()) p->distortion.assign(5 * (size_t)C, 0.0);
+        if (!p->distortion.empty()) { p->distortion[5 * (size_t)k] = hs[6 * (size_t)k + 4]; p->distortion[5 * (size_t)k + 1] = hs[6 * (size_t)k + 5]; }
+      }
+    }
     return RSBA_OK;
   }
 };

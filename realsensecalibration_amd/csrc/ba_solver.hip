@@ -2590,11 +2590,13 @@ int rsba_solver_create(rsba_problem* p, const rsba_options* o, rsba_solver** out
     rc = rsba::UploadPoints(s);
     if (rc == RSBA_OK && s->tiled.tree_error) s->tiled.error_flag = reinterpret_cast<int*>(s->res_host + RES_SIZE + 4);   // (zeroed above)
   } else {
-    // free intrinsics (rsba_problem_set_intrinsics_free): the dense path whatever schur_impl says — the time-eliminating kernels have
-    // two slots per residual block; read here and fixed for this solver, like the masks of constant components
+    // free intrinsics (rsba_problem_set_intrinsics_free): the dense path under schur_impl 0, 1 and 2; under 3 the time blocks are
+    // eliminated and the intrinsics blocks join the reduced system (ba_marker_intr_split.hpp).  Read here and fixed for this solver,
+    // like the masks of constant components
     if (!p->intrinsics_free.empty() && p->intrinsics_free.size() != (size_t)p->num_cameras) { rsba::FreeSolver(s); return RSBA_ERR_ARG; }
     s->free_intrinsics = p->has_free_intrinsics();
-    s->eliminate_times = !s->free_intrinsics && rsba::MarkerSchurDevice::Wanted(*p, opt.schur_impl);
+    const bool elim_intr = s->free_intrinsics && opt.schur_impl == 3;
+    s->eliminate_times = (!s->free_intrinsics || elim_intr) && rsba::MarkerSchurDevice::Wanted(*p, opt.schur_impl);
     // the loss instances: a robust loss, or a problem that carries observation weights (all ones included: how a caller asks for
     // rsba_solver_set_observation_weights); once, here
     // ... or block priors: their cost travels where rho(s) does and stays out of the raw sum of squares (k_marker_prior_rows,
@@ -2610,7 +2612,7 @@ int rsba_solver_create(rsba_problem* p, const rsba_options* o, rsba_solver** out
       for (const auto& kv : p->block_priors) if (!named[kv.first]) { rsba::FreeSolver(s); return RSBA_ERR_UNSUPPORTED; }
       s->num_priors = (int)p->block_priors.size();
     }
-    rc = s->eliminate_times ? s->marker_schur.Upload(*p, s->weighted) : s->marker.Upload(*p, s->weighted);
+    rc = s->eliminate_times ? s->marker_schur.Upload(*p, s->weighted, elim_intr) : s->marker.Upload(*p, s->weighted);
     if (s->eliminate_times && rc == RSBA_ERR_UNSUPPORTED) {
       // duplicate detections, or a time wider than the kernels' LDS: the dense path is general
       s->marker_schur.Free();
@@ -2780,7 +2782,7 @@ int rsba_solver_full_report(const rsba_solver* s, char* buf, int32_t capacity) {
     // blocks no residual touches never enter the ceres::Problem (camera 0 / marker 0 of the reference's wiring); constant ones leave the reduced program
     blocks0 = nu; params0 = 6LL * nu; blocks1 = nu - nconst; params1 = 6LL * (nu - nconst);
     // the intrinsics blocks this solver refines: parameter blocks of six (held components stay in the count, as Ceres' ambient sizes do)
-    for (int m : s->marker.intr_mask) if (m != 0) { ++blocks0; ++blocks1; params0 += 6; params1 += 6; }
+    for (int m : s->eliminate_times ? s->marker_schur.intr_mask : s->marker.intr_mask) if (m != 0) { ++blocks0; ++blocks1; params0 += 6; params1 += 6; }
     rblocks = p.num_observations + s->num_priors; residuals = 8 * p.num_observations + 6LL * s->num_priors;
   }
   static const char* kTerm[] = {"CONVERGENCE", "NO_CONVERGENCE", "FAILURE"};

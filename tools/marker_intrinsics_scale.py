@@ -1,14 +1,17 @@
 """The cost of staying on the dense path with free intrinsics (rsba_problem_set_intrinsics_free): per-iteration time of the dense
 marker-chain solve on one rig with and without them, and of the time-eliminating path such a solver gives up (DESIGN §8,
-profiles/marker_intrinsics_scale.jsonl).
+profiles/marker_intrinsics_scale.jsonl), and of the eliminating path with free intrinsics (schur_impl = 3,
+profiles/marker_intrinsics_elim_scale.jsonl).
 
-    python tools/marker_intrinsics_scale.py [reps=3] [shape=4,200,16] [mask=0x3f] [out=PATH]
+    python tools/marker_intrinsics_scale.py [reps=3] [shape=4,200,16] [mask=0x3f] [dense=1] [out=PATH]
 
-Three configurations of one problem (synthetic.make_marker_chain(shape, seed=11), intrinsics displaced as the tests displace them), in
+Four configurations of one problem (synthetic.make_marker_chain(shape, seed=11), intrinsics displaced as the tests displace them), in
 one process, the repetitions alternating between them:
     dense, intrinsics fixed    schur_impl 0: the parent's kernels
     dense, intrinsics free     `mask` on every camera: the k_marker_intr_* kernels, 6 more columns per camera
     eliminating, fixed         schur_impl 2: what a solver without free intrinsics may take instead
+    eliminating, free          schur_impl 3 with `mask`: the time blocks eliminated, the intrinsics blocks in the reduced system
+dense=0 skips the two dense configurations (a shape whose dense system is refused with free intrinsics, or too large without).
 Per repetition a fresh solver: one warm-up run, then one run timed by the host clock (rsba_summary's minimizer_seconds: every step ends
 in a stream synchronise) and one profiled run (profile_kernels = 1: the solver's own HIP event pairs around every kernel).  One line
 per configuration: ms_per_iteration = minimizer time / (iterations + 1), kernel_ms_per_step = the events' total over the steps
@@ -29,7 +32,10 @@ KW = dict(a.split("=", 1) for a in sys.argv[1:] if "=" in a)
 REPS = int(KW.get("reps", 3))
 C_, T_, M_ = (int(v) for v in KW.get("shape", "4,200,16").split(","))
 MASK = int(KW.get("mask", "0x3f"), 0)
-CONFIGS = [("dense, intrinsics fixed", 0, 0), ("dense, intrinsics free (mask 0x%02x on every camera)" % MASK, 0, MASK), ("eliminating, intrinsics fixed", 2, 0)]
+CONFIGS = [("dense, intrinsics fixed", 0, 0), ("dense, intrinsics free (mask 0x%02x on every camera)" % MASK, 0, MASK), ("eliminating, intrinsics fixed", 2, 0),
+           ("eliminating, intrinsics free (mask 0x%02x on every camera)" % MASK, 3, MASK)]
+if int(KW.get("dense", 1)) == 0:
+    CONFIGS = [c for c in CONFIGS if c[1] != 0]
 
 base = synthetic.make_marker_chain(C_, T_, M_, seed=11)
 prob = dict(base, intr=iref.displaced_intrinsics(base["intr"]))
