@@ -328,7 +328,8 @@ const double* rsba_problem_distortion(const rsba_problem* p);
  *     rsba_solver_set_block_prior, a robust loss, constant blocks, constant components and priors on pose blocks;
  *   - rsba_solver_evaluate, rsba_solver_evaluate_jacobian, rsba_solver_jacobian_structure, rsba_solver_covariance_compute and
  *     rsba_solver_set_parameters return RSBA_ERR_UNSUPPORTED: their outputs are indexed by parameter offset and have no place for the
- *     intrinsics blocks.
+ *     intrinsics blocks.  rsba_solver_set_extended_layout (below) gives them one: evaluate, set_parameters and the covariance then
+ *     work; the two Jacobian calls stay refused.
  * All masks zero: the kernels and the bits of a problem on which this was never called. */
 int rsba_problem_set_intrinsics_free(rsba_problem* p, int32_t camera_idx, int32_t free_mask);
 /* the camera's mask; 0 when none was set */
@@ -713,6 +714,38 @@ int rsba_solver_evaluate_jacobian(rsba_solver* s, const rsba_evaluate_options* o
  * (one max over [cameras, -cameras], 12C doubles, compared as values); a mismatch is RSBA_ERR_ARG on every rank with nothing
  * changed.  A sharded group set to x1 then runs the bits of a group created at x1. */
 int rsba_solver_set_parameters(rsba_solver* s, const double* parameters);
+
+/* The extended layout of a marker-chain solver with free intrinsics (rsba_problem_set_intrinsics_free), on either of its paths: the
+ * solver's own state layout — the problem's num_parameters pose values, then six values fx fy cx cy k1 k2 per camera index, camera k
+ * at offset num_parameters + 6 k.  EVERY camera index has a slot, with a mask or without.  rsba_solver_num_extended_parameters is
+ * its length, num_parameters + 6 num_cameras (num_parameters on the point model, which has no such slots); NULL: -RSBA_ERR_ARG.
+ * on = 0 (the default): every query behaves as described at rsba_problem_set_intrinsics_free, refusals included.  The point model,
+ * and a marker-chain solver without free intrinsics (its intrinsics are constants of the problem with no state slot):
+ * RSBA_ERR_UNSUPPORTED.  Switching it, in either direction, drops a covariance result as rsba_solver_set_parameters does and
+ * changes nothing else: a run's bits are the same.  With on != 0:
+ *   - rsba_solver_evaluate: residuals and cost by the rules above (the problem's observation order, loss and weights under
+ *     apply_loss_function, prior residuals behind the observations'), evaluated with the STATE's fx fy cx cy k1 k2; p1 p2 k3 stay the
+ *     problem's.  The gradient has rsba_solver_num_extended_parameters entries: the pose slots as on any solver, an intrinsics slot
+ *     J'r of that component's column, and 0.0 for a held component (mask bit clear), a camera with mask 0 and a camera no observation
+ *     names.  The dense and the time-eliminating path return identical bits at identical values; two calls return identical bits.
+ *   - rsba_solver_set_parameters takes rsba_solver_num_extended_parameters values.  All 6 num_cameras trailing values go into the
+ *     start state and the current state: a held component or a camera with mask 0 is a constant whose value the caller may change.
+ *     A solver created at x0 and set to x1 then runs the bits of a solver created from a problem whose parameters, intrinsics and
+ *     k1 k2 are x1.  rsba_solver_download writes the state's six values of EVERY camera into the problem's intrinsics and distortion
+ *     arrays — the refined ones and the held or mask-0 ones this call changed — so that the problem is consistent with the poses
+ *     it gets (without this call those keep their bits: the state started from them; a problem without a distortion array gets one
+ *     when k1 or k2 is free or was set to a non-zero value).
+ *   - rsba_solver_covariance_compute works on both paths: an intrinsics block with a mask is one more block with six columns in the
+ *     system, behind the pose blocks' (time-eliminating path: the time blocks are eliminated over camera, marker and intrinsics
+ *     blocks).  rsba_solver_covariance_block and rsba_solver_covariance_blocks take num_parameters + 6 k as the offset of camera k's
+ *     block: any pair among camera, marker and intrinsics blocks is a 6 x 6 block of the inverse; a camera with mask 0 gives zeros, a
+ *     held component zero rows and columns (a constant component, as of a pose block); a camera no observation names: RSBA_ERR_ARG.
+ *     Pairs with time blocks and rsba_solver_time_covariances work on the dense path; on the time-eliminating path of such a solver
+ *     they return RSBA_ERR_UNSUPPORTED (the cross-block kernel does not know the intrinsics blocks yet).  An unobservable intrinsic
+ *     is RSBA_ERR_RANK_DEFICIENT, as any singular system.
+ *   - rsba_solver_jacobian_structure and rsba_solver_evaluate_jacobian: RSBA_ERR_UNSUPPORTED, as with the layout off. */
+int rsba_solver_set_extended_layout(rsba_solver* s, int32_t on);
+int64_t rsba_solver_num_extended_parameters(const rsba_solver* s);
 /* New observation weights (rsba_problem_set_observation_weights: semantics and validation) on a resident marker-chain solver, the way
  * rsba_solver_set_parameters changes values: they take effect with the next run, evaluate, Jacobian or covariance call.  Nothing is
  * planned or allocated again; parameters, iteration log and last summary stay; a covariance result is dropped.  The problem's own copy

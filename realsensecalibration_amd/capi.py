@@ -40,6 +40,7 @@ EXPORTS = [
     "rsba_marker_pose_from_corners", "rsba_marker_poses_from_corners", "rsba_problem_initial_time_poses", "rsba_problem_start_rig", "rsba_problem_start_scene",
     "rsba_marker_pose_from_corners_both", "rsba_marker_poses_from_corners_both", "rsba_problem_start_rig2", "rsba_problem_start_scene2",
     "rsba_problem_set_intrinsics_free", "rsba_problem_intrinsics_free", "rsba_problem_intrinsics",
+    "rsba_solver_set_extended_layout", "rsba_solver_num_extended_parameters",
 ]
 INTRINSICS_COMPONENTS = ("fx", "fy", "cx", "cy", "k1", "k2")   # bit q of rsba_problem_set_intrinsics_free's mask
 START_BOTH_SOLUTIONS = 1   # RSBA_START_BOTH_SOLUTIONS
@@ -178,6 +179,9 @@ def load():
     lib.rsba_solver_jacobian_structure.argtypes = [C.c_void_p] * 6
     lib.rsba_solver_evaluate_jacobian.argtypes = [C.c_void_p] * 3
     lib.rsba_solver_set_parameters.argtypes = [C.c_void_p, C.c_void_p]
+    lib.rsba_solver_set_extended_layout.argtypes = [C.c_void_p, C.c_int32]
+    lib.rsba_solver_num_extended_parameters.argtypes = [C.c_void_p]
+    lib.rsba_solver_num_extended_parameters.restype = C.c_int64
     lib.rsba_solver_comm_abort.argtypes = [C.c_void_p]
     lib.rsba_problem_set_observation_weights.argtypes = [C.c_void_p, C.c_void_p]
     lib.rsba_problem_observation_weights.argtypes = [C.c_void_p]
@@ -536,6 +540,7 @@ class Solver:
         self.problem = problem
         self.opts = opts or default_options()
         self.h = C.c_void_p()
+        self._extended = False   # what set_extended_layout() last told the library: the length of evaluate()'s gradient and set_parameters()'s vector
         _chk(load().rsba_solver_create(problem.h, C.byref(self.opts), C.byref(self.h)), "rsba_solver_create")
 
     def run(self):
@@ -652,6 +657,27 @@ class Solver:
     def marker_offset(self, marker_idx):
         return 6 * (self.problem.num_cameras + self.problem.num_times + int(marker_idx))
 
+    # ---- free intrinsics: the extended layout (rsba_solver_set_extended_layout)
+    def set_extended_layout(self, on=True):
+        """A marker-chain solver with free intrinsics: evaluate(), set_parameters() and the covariance calls index the solver's
+        state layout — the problem's parameters, then fx fy cx cy k1 k2 of every camera index (intrinsics_offset).  Off (the
+        default): those calls are refused on such a solver.  Drops a covariance result; the run's bits do not change."""
+        _chk(load().rsba_solver_set_extended_layout(self.h, 1 if on else 0), "rsba_solver_set_extended_layout")
+        self._extended = bool(on)
+
+    def num_extended_parameters(self):
+        n = int(load().rsba_solver_num_extended_parameters(self.h))
+        if n < 0:
+            raise RsbaError(-n, "rsba_solver_num_extended_parameters")
+        return n
+
+    def intrinsics_offset(self, camera_idx):
+        """The offset of camera camera_idx's intrinsics block under the extended layout."""
+        return self.problem.num_parameters + 6 * int(camera_idx)
+
+    def _num_values(self):
+        return self.num_extended_parameters() if self._extended else self.problem.num_parameters
+
     def _block_size(self, offset):
         if self.problem.model == MODEL_POINTS and offset >= 6 * self.problem.num_cameras:
             return 3
@@ -670,7 +696,7 @@ class Solver:
         o.apply_loss_function = 1 if apply_loss_function else 0
         cost = C.c_double()
         r = np.zeros(self.num_residuals) if residuals else None
-        g = np.zeros(self.problem.num_parameters) if gradient else None
+        g = np.zeros(self._num_values()) if gradient else None
         _chk(load().rsba_solver_evaluate(self.h, C.byref(o), C.byref(cost), _vp(r) if residuals else None, _vp(g) if gradient else None),
              "rsba_solver_evaluate")
         return cost.value, r, g
@@ -697,11 +723,12 @@ class Solver:
         return values[:nnz.value]
 
     def set_parameters(self, x):
-        """New values for every parameter (the problem's layout): the start of the next run() and the current state that
-        evaluate(), covariance_compute() and download() read.  Nothing is planned again."""
+        """New values for every parameter (the problem's layout; under the extended layout the cameras' six values behind it): the
+        start of the next run() and the current state that evaluate(), covariance_compute() and download() read.  Nothing is
+        planned again."""
         x = np.ascontiguousarray(x, np.float64)
-        if x.shape != (self.problem.num_parameters,):
-            raise ValueError("set_parameters: %d values expected" % self.problem.num_parameters)
+        if x.shape != (self._num_values(),):
+            raise ValueError("set_parameters: %d values expected" % self._num_values())
         _chk(load().rsba_solver_set_parameters(self.h, _vp(x)), "rsba_solver_set_parameters")
 
     def set_observation_weights(self, w):

@@ -712,6 +712,189 @@ k_cov_mc_lin(int T, const int* __restrict__ tptr, const CovMcRow* __restrict__ r
   }
 }
 
+#define RSBA_COV_MCI_LDS 109   // doubles per row of the staged W blocks: cam 6x6 | marker 6x6 | intrinsics 6x6 (+1: bank padding)
+
+// k_cov_mc_lin for a solver with free intrinsics under the extended layout: a row has a fourth block, the detecting camera's
+// fx fy cx cy k1 k2 (block nb + camera of pos; the base camera has one too), rows of 2 x 24 per corner — MarkerCornerResidualJacobian<true>'s
+// 18 columns and the six analytic ones (MarkerCornerIntrinsicsTerms).  six: the compute's snapshot of the state's values, [C][6];
+// dist: the path's coefficients [C][5], of which p1 p2 k3 are read.  One instance: the corrector and the weights are applied when
+// loss != 0 or wts != nullptr (a factor of exactly one otherwise), the masks always travel — sub24[q]: the constant components among
+// row q's 24 local columns camera | time | marker | intrinsics, a held intrinsics component being one (its column is zeros, S gets the
+// unit diagonal from k_cov_subset_diag, S^-1 its zeros from k_cov_subset_sinv).
+// An eliminated time: S -= W_x V_t^-1 W_y' over the camera, marker AND intrinsics blocks of its rows.  The three x blocks are taken one
+// at a time — Y_x = W_x V_t^-1 of the lane's row is 36 doubles, all three would not fit beside V_t^-1 — and the rows' W are staged
+// again for each (the rows are cheap to form again; nothing is kept between the passes).
+__global__ void __launch_bounds__(64)
+k_cov_mc_intr_lin(int T, const int* __restrict__ tptr, const CovMcRow* __restrict__ rows, const double* __restrict__ obs8, const double* __restrict__ six,
+                  const double* __restrict__ dist, const int* __restrict__ sub24, const double* __restrict__ pc, const int* __restrict__ pos, int nb,
+                  const unsigned char* __restrict__ elim, double half_side, double rcond, int n, double* __restrict__ S, int* __restrict__ flags,
+                  double loss, const double* __restrict__ wts) {
+  __shared__ double Wl[64 * RSBA_COV_MCI_LDS];
+  __shared__ double Vil[36];   // V_t^-1 of the time at hand: read where Y is formed, not held in registers across the staging
+  __shared__ int Pl[64][3];
+  const int lane = threadIdx.x;
+  // one row's four corners: J (2 x 24 each, row stride 24) through f(J)
+  auto corners = [&](int q, auto&& f) {
+    const CovMcRow rw = rows[q];
+    const double* o8 = obs8 + 8 * (size_t)q;
+    const double* pcc = rw.cam_block >= 0 ? pc + (size_t)rw.cam_block * CC_STRIDE : nullptr;
+    const double* pct = pc + (size_t)rw.time_block * CC_STRIDE;
+    const double* pcm = rw.marker_block >= 0 ? pc + (size_t)rw.marker_block * CC_STRIDE : nullptr;
+    const double* sv = six + 6 * (size_t)rw.camera;
+    const double intr4[4] = {sv[0], sv[1], sv[2], sv[3]};
+    const double kd5[5] = {sv[4], sv[5], dist[5 * (size_t)rw.camera + 2], dist[5 * (size_t)rw.camera + 3], dist[5 * (size_t)rw.camera + 4]};
+    double sq = 1.0;
+    if (loss != 0.0 || wts != nullptr) {
+      double ss = 0.0;
+#pragma unroll 1
+      for (int k = 0; k < 4; ++k) {
+        const double cx = (k == 0 || k == 3) ? -half_side : half_side, cy = k < 2 ? half_side : -half_side;
+        double r[2], J[36];
+        MarkerCornerResidualJacobian<true>(pcc, pct, pcm, intr4, cx, cy, o8[2 * k], o8[2 * k + 1], r, J, kd5);
+        ss += r[0] * r[0] + r[1] * r[1];
+      }
+      (void)LossAndScale(loss, ss, &sq);
+      if (wts != nullptr) sq *= sqrt(wts[q]);
+    }
+    const int sub = sub24[q];
+#pragma unroll 1
+    for (int k = 0; k < 4; ++k) {
+      const double cx = (k == 0 || k == 3) ? -half_side : half_side, cy = k < 2 ? half_side : -half_side;
+      double r[2], Jp[36], it[5], J[48];
+      MarkerCornerResidualJacobian<true>(pcc, pct, pcm, intr4, cx, cy, o8[2 * k], o8[2 * k + 1], r, Jp, kd5);
+      MarkerCornerIntrinsicsTerms(pcc, pct, pcm, intr4, kd5, cx, cy, it);
+#pragma unroll
+      for (int e = 0; e < 18; ++e) { J[e] = Jp[e]; J[24 + e] = Jp[18 + e]; }
+      J[18] = it[0]; J[19] = 0.0; J[20] = 1.0; J[21] = 0.0; J[22] = it[2]; J[23] = it[2] * it[4];
+      J[42] = 0.0; J[43] = it[1]; J[44] = 0.0; J[45] = 1.0; J[46] = it[3]; J[47] = it[3] * it[4];
+#pragma unroll
+      for (int e = 0; e < 48; ++e) J[e] = ((sub >> (e % 24)) & 1) ? 0.0 : J[e] * sq;
+      f(J);
+    }
+  };
+  // stage W_cam, W_marker, W_intr (= sum over corners of J_x' J_t) of row q into this lane's LDS row, with the blocks' positions
+  auto stage = [&](int q, bool act) {
+    double* w = Wl + lane * RSBA_COV_MCI_LDS;
+    for (int e = 0; e < 108; ++e) w[e] = 0.0;
+    Pl[lane][0] = -1; Pl[lane][1] = -1; Pl[lane][2] = -1;
+    if (!act) return;
+    const CovMcRow rw = rows[q];
+    Pl[lane][0] = rw.cam_block >= 0 ? pos[rw.cam_block] : -1;
+    Pl[lane][1] = rw.marker_block >= 0 ? pos[rw.marker_block] : -1;
+    Pl[lane][2] = pos[nb + rw.camera];
+    corners(q, [&](const double* J) {
+      for (int x = 0; x < 3; ++x) {
+        const int xo = x == 0 ? 0 : (x == 1 ? 12 : 18);
+        for (int a = 0; a < 6; ++a)
+          for (int l = 0; l < 6; ++l) w[36 * x + 6 * a + l] += J[xo + a] * J[6 + l] + J[24 + xo + a] * J[24 + 6 + l];
+      }
+    });
+  };
+  for (int t = blockIdx.x; t < T; t += gridDim.x) {
+    const int b = tptr[t], k = tptr[t + 1] - b;
+    if (k == 0) continue;
+    const bool el = elim[t] != 0;
+    double V[21];
+#pragma unroll
+    for (int e = 0; e < 21; ++e) V[e] = 0.0;
+    // J'J of every row among its blocks that have columns (upper blocks), V_t for an eliminated time
+    __syncthreads();   // (the last time's staged rows have been read)
+    for (int q = lane; q < k; q += 64) {
+      const CovMcRow rw = rows[b + q];
+      const int blk[4] = {rw.cam_block, rw.time_block, rw.marker_block, nb + rw.camera};
+      int ps[4];
+      for (int x = 0; x < 4; ++x) ps[x] = blk[x] >= 0 ? pos[blk[x]] : -1;
+      // (the corner's rows go through the lane's own LDS row, free until the staging below: the sixteen block pairs are walked by
+      //  rolled loops that index the rows, which registers cannot be)
+      double* jl = Wl + lane * RSBA_COV_MCI_LDS;
+      corners(b + q, [&](const double* J) {
+#pragma unroll
+        for (int e = 0; e < 48; ++e) jl[e] = J[e];
+#pragma unroll 1
+        for (int xy = 0; xy < 16; ++xy) {
+          const int x = xy >> 2, y = xy & 3;
+          if (ps[x] < 0 || ps[y] < 0 || ps[x] > ps[y] || (ps[x] == ps[y] && x != y)) continue;
+          double* Sb = S + (size_t)ps[x] * n + ps[y];
+#pragma unroll 1
+          for (int a = 0; a < 6; ++a) {
+            const double ju = jl[6 * x + a], jv = jl[24 + 6 * x + a];
+            for (int c = (x == y ? a : 0); c < 6; ++c) unsafeAtomicAdd(&Sb[(size_t)a * n + c], ju * jl[6 * y + c] + jv * jl[24 + 6 * y + c]);
+          }
+        }
+        if (el) {
+          int e = 0;
+#pragma unroll
+          for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int c = a; c < 6; ++c) { V[e] += J[6 + a] * J[6 + c] + J[30 + a] * J[30 + c]; ++e; }
+        }
+      });
+    }
+    if (!el) continue;
+#pragma unroll
+    for (int e = 0; e < 21; ++e) V[e] = WaveSum(V[e]);
+    SubsetUnitDiagonal((sub24[b] >> 6) & 63, V);
+    {
+      double Vi[36];
+      const bool ok = CovSym6Inverse(V, rcond, Vi);
+      if (!ok) {
+        if (lane == 0) atomicOr(&flags[COV_FLAG_POINT], 1);
+        continue;
+      }
+      if (lane == 0) {
+#pragma unroll
+        for (int e = 0; e < 36; ++e) Vil[e] = Vi[e];
+      }
+    }
+#pragma unroll 1
+    for (int x = 0; x < 3; ++x) {
+      for (int qa0 = 0; qa0 < k; qa0 += 64) {
+        __syncthreads();
+        stage(b + qa0 + lane, qa0 + lane < k);
+        __syncthreads();
+        // Y_x = W_x V_t^-1 of this lane's row
+        double Y[36];
+        const double* w = Wl + lane * RSBA_COV_MCI_LDS + 36 * x;
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+          for (int l = 0; l < 6; ++l) {
+            double v = 0.0;
+#pragma unroll
+            for (int m = 0; m < 6; ++m) v += w[6 * a + m] * Vil[6 * m + l];
+            Y[6 * a + l] = v;
+          }
+        const int px = Pl[lane][x];
+        for (int qb0 = 0; qb0 < k; qb0 += 64) {
+          __syncthreads();
+          stage(b + qb0 + lane, qb0 + lane < k);
+          __syncthreads();
+          const int nbq = min(64, k - qb0);
+          for (int bb = 0; bb < nbq; ++bb) {
+            const double* wb = Wl + bb * RSBA_COV_MCI_LDS;
+#pragma unroll 1
+            for (int y = 0; y < 3; ++y) {
+              const int py = Pl[bb][y];
+              if (px < 0 || py < 0 || px > py) continue;
+              double* Sb = S + (size_t)px * n + py;
+#pragma unroll
+              for (int a = 0; a < 6; ++a)
+#pragma unroll
+                for (int c = 0; c < 6; ++c) {
+                  if (px == py && c < a) continue;
+                  double v = 0.0;
+#pragma unroll
+                  for (int l = 0; l < 6; ++l) v += Y[6 * a + l] * wb[36 * y + 6 * c + l];
+                  unsafeAtomicAdd(&Sb[(size_t)a * n + c], -v);
+                }
+            }
+          }
+        }
+      }
+    }
+  }
+}
+
 // ---- any pair of blocks (rsba_solver_covariance_blocks, rsba_solver_time_covariances) ----------------------------------------
 // With e the eliminated blocks (time blocks on the time-eliminating marker-chain path, points on the point model), V_e the
 // undamped corrected diagonal block, W_e the blocks J_x'J_e, Y_e = W_e V_e^-1 and Sigma = S^-1 (cov_sinv):

@@ -51,9 +51,11 @@ struct CovSingle {
 struct CovLayout {
   int model = RSBA_MODEL_POINTS;
   int C = 0, T = 0, M = 0, P = 0;
+  int I = 0;                         // marker chain under the extended layout (CovMarkerIntrColumns): C intrinsics blocks behind [C | T | M],
+                                     // camera k's at block C + T + M + k, offset 6 (C + T + M + k); 0 otherwise
   int n = 0;                         // columns of the system: six per block with pos >= 0
-  std::vector<uint8_t> ref;          // per camera (point model) / per block of [C | T | M]: some residual references it (a sharded
-                                     // solver: on some rank)
+  std::vector<uint8_t> ref;          // per camera (point model) / per block of [C | T | M] (| the I intrinsics blocks): some residual
+                                     // references it (a sharded solver: on some rank)
   std::vector<uint8_t> ref_pt;       // point model: the same per point, this rank's
   std::vector<int> pos;              // per camera / per block: its first column, -1: constant, unreferenced or eliminated
   std::vector<unsigned char> elim;   // marker chain, per time: eliminated (free, referenced, time-eliminating path); max(T, 1) entries
@@ -61,7 +63,8 @@ struct CovLayout {
   std::vector<int> pt_dev;           // point model: a point's index in the problem -> its position on the device (empty: the same)
 
   bool points() const { return model == RSBA_MODEL_POINTS; }
-  int blocks() const { return points() ? C : C + T + M; }
+  int blocks() const { return points() ? C : C + T + M; }   // the pose blocks
+  int all_blocks() const { return blocks() + I; }           // ... and the intrinsics blocks behind them: the entries of ref and pos
   bool is_time(int b) const { return !points() && b >= C && b < C + T; }
   // a block whose rows are formed: with columns, or eliminated
   bool is_free(int b) const { return pos[b] >= 0 || (is_time(b) && elim[b - C]); }
@@ -73,7 +76,7 @@ struct CovLayout {
 
   // Offset -> block: cameras and pose blocks step by 6, points by 3 behind the poses.  RSBA_ERR_ARG: the offset starts no block.
   int BlockOf(int64_t off, bool* point, int* idx) const {
-    const int64_t pose_end = 6LL * blocks();
+    const int64_t pose_end = 6LL * all_blocks();
     if (off < 0) return RSBA_ERR_ARG;
     if (off < pose_end) {
       if (off % 6) return RSBA_ERR_ARG;
@@ -127,7 +130,7 @@ struct CovLayout {
 // order belongs to the solver, not to a compute).
 inline void CovPointReferenced(int C, int P, int64_t N, const int32_t* camera_index, const int32_t* point_index, const std::vector<uint8_t>& const_pt,
                                std::vector<uint8_t>* ref_cam, CovLayout* L) {
-  L->model = RSBA_MODEL_POINTS; L->C = C; L->T = 0; L->M = 0; L->P = P;
+  L->model = RSBA_MODEL_POINTS; L->C = C; L->T = 0; L->M = 0; L->P = P; L->I = 0;
   L->const_pt = const_pt;
   L->elim.clear();
   ref_cam->assign(C, 0);
@@ -149,7 +152,7 @@ inline void CovPointColumns(const std::vector<uint8_t>& ref_cam, const std::vect
 // referenced times are eliminated instead.
 inline void CovMarkerColumns(const rsba_problem& p, const std::vector<uint8_t>& block_constant, bool eliminate_times, CovLayout* L) {
   const int C = p.num_cameras, T = p.num_times, M = p.num_markers, nb = C + T + M;
-  L->model = p.model; L->C = C; L->T = T; L->M = M; L->P = 0;
+  L->model = p.model; L->C = C; L->T = T; L->M = M; L->P = 0; L->I = 0;
   L->ref_pt.clear(); L->const_pt.clear();
   L->ref.assign(nb, 0);
   for (int64_t i = 0; i < p.num_observations; ++i) {
@@ -164,6 +167,23 @@ inline void CovMarkerColumns(const rsba_problem& p, const std::vector<uint8_t>& 
     if (!L->ref[b] || (b < (int)block_constant.size() && block_constant[b])) continue;
     if (eliminate_times && L->is_time(b)) { L->elim[b - C] = 1; continue; }
     L->pos[b] = L->n; L->n += 6;
+  }
+}
+
+// ... a solver with free intrinsics under the extended layout, behind CovMarkerColumns: one more block per camera index.  A camera an
+// observation names is referenced; one with a non-zero mask gets six columns behind the pose blocks', ascending camera index (a
+// held component is a constant component of it: CovPlanMarkerIntrRows); mask 0: a constant block, zeros.  intr_mask may be shorter
+// than C (missing entries: 0).
+inline void CovMarkerIntrColumns(const rsba_problem& p, const std::vector<int>& intr_mask, CovLayout* L) {
+  const int C = L->C, nb = L->blocks();
+  L->I = C;
+  L->ref.resize((size_t)nb + C, 0);
+  L->pos.resize((size_t)nb + C, -1);
+  for (int64_t i = 0; i < p.num_observations; ++i) L->ref[nb + p.camera_index[i]] = 1;
+  for (int k = 0; k < C; ++k) {
+    const int mask = k < (int)intr_mask.size() ? intr_mask[k] & 63 : 0;
+    if (!L->ref[nb + k] || mask == 0) continue;
+    L->pos[nb + k] = L->n; L->n += 6;
   }
 }
 
@@ -218,6 +238,25 @@ inline CovMarkerRows CovPlanMarkerRows(const rsba_problem& p, const CovLayout& L
       R.sub18[q] = (rw.cam_block >= 0 ? bsub[rw.cam_block] : 0) | (bsub[rw.time_block] << 6) | (rw.marker_block >= 0 ? bsub[rw.marker_block] << 12 : 0);
     }
     R.bsub.swap(bsub);
+  }
+  return R;
+}
+
+// ... with intrinsics blocks (CovMarkerIntrColumns ran on L): the masks are always built.  bsub has all_blocks() entries, an intrinsics
+// block with columns holding its CLEAR mask bits (the components the solve does not refine); sub18 carries a row's detecting
+// camera's in bits 18-23 (all six where the camera has no columns: k_cov_mc_intr_lin forms no such column anyway).
+inline CovMarkerRows CovPlanMarkerIntrRows(const rsba_problem& p, const CovLayout& L, const double* weights, const std::vector<uint8_t>& subset,
+                                           const std::vector<int>& intr_mask) {
+  CovMarkerRows R = CovPlanMarkerRows(p, L, weights, subset);
+  const int nb = L.blocks();
+  const size_t N = (size_t)p.num_observations;
+  if (!R.with_sub) { R.bsub.assign(nb, 0); R.sub18.assign(R.rows.size(), 0); R.with_sub = true; }
+  R.bsub.resize((size_t)nb + L.I, 0);
+  for (int k = 0; k < L.I; ++k)
+    if (L.pos[nb + k] >= 0) R.bsub[nb + k] = (unsigned char)(~(k < (int)intr_mask.size() ? intr_mask[k] : 0) & 63);
+  for (size_t q = 0; q < N; ++q) {
+    const int b = nb + R.rows[q].camera;
+    R.sub18[q] |= (L.pos[b] >= 0 ? R.bsub[b] : 63) << 18;
   }
   return R;
 }

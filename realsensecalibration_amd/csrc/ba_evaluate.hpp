@@ -12,6 +12,7 @@
 //                     segments, one workgroup each (k_eval_cam_grad), the segments' sums added in order (k_eval_cam_sum)
 //   marker chain      J'r of every observation (18 values, camera | time | marker) from one thread, then one workgroup per block
 //                     of [C | T | M] over the block's (observation, slot) list (k_eval_marker_block_sum)
+//                     (free intrinsics under the extended layout: 24 values and C more blocks, k_eval_marker_intr)
 // A workgroup's sum is: a thread's own terms in ascending order with stride 256, the wavefront's butterfly, the four wavefronts
 // left to right (EvalBlockSum).
 //
@@ -190,6 +191,69 @@ k_eval_marker(int N, const EvalMarkerRow* __restrict__ rows, const double* __res
       const double w = sq * sq;
 #pragma unroll
       for (int q = 0; q < 18; ++q) obs_grad[18 * (size_t)i + q] = w * g[q];
+    }
+  }
+  rho = WaveSum(rho);
+  if (threadIdx.x == 0) cost_parts[blockIdx.x] = rho;
+}
+
+// A solver with free intrinsics under the extended layout (rsba_solver_set_extended_layout), both paths: k_eval_marker's walk with the
+// camera values of the STATE — params continues behind the nfull pose values with fx fy cx cy k1 k2 of every camera; p1 p2 k3 stay
+// dist's [C][5] — and, kGrad, six more J'r values per observation: the analytic columns of k_marker_intr_eval,
+//   du / d (fx cx k1 k2) = xd, 1, fx x r2, fx x r2^2     dv / d (fy cy k1 k2) = yd, 1, fy y r2, fy y r2^2
+// at the normalised point (x, y) the corner's chain gives (MarkerCornerIntrinsicsTerms, ba_math.hpp).  The 18 pose values go to obs_grad[18 i ..], the six to
+// obs_grad[18 N + 6 i ..] (EvalMarkerIntrPlan: k_eval_marker_block_sum reads both through its lists).  Always the distortion form and
+// always the weights' pointer test, as k_eval_marker<., true>.
+template <bool kGrad>
+__global__ void __launch_bounds__(64)
+k_eval_marker_intr(int N, const EvalMarkerRow* __restrict__ rows, const double* __restrict__ obs8, const double* __restrict__ params, int nfull,
+                   const double* __restrict__ dist, const double* __restrict__ pc, double half_side, double loss, double* __restrict__ residuals,
+                   double* __restrict__ obs_grad, double* __restrict__ cost_parts, const double* __restrict__ wts) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  double rho = 0.0;
+  if (i < N) {
+    const EvalMarkerRow rw = rows[i];
+    const double* o8 = obs8 + 8 * (size_t)i;
+    const double* pcc = rw.cam_block >= 0 ? pc + (size_t)rw.cam_block * CC_STRIDE : nullptr;
+    const double* pct = pc + (size_t)rw.time_block * CC_STRIDE;
+    const double* pcm = rw.marker_block >= 0 ? pc + (size_t)rw.marker_block * CC_STRIDE : nullptr;
+    const double* sv = params + (size_t)nfull + 6 * (size_t)rw.camera;
+    const double intr4[4] = {sv[0], sv[1], sv[2], sv[3]};
+    const double kd5[5] = {sv[4], sv[5], dist[5 * (size_t)rw.camera + 2], dist[5 * (size_t)rw.camera + 3], dist[5 * (size_t)rw.camera + 4]};
+    double g[24], ss = 0.0;
+#pragma unroll
+    for (int q = 0; q < 24; ++q) g[q] = 0.0;
+#pragma unroll 1
+    for (int k = 0; k < 4; ++k) {
+      const double cx = (k == 0 || k == 3) ? -half_side : half_side, cy = k < 2 ? half_side : -half_side;
+      double rk[2], J[36];
+      MarkerCornerResidualJacobian<true>(pcc, pct, pcm, intr4, cx, cy, o8[2 * k], o8[2 * k + 1], rk, J, kd5);
+      ss += rk[0] * rk[0] + rk[1] * rk[1];
+      if (residuals != nullptr) { residuals[8 * (size_t)i + 2 * k] = rk[0]; residuals[8 * (size_t)i + 2 * k + 1] = rk[1]; }
+      if constexpr (kGrad) {
+#pragma unroll
+        for (int q = 0; q < 18; ++q) g[q] += J[q] * rk[0] + J[18 + q] * rk[1];
+        double it[5];
+        MarkerCornerIntrinsicsTerms(pcc, pct, pcm, intr4, kd5, cx, cy, it);
+        const double xd = it[0], yd = it[1], gx = it[2], gy = it[3], r2 = it[4];
+        g[18] += xd * rk[0]; g[19] += yd * rk[1]; g[20] += rk[0]; g[21] += rk[1];
+        g[22] += gx * rk[0] + gy * rk[1];
+        g[23] += (gx * r2) * rk[0] + (gy * r2) * rk[1];
+      }
+    }
+    double sq;
+    rho = LossAndScale(loss, ss, &sq);
+    if (wts != nullptr) { const double a = wts[i]; rho *= a; sq *= sqrt(a); }
+    if (residuals != nullptr && sq != 1.0) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) residuals[8 * (size_t)i + e] *= sq;
+    }
+    if constexpr (kGrad) {
+      const double w = sq * sq;
+#pragma unroll
+      for (int q = 0; q < 18; ++q) obs_grad[18 * (size_t)i + q] = w * g[q];
+#pragma unroll
+      for (int q = 0; q < 6; ++q) obs_grad[18 * (size_t)N + 6 * (size_t)i + q] = w * g[18 + q];
     }
   }
   rho = WaveSum(rho);

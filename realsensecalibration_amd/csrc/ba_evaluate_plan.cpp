@@ -74,6 +74,39 @@ std::vector<unsigned char> EvalMarkerLive(int num_blocks, const std::vector<Eval
   return live;
 }
 
+EvalMarkerIntrPlan PlanEvalMarkerIntr(int num_blocks, int C, const std::vector<EvalMarkerRow>& rows, const std::vector<uint8_t>& block_constant,
+                                      const std::vector<uint8_t>& block_subset, const std::vector<int>& intr_mask) {
+  EvalMarkerIntrPlan x;
+  const size_t N = rows.size();
+  const size_t nb = (size_t)num_blocks, nbx = nb + (size_t)C;
+  const EvalMarkerLists pose = BuildEvalMarkerLists(num_blocks, rows);
+  // the cameras' detections behind the pose blocks' entries: a counting sort, ascending observations
+  std::vector<int> count((size_t)C, 0);
+  for (const EvalMarkerRow& r : rows) count[r.camera]++;
+  x.lists.ptr.assign(pose.ptr.begin(), pose.ptr.end());
+  x.lists.ptr.resize(nbx + 1);
+  for (int k = 0; k < C; ++k) x.lists.ptr[nb + k + 1] = x.lists.ptr[nb + k] + count[k];
+  x.lists.obs = pose.obs; x.lists.slot = pose.slot;
+  x.lists.obs.resize(pose.obs.size() + N); x.lists.slot.resize(pose.slot.size() + N);
+  std::vector<int> fill(x.lists.ptr.begin() + nb, x.lists.ptr.end() - 1);
+  for (size_t i = 0; i < N; ++i) {
+    const int q = fill[rows[i].camera]++;
+    x.lists.obs[q] = (int)(N + i / 3);
+    x.lists.slot[q] = (unsigned char)(i % 3);
+  }
+  x.live = EvalMarkerLive(num_blocks, rows, block_constant);
+  x.live.resize(nbx, 0);
+  x.held.assign(nbx, 0);
+  for (size_t b = 0; b < nb && b < block_subset.size(); ++b) x.held[b] = x.live[b] ? (unsigned char)(block_subset[b] & 63) : 0;
+  for (int k = 0; k < C; ++k) {
+    const int mask = (size_t)k < intr_mask.size() ? intr_mask[k] & 63 : 0;
+    if (mask == 0 || count[k] == 0) continue;
+    x.live[nb + k] = 1;
+    x.held[nb + k] = (unsigned char)(~mask & 63);
+  }
+  return x;
+}
+
 static bool IsConstant(const std::vector<uint8_t>& flags, int b) { return b >= 0 && (size_t)b < flags.size() && flags[b] != 0; }
 
 static EvalJacobianLayout FinishLayout(EvalJacobianLayout l, int rows_per_obs) {

@@ -56,6 +56,21 @@ EvalMarkerLists BuildEvalMarkerLists(int num_blocks, const std::vector<EvalMarke
 // ... and the live mask of the blocks of [C | T | M] (block b sits at 6 b).  block_constant may be shorter than num_blocks.
 std::vector<unsigned char> EvalMarkerLive(int num_blocks, const std::vector<EvalMarkerRow>& rows, const std::vector<uint8_t>& block_constant);
 
+// ---- a marker-chain solver with free intrinsics under the extended layout (rsba_solver_set_extended_layout): the gradient has C more
+// blocks behind [C | T | M], camera k's fx fy cx cy k1 k2 at block num_blocks + k.  k_eval_marker_intr writes observation i's pose
+// J'r at obs_grad[18 i ..] as k_eval_marker does and its six intrinsics values at obs_grad[18 N + 6 i ..], behind all of them; the
+// sum kernel (k_eval_marker_block_sum, unchanged) reads the six values at 18 obs + 6 slot, so the entry of observation i in an
+// intrinsics block's list is (obs, slot) = (N + i / 3, i % 3): 18 (N + i / 3) + 6 (i % 3) = 18 N + 6 i.
+struct EvalMarkerIntrPlan {
+  EvalMarkerLists lists;              // num_blocks + C lists: the pose blocks' as BuildEvalMarkerLists gives them, then a camera's detections, ascending
+  std::vector<unsigned char> live;    // num_blocks + C: an intrinsics block is live when its mask is not 0 and an observation names the camera
+  std::vector<unsigned char> held;    // num_blocks + C: per live block the components written as 0.0 — a pose block's subset mask, an intrinsics
+                                      // block's clear mask bits; 0 for a block that is not live (all of its slots are 0.0 already)
+};
+// block_constant / block_subset / intr_mask may be shorter than their counts (missing entries: free / no mask / mask 0).
+EvalMarkerIntrPlan PlanEvalMarkerIntr(int num_blocks, int C, const std::vector<EvalMarkerRow>& rows, const std::vector<uint8_t>& block_constant,
+                                      const std::vector<uint8_t>& block_subset, const std::vector<int>& intr_mask);
+
 // ---- the Jacobian of rsba_solver_evaluate_jacobian, in compressed-row form (ba_evaluate_jacobian.hpp)
 // Rows in the problem's observation order (2 per observation on the point model, 8 on the marker chain), columns = parameter
 // offsets.  A row holds every column of every block its observation names as a parameter and that is not constant — camera, then

@@ -940,16 +940,18 @@ struct MarkerDevice {
   int Download(rsba_problem* p) {
     if (hipMemcpy(p->parameters.data(), params[cur], nfull * 8, hipMemcpyDeviceToHost) != hipSuccess) return RSBA_ERR_HIP;
     if (with_intr) {
-      // the refined values into the problem's own arrays (a camera without a block, and a held component, keep their bits: the
-      // state started from them); a distortion array appears when k1 or k2 was free and the problem had none
+      // the state's six values of EVERY camera into the problem's own arrays: the refined ones, and those rsba_solver_set_parameters
+      // changed under the extended layout (a held component, a camera without a block).  Without such a call these keep their bits: the
+      // state started from them.  A distortion array appears when the problem had none and k1 or k2 was free, or was set to non-zero
       const int C = (int)intr_mask.size();
       std::vector<double> hs(6 * (size_t)C);
       if (hipMemcpy(hs.data(), params[cur] + nfull, hs.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return RSBA_ERR_HIP;
+      bool want_dist = !p->distortion.empty();
+      for (int k = 0; k < C; ++k) want_dist = want_dist || (intr_mask[k] & 0x30) || hs[6 * (size_t)k + 4] != 0.0 || hs[6 * (size_t)k + 5] != 0.0;
+      if (want_dist && p->distortion.empty()) p->distortion.assign(5 * (size_t)C, 0.0);
       for (int k = 0; k < C; ++k) {
-        if (intr_mask[k] == 0) continue;
         for (int q = 0; q < 4; ++q) p->intrinsics[4 * (size_t)k + q] = hs[6 * (size_t)k + q];
-        if ((intr_mask[k] & 0x30) && p->distortion.empty()) p->distortion.assign(5 * (size_t)C, 0.0);
-        if (!p->distortion.empty()) { p->distortion[5 * (size_t)k] = hs[6 * (size_t)k + 4]; p->distortion[5 * (size_t)k + 1] = hs[6 * (size_t)k + 5]; }
+        if (want_dist) { p->distortion[5 * (size_t)k] = hs[6 * (size_t)k + 4]; p->distortion[5 * (size_t)k + 1] = hs[6 * (size_t)k + 5]; }
       }
     }
     return RSBA_OK;

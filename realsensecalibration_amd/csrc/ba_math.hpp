@@ -343,6 +343,34 @@ RSBA_HD void MarkerCornerResidualJacobian(const double* pc_cam, const double* pc
   }
 }
 
+// What the six intrinsics columns of a corner's rows are made of (free intrinsics: fx fy cx cy k1 k2 as one more block), beside
+// MarkerCornerResidualJacobian<true>: the corner's chain and ProjectCorner<true>'s normalised point again, for the values those two
+// do not return.  The projection is linear in each of the six:
+//   du / d (fx cx k1 k2) = xd, 1, gx, gx r2     dv / d (fy cy k1 k2) = yd, 1, gy, gy r2      gx = fx x r2, gy = fy y r2
+// (k_marker_intr_eval's columns).  t = {xd, yd, gx, gy, r2}.
+RSBA_HD void MarkerCornerIntrinsicsTerms(const double* pc_cam, const double* pc_time, const double* pc_marker, const double* intr4,
+                                         const double* dist5, double cx, double cy, double t[5]) {
+  double p[3] = {cx, cy, 0.0};
+  auto move = [&p](const double* pc) {
+    const double* R = pc + CC_R;
+    const double q0 = R[0] * p[0] + R[1] * p[1] + R[2] * p[2], q1 = R[3] * p[0] + R[4] * p[1] + R[5] * p[2], q2 = R[6] * p[0] + R[7] * p[1] + R[8] * p[2];
+    p[0] = q0 + pc[CC_T]; p[1] = q1 + pc[CC_T + 1]; p[2] = q2 + pc[CC_T + 2];
+  };
+  if (pc_marker) move(pc_marker);
+  move(pc_time);
+  if (pc_cam) move(pc_cam);
+  const double iz = 1.0 / p[2];
+  const double x = p[0] * iz, y = p[1] * iz;
+  const double xx = x * x, yy = y * y, xy = x * y;
+  const double r2 = xx + yy;
+  const double rad = 1.0 + r2 * (dist5[0] + r2 * (dist5[1] + r2 * dist5[4]));
+  t[0] = x * rad + (2.0 * dist5[2] * xy + dist5[3] * (r2 + 2.0 * xx));
+  t[1] = y * rad + (dist5[2] * (r2 + 2.0 * yy) + 2.0 * dist5[3] * xy);
+  t[2] = intr4[0] * x * r2;
+  t[3] = intr4[1] * y * r2;
+  t[4] = r2;
+}
+
 // One of the three 2 x 6 blocks of MarkerCornerResidualJacobian's rows (part 0: camera block + the residuals, 1: time
 // block, 2: marker block), the same arithmetic: k_time_eliminate stages a corner on three lanes.  The intrinsics come by
 // value (the caller fetched them a tile ahead).  J has the row stride 18 of the full rows; a block whose pose is not a

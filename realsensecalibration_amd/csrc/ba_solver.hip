@@ -376,7 +376,10 @@ struct rsba_solver {
   std::vector<uint8_t> eval_subset;   // marker chain: the blocks' masks of constant components as they were at create (empty: none set)
   int num_priors = 0;                 // marker chain: the priors (rsba_problem_set_block_prior) the solver was created with
   bool free_intrinsics = false;       // marker chain: some camera's intrinsics are refined (rsba_problem_set_intrinsics_free): the dense path with
-                                      // MarkerDevice's k_marker_intr_* kernels; evaluate, the Jacobian, the covariance and set_parameters are refused
+                                      // MarkerDevice's k_marker_intr_* kernels (schur_impl = 3: the time-eliminating path); by default evaluate, the
+                                      // Jacobian, the covariance and set_parameters are refused
+  bool extended_layout = false;       // ... unless the caller switched the extended layout on (rsba_solver_set_extended_layout): evaluate and
+                                      // set_parameters then index the state's layout, num_parameters + 6 per camera index
 
   // ---- the three above on a solver with a communicator (ShardedQuery): the request word and the camera check travel from here
   double* query_buf = nullptr;                 // device scratch, kept between calls (grows only)
@@ -2091,6 +2094,60 @@ static int CovarianceMarker(rsba_solver* s, const rsba_covariance_options& co) {
   return rc;
 }
 
+// ... of a solver with free intrinsics under the extended layout: the cameras' intrinsics blocks are more blocks with columns in S,
+// behind the pose blocks' (CovMarkerIntrColumns), linearised by k_cov_mc_intr_lin at a snapshot of the state's fx fy cx cy k1 k2
+// taken here, beside pc.  The inverse, the priors and the treatment of constant components (a held intrinsics component is one) are
+// CovarianceMarker's.  The pair queries of the time-eliminating path that need k_cov_mc_cross are refused (CovarianceBlocks,
+// rsba_solver_time_covariances): that kernel does not know the fourth block.
+static int CovarianceMarkerIntr(rsba_solver* s, const rsba_covariance_options& co) {
+  const rsba_problem& p = *s->prob;
+  const bool elim_path = s->eliminate_times;
+  const std::vector<int>& intr_mask = elim_path ? s->marker_schur.intr_mask : s->marker.intr_mask;
+  CovLayout& L = s->cov_layout;
+  CovMarkerColumns(p, p.block_constant, elim_path, &L);
+  CovMarkerIntrColumns(p, intr_mask, &L);
+  const int T = L.T, C = L.C, nb = L.blocks(), nbx = L.all_blocks(), n = L.n;
+  const bool use_w = s->weights_given && co.apply_loss_function;
+  const CovMarkerRows R = CovPlanMarkerIntrRows(p, L, use_w ? s->obs_w.data() : nullptr, s->eval_subset, intr_mask);
+  double *pc = nullptr, *obs_d = nullptr, *six = nullptr, *wrow_d = nullptr;
+  int *pos = nullptr, *tptr_d = nullptr, *sub24_d = nullptr;
+  CovMcRow* rows_d = nullptr;
+  unsigned char *elim_d = nullptr, *bsub_d = nullptr;
+  auto extra = [&](CovCarve& cv) {
+    sub24_d = cv.take<int>(R.sub18.size()); bsub_d = cv.take<unsigned char>(nbx);
+    if (use_w) wrow_d = cv.take<double>(R.wrow.size());
+    pc = cv.take<double>((size_t)CC_STRIDE * nb); six = cv.take<double>(6 * (size_t)C); obs_d = cv.take<double>(R.obs.size());
+    pos = cv.take<int>(nbx); tptr_d = cv.take<int>(T + 1); rows_d = cv.take<CovMcRow>(R.rows.size()); elim_d = cv.take<unsigned char>(L.elim.size());
+  };
+  const double* params = elim_path ? (s->has_run ? s->marker_schur.params[s->marker_schur.cur] : s->marker_schur.params0)
+                                   : (s->has_run ? s->marker.params[s->marker.cur] : s->marker.params0);
+  const double rcond = co.min_reciprocal_condition_number;
+  const double loss = !co.apply_loss_function || !(s->opt.huber_delta > 0.0) ? 0.0 : (s->opt.loss_type == RSBA_LOSS_CAUCHY ? -s->opt.huber_delta : s->opt.huber_delta);
+  hipStream_t st = s->stream;
+  const int rc = CovRun(s, n, rcond, extra, [&](CovSystem& y, auto& hip) {
+    auto upload = [&](auto* dst, const auto& v) { hip(hipMemcpyAsync(dst, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice, st)); };
+    upload(obs_d, R.obs); upload(pos, L.pos); upload(tptr_d, R.tptr); upload(rows_d, R.rows); upload(elim_d, L.elim);
+    upload(sub24_d, R.sub18); upload(bsub_d, R.bsub);
+    if (use_w) upload(wrow_d, R.wrow);
+    // the snapshot: the pose constants and the cameras' six values as the state has them now
+    k_cov_pose_constants<<<(nb + 255) / 256, 256, 0, st>>>(nb, params, pc);
+    hip(hipMemcpyAsync(six, params + p.parameters.size(), 6 * (size_t)C * sizeof(double), hipMemcpyDeviceToDevice, st));
+    k_cov_mc_intr_lin<<<std::max(1, std::min(T, 4096)), 64, 0, st>>>(T, tptr_d, rows_d, obs_d, six, s->dist_dev, sub24_d, pc, pos, nb, elim_d, p.marker_side / 2,
+                                                                    rcond, y.n, y.S, y.flags, loss, wrow_d);
+    if (s->num_priors > 0 && y.n > 0) {
+      const PriorDevice& pd = elim_path ? s->marker_schur.prior : s->marker.prior;
+      k_cov_prior<<<(36 * pd.K + 255) / 256, 256, 0, st>>>(pd.K, pd.full, pd.mask, pd.ab, pos, y.n, y.S);
+    }
+    k_cov_subset_diag<<<(6 * nbx + 255) / 256, 256, 0, st>>>(nbx, pos, bsub_d, y.n, y.S);
+    // (the host vectors outlive CovRun, which synchronises the stream before it returns)
+  }, [](CovSystem&, auto&) { return RSBA_OK; });
+  if (rc == RSBA_OK && n > 0) {
+    k_cov_subset_sinv<<<nbx, 256, 0, st>>>(pos, bsub_d, n, s->cov_sinv);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { s->cov_valid = false; return RSBA_ERR_HIP; }
+  }
+  return rc;
+}
+
 
 // ------------------------------------------------------------------------------------------------
 // Any pair of blocks of a covariance result (rsba_solver_covariance_blocks, rsba_solver_time_covariances; kernels and maths:
@@ -2164,6 +2221,10 @@ static int CovarianceBlocks(rsba_solver* s, int64_t num_pairs, const int64_t* of
   std::vector<CovPair> pairs;
   int rc;
   if ((rc = CovResolvePairs(L, num_pairs, offsets_a, offsets_b, &pairs))) return rc;
+  // free intrinsics: a pair with an ELIMINATED time block (kind TIME: the time-eliminating path only; the dense path's time blocks
+  // have columns and are REDUCED) needs k_cov_mc_cross, which does not know the intrinsics blocks (rsba.h)
+  if (L.I > 0 && s->eliminate_times)
+    for (const CovPair& pr : pairs) if (pr.a.kind == CovBlockRef::TIME || pr.b.kind == CovBlockRef::TIME) return RSBA_ERR_UNSUPPORTED;
   if (L.points() && L.pt_dev.empty() && !s->pt_perm.empty()) L.BuildPointDev(s->pt_perm);
   const CovQueryPlan Q = CovPlanPairs(L, pairs);
   double* stage_d = nullptr;
@@ -2225,6 +2286,17 @@ static int EvalBuildTables(rsba_solver* s) {
   } else {
     const int nb = p.num_cameras + p.num_times + p.num_markers;
     const std::vector<EvalMarkerRow> rows = EvalMarkerRows(p);
+    if (s->free_intrinsics) {
+      // the extended layout's lists over [C | T | M | C intrinsics blocks] (evaluate is refused on such a solver without it); the
+      // masks always travel: an intrinsics block's held components are zeroed like a pose block's constant ones
+      const EvalMarkerIntrPlan x = PlanEvalMarkerIntr(nb, p.num_cameras, rows, s->eval_const_block, s->eval_subset,
+                                                      s->eliminate_times ? s->marker_schur.intr_mask : s->marker.intr_mask);
+      if ((rc = EvalUpload(&e.rows, rows)) || (rc = EvalUpload(&e.obs8, p.observations)) || (rc = EvalUpload(&e.list_ptr, x.lists.ptr)) ||
+          (rc = EvalUpload(&e.list_obs, x.lists.obs)) || (rc = EvalUpload(&e.list_slot, x.lists.slot)) || (rc = EvalUpload(&e.live, x.live)) ||
+          (rc = EvalUpload(&e.bsub, x.held)))
+        return rc;
+      return RSBA_OK;
+    }
     const EvalMarkerLists lists = BuildEvalMarkerLists(nb, rows);
     const std::vector<unsigned char> live = EvalMarkerLive(nb, rows, s->eval_const_block);
     if ((rc = EvalUpload(&e.rows, rows)) || (rc = EvalUpload(&e.obs8, p.observations)) || (rc = EvalUpload(&e.intr, p.intrinsics)) ||
@@ -2260,15 +2332,18 @@ static int EvaluateOnDevice(rsba_solver* s, bool apply_loss, double* cost, doubl
   const bool points = p.model == RSBA_MODEL_POINTS;
   const size_t N = (size_t)p.num_observations, nres = (size_t)p.obs_dim() * N + 6 * (size_t)s->num_priors, npar = p.parameters.size();
   const int C = p.num_cameras, nb = points ? 0 : C + p.num_times + p.num_markers;
+  const bool ext = s->extended_layout;            // free intrinsics: the state's layout, C more blocks behind [C | T | M]
+  const size_t ngrad = npar + (ext ? 6 * (size_t)C : 0);
+  const int nbx = nb + (ext ? C : 0);
   const int grid = points ? std::max(1, std::min((s->P + 3) / 4, 8192)) : (int)std::max<size_t>(1, (N + 63) / 64);   // = the cost's partials
   const double loss = !apply_loss || !(s->opt.huber_delta > 0.0) ? 0.0 : (s->opt.loss_type == RSBA_LOSS_CAUCHY ? -s->opt.huber_delta : s->opt.huber_delta);
   double *posec = nullptr, *res_d = nullptr, *grad_d = nullptr, *work = nullptr, *cost_parts = nullptr, *cost_d = nullptr, *pay = nullptr, *prior_pe = nullptr;
   auto carve = [&](CovCarve& cv) {
     posec = cv.take<double>((size_t)CC_STRIDE * (points ? C : nb));
     res_d = residuals ? cv.take<double>(nres) : nullptr;
-    grad_d = gradient ? cv.take<double>(npar) : nullptr;
+    grad_d = gradient ? cv.take<double>(ngrad) : nullptr;
     // the camera gradient's segment sums / every observation's J'r
-    work = gradient ? cv.take<double>(points ? (size_t)C * RSBA_EVAL_CAM_SEGS * 6 : 18 * N) : nullptr;
+    work = gradient ? cv.take<double>(points ? (size_t)C * RSBA_EVAL_CAM_SEGS * 6 : (ext ? 24 : 18) * N) : nullptr;
     cost_parts = cv.take<double>(grid + (s->num_priors > 0 ? 1 : 0));   // (the priors' share: one more partial)
     cost_d = cv.take<double>(1);
     if (s->num_priors > 0) prior_pe = cv.take<double>(s->num_priors);
@@ -2293,7 +2368,16 @@ static int EvaluateOnDevice(rsba_solver* s, bool apply_loss, double* cost, doubl
                                               : (s->has_run ? s->marker.params[s->marker.cur] : s->marker.params0);
     k_cov_pose_constants<<<(nb + 255) / 256, 256, 0, st>>>(nb, params, posec);
     const double* wts = apply_loss && s->weights_given ? s->obs_w_dev : nullptr;   // (the weights go with the loss, as in Ceres)
-    if (gradient) {
+    if (ext) {
+      // the state's fx fy cx cy k1 k2 (params behind its npar pose values), p1 p2 k3 from the path's coefficient array (always there)
+      if (gradient) {
+        k_eval_marker_intr<true><<<grid, 64, 0, st>>>((int)N, e.rows, e.obs8, params, (int)npar, s->dist_dev, posec, p.marker_side / 2, loss, res_d, work, cost_parts, wts);
+        k_eval_marker_block_sum<<<nbx, 256, 0, st>>>(e.list_ptr, e.list_obs, e.list_slot, work, e.live, grad_d);
+        k_eval_subset_gradient<<<(6 * nbx + 255) / 256, 256, 0, st>>>(nbx, e.bsub, grad_d);
+      } else {
+        k_eval_marker_intr<false><<<grid, 64, 0, st>>>((int)N, e.rows, e.obs8, params, (int)npar, s->dist_dev, posec, p.marker_side / 2, loss, res_d, nullptr, cost_parts, wts);
+      }
+    } else if (gradient) {
       if (s->dist_dev) k_eval_marker<true, true><<<grid, 64, 0, st>>>((int)N, e.rows, e.obs8, IntrDist{e.intr, s->dist_dev}, posec, p.marker_side / 2, loss, res_d, work, cost_parts, wts);
       else k_eval_marker<true><<<grid, 64, 0, st>>>((int)N, e.rows, e.obs8, e.intr, posec, p.marker_side / 2, loss, res_d, work, cost_parts, wts);
       k_eval_marker_block_sum<<<nb, 256, 0, st>>>(e.list_ptr, e.list_obs, e.list_slot, work, e.live, grad_d);
@@ -2331,7 +2415,7 @@ static int EvaluateOnDevice(rsba_solver* s, bool apply_loss, double* cost, doubl
   }
   if (cost) hip(hipMemcpyAsync(cost, cost_d, sizeof(double), hipMemcpyDeviceToHost, st));
   if (residuals && nres > 0) hip(hipMemcpyAsync(residuals, res_d, nres * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (gradient && npar > 0) hip(hipMemcpyAsync(gradient, grad_d, npar * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (gradient && ngrad > 0) hip(hipMemcpyAsync(gradient, grad_d, ngrad * sizeof(double), hipMemcpyDeviceToHost, st));
   hip(hipStreamSynchronize(st));
   return rc;
 }
@@ -2479,7 +2563,8 @@ static int SetParametersOnDevice(rsba_solver* s, const double* x) {
     if (rc != RSBA_OK) return rc;
   } else {
     double* params0 = s->eliminate_times ? s->marker_schur.params0 : s->marker.params0;
-    HIPCHK(hipMemcpy(params0, x, p.parameters.size() * sizeof(double), hipMemcpyHostToDevice));
+    // (the extended layout: the six values of every camera behind the poses, as params0 keeps them)
+    HIPCHK(hipMemcpy(params0, x, (p.parameters.size() + (s->extended_layout ? 6 * (size_t)p.num_cameras : 0)) * sizeof(double), hipMemcpyHostToDevice));
     int rc = s->eliminate_times ? s->marker_schur.Reset(st) : s->marker.Reset(st);
     if (rc != RSBA_OK) return rc;
   }
@@ -2931,12 +3016,13 @@ int rsba_solver_covariance_compute(rsba_solver* s, const rsba_covariance_options
     return rsba::ShardedLeave(s, rc);
   }
   if (bad) return RSBA_ERR_ARG;
-  if (s->free_intrinsics) return RSBA_ERR_UNSUPPORTED;   // (no place for the intrinsics blocks: rsba.h)
+  if (s->free_intrinsics && !s->extended_layout) return RSBA_ERR_UNSUPPORTED;   // (no place for the intrinsics blocks: rsba.h)
   s->cov_valid = false;
   ++s->cov_epoch;
   if (hipSetDevice(s->device) != hipSuccess) return RSBA_ERR_HIP;
   if (hipStreamSynchronize(s->stream) != hipSuccess) return RSBA_ERR_HIP;
-  return s->prob->model == RSBA_MODEL_POINTS ? rsba::CovariancePoints(s, co, nullptr) : rsba::CovarianceMarker(s, co);
+  if (s->prob->model == RSBA_MODEL_POINTS) return rsba::CovariancePoints(s, co, nullptr);
+  return s->extended_layout ? rsba::CovarianceMarkerIntr(s, co) : rsba::CovarianceMarker(s, co);
 }
 
 int rsba_solver_covariance_block(const rsba_solver* s, int64_t offset_a, int64_t offset_b, double* out) {
@@ -2977,8 +3063,23 @@ int rsba_solver_time_covariances(rsba_solver* s, double* out) {
   if (!s || !out) return RSBA_ERR_ARG;
   if (s->prob->model == RSBA_MODEL_POINTS) return RSBA_ERR_UNSUPPORTED;
   if (!s->cov_valid) return RSBA_ERR_ARG;
+  if (s->cov_layout.I > 0 && s->eliminate_times) return RSBA_ERR_UNSUPPORTED;   // (free intrinsics: as rsba_solver_covariance_blocks' time pairs)
   if (hipSetDevice(s->device) != hipSuccess) return RSBA_ERR_HIP;
   return rsba::CovarianceTimes(s, out);
+}
+
+int rsba_solver_set_extended_layout(rsba_solver* s, int32_t on) {
+  if (!s) return RSBA_ERR_ARG;
+  // the point model has no intrinsics blocks; a marker-chain solver without free intrinsics keeps them as constants of the problem
+  if (!s->free_intrinsics) return RSBA_ERR_UNSUPPORTED;
+  s->extended_layout = on != 0;
+  s->cov_valid = false;   // (its blocks were named under the other layout)
+  return RSBA_OK;
+}
+
+int64_t rsba_solver_num_extended_parameters(const rsba_solver* s) {
+  if (!s) return -(int64_t)RSBA_ERR_ARG;
+  return (int64_t)s->prob->parameters.size() + (s->prob->is_marker_chain() ? 6 * (int64_t)s->prob->num_cameras : 0);
 }
 
 int64_t rsba_solver_num_residuals(const rsba_solver* s) {
@@ -2990,7 +3091,8 @@ int rsba_solver_evaluate(rsba_solver* s, const rsba_evaluate_options* o, double*
   if (!s) return RSBA_ERR_ARG;
   rsba_evaluate_options eo;
   if (o) eo = *o; else rsba_evaluate_options_default(&eo);
-  if (s->free_intrinsics) return RSBA_ERR_UNSUPPORTED;   // (the gradient is indexed by parameter offset: no place for the intrinsics blocks)
+  // (the gradient is indexed by parameter offset: the intrinsics blocks have a place under the extended layout only)
+  if (s->free_intrinsics && !s->extended_layout) return RSBA_ERR_UNSUPPORTED;
   if (!cost && !residuals && !gradient) return RSBA_OK;
   if (s->comm) {
     if (s->prob->model != RSBA_MODEL_POINTS) return RSBA_ERR_UNSUPPORTED;   // (a marker-chain solver has one rank: nobody waits)
@@ -3064,8 +3166,8 @@ int rsba_solver_set_block_prior(rsba_solver* s, int64_t parameter_offset, const 
 
 int rsba_solver_set_parameters(rsba_solver* s, const double* parameters) {
   if (!s) return RSBA_ERR_ARG;
-  if (s->free_intrinsics) return RSBA_ERR_UNSUPPORTED;   // (the array has no place for the intrinsics blocks)
-  const size_t n = s->prob->parameters.size();
+  if (s->free_intrinsics && !s->extended_layout) return RSBA_ERR_UNSUPPORTED;   // (the array has no place for the intrinsics blocks)
+  const size_t n = s->prob->parameters.size() + (s->extended_layout ? 6 * (size_t)s->prob->num_cameras : 0);
   if (s->comm) {
     // collective (rsba.h): NULL or a non-finite value on this rank alone travels in the request word, the group refuses together
     // and nothing changes on any rank; then every rank must have passed the same camera blocks
